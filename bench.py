@@ -5,15 +5,21 @@ Contract (driver): `python bench.py --gpus N --steps K --warmup W`; for N>1 laun
 torch.distributed.run, one rank per GPU.  A step = one pass of the hot path (K0 front end -> activity mask -> K1 tile
 search -> K2a/K2 deblock level search + filter -> K3 CDEF -> K5 loop restoration -> K4 entropy coding -> pack/D2H -> host
 OBU+container assembly) over one batch of synthetic images that is ALREADY RESIDENT in HBM (RGB8, uploaded before the
-timed region): that is `value`.  The same run then repeats the timed loop with the H2D of every batch (pinned host memory ->
+timed region): that is `value`, and `ms_per_step` is one timed step.  Images shard across ranks with no data-path collective
+(weak scaling: --batch images per GPU); every resident batch slot holds DIFFERENT images.  Rank 0 prints one JSON line.
+A plain run does only that: set-up, --warmup steps, --steps timed steps, the outputs of the last step if --dump-outputs
+DIR is given (rank 0's .avif files as .npy arrays, for comparing two builds on identical inputs), and the line.
+
+--full adds what the headline does not need.  It repeats the timed loop with the H2D of every batch (pinned host memory ->
 HBM, async on the batch's stream, overlapped with the other slots' compute) inside the region: `value_pcie_inclusive`, the
-"encode-only" clock of SURVEY.md 8(d) (RGBA8/RGB8 in pinned host memory -> .avif bytes in host memory).
-Images shard across ranks with no data-path collective (weak scaling: --batch images per GPU); every resident batch slot
-holds DIFFERENT images.  Rank 0 prints one JSON line; `roofline` is for the dominant kernel (tile search) from HIP events of
-a launch with nothing else in flight, `cpu_baseline` is the scalar C oracle (a port, not the reference) on this box's host
-cores, `cpu_baseline_standin` is libaom (through Pillow) at its matching speed on the same inputs -- both stand-ins: the
-reference itself (rav1e) cannot be built in this image.  `--secondary` adds single-image latency lines for BASELINE
-configs 2, 3 and 5; `--end-to-end N` adds the PNG-file -> .avif-file clock of the command line on N synthetic PNGs (256 by default at one GPU).
+"encode-only" clock of SURVEY.md 8(d) (RGBA8/RGB8 in pinned host memory -> .avif bytes in host memory).  `roofline` is for
+the dominant kernel (tile search) from HIP events of one more launch with nothing else in flight, `output_identity` checks
+every file against the oracle's sha256 manifest, `cpu_baseline` is the scalar C oracle (a port, not the reference) on the
+host's usable cores, `cpu_baseline_standin` is libaom (through Pillow) at its matching speed on the same inputs -- both
+stand-ins for the reference itself (rav1e), which the project does not build.  `threads_host_cores` / `threads_16` time the batch
+with a bounded tile target, and `end_to_end` is the PNG-file -> .avif-file clock of the command line on 256 synthetic PNGs
+at one GPU (`--end-to-end N` sets N, with or without --full).  `--secondary` adds single-image latency lines for BASELINE
+configs 2, 3 and 5.
 """
 import argparse
 import json
@@ -171,6 +177,28 @@ def check_identity(batches, image_index, B, cfg, manifest=None):
     if bad:
         r["first_mismatches"] = bad
     return r
+
+
+DUMP_BUDGET_BYTES = 64 * 10**6
+
+
+def dump_outputs(d, bt, B):
+    """--dump-outputs: what a caller of the timed path receives from its last step, the B EncodedImages of the slot that step ran on, as .npy files in
+    `d`: avif_file_len, color_byte_size, alpha_byte_size (float64, one per image) and avif_file_bytes (float32, every file's bytes concatenated in image
+    order).  When the bytes would take the whole file set past DUMP_BUDGET_BYTES, avif_file_bytes holds the bytes at a fixed sample of positions
+    instead: sorted(numpy.random.default_rng(0).choice(total, k, replace=False)), which is the same for two runs whose files have the same lengths."""
+    import numpy as np
+    files = [bt.get(i) for i in range(B)]
+    small = {'avif_file_len': np.array([len(f.avif_file) for f in files], np.float64),
+             'color_byte_size': np.array([f.color_byte_size for f in files], np.float64),
+             'alpha_byte_size': np.array([f.alpha_byte_size for f in files], np.float64)}
+    data = np.frombuffer(b''.join(f.avif_file for f in files), dtype=np.uint8)
+    k = (DUMP_BUDGET_BYTES - sum(a.nbytes for a in small.values()) - 4 * 4096) // 4      # 4096: room for each .npy header
+    if data.size > k:
+        data = data[np.sort(np.random.default_rng(0).choice(data.size, k, replace=False))]
+    os.makedirs(d, exist_ok=True)
+    for name, a in dict(small, avif_file_bytes=data.astype(np.float32)).items():
+        np.save(os.path.join(d, name + '.npy'), a)
 
 
 def _oracle_worker(jobs):
@@ -383,12 +411,15 @@ def main():
     ap.add_argument('--speed', type=int, default=4)
     ap.add_argument('--quality', type=float, default=80.0)
     ap.add_argument('--depth', type=int, default=10)
+    ap.add_argument('--full', action='store_true', help='also measure and check what the headline does not need: value_pcie_inclusive, roofline / roofline_valu '
+                    '(one more step), output_identity, the CPU baselines, the threads lines and end_to_end; the --no-* options below leave parts of it out')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps, write the .avif files of the last step (rank 0) as float32 / float64 .npy arrays into DIR')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-identity-check', action='store_true')
     ap.add_argument('--manifest', default=None, help='sha256 manifest to check the outputs against (default: tests/golden/bench_manifest.json, the default workload)')
     ap.add_argument('--no-pcie-loop', action='store_true', help='skip the second timed loop (H2D inside the region)')
     ap.add_argument('--secondary', action='store_true', help='also time BASELINE configs 2, 3 and 5 (single images; config 5 takes a while)')
-    ap.add_argument('--end-to-end', type=int, default=-1, metavar='N', help='PNG files -> .avif files through the cavif_mi command line on N synthetic PNGs (default: 256 at N=1 GPU -- BASELINE config 4 is a batch of 256 files --, 0 = skip)')
+    ap.add_argument('--end-to-end', type=int, default=-1, metavar='N', help='PNG files -> .avif files through the cavif_mi command line on N synthetic PNGs (default: 256 at N=1 GPU with --full -- BASELINE config 4 is a batch of 256 files --, else 0; 0 = skip)')
     ap.add_argument('--threads', type=int, default=0, help='ravif with_num_threads / cavif -j: T bounds the tile target (av1encoder.rs:665-668); 0 = unspecified (None): uncapped on a GPU')
     ap.add_argument('--no-threads-line', action='store_true', help='skip the secondary line at T = host cores (what `cavif -j0` would ask for on this box)')
     ap.add_argument('--pipeline', type=int, default=4, help='resident batch slots driven in rotation (one batch entropy-codes and filters while the others search). Measured on resident inputs, 20 steps (profiles/r06s_pipeline_sweep.txt): 1 slot 495.5, 2 slots 482.6, 3 slots 483.3, 4 slots 497.9 ... 502.7 MPix/s; at the end of the round (profiles/r06Y_pipeline_sweep.txt): 1 / 2 / 3 / 4 / 5 / 6 / 8 slots 537 / 519 / 525 / 533 ... 543 / 534 / 538 / 540 -- two or three slots interleave one search with the other slots\' filter / entropy kernels badly. The product stream path (mi_ravif_encode_stream, MI_STREAM_SLOTS_DEFAULT = 2) keeps two objects per image shape because on a 256-file job every further object costs 0.07 s of allocation, more than its overlap returns (profiles/r05zk_e2e_knobs.txt); its clock is the end_to_end line')
@@ -502,8 +533,10 @@ def main():
 
     own_done = [0.0]
     elapsed, stats, per_rank = timed(False)                      # `value`: inputs resident in HBM
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, batches[(args.steps - 1) % depth_q], B)     # the slot the last timed step ran on
     elapsed_pcie = None
-    if not args.no_pcie_loop:
+    if args.full and not args.no_pcie_loop:
         elapsed_pcie, _, _ = timed(True)                            # `value_pcie_inclusive`: H2D from pinned host memory inside the region
     search_ms, stage_acc = [], {}
     for st in stats:
@@ -511,14 +544,15 @@ def main():
         for k_, v_ in st.items():
             stage_acc[k_] = stage_acc.get(k_, 0.0) + v_
 
-    # one more step with nothing else in flight (outside the timed region): the tile search's launch duration without the
-    # stretching that overlapping launches of the other batch slots cause.  This is the kernel's busy time (it agrees with
-    # the rocprofv3 kernel trace, profiles/), and it is what roofline.achieved / frac are computed from.
-    batches[0].encode_async(); batches[0].wait()
-    isolated_k1_ms = batches[0].stage_ms()['tile_search']
+    if args.full:
+        # one more step with nothing else in flight (outside the timed region): the tile search's launch duration without the
+        # stretching that overlapping launches of the other batch slots cause.  This is the kernel's busy time (it agrees with
+        # the rocprofv3 kernel trace, profiles/), and it is what roofline.achieved / frac are computed from.
+        batches[0].encode_async(); batches[0].wait()
+        isolated_k1_ms = batches[0].stage_ms()['tile_search']
     # every file of every slot of this rank against the oracle's sha256 manifest (tests/golden/bench_manifest.json); no oracle run here
     identity = None
-    if not args.no_identity_check:
+    if args.full and not args.no_identity_check:
         identity = check_identity(batches, image_index, B, {"width": w, "height": h, "speed": args.speed, "quality": args.quality, "bit_depth": args.depth}, args.manifest)
         if dist is not None:
             import torch
@@ -529,9 +563,6 @@ def main():
     if rank == 0:
         total_px = world * B * w * h * args.steps
         value = total_px / 1e6 / elapsed
-        k1_overlapped = sum(search_ms) / len(search_ms)                  # ms per launch inside the timed region (slots overlap)
-        algo = ALGO_BYTES_PER_PX.get(args.depth, 10.0) * B * w * h        # algorithmic HBM-read bytes per launch
-        achieved = algo / (isolated_k1_ms / 1e3) / 1e9
         out = {
             "metric": "MPix/s encoded at speed=4 q=80, 1080p batch; bit-exact vs CPU oracle",
             "value": round(value, 3), "unit": "MPix/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -545,34 +576,38 @@ def main():
                                       else "T = threads unspecified (ravif None): target w*h/min_tile_size^2 uncapped -> %d tiles per image" % (batch.num_tiles() // B),
                        "tools": "partition 4..16, 13 modes + angle deltas, tx-type + tx-size RDO (TX_MODE_SELECT), CfL, Tune::Psychovisual, deblock level search, CDEF search, sgrproj loop restoration (reduced sets)",
                        "parallelism": "images sharded across %d GPU(s), no collective; %d resident batch slot(s) per GPU, each holding different images, driven in rotation (the product's stream path keeps 2 per image shape: allocation time on a file job, see end_to_end; on resident inputs 1 / 2 / 3 / 4 slots measure 495 / 483 / 483 / 498-503 MPix/s, profiles/r06s_pipeline_sweep.txt)" % (world, depth_q)},
-            "roofline": {"bound": "hbm", "kernel": "tile_search_kernel", "achieved": round(achieved, 4), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 8), "frac_of_measured_copy_peak": round(achieved / HBM_COPY_PEAK_GBS, 8),
-                         "traffic": hbm_traffic_bytes("tile_search_kernel", {"images_per_gpu": B, "width": w, "height": h, "speed": args.speed,
-                                                                             "quality": args.quality, "bit_depth": args.depth}),
-                         "traffic_note": "bytes per launch, (2*FETCH_SIZE+WRITE_SIZE) from profiles/hbm_counters.json (separate rocprofv3 --pmc passes); far above the algorithmic bytes: the search's own trial commits, the partition walker's area snapshots, partial-line coefficient writes and register spills (profiles/r06_kernel_resources.txt: 544 B of scratch per lane in the kernel, 80 ... 272 B of it in the block searches since the paired chains of round 6 -- profiles/r06u_k1_traffic_by_variant.txt attributes a third of the traffic to them), served by L2 / Infinity Cache; not what limits the kernel -- see roofline_valu; TCP / TCC request, hit and stall counters of the same run: profiles/r06_final_pmc_summary.json",
-                         "frac_of_step": round(algo / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 8),
-                         "frac_note": "frac = algorithmic bytes / the dominant kernel's launch time; frac_of_step = the same bytes / the driver-timed step (every kernel of the step: the 4 B/px RGB read belongs to the front-end kernel, the 6 B/px plane reads to the tile search)",
-                         "algorithmic_bytes_per_launch": algo, "avg_launch_ms": round(isolated_k1_ms, 3),
-                         "launch_ms_note": "HIP events on the batch stream around the launch, one step with nothing else in flight (= rocprofv3 kernel-trace average)",
-                         "overlapped_launch_ms": round(k1_overlapped, 3)},
-            "roofline_valu": valu_roofline("tile_search_kernel", {"images_per_gpu": B, "width": w, "height": h, "speed": args.speed, "quality": args.quality, "bit_depth": args.depth}, isolated_k1_ms, B * w * h),
-            "ms_per_step_per_rank": {"min": round(min(per_rank) / args.steps * 1e3, 3), "max": round(max(per_rank) / args.steps * 1e3, 3), "ranks": len(per_rank),
-                                     "note": "each rank's own clock from the opening barrier to its last wait; ms_per_step is the MAX over ranks around both barriers"},
-            "stage_ms_per_step": {k_: round(v_ / args.steps, 3) for k_, v_ in stage_acc.items()},
         }
+        if args.full:
+            k1_overlapped = sum(search_ms) / len(search_ms)                  # ms per launch inside the timed region (slots overlap)
+            algo = ALGO_BYTES_PER_PX.get(args.depth, 10.0) * B * w * h        # algorithmic HBM-read bytes per launch
+            achieved = algo / (isolated_k1_ms / 1e3) / 1e9
+            out["roofline"] = {"bound": "hbm", "kernel": "tile_search_kernel", "achieved": round(achieved, 4), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": round(achieved / HBM_PEAK_GBS, 8), "frac_of_measured_copy_peak": round(achieved / HBM_COPY_PEAK_GBS, 8),
+                               "traffic": hbm_traffic_bytes("tile_search_kernel", {"images_per_gpu": B, "width": w, "height": h, "speed": args.speed,
+                                                                                   "quality": args.quality, "bit_depth": args.depth}),
+                               "traffic_note": "bytes per launch, (2*FETCH_SIZE+WRITE_SIZE) from profiles/hbm_counters.json (separate rocprofv3 --pmc passes); far above the algorithmic bytes: the search's own trial commits, the partition walker's area snapshots, partial-line coefficient writes and register spills (profiles/r06_kernel_resources.txt: 544 B of scratch per lane in the kernel, 80 ... 272 B of it in the block searches since the paired chains of round 6 -- profiles/r06u_k1_traffic_by_variant.txt attributes a third of the traffic to them), served by L2 / Infinity Cache; not what limits the kernel -- see roofline_valu; TCP / TCC request, hit and stall counters of the same run: profiles/r06_final_pmc_summary.json",
+                               "frac_of_step": round(algo / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 8),
+                               "frac_note": "frac = algorithmic bytes / the dominant kernel's launch time; frac_of_step = the same bytes / the driver-timed step (every kernel of the step: the 4 B/px RGB read belongs to the front-end kernel, the 6 B/px plane reads to the tile search)",
+                               "algorithmic_bytes_per_launch": algo, "avg_launch_ms": round(isolated_k1_ms, 3),
+                               "launch_ms_note": "HIP events on the batch stream around the launch, one step with nothing else in flight (= rocprofv3 kernel-trace average)",
+                               "overlapped_launch_ms": round(k1_overlapped, 3)}
+            out["roofline_valu"] = valu_roofline("tile_search_kernel", {"images_per_gpu": B, "width": w, "height": h, "speed": args.speed, "quality": args.quality, "bit_depth": args.depth}, isolated_k1_ms, B * w * h)
+        out["ms_per_step_per_rank"] = {"min": round(min(per_rank) / args.steps * 1e3, 3), "max": round(max(per_rank) / args.steps * 1e3, 3), "ranks": len(per_rank),
+                                       "note": "each rank's own clock from the opening barrier to its last wait; ms_per_step is the MAX over ranks around both barriers"}
+        out["stage_ms_per_step"] = {k_: round(v_ / args.steps, 3) for k_, v_ in stage_acc.items()}
         if elapsed_pcie is not None:
             out["value_pcie_inclusive"] = round(total_px / 1e6 / elapsed_pcie, 3)
             out["pcie_note"] = "same loop with every batch's H2D (pinned host -> HBM, %.1f MB per step, async on the slot's stream) inside the timed region" % (B * w * h * 3 / 1e6)
-        if not args.no_identity_check:
+        if identity is not None:
             out["output_identity"] = identity
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(w, h, args.speed, args.quality, args.depth)
             out["cpu_baseline_standin"] = cpu_standin(w, h, args.speed, args.quality, args.depth)
     tiles_per_image = batch.num_tiles() // B
     for bt in batches:
         bt.close()
     if rank == 0:
-        if world == 1 and not args.no_threads_line and B <= MANIFEST_IMAGES:
+        if world == 1 and args.full and not args.no_threads_line and B <= MANIFEST_IMAGES:
             T = host_cores()
             timgs = synth_images(w, h, list(range(B)))
             out["threads_host_cores"] = threads_line(m, T, timgs, B, w, h, args.speed, args.quality, args.depth, device, default_tiles=tiles_per_image)
@@ -586,7 +621,7 @@ def main():
                 single_image_line(m, "config 3: 1 x 4096x4096 RGBA (alpha plane = second frame), speed 4, q80", 4096, 4096, True, 3, 4, 80.0, aq, 10, device),
                 single_image_line(m, "config 5: 1 x 7680x4320 RGB, speed 1, q80, 10-bit (reference asks for <= 7 tiles -> 8)", 7680, 4320, False, 5, 1, 80.0, aq, 10, device, reps=1),
             ]
-        n_e2e = args.end_to_end if args.end_to_end >= 0 else (256 if world == 1 else 0)
+        n_e2e = args.end_to_end if args.end_to_end >= 0 else (256 if world == 1 and args.full else 0)
         if n_e2e:
             out["end_to_end"] = end_to_end(n_e2e, w, h, args.speed, args.quality, args.depth, encode_only_s=n_e2e / float(args.batch) * out["ms_per_step"] / 1e3)
         print(json.dumps(out), flush=True)

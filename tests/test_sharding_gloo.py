@@ -108,7 +108,7 @@ def test_bench_gpus_2_spawns_two_ranks_by_itself(oracle, tmp_path):
     env = dict(emu.env(), MI_BENCH_SHARE_DEVICES='1', MI_SYNTH_CACHE=str(tmp_path / 'cache'))
     env.pop('WORLD_SIZE', None); env.pop('RANK', None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '0', '--batch', str(B), '--width', str(w), '--height', str(h),
-                          '--pipeline', str(slots), '--no-cpu-baseline', '--no-pcie-loop', '--end-to-end', '0', '--manifest', str(mpath)], capture_output=True, text=True, env=env, timeout=900)
+                          '--pipeline', str(slots), '--full', '--no-cpu-baseline', '--no-pcie-loop', '--end-to-end', '0', '--manifest', str(mpath)], capture_output=True, text=True, env=env, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     res = json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][-1])
     assert res['n_gpus'] == 2 and res['ms_per_step_per_rank']['ranks'] == 2
