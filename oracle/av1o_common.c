@@ -110,6 +110,42 @@ size_t re_finish(RangeEnc *e, uint8_t **out) {
   return nb;
 }
 
+/* split_or_horz / split_or_vert of a partition node at the frame edge (spec 5.11.4): the sum of the probabilities, in the row as it stands, of the
+ * partitions that split the block this way */
+uint32_t av1o_partition_edge_psum(const uint16_t *cdf, int has_cols) {
+  #define PP(i) ((uint32_t)((i) > 0 ? cdf[(i) - 1] : 32768) - cdf[i])
+  if (has_cols) return PP(2) + PP(3) + PP(4) + PP(6) + PP(7) + PP(9);      /* VERT SPLIT HORZ_A VERT_A VERT_B VERT_4 */
+  return PP(1) + PP(3) + PP(4) + PP(5) + PP(6) + PP(8);                    /* HORZ SPLIT HORZ_A HORZ_B VERT_A HORZ_4 */
+  #undef PP
+}
+/* Tests only (tests/test_k4_coder.py): the entropy kernel's record stream coded by this file's coder.  Records (tile_entropy.h): bits 31..30 = 00 an adaptive
+ * symbol (bits 0..15 the row's offset in cdf, 16..19 the symbol, 20..23 the alphabet size - 1) or, with bit 29, the partition-edge bool of that row (bit 16 =
+ * has_cols); 01 bounds (bits 0..9 fl >> 6, 10..19 fh >> 6, 20..23 N - 1 - s).  Returns the byte count (bytes in *out, av1o_free), 0 with *out = NULL for a
+ * record it cannot code; cdf ends as the adapted table. */
+size_t av1o_test_code_records(const uint32_t *recs, size_t n, uint16_t *cdf, size_t ncdf, uint8_t **out) {
+  RangeEnc e;
+  re_init(&e);
+  *out = NULL;
+  for (size_t i = 0; i < n; i++) {
+    const uint32_t r = recs[i], off = r & 0xFFFFu;
+    if ((r >> 30) == 0u && (r & 0x20000000u)) {
+      if (off + 10 >= ncdf) { re_free(&e); return 0; }
+      const uint16_t bc[3] = { (uint16_t)av1o_partition_edge_psum(cdf + off, (int)((r >> 16) & 1u)), 0, 0 };
+      re_symbol_noadapt(&e, 1, bc, 2);
+    } else if ((r >> 30) == 0u) {
+      const int s = (int)((r >> 16) & 15u), ns = (int)((r >> 20) & 15u) + 1;
+      if (off + (uint32_t)ns >= ncdf || s >= ns) { re_free(&e); return 0; }
+      re_symbol(&e, s, cdf + off, ns);
+    } else if ((r >> 30) == 1u) {                /* as symbol 1 of a two-entry inverse CDF (fl, fh) with N - 1 - s = nms */
+      const uint16_t b2[2] = { (uint16_t)((r & 1023u) << 6), (uint16_t)(((r >> 10) & 1023u) << 6) };
+      re_symbol_noadapt(&e, 1, b2, (int)((r >> 20) & 15u) + 2);
+    } else { re_free(&e); return 0; }
+  }
+  const size_t nb = re_finish(&e, out);
+  re_free(&e);
+  return nb;
+}
+
 /* ---------------- tx type helpers (spec 5.11.47 get_tx_set, 6.10.19 tables) ---------------- */
 static const uint8_t kInvSet1[7] = { IDTX, DCT_DCT, V_DCT, H_DCT, ADST_ADST, ADST_DCT, DCT_ADST };
 static const uint8_t kInvSet2[5] = { IDTX, DCT_DCT, ADST_ADST, ADST_DCT, DCT_ADST };

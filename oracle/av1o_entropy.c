@@ -268,11 +268,7 @@ static void write_partition(TileW *w, int r, int c, int bs) {
     if (has_rows && has_cols) re_symbol(&w->ec, part, cdf, ns);
     else if (has_rows || has_cols) {
       /* split_or_horz / split_or_vert: bool from gathered partition probabilities, not adapted */
-      #define PP(i) ((uint32_t)((i) > 0 ? cdf[(i) - 1] : 32768) - cdf[i])
-      uint32_t psum;
-      if (has_cols) psum = PP(2) + PP(3) + PP(4) + PP(6) + PP(7) + PP(9);      /* VERT SPLIT HORZ_A VERT_A VERT_B VERT_4 */
-      else psum = PP(1) + PP(3) + PP(4) + PP(5) + PP(6) + PP(8);               /* HORZ SPLIT HORZ_A HORZ_B VERT_A HORZ_4 */
-      #undef PP
+      const uint32_t psum = av1o_partition_edge_psum(cdf, has_cols);
       uint16_t bc[3] = { (uint16_t)psum, 0, 0 };   /* inverse cdf: P(symbol 0) = 32768 - psum */
       part = PARTITION_SPLIT;                        /* this encoder always splits at frame edges */
       re_symbol_noadapt(&w->ec, 1, bc, 2);

@@ -56,6 +56,9 @@ void re_symbol(RangeEnc *e, int s, uint16_t *icdf, int nsyms);    /* encodes + a
 void re_symbol_noadapt(RangeEnc *e, int s, const uint16_t *icdf, int nsyms);
 void re_literal(RangeEnc *e, uint32_t v, int nbits);               /* L(n): equiprobable bits, MSB first */
 size_t re_finish(RangeEnc *e, uint8_t **out);                      /* returns malloc'd bytes */
+uint32_t av1o_partition_edge_psum(const uint16_t *cdf, int has_cols);   /* split_or_horz / split_or_vert: P(the partitions that split this way) */
+/* tests only: a record stream in the entropy kernel's formats (cavif_rs_amd/csrc/tile_entropy.h) through the coder above; cdf [ncdf] in / out */
+size_t av1o_test_code_records(const uint32_t *recs, size_t n, uint16_t *cdf, size_t ncdf, uint8_t **out);
 
 /* ---------------- frame state ---------------- */
 typedef struct Av1oFrame {
