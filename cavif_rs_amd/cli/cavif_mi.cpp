@@ -1,8 +1,9 @@
 // cavif_mi -- the cavif command line (src/main.rs) on top of libmi_avif.so: same flags, path rules and report line;
 // the rayon fan-out over files (src/main.rs:223) becomes mi_ravif_encode_batch (one host thread per MI355X).
 //   cavif_mi [-Q n] [-s n] [-j n] [-f] [-o path] [-q] [--dirty-alpha] [--color ycbcr|rgb] [--depth 8|10|auto] IMAGES...
-// Differences, deliberate: PNG input only (the reference also reads JPEG through load_image), `--devices a,b,..`
-// selects HIP devices (default: all), and there is no CPU fallback -- without a GPU every file fails loudly.
+// Input: PNG and baseline / progressive 8-bit JPEG, told apart by their first bytes as load_image does (mi_image_decode_rgba; a JPEG's Huffman decoding
+// runs in the loader thread, the rest of its decoding on the GPU).  Differences, deliberate: `--devices a,b,..` selects HIP devices (default: all), and
+// there is no CPU fallback -- without a GPU every file fails loudly.
 #include <sched.h>
 #include <sys/stat.h>
 #include <cerrno>
@@ -202,16 +203,18 @@ int main(int argc, char **argv) {
   // load + decide output paths (process(), :169-200); failures are collected per file and reported at the end
   struct Job { std::string in_name, out_path; bool out_stdio = false; uint8_t *rgba = nullptr; uint32_t w = 0, h = 0; std::string error; };
   std::vector<Job> jobs(files.size());
-  // the reference loads inside files.into_par_iter() (src/main.rs:223): file reads + PNG decodes fan out over the host cores
-  auto load = [&](size_t i) {
+  // the reference loads inside files.into_par_iter() (src/main.rs:223): file reads + PNG / JPEG entropy decodes fan out over the host cores; `dev` is the
+  // HIP device that finishes a JPEG (dequantisation, IDCT, upsampling, colour)
+  auto load = [&](size_t i, int dev) {
     Job &j = jobs[i]; const Input &in = files[i];
     j.in_name = in.is_stdio ? "stdin" : in.path;
     std::vector<uint8_t> data;
     if (in.is_stdio) { if (!read_all(stdin, data)) j.error = "Unable to read stdin"; }
     else { FILE *f = fopen(in.path.c_str(), "rb"); if (!f || !read_all(f, data)) j.error = "Unable to read input image " + in.path + ": " + strerror(errno); if (f) fclose(f); }
     if (j.error.empty()) {
-      const int st = mi_png_decode_rgba(data.data(), data.size(), &j.rgba, &j.w, &j.h);
-      if (st) j.error = st == MI_UNSUPPORTED ? "unsupported image format (this build reads PNG)" : "corrupt PNG data";
+      const int st = mi_image_decode_rgba(data.data(), data.size(), dev, &j.rgba, &j.w, &j.h);
+      if (st) j.error = st == MI_UNSUPPORTED ? "unsupported image format (this build reads PNG and baseline/progressive 8-bit JPEG)" :
+                        st == MI_NO_DEVICE ? "no HIP device (this encoder has no CPU fallback)" : "corrupt image data";
     }
     if (!have_output) { if (in.is_stdio) j.out_stdio = true; else j.out_path = with_extension_avif(in.path); }
     else if (output_stdio) j.out_stdio = true;
@@ -234,15 +237,19 @@ int main(int argc, char **argv) {
   size_t released = 0;                                              // guarded by mu: images the encoder is done reading (or that failed to load)
   std::atomic<size_t> next{ 0 };
   std::vector<std::thread> pool;
-  auto loader = [&] {
+  // loader t decodes its JPEGs on device devices[t % ndev]; without --devices that is device t % (count of visible devices) once the count is known and device 0
+  // until then (the loaders do not wait for the runtime to come up)
+  std::atomic<int> ndev_visible{ 0 };
+  auto loader = [&](size_t t) {
     for (size_t i; (i = next.fetch_add(1)) < files.size();) {
       { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return i < released + window; }); }
-      load(i);
+      const int nv = ndev_visible.load();
+      load(i, !devices.empty() ? devices[t % devices.size()] : nv > 0 ? (int)(t % (size_t)nv) : 0);
       { std::lock_guard<std::mutex> lk(mu); loaded[i] = 1; if (!jobs[i].error.empty()) released++; }
       cv.notify_all();
     }
   };
-  for (size_t t = 0; t < nw; t++) pool.emplace_back(loader);
+  for (size_t t = 0; t < nw; t++) pool.emplace_back(loader, t);
   struct Ctx { std::vector<Job> *jobs; std::mutex *mu; std::condition_variable *cv; std::vector<char> *loaded; size_t *released; } ctx{ &jobs, &mu, &cv, &loaded, &released };
   auto fetch = [](void *user, size_t i, mi_image_desc *d) -> int {
     Ctx *c = (Ctx *)user;
@@ -262,9 +269,10 @@ int main(int argc, char **argv) {
   std::vector<mi_encoded_image> enc_out(jobs.size()); std::vector<int> status(jobs.size(), MI_OK);
   if (timing) fprintf(stderr, "[timing] setup %.3f s (tile target bounded by %d threads)\n", now_s() - t_start, enc.threads);
   const size_t ndev_used = devices.empty() ? (size_t)std::max(1, mi_device_count()) : devices.size();      // brings the HIP runtime up while the loaders run
+  if (devices.empty()) ndev_visible = (int)ndev_used;
   const size_t nw_all = std::min<size_t>(files.size(), std::min<size_t>(loaders_cap, getenv("CAVIF_MI_LOADERS") ? nw : loaders_per_device * (ndev_used + 1)));
   { std::lock_guard<std::mutex> lk(mu); window = 4 * 32 * ndev_used + nw_all; }
-  for (size_t t = nw; t < nw_all; t++) pool.emplace_back(loader);
+  for (size_t t = nw; t < nw_all; t++) pool.emplace_back(loader, t);
   cv.notify_all();
   if (timing) fprintf(stderr, "[timing] HIP runtime up %.3f s\n", now_s() - t_start);
   const int rc_all = mi_ravif_encode_stream(&enc, jobs.size(), fetch, release, &ctx, enc_out.data(), status.data(), devices.empty() ? nullptr : devices.data(), (int)devices.size());

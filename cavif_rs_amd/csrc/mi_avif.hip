@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <mutex>
+#include <condition_variable>
 #include <memory>
 #include <thread>
 #include <atomic>
@@ -15,6 +16,8 @@
 #include <algorithm>
 #include "host_av1.h"
 #include "png_reader.h"
+#include "jpeg_reader.h"
+#include "dev_jpeg.h"
 #include "tile_search.h"
 #include "tile_entropy.h"
 #include "loopfilter.h"
@@ -886,10 +889,73 @@ static void pool_release(mi_batch *b) {
   }
   for (mi_batch *x : evict) mi_batch_destroy(x);
 }
+
+// ---- JPEG input: decode contexts ----
+// mi_jpeg_decode_rgba is called from many loader threads at once (the command line runs a few dozen).  Each call borrows a context -- its own stream, pinned
+// staging and device buffers, all grown on demand and never shrunk -- from a per-device free list and hands it back: no hipMalloc per call in the steady
+// state.  At most MI_JPEG_CTX_MAX contexts exist per device: a caller that finds them all busy waits for one (the device part of a decode is a fraction of
+// the call, the Huffman decoding before it needs no context), because allocating and freeing pinned and device memory per call stalls every other stream of
+// the process (measured: profiles/jpeg_input.md).  mi_release_cached() frees the idle ones.
+struct JpegCtx {
+  int device = 0; hipStream_t stream = nullptr;
+  uint8_t *h_in = nullptr, *d_in = nullptr, *d_planes = nullptr, *d_rgba = nullptr, *h_rgba = nullptr;
+  size_t h_in_cap = 0, d_in_cap = 0, d_planes_cap = 0, d_rgba_cap = 0, h_rgba_cap = 0;
+};
+static constexpr int MI_JPEG_CTX_MAX = 8;
+static std::mutex g_jpeg_mu;
+static std::condition_variable g_jpeg_cv;
+static std::vector<JpegCtx *> g_jpeg_free;                    // never destroyed at process exit (the runtime may be gone by then)
+static std::vector<int> g_jpeg_live;                          // contexts in existence per device, idle or borrowed
+static void jpeg_ctx_destroy(JpegCtx *c) {
+  (void)hipSetDevice(c->device);
+  if (c->h_in) (void)hipHostFree(c->h_in);
+  if (c->h_rgba) (void)hipHostFree(c->h_rgba);
+  if (c->d_in) (void)hipFree(c->d_in);
+  if (c->d_planes) (void)hipFree(c->d_planes);
+  if (c->d_rgba) (void)hipFree(c->d_rgba);
+  if (c->stream) (void)hipStreamDestroy(c->stream);
+  delete c;
+}
+static JpegCtx *jpeg_ctx_acquire(int device) {
+  {
+    std::unique_lock<std::mutex> lk(g_jpeg_mu);
+    if ((size_t)device >= g_jpeg_live.size()) g_jpeg_live.resize((size_t)device + 1, 0);
+    for (;;) {
+      for (size_t i = g_jpeg_free.size(); i-- > 0;) if (g_jpeg_free[i]->device == device) { JpegCtx *c = g_jpeg_free[i]; g_jpeg_free.erase(g_jpeg_free.begin() + i); return c; }
+      if (g_jpeg_live[device] < MI_JPEG_CTX_MAX) { g_jpeg_live[device]++; break; }
+      g_jpeg_cv.wait(lk);
+    }
+  }
+  JpegCtx *c = new JpegCtx; c->device = device;
+  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
+    delete c;
+    { std::lock_guard<std::mutex> lk(g_jpeg_mu); g_jpeg_live[device]--; }
+    g_jpeg_cv.notify_one();
+    return nullptr;
+  }
+  return c;
+}
+static void jpeg_ctx_release(JpegCtx *c) {
+  { std::lock_guard<std::mutex> lk(g_jpeg_mu); g_jpeg_free.push_back(c); }
+  g_jpeg_cv.notify_one();
+}
+// the buffer holds at least `need` bytes afterwards (the context is idle whenever this runs: every public call ends with a stream sync)
+static bool jpeg_grow(uint8_t *&p, size_t &cap, size_t need, bool pinned) {
+  if (need <= cap) return true;
+  if (p) { if (pinned) (void)hipHostFree(p); else (void)hipFree(p); p = nullptr; cap = 0; }
+  need = (need + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
+  if ((pinned ? hipHostMalloc(&p, need) : hipMalloc(&p, need)) != hipSuccess) { p = nullptr; return false; }
+  cap = need; return true;
+}
+
 void mi_release_cached(void) {
   std::vector<std::pair<PoolKey, mi_batch *>> all;
   { std::lock_guard<std::mutex> lk(g_pool_mu); all.swap(g_pool); }
   for (auto &x : all) mi_batch_destroy(x.second);
+  std::vector<JpegCtx *> ctxs;
+  { std::lock_guard<std::mutex> lk(g_jpeg_mu); ctxs.swap(g_jpeg_free); for (JpegCtx *c : ctxs) g_jpeg_live[c->device]--; }
+  g_jpeg_cv.notify_all();
+  for (JpegCtx *c : ctxs) jpeg_ctx_destroy(c);
 }
 
 static int encode_one(const mi_ravif_encoder *e, const uint8_t *px, int channels, uint32_t w, uint32_t h, size_t stride_px, mi_encoded_image *out) {
@@ -916,6 +982,91 @@ int mi_png_decode_rgba(const uint8_t *data, size_t len, uint8_t **rgba, uint32_t
     memcpy(*rgba, px.data(), px.size());
     return MI_OK;
   } catch (const std::exception &) { return MI_ENCODING_ERROR; }
+}
+
+// The seam of the JPEG path: coefficients of one parsed file -> RGBA8 rows of stride_px pixels at a DEVICE pointer, on `stream`.  Pinned staging of the
+// quantisation tables + coefficients, one H2D, the two kernels of dev_jpeg.h, no sync (probe builds with MI_AVIF_TIMING sync between the steps to time
+// them).  Its own function so that a caller can point d_rgba at memory that is consumed on the device (a batch's HBM input slot) instead of a buffer
+// that goes back to the host.  The caller has made `device` current and owns ctx until the stream has drained.
+static int jpeg_decode_to_device(const JpegCoeffs &jc, int device, uint8_t *d_rgba, size_t stride_px, hipStream_t stream, JpegCtx &ctx, double *step_ms) {
+  (void)device;
+  JpegDevGeom g; memset(&g, 0, sizeof(g));
+  g.w = jc.w; g.h = jc.h; g.ncomp = (uint32_t)jc.ncomp; g.color = (uint32_t)jc.color; g.nblocks = (uint32_t)jc.nblocks;
+  for (int c = 0; c < 3; c++) {
+    g.first_block[c] = g.nblocks;
+    if (c >= jc.ncomp) continue;
+    const JpegComp &k = jc.comp[c];
+    g.first_block[c] = (uint32_t)k.first_block; g.plane_off[c] = (unsigned long long)k.first_block * 64;
+    g.bw[c] = k.bw; g.bh[c] = k.bh; g.cw[c] = k.cw; g.ch[c] = k.ch;
+  }
+  g.hr = jc.ncomp == 3 ? (uint32_t)(jc.comp[0].h / jc.comp[1].h) : 1; g.vr = jc.ncomp == 3 ? (uint32_t)(jc.comp[0].v / jc.comp[1].v) : 1;
+  const size_t quant_bytes = 3 * 64 * sizeof(uint16_t), in_bytes = quant_bytes + jc.nblocks * 64 * sizeof(int16_t);
+  if (!jpeg_grow(ctx.h_in, ctx.h_in_cap, in_bytes, true) || !jpeg_grow(ctx.d_in, ctx.d_in_cap, in_bytes, false) || !jpeg_grow(ctx.d_planes, ctx.d_planes_cap, jc.nblocks * 64, false)) return MI_ENCODING_ERROR;
+  const auto t0 = std::chrono::steady_clock::now();
+  memset(ctx.h_in, 0, quant_bytes);
+  for (int c = 0; c < jc.ncomp; c++) memcpy(ctx.h_in + c * 64 * sizeof(uint16_t), jc.comp[c].quant, 64 * sizeof(uint16_t));
+  memcpy(ctx.h_in + quant_bytes, jc.coef.data(), jc.nblocks * 64 * sizeof(int16_t));
+  auto lap = [&](int i) { if (step_ms) { (void)hipStreamSynchronize(stream); step_ms[i] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); } };
+  HIP_OK(hipMemcpyAsync(ctx.d_in, ctx.h_in, in_bytes, hipMemcpyHostToDevice, stream));
+  lap(0);
+  hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((jc.nblocks + MI_JPEG_IDCT_BLOCKS - 1) / MI_JPEG_IDCT_BLOCKS)), dim3(256), 0, stream,
+                     (const int16_t *)(ctx.d_in + quant_bytes), (const uint16_t *)ctx.d_in, g, ctx.d_planes);
+  const int vec16 = (stride_px % 4 == 0 && ((uintptr_t)d_rgba & 15) == 0) ? 1 : 0;
+  hipLaunchKernelGGL(jpeg_rgba_kernel, dim3(((jc.w + 3) / 4 + 63) / 64, jc.h), dim3(64), 0, stream, (const uint8_t *)ctx.d_planes, g, d_rgba, stride_px, vec16);
+  HIP_OK(hipGetLastError());
+  lap(1);
+  return MI_OK;
+}
+
+static int jpeg_decode_with(JpegCtx &ctx, const JpegCoeffs &jc, uint8_t *dst, double *step_ms) {
+  const size_t out_bytes = (size_t)jc.w * jc.h * 4;
+  if (!jpeg_grow(ctx.d_rgba, ctx.d_rgba_cap, out_bytes, false) || !jpeg_grow(ctx.h_rgba, ctx.h_rgba_cap, out_bytes, true)) return MI_ENCODING_ERROR;
+  const int st = jpeg_decode_to_device(jc, ctx.device, ctx.d_rgba, jc.w, ctx.stream, ctx, step_ms);
+  if (st) { (void)hipStreamSynchronize(ctx.stream); return st; }
+  const auto t0 = std::chrono::steady_clock::now();
+  HIP_OK(hipMemcpyAsync(ctx.h_rgba, ctx.d_rgba, out_bytes, hipMemcpyDeviceToHost, ctx.stream));
+  HIP_OK(hipStreamSynchronize(ctx.stream));
+  if (step_ms) step_ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  memcpy(dst, ctx.h_rgba, out_bytes);
+  if (step_ms) step_ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - step_ms[2];
+  return MI_OK;
+}
+
+// JPEG -> RGBA8 (load_image::load_data + load_rgba, src/main.rs:255-283, for JPEG bytes): Huffman decoding on the host, everything after it on the device
+int mi_jpeg_decode_rgba(const uint8_t *data, size_t len, int device, uint8_t **rgba, uint32_t *w, uint32_t *h) {
+  if (!data || !rgba || !w || !h) return MI_INVALID_ARGUMENT;
+  try {                                                       // nothing may unwind through the C ABI
+    const bool timing = mi_timing_enabled();
+    const auto t0 = std::chrono::steady_clock::now();
+    JpegCoeffs jc;
+    int st = jpeg_read_coeffs(data, len, jc);                 // header and stream errors come first: they need no device
+    if (st) return st;
+    const double parse_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (device < 0) return MI_INVALID_ARGUMENT;
+    if (mi_device_count() <= device) return MI_NO_DEVICE;     // no CPU fallback
+    if (hipSetDevice(device) != hipSuccess) return MI_NO_DEVICE;
+    uint8_t *px = (uint8_t *)malloc((size_t)jc.w * jc.h * 4);
+    if (!px) return MI_ENCODING_ERROR;
+    JpegCtx *ctx = jpeg_ctx_acquire(device);
+    if (!ctx) { free(px); return MI_ENCODING_ERROR; }
+    double step_ms[4] = { 0, 0, 0, 0 };
+    st = jpeg_decode_with(*ctx, jc, px, timing ? step_ms : nullptr);
+    jpeg_ctx_release(ctx);
+    if (st) { free(px); return st; }
+    if (timing) fprintf(stderr, "[jpeg] %ux%u %zu bytes: parse+entropy %.3f ms, staging+H2D %.3f ms, kernels %.3f ms, D2H %.3f ms, copy-out %.3f ms\n", jc.w, jc.h, len, parse_ms,
+                        step_ms[0], step_ms[1] - step_ms[0], step_ms[2], step_ms[3]);
+    *rgba = px; *w = jc.w; *h = jc.h;
+    return MI_OK;
+  } catch (const std::exception &) { return MI_ENCODING_ERROR; }
+}
+
+// load_rgba (src/main.rs:255-283) for the formats this library reads, told apart by their first bytes as load_image does
+int mi_image_decode_rgba(const uint8_t *data, size_t len, int device, uint8_t **rgba, uint32_t *w, uint32_t *h) {
+  if (!data || !rgba || !w || !h) return MI_INVALID_ARGUMENT;
+  static const uint8_t png_sig[8] = { 0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A };
+  if (len >= 8 && !memcmp(data, png_sig, 8)) return mi_png_decode_rgba(data, len, rgba, w, h);
+  if (len >= 2 && data[0] == 0xFF && data[1] == 0xD8) return mi_jpeg_decode_rgba(data, len, device, rgba, w, h);
+  return MI_UNSUPPORTED;
 }
 
 // The reference's files.into_par_iter() (src/main.rs:223) over the GPUs of one node: images are independent, so a host

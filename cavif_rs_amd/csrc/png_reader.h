@@ -1,8 +1,8 @@
 // png_reader.h -- PNG -> RGBA8, the input side of the cavif CLI (reference: load_rgba, src/main.rs:265-283, which maps
 // every load_image pixel kind to RGBA8: RGB -> alpha 255, 16-bit -> high byte, gray -> r=g=b).
 // Host C++ over zlib's inflate; written from the PNG specification (chunks IHDR / PLTE / tRNS / IDAT / IEND, the five
-// scanline filters, Adam7).  JPEG input (the reference also accepts it through load_image) is not handled: callers get
-// MI_UNSUPPORTED.
+// scanline filters, Adam7).  JPEG bytes get MI_UNSUPPORTED here: the reference's other input format has its own reader
+// (jpeg_reader.h + dev_jpeg.h), and mi_image_decode_rgba picks between the two.
 #pragma once
 #include <algorithm>
 #include <zlib.h>

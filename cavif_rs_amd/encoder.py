@@ -91,6 +91,8 @@ def load_library():
                                     C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.POINTER(C.c_uint8))]
     L.mi_avif_serialize.restype = C.c_size_t
     L.mi_free.argtypes = [C.c_void_p]
+    for fn in (L.mi_jpeg_decode_rgba, L.mi_image_decode_rgba):
+        fn.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     _LIB = L
     return L
 
@@ -118,6 +120,28 @@ def rgb_to_ycbcr(rgb, depth):
     o = (C.c_uint16 * 3)()
     load_library().mi_rgb_to_ycbcr(a, depth, o)
     return tuple(o)
+
+
+def _decode(fn, data, device):
+    data = bytes(data)
+    out = C.POINTER(C.c_uint8)()
+    w, h = C.c_uint32(), C.c_uint32()
+    st = fn(data, len(data), int(device), C.byref(out), C.byref(w), C.byref(h))
+    if st:
+        raise AvifError(st)
+    a = np.ctypeslib.as_array(out, shape=(h.value, w.value, 4)).copy()
+    load_library().mi_free(out)
+    return a
+
+
+def decode_jpeg(data, device=0):
+    """mi_jpeg_decode_rgba: JPEG bytes -> uint8 array (h, w, 4); Huffman decoding on the host, the rest on HIP device `device`."""
+    return _decode(load_library().mi_jpeg_decode_rgba, data, device)
+
+
+def load_rgba(data, device=0):
+    """load_rgba (src/main.rs:255-283) for the formats this library reads: PNG (host) or JPEG (device `device`) bytes -> uint8 array (h, w, 4)."""
+    return _decode(load_library().mi_image_decode_rgba, data, device)
 
 
 class EncodedImage:

@@ -106,12 +106,24 @@ int  mi_ravif_encode_stream(const mi_ravif_encoder *e, size_t n, mi_fetch_fn fet
 
 /* The one-call entry points above (mi_ravif_encode_rgba / _rgb / _batch / _stream) keep their device arenas and pinned staging in
  * a process-wide pool keyed by (device, shape, settings), so a loop of calls with the same settings pays the allocation once
- * (what a long-lived rav1e thread pool is to the reference).  At most 12 objects / 96 GB are retained; this frees them now. */
+ * (what a long-lived rav1e thread pool is to the reference).  At most 12 objects / 96 GB are retained; this frees them now, and the idle JPEG
+ * decode contexts (at most 8 exist per device) with them. */
 void mi_release_cached(void);
 
 /* PNG -> RGBA8 as cavif's load_rgba does (src/main.rs:265-283: RGB gets alpha 255, 16-bit samples keep their high byte, gray is
  * replicated); all colour types, bit depths, tRNS and Adam7.  Host code over zlib.  *rgba is malloc'd (mi_free), w*h*4 bytes. */
 int  mi_png_decode_rgba(const uint8_t *data, size_t len, uint8_t **rgba, uint32_t *w, uint32_t *h);
+/* JPEG -> RGBA8, the other format cavif's loader takes (load_image::load_data, src/main.rs:258; load_rgba :265-283: alpha 255, gray replicated).
+ * Baseline / extended sequential and progressive Huffman files, 8 bit, one component or three at 4:4:4 / 4:2:2 / 4:2:0; arithmetic coding, lossless,
+ * hierarchical, 12-bit, four-component files and other sampling ratios are MI_UNSUPPORTED, broken or incomplete streams MI_ENCODING_ERROR.  Huffman
+ * decoding runs on the host, dequantisation + IDCT + chroma upsampling + YCbCr->RGB on HIP device `device`; the pixels are libjpeg's (integer "islow"
+ * IDCT, "fancy" upsampling), embedded ICC profiles and EXIF orientation are ignored.  Data errors are reported before the device is looked at, then
+ * MI_NO_DEVICE when there is no such device: no CPU fallback.  *rgba is malloc'd (mi_free), w*h*4 bytes.  Calls from many threads share a pool of at most 8
+ * decode contexts per device (stream + staging; a call that finds all of them busy waits for one) that mi_release_cached() frees. */
+int  mi_jpeg_decode_rgba(const uint8_t *data, size_t len, int device, uint8_t **rgba, uint32_t *w, uint32_t *h);
+/* load_rgba (src/main.rs:255-283) over both: the first bytes decide -- PNG -> mi_png_decode_rgba (host, `device` unused), FF D8 -> mi_jpeg_decode_rgba,
+ * anything else MI_UNSUPPORTED. */
+int  mi_image_decode_rgba(const uint8_t *data, size_t len, int device, uint8_t **rgba, uint32_t *w, uint32_t *h);
 
 /* ---- batch: the data-parallel path (src/main.rs:223 files.into_par_iter()); images resident in HBM ---- */
 typedef struct mi_batch mi_batch;

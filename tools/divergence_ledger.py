@@ -14,6 +14,9 @@ VARIANTS = [('shipped (HIP == oracle)', {}),
             ('CLOSED in round 6, switched BACK: every sub-block of a split transform picks its own tx type (rounds 1-5)', {'AV1O_ABL_SUB_TXTYPE': '1'}),
             ('CLOSED in round 6, switched BACK: 4x4-Hadamard SATD for every block size (rounds 1-5)', {'AV1O_ABL_SATD4': '1'}),
             ('both closed ones switched back = the round-5 encoder', {'AV1O_ABL_SUB_TXTYPE': '1', 'AV1O_ABL_SATD4': '1'})]
+# differences that no oracle switch can toggle: listed with the table so that one place names them all
+NOTES = ['JPEG input: pixels are libjpeg\'s (integer islow IDCT, fancy upsampling, 16.16 YCbCr->RGB; DESIGN.md section 5a), pinned against Pillow; the reference\'s decoder '
+         '(load_image) may differ by a rounding step per sample, and embedded ICC profiles (applied there through lcms2) and EXIF orientation are ignored here.']
 def run(env):
     code = (
         "import sys, json, io, numpy as np\nsys.path.insert(0, %r)\n"
@@ -44,5 +47,7 @@ if __name__ == '__main__':
         mse = sum(s[1] for s in r['sets']) / len(r['sets'])
         print('| %s%s | %d | %d / %d | %d / %d | %d (%+.2f %%) | %.2f |' % (name, (' `' + ' '.join(k + '=1' for k in env) + '`') if env else '', r['encode8_opaque'], r['encode8_with_alpha'][0], r['encode8_with_alpha'][1],
                                                                        r['encode8_cleans_alpha'][0], r['encode8_cleans_alpha'][1], tot, 100.0 * (tot - tot0) / tot0, mse))
+    for n in NOTES:
+        print('\n* ' + n)
     if len(sys.argv) > 2 and sys.argv[1] == '--json':
         json.dump({name: r for name, _, r in res}, open(sys.argv[2], 'w'), indent=1)
