@@ -9,11 +9,12 @@
 
 // rav1e rdo_tx_size_type searches tx_depth 0..2 (rdo_tx_depth = 2) when rdo_tx_decision is on; 1 = one level only (oracle AV1O_TX_DEPTH_MAX)
 #define MI_TX_DEPTH_MAX 2
-// Block / transform size codes 5 (4x8) and 6 (8x4) appear in m_bsize / m_txsize: PARTITION_HORZ / PARTITION_VERT of 8x8 nodes (dev_rect.h).
 #define MI_MAX_TILE_COLS 64
 #define MI_MAX_TILE_ROWS 64
 
 enum { BS_4 = 0, BS_8 = 1, BS_16 = 2, BS_32 = 3, BS_64 = 4 };
+// Block / transform size codes 5 (4x8) and 6 (8x4) appear in m_bsize / m_txsize: PARTITION_HORZ / PARTITION_VERT of 8x8 nodes (dev_rect.h).
+enum { BS_4X8 = 5, BS_8X4 = 6 };
 enum { DC_PRED = 0, V_PRED, H_PRED, D45_PRED, D135_PRED, D113_PRED, D157_PRED, D203_PRED, D67_PRED,
        SMOOTH_PRED, SMOOTH_V_PRED, SMOOTH_H_PRED, PAETH_PRED, UV_CFL_PRED };
 enum { DCT_DCT = 0, ADST_DCT, DCT_ADST, ADST_ADST, FLIPADST_DCT, DCT_FLIPADST, FLIPADST_FLIPADST,
@@ -107,6 +108,8 @@ __device__ __forceinline__ int imax_(int a, int b) { return a > b ? a : b; }
 __device__ __forceinline__ int iclamp_(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __device__ __forceinline__ int iabs_(int a) { return a < 0 ? -a : a; }
 __device__ __forceinline__ int round2_(int x, int n) { return n == 0 ? x : (x + (1 << (n - 1))) >> n; }
+__device__ __forceinline__ int dim_wl(int code) { return code <= 4 ? 2 + code : (code == 5 ? 2 : 3); }   // log2 width / height in samples of a block / transform size code
+__device__ __forceinline__ int dim_hl(int code) { return code <= 4 ? 2 + code : (code == 5 ? 3 : 2); }
 
 // run-time indexed small tables without a memory lookup: 4-bit / 8-bit entries packed into a 64-bit immediate
 __device__ __forceinline__ int lut4(unsigned long long tab, int i) { return (int)((tab >> (4 * i)) & 15); }
@@ -262,6 +265,15 @@ __device__ __forceinline__ int scan_pos(const LDS uint16_t *ls, int n, int cls, 
   if (cls == TXC_VERT) return i;                       // mrow scan
   const int c = i / n, r = i - c * n; return r * n + c; // mcol scan
 }
+// the 2:1 transforms of 8x4 / 4x8 blocks (dev_rect.h): spec Default_Scan_4x8 (tall: each anti-diagonal from its top-right end) / Default_Scan_8x4 (wide: from its bottom-left end)
+static __device__ const uint8_t rect_scan_4x8[32] = { 0, 1, 4, 2, 5, 8, 3, 6, 9, 12, 7, 10, 13, 16, 11, 14, 17, 20, 15, 18, 21, 24, 19, 22, 25, 28, 23, 26, 29, 27, 30, 31 };
+static __device__ const uint8_t rect_scan_8x4[32] = { 0, 8, 1, 16, 9, 2, 24, 17, 10, 3, 25, 18, 11, 4, 26, 19, 12, 5, 27, 20, 13, 6, 28, 21, 14, 7, 29, 22, 15, 30, 23, 31 };
+__device__ __forceinline__ int rect_scan_pos(int wl, int hl, int cls, int i) {
+  const int w = 1 << wl, h = 1 << hl;
+  if (cls == TXC_2D) return hl > wl ? rect_scan_4x8[i] : rect_scan_8x4[i];
+  if (cls == TXC_VERT) return i;                              // mrow
+  const int c = i / h, r = i - c * h; return r * w + c;       // mcol
+}
 // intra tx-type CDF row for luma; returns -1 when the type is not signalled.  `reduced`: the frame's reduced_tx_set switch (a constant in the tile-search kernels
 // instantiated for a fixed tool set, tile_search.h Tools)
 template <typename FP> __device__ __forceinline__ int intra_tx_cdf_r(FP f, bool reduced, int txs, int ymode, int *nsyms, int *set_out) {
@@ -272,3 +284,11 @@ template <typename FP> __device__ __forceinline__ int intra_tx_cdf_r(FP f, bool 
   *nsyms = 5; return CDF_INTRA_TX2 + (txs * 13 + ymode) * CDF_INTRA_TX2_STRIDE;
 }
 template <typename FP> __device__ __forceinline__ int intra_tx_cdf(FP f, int txs, int ymode, int *nsyms, int *set_out) { return intra_tx_cdf_r(f, f->reduced_tx_set != 0, txs, ymode, nsyms, set_out); }
+// tx set / CDF row of a 2:1 transform (oracle av1o_tx_set / av1o_intra_tx_cdf): the larger dimension (8) bounds the set, the smaller (4) indexes the CDFs
+template <typename FP> __device__ __forceinline__ int rect_tx_cdf(FP f, bool reduced, int ymode, int *nsyms, int *set_out) {
+  const int set = reduced ? 2 : 1;
+  *set_out = set;
+  if (f->base_q_idx == 0) { *nsyms = 0; return -1; }
+  if (set == 1) { *nsyms = 7; return CDF_INTRA_TX1 + ymode * CDF_INTRA_TX1_STRIDE; }
+  *nsyms = 5; return CDF_INTRA_TX2 + ymode * CDF_INTRA_TX2_STRIDE;
+}

@@ -34,6 +34,32 @@ template <typename FP, typename TP> __device__ inline void txb_ctx_dev(FP f, TP 
     *skip_ctx = 7 + (any_a != 0) + (any_l != 0) + (bs > txs ? 3 : 0);
   }
 }
+// all_zero / dc_sign contexts of a transform block of w4 x h4 cells inside a block (txb_ctx_dev with both dimensions); `whole`: the transform is the block
+template <typename FP, typename TP> __device__ inline void txb_ctx_wh(FP f, TP t, int plane, int r4, int c4, int w4, int h4, int whole, int *skip_ctx, int *dc_ctx) {
+  const int ms = f->mi_stride;
+  int top = 0, left = 0, dcs = 0, any_a = 0, any_l = 0;
+  const int k = LANE;
+  if (k < imax_(w4, h4)) {
+    const bool ha = k < w4 && r4 - 1 >= t->mi_row_start && c4 + k < f->mi_cols, hl = k < h4 && c4 - 1 >= t->mi_col_start && r4 + k < f->mi_rows;
+    const int ia = ha ? (r4 - 1) * ms + c4 + k : r4 * ms + c4, il = hl ? (r4 + k) * ms + c4 - 1 : r4 * ms + c4;
+    const int la = f->m_lvl[plane][ia], da = f->m_dc[plane][ia], ll = f->m_lvl[plane][il], dl = f->m_dc[plane][il];
+    if (ha) { top = la; any_a = la | da; dcs += da == 1 ? -1 : (da == 2 ? 1 : 0); }
+    if (hl) { left = ll; any_l = ll | dl; dcs += dl == 1 ? -1 : (dl == 2 ? 1 : 0); }
+  }
+  top = wave_max_i32(top); left = wave_max_i32(left); dcs = wave_sum_i32(dcs);
+  any_a = wave_or_i32(any_a); any_l = wave_or_i32(any_l);
+  *dc_ctx = dcs < 0 ? 1 : (dcs > 0 ? 2 : 0);
+  if (plane == 0) {
+    int ctx;
+    if (whole) ctx = 0;
+    else if (top == 0 && left == 0) ctx = 1;
+    else if (top == 0 || left == 0) ctx = 2 + (imax_(top, left) > 3);
+    else if (imax_(top, left) <= 3) ctx = 4;
+    else if (imin_(top, left) <= 3) ctx = 5;
+    else ctx = 6;
+    *skip_ctx = ctx;
+  } else *skip_ctx = 7 + (any_a != 0) + (any_l != 0) + (whole ? 0 : 3);
+}
 
 __device__ __forceinline__ int eob_to_pt(int eob) { return eob < 3 ? eob : (32 - __clz(eob - 1) + 1); }
 __device__ __forceinline__ int eob_pt_cdf(int eob_multi, int pt, int cls) {

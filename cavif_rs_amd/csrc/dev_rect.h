@@ -3,19 +3,6 @@
 // two halves of the tx-size trial and the chroma candidates run four per wavefront (eval_group_wh, one candidate per 16-lane row) like the square
 // small blocks; the SATD stage and the full mode set of speed <= 1 keep one candidate per wavefront.
 #pragma once
-enum { BS_4X8 = 5, BS_8X4 = 6 };
-__device__ __forceinline__ int dim_wl(int code) { return code <= 4 ? 2 + code : (code == 5 ? 2 : 3); }   // log2 width / height in samples
-__device__ __forceinline__ int dim_hl(int code) { return code <= 4 ? 2 + code : (code == 5 ? 3 : 2); }
-
-// spec Default_Scan_4x8 (tall: each anti-diagonal from its top-right end) / Default_Scan_8x4 (wide: from its bottom-left end)
-static __device__ const uint8_t rect_scan_4x8[32] = { 0, 1, 4, 2, 5, 8, 3, 6, 9, 12, 7, 10, 13, 16, 11, 14, 17, 20, 15, 18, 21, 24, 19, 22, 25, 28, 23, 26, 29, 27, 30, 31 };
-static __device__ const uint8_t rect_scan_8x4[32] = { 0, 8, 1, 16, 9, 2, 24, 17, 10, 3, 25, 18, 11, 4, 26, 19, 12, 5, 27, 20, 13, 6, 28, 21, 14, 7, 29, 22, 15, 30, 23, 31 };
-__device__ __forceinline__ int rect_scan_pos(int wl, int hl, int cls, int i) {
-  const int w = 1 << wl, h = 1 << hl;
-  if (cls == TXC_2D) return hl > wl ? rect_scan_4x8[i] : rect_scan_8x4[i];
-  if (cls == TXC_VERT) return i;                              // mrow
-  const int c = i / h, r = i - c * h; return r * w + c;       // mcol
-}
 
 // raw edges of a w x h block: above[-1 .. w+h-1], left[-1 .. w+h-1] (oracle av1o_predict_intra_wh edge preparation)
 __device__ inline void load_edges_wh(const LDS FrameDev *f, int plane, int x, int y, int w, int h, int have_left, int have_above, int have_ar, int have_bl,
@@ -180,15 +167,6 @@ template <int W, int H> __device__ inline void inv_txfm_rect_add(const LDS int32
     for (int i = 0; i < H; i++) rec[i * W + j] = (uint16_t)iclamp_((int)rec[i * W + j] + round2_(x[i], 4), 0, mx);
   }
   WAVE_SYNC();
-}
-
-// tx set / CDF row of a 2:1 transform (oracle av1o_tx_set / av1o_intra_tx_cdf): the larger dimension (8) bounds the set, the smaller (4) indexes the CDFs
-template <int TS, typename FP> __device__ __forceinline__ int rect_tx_cdf(FP f, int ymode, int *nsyms, int *set_out) {
-  const int set = Tools<TS>::reduced_tx_set(f) ? 2 : 1;
-  *set_out = set;
-  if (f->base_q_idx == 0) { *nsyms = 0; return -1; }
-  if (set == 1) { *nsyms = 7; return CDF_INTRA_TX1 + ymode * CDF_INTRA_TX1_STRIDE; }
-  *nsyms = 5; return CDF_INTRA_TX2 + ymode * CDF_INTRA_TX2_STRIDE;
 }
 
 // Quantise (rav1e dead-zone rule as quantize_dev), level map, rate (oracle av1o_code_coeffs priced against the static table, one scan position per
@@ -508,32 +486,6 @@ template <int WL, int HL> __device__ inline void commit_rect(const LDS FrameDev 
 template <int WL, int HL> __device__ __forceinline__ void fill_rect(uint8_t *m, int ms, int r, int c, int v) {
   if (LANE < 2) m[(r + (HL == 3 ? LANE : 0)) * ms + c + (WL == 3 ? LANE : 0)] = (uint8_t)v;
 }
-// all_zero / dc_sign contexts of a transform block of w4 x h4 cells inside a block (txb_ctx_dev with both dimensions); `whole`: the transform is the block
-template <typename FP, typename TP> __device__ inline void txb_ctx_wh(FP f, TP t, int plane, int r4, int c4, int w4, int h4, int whole, int *skip_ctx, int *dc_ctx) {
-  const int ms = f->mi_stride;
-  int top = 0, left = 0, dcs = 0, any_a = 0, any_l = 0;
-  const int k = LANE;
-  if (k < imax_(w4, h4)) {
-    const bool ha = k < w4 && r4 - 1 >= t->mi_row_start && c4 + k < f->mi_cols, hl = k < h4 && c4 - 1 >= t->mi_col_start && r4 + k < f->mi_rows;
-    const int ia = ha ? (r4 - 1) * ms + c4 + k : r4 * ms + c4, il = hl ? (r4 + k) * ms + c4 - 1 : r4 * ms + c4;
-    const int la = f->m_lvl[plane][ia], da = f->m_dc[plane][ia], ll = f->m_lvl[plane][il], dl = f->m_dc[plane][il];
-    if (ha) { top = la; any_a = la | da; dcs += da == 1 ? -1 : (da == 2 ? 1 : 0); }
-    if (hl) { left = ll; any_l = ll | dl; dcs += dl == 1 ? -1 : (dl == 2 ? 1 : 0); }
-  }
-  top = wave_max_i32(top); left = wave_max_i32(left); dcs = wave_sum_i32(dcs);
-  any_a = wave_or_i32(any_a); any_l = wave_or_i32(any_l);
-  *dc_ctx = dcs < 0 ? 1 : (dcs > 0 ? 2 : 0);
-  if (plane == 0) {
-    int ctx;
-    if (whole) ctx = 0;
-    else if (top == 0 && left == 0) ctx = 1;
-    else if (top == 0 || left == 0) ctx = 2 + (imax_(top, left) > 3);
-    else if (imax_(top, left) <= 3) ctx = 4;
-    else if (imin_(top, left) <= 3) ctx = 5;
-    else ctx = 6;
-    *skip_ctx = ctx;
-  } else *skip_ctx = 7 + (any_a != 0) + (any_l != 0) + (whole ? 0 : 3);
-}
 
 template <int MAXN, int BSR, int NW, int TS>
 __device__ MI_K1_TRY_ATTR long long try_block_rect(const Ctx<MAXN, NW, TS> k, int r, int c, long long budget = J_INF) {
@@ -599,7 +551,7 @@ __device__ MI_K1_TRY_ATTR long long try_block_rect(const Ctx<MAXN, NW, TS> k, in
   // ---- full RD over the surviving modes x tx types (no angle deltas below 8x8): evaluation e = ci * ntx + ti by wave e % NW ----
   const int ncand = Tools<TS>::FULL ? 7 : 3;
   int tx_ns = 0, tx_set = 0;
-  const int tx_off0 = rect_tx_cdf<TS>(f, 0, &tx_ns, &tx_set);
+  const int tx_off0 = rect_tx_cdf(f, Tools<TS>::reduced_tx_set(f), 0, &tx_ns, &tx_set);
   const int ntx = (Tools<TS>::rdo_tx(f) && tx_off0 >= 0) ? tx_ns : 1;
   // the surviving modes are predicted once (candidate ci by wave ci % NW) into the prediction cache and shared by their tx-type trials
   LDS uint16_t *pcache = MAXN <= 16 ? (LDS uint16_t *)SH->lpred : (LDS uint16_t *)SH->split_rec;      // [7][NN]; both are free until the tx-size trial
@@ -622,7 +574,7 @@ __device__ MI_K1_TRY_ATTR long long try_block_rect(const Ctx<MAXN, NW, TS> k, in
       const int ee = live ? e : 0, ci = ee / ntx, ti = ee - ci * ntx, m = SH->order[ci];
       const uint32_t mode_rate = ycost[m];
       int ns2, set2;
-      const int tx_off = rect_tx_cdf<TS>(f, m, &ns2, &set2);
+      const int tx_off = rect_tx_cdf(f, Tools<TS>::reduced_tx_set(f), m, &ns2, &set2);
       int txtype;
       if (ntx > 1) txtype = sym_to_txtype(tx_set, ti);
       else { txtype = mode_to_txtype(m); if (tx_off < 0 || txtype_to_sym(tx_set, txtype) < 0) txtype = DCT_DCT; }
@@ -656,7 +608,7 @@ __device__ MI_K1_TRY_ATTR long long try_block_rect(const Ctx<MAXN, NW, TS> k, in
     const LDS uint16_t *cpred = pcache + ci * NN;
     const uint32_t mode_rate = ycost[m];
     int ns2, set2;
-    const int tx_off = rect_tx_cdf<TS>(f, m, &ns2, &set2);
+    const int tx_off = rect_tx_cdf(f, Tools<TS>::reduced_tx_set(f), m, &ns2, &set2);
     int txtype;
     if (ntx > 1) txtype = sym_to_txtype(tx_set, ti);
     else { txtype = mode_to_txtype(m); if (tx_off < 0 || txtype_to_sym(tx_set, txtype) < 0) txtype = DCT_DCT; }

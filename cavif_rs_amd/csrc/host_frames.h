@@ -230,9 +230,6 @@ template <int MAXBS, int NW, bool BU, int TS> static hipError_t launch_search_t(
     e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
     if (e != hipSuccess) return e;
     resident[device] = std::max(1, per_cu) * std::max(1, cus);
-#ifdef MI_TUNING_KNOBS                                  // probe builds only: MI_K1_GRID_PER_CU=n asks for fewer persistent workgroups per CU than fit
-    if (const char *v = getenv("MI_K1_GRID_PER_CU")) { const int n = atoi(v); if (n > 0 && n < per_cu) resident[device] = n * std::max(1, cus); }
-#endif
   }
   const int grid = std::min(nitems, resident[device]);
   if (grid_out) { *grid_out = grid; return hipSuccess; }   // dry run: the caller sizes the snapshot pool
@@ -257,24 +254,23 @@ static hipError_t launch_search(int maxbs, bool bottomup, int tools, const Frame
 #endif
 #undef MI_LAUNCH_
 }
-// jobs must all belong to frames of the same block-size class
-// K4, one instantiation per block-size class like K1 (jobs + first_job .. first_job + njobs of the grouped job list)
+// K4, one instantiation per block-size class like K1 (jobs + first_job .. first_job + njobs of the grouped job list); the jobs must all belong to frames of the same class
+template <int MAXBS, int NA> static hipError_t launch_entropy_t(const FrameDev *d_frames, const TileJob *d_jobs, int njobs, uint16_t *d_precarry, uint32_t pre_cap, uint32_t *d_recbuf, uint32_t rec_cap, hipStream_t s) {
+  hipLaunchKernelGGL((tile_entropy_kernel<MAXBS, NA>), dim3(njobs), dim3(MI_K4_THREADS_OF(NA)), sizeof(EntropyLds<(MAXBS <= 2 ? 16 : 32)>), s, d_frames, d_jobs, njobs, d_precarry, pre_cap, d_recbuf, rec_cap);
+  return hipGetLastError();
+}
 static hipError_t launch_entropy(int maxbs, const FrameDev *d_frames, const TileJob *d_jobs, int njobs, uint16_t *d_precarry, uint32_t pre_cap, uint32_t *d_recbuf, uint32_t rec_cap, hipStream_t s) {
   if (njobs <= 0) return hipSuccess;
+#define MI_LAUNCH_(MB, NA_) launch_entropy_t<MB, NA_>(d_frames, d_jobs, njobs, d_precarry, pre_cap, d_recbuf, rec_cap, s)
+#ifdef MI_FAST_BUILD                                     // experiment builds only (tools/build_variant.sh): the headline configuration's instantiation and nothing else
+  return MI_LAUNCH_(2, MI_K4_ADAPTERS);
+#else
   // a launch that leaves wave slots free (fewer than 512 tiles: 6 waves each still fit the device in one round) runs four adapter waves per tile
   const bool sparse = njobs < 512;
-#ifdef MI_FAST_BUILD
-  hipLaunchKernelGGL((tile_entropy_kernel<2, MI_K4_ADAPTERS>), dim3(njobs), dim3(MI_K4_THREADS_OF(MI_K4_ADAPTERS)), sizeof(EntropyLds<16>), s, d_frames, d_jobs, njobs, d_precarry, pre_cap, d_recbuf, rec_cap);
-  return hipGetLastError();
+  if (maxbs <= 2) return sparse ? MI_LAUNCH_(2, MI_K4_ADAPTERS_SPARSE) : MI_LAUNCH_(2, MI_K4_ADAPTERS);
+  return sparse ? MI_LAUNCH_(4, MI_K4_ADAPTERS_SPARSE) : MI_LAUNCH_(4, MI_K4_ADAPTERS);
 #endif
-  if (maxbs <= 2) {
-    if (sparse) hipLaunchKernelGGL((tile_entropy_kernel<2, MI_K4_ADAPTERS_SPARSE>), dim3(njobs), dim3(MI_K4_THREADS_OF(MI_K4_ADAPTERS_SPARSE)), sizeof(EntropyLds<16>), s, d_frames, d_jobs, njobs, d_precarry, pre_cap, d_recbuf, rec_cap);
-    else hipLaunchKernelGGL((tile_entropy_kernel<2, MI_K4_ADAPTERS>), dim3(njobs), dim3(MI_K4_THREADS_OF(MI_K4_ADAPTERS)), sizeof(EntropyLds<16>), s, d_frames, d_jobs, njobs, d_precarry, pre_cap, d_recbuf, rec_cap);
-  } else {
-    if (sparse) hipLaunchKernelGGL((tile_entropy_kernel<4, MI_K4_ADAPTERS_SPARSE>), dim3(njobs), dim3(MI_K4_THREADS_OF(MI_K4_ADAPTERS_SPARSE)), sizeof(EntropyLds<32>), s, d_frames, d_jobs, njobs, d_precarry, pre_cap, d_recbuf, rec_cap);
-    else hipLaunchKernelGGL((tile_entropy_kernel<4, MI_K4_ADAPTERS>), dim3(njobs), dim3(MI_K4_THREADS_OF(MI_K4_ADAPTERS)), sizeof(EntropyLds<32>), s, d_frames, d_jobs, njobs, d_precarry, pre_cap, d_recbuf, rec_cap);
-  }
-  return hipGetLastError();
+#undef MI_LAUNCH_
 }
 
 // The work list of a set of tile jobs (grouped by block-size class, class_begin[2..5]) and the device objects a queue launch needs: the items, the claim
@@ -360,12 +356,8 @@ static int search_enqueue(SearchQueue &q, const std::vector<FramePlan> &frames, 
     // allow.  Until round 5 a full batch used whole-superblock flags and 2 * row + column: K1 106.6 -> 103.0 ms on 32 x 1080p, 121.1 -> 110.6 ms with 16 tiles per
     // image, where the longest tile's chain and not the device's throughput bounds the launch (profiles/r05zr_k1_sync_grain_and_order.txt).  64x64 superblocks
     // are their own roots: whole-superblock flags, two columns per row.
-    bool fine = cls < 4;
-    int key_a = fine ? 3 : 2, key_b = fine ? 2 : 1;
-#ifdef MI_TUNING_KNOBS
-    if (const char *v = getenv("MI_K1_FINE")) fine = cls < 4 && atoi(v) != 0;
-    if (const char *v = getenv("MI_K1_KEY")) { int a = 0, b = 0; if (sscanf(v, "%d,%d", &a, &b) == 2 && a > b && b > 0 && a < 64) { key_a = a; key_b = b; } }
-#endif
+    const bool fine = cls < 4;
+    const int key_a = fine ? 3 : 2, key_b = fine ? 2 : 1;
     std::vector<std::vector<SbItem>> by_key;
     for (int j = class_begin[cls]; j < class_begin[cls + 1]; j++) {
       const TileJob &tj = jobs[j]; const FramePlan &p = frames[tj.frame];

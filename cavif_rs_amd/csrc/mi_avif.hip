@@ -20,8 +20,8 @@
 #include "dev_jpeg.h"
 #include "host_frames.h"
 
-// The product library reads no environment variables; probe builds (-DMI_TUNING_KNOBS: tools/) get MI_AVIF_TIMING=1 (host-side timeline on stderr),
-// MI_K1_GRID_PER_CU=n (fewer persistent search workgroups per CU) and, with -DMI_DEBUG_HOOKS=1, MI_DEBUG_LEVEL (bisect levels of the tile search).
+// The product library reads no environment variables; probe builds (tools/) get MI_AVIF_TIMING=1 (-DMI_TUNING_KNOBS: host-side timeline on stderr)
+// and MI_DEBUG_LEVEL (-DMI_DEBUG_HOOKS=1: bisect levels of the tile search).
 // the streaming form's rotation: resident batch objects per image shape, and the first run's share of a full run
 #ifndef MI_STREAM_SLOTS_DEFAULT
 #define MI_STREAM_SLOTS_DEFAULT 2          /* 256 x 1080p files end to end: 1.32 s with two, 1.48 with three, 1.51 with four (profiles/r05zk_e2e_knobs.txt, matrix 5) */
@@ -595,10 +595,7 @@ int mi_ravif_encode_stream(const mi_ravif_encoder *e, size_t n, mi_fetch_fn fetc
     { size_t fr = 0, tot = 0; if (hipSetDevice(dev) == hipSuccess && hipMemGetInfo(&fr, &tot) == hipSuccess && fr) budget = fr / 10 * 6; }
     { int sharing = 0; for (int d2 : devs) sharing += d2 == dev; budget /= (size_t)std::max(1, sharing); }      // workers on the same ordinal (devices = [0, 0]) split what is free
     static constexpr int NSLOT_MAX = 4;
-    int NSLOT = MI_STREAM_SLOTS_DEFAULT;
-#ifdef MI_TUNING_KNOBS
-    if (const char *v = getenv("MI_STREAM_SLOTS")) NSLOT = std::min(NSLOT_MAX, std::max(1, atoi(v)));
-#endif
+    const int NSLOT = MI_STREAM_SLOTS_DEFAULT;
     struct Slot { mi_batch *b = nullptr; std::future<mi_batch *> making; std::vector<size_t> idx; bool busy = false; size_t bytes = 0; };
     struct Shape { uint32_t w, h; int ch; size_t cap; Slot slot[NSLOT_MAX]; int next = 0; size_t runs = 0, last_use = 0; };
     std::vector<std::unique_ptr<Shape>> shapes;
@@ -679,10 +676,7 @@ int mi_ravif_encode_stream(const mi_ravif_encoder *e, size_t n, mi_fetch_fn fetc
     size_t claims = 0;
     for (;;) {
       // every claim is a full run, the first one included (MI_STREAM_FIRST_RUN_NUM / _DEN)
-      size_t first_run = std::max<size_t>(1, max_run * MI_STREAM_FIRST_RUN_NUM / MI_STREAM_FIRST_RUN_DEN);
-#ifdef MI_TUNING_KNOBS
-      if (const char *v = getenv("MI_STREAM_FIRST_RUN")) first_run = std::min(max_run, (size_t)std::max(1, atoi(v)));
-#endif
+      const size_t first_run = std::max<size_t>(1, max_run * MI_STREAM_FIRST_RUN_NUM / MI_STREAM_FIRST_RUN_DEN);
       const size_t want = claims++ == 0 ? first_run : max_run;
       const size_t i0 = cursor.fetch_add(want);                // claim the index range [i0, i1)
       if (i0 >= n) break;

@@ -61,12 +61,7 @@ __device__ __forceinline__ void re_flush_units(RangeEncDev *e, uint32_t end) {
 #define K4_BIT(b) ((b) ? K4_BOUNDS(256u, 0u, 0u) : K4_BOUNDS(512u, 256u, 1u))
 // adapter waves per tile: two when the launch fills the device (1024 tiles x 4 waves = every SIMD's four wave slots at K4's register count; four
 // adapters were measured slower there: a second round of workgroups), four when it does not (single images: the adapters are the busiest stage)
-#ifndef MI_K4_ADAPTERS
 #define MI_K4_ADAPTERS 2
-#endif
-#ifndef MI_K4_LB_EXTRA
-#define MI_K4_LB_EXTRA                             /* probe builds: a second __launch_bounds__ argument (workgroups per CU) */
-#endif
 #define MI_K4_ADAPTERS_SPARSE 4
 #define MI_K4_THREADS_OF(NA) (64 * (2 + (NA)))
 // records of a typical worst superblock: per coefficient the base level, four base-range symbols, the sign and two more; per transform
@@ -78,26 +73,14 @@ __device__ __forceinline__ void re_flush_units(RangeEncDev *e, uint32_t end) {
 #define MI_K4_TXB_RECORDS ((uint32_t)(1024 * 36 + 1024))
 // which adapter owns a CDF row: the low bits of its offset (the hot tables have strides 5 and 3: neighbouring contexts and the same context of
 // neighbouring transform sizes land on different waves)
-// MI_K4_SPREAD (measured, not kept): with two adapter waves the producer and the coder take rows as well -- owners 2 and 3: the producer turns its own rows' records
-// into bounds before it hands a buffer on, the coder right before it codes one (a row's state only depends on the symbols coded through it, in order, and each of
-// them meets the buffers in order).  After the coder lost its `low` arithmetic (RangeEncDev) the second adapter was the busiest stage of a long tile by a third
-// (12.8 ms against 7.5 / 9.5 / 8.7, profiles/r06k_k4_stage_profiles.txt); the table below -- owner by (context index + table block) & 7, fitted on the oracle's symbol
-// streams of two 1080p pictures -- evens the four stages out (all 8 ... 11 ms, profiles/r06m_k4s2_stage.txt), the bytes are the same, and the kernel is SLOWER:
-// 15.5 against 14.6 ms (profiles/r06l_*, r06m_*).  The four waves of a SIMD -- one stage of each of four tiles -- share its instruction issue: what the two extra
-// passes over every buffer add is paid by all of them, and a tile does not end sooner for being balanced.
-#ifndef MI_K4_SPREAD
-#define MI_K4_SPREAD 0
-#endif
-#ifndef MI_K4_SPREAD_LUT
-#define MI_K4_SPREAD_LUT 0x8704u                         /* 2 bits per bucket, bucket 0 first: 0 1 0 0 3 1 0 2 */
-#endif
+// (Measured and not kept: with two adapter waves, giving the producer and the coder rows of their own -- an owner table fitted on the oracle's symbol streams -- evens the
+// four stages out, 8 ... 11 ms each instead of 7.5 / 9.5 / 12.8 / 8.7, with the same bytes.  The kernel is slower, 15.5 against 14.6 ms: the four waves of a SIMD, one stage
+// of each of four tiles, share its instruction issue, so the two extra passes over every buffer are paid by all of them -- profiles/r06k_k4_stage_profiles.txt, r06l_*, r06m_*.)
 template <int NA> __device__ __forceinline__ int k4_row_owner(uint32_t row) {
-  static_assert(NA == 2 || NA == 3 || NA == 4, "two, three or four adapters");
+  static_assert(NA == 2 || NA == 4, "two or four adapters");
   // the parity (or the low two bits) of (context index + table block) of the stride-5 tables -- the coefficient base-level rows are 85 % of all
   // adaptive symbols and four of them (contexts 21 / 22 of the 16x16 luma and chroma blocks) carry 70 %; plain offset parity put 68 % of a 1080p
   // tile's symbols on one of two waves, this puts 53 ... 58 % there, and 35 ... 43 % on the busiest of four (measured on the oracle's symbol stream)
-  if constexpr (NA == 3) return (int)((row / 5u + row / 210u) % 3u);
-  if constexpr (NA == 2 && MI_K4_SPREAD) return (int)((MI_K4_SPREAD_LUT >> (2u * ((row / 5u + row / 210u) & 7u))) & 3u);
   return (int)((row / 5u + row / 210u) & (uint32_t)(NA - 1));
 }
 // exclusive prefix sum over the 64 lanes (lane order), *total = the wave's sum
@@ -284,7 +267,6 @@ struct TileWriter {                                                 // the produ
   LDS int32_t *qc; LDS uint8_t *lev; const LDS uint16_t *ls;       // LDS staging + LDS copy of the scan tables
   LDS uint16_t *rec_off, *rec_br; LDS uint32_t *rec_lv;            // per-coefficient context rows / levels of the current transform block
   LDS int *lr_ref;                                                  // RefSgrXqd[plane][2]
-  LDS uint16_t *cdf; int own_rows;                                  // the tables; own_rows: the producer adapts the rows k4_row_owner gives it (owner 2)
   int cdef_pending;                                                 // the 64x64 superblock being walked has not signalled its cdef_idx yet
   int sb_cols_tile;
   // Frame scalars that steer the walk, pinned to SGPRs once per tile: every control value the walk loads (skip, modes, transform sizes, eob,
@@ -298,18 +280,11 @@ struct TileWriter {                                                 // the produ
 // the producer's emitters (wave-uniform arguments; lane 0 stores)
 __device__ __forceinline__ void k4_put(TileWriter *w, uint32_t rec) { if (LANE == 0 && w->n < w->cap) w->out[w->n] = rec; w->n++; }
 __device__ __forceinline__ void k4_sym(TileWriter *w, int s, int off, int ns) { k4_put(w, K4_REC(uni32(off), uni32(s), uni32(ns))); }
-// (one copy of the adapter loop for the producer's hand-off sites; the arguments by value: the writer's state stays in registers)
-__device__ __attribute__((noinline)) void k4_adapt_own_rows(LDS uint16_t *cdf, uint32_t *buf, int n, int owner) {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");  // the records were stored by other lanes of this wave
-  WAVE_SYNC();
-  k4_adapt_sb<2>(cdf, buf, n, owner);
-}
 // The producer hands its buffer to the adapters: publishes the count, meets the other stages at the workgroup barrier (they sit in the kernel's
 // stage loop; a barrier is a barrier wherever the wave executes it) and moves on to the next of the three buffers.  `last`: the tile ends here.
 // (Measured and not kept, profiles/r06n_*: a ring of six half-size buffers with release / acquire counters in LDS instead of the barrier -- stages running ahead of
 // each other -- is byte-identical and exactly as fast, 14.65 ms: what a tile loses against its busiest stage is not the lockstep.)
 __device__ __forceinline__ void k4_handoff(TileWriter *w, bool last) {
-  if (w->own_rows) k4_adapt_own_rows(w->cdf, w->out, (int)(w->n < w->cap ? w->n : w->cap), 2);
   WAVE_SYNC();
   if (LANE == 0) { w->nrec[w->chunk % 3] = w->n; if (last) *w->total = w->chunk + 1; }
   __syncthreads();
@@ -634,7 +609,7 @@ template <int BSR> __device__ __forceinline__ void write_block_rect(TileWriter *
       int txtype, off = -1, sym = 0, ns = 0, set;
       if (p == 0) {
         txtype = v_txt;
-        off = split ? intra_tx_cdf(&w->txc, 0, ymode, &ns, &set) : rect_tx_cdf<0>(&w->txc, ymode, &ns, &set);
+        off = split ? intra_tx_cdf(&w->txc, 0, ymode, &ns, &set) : rect_tx_cdf(&w->txc, w->txc.reduced_tx_set != 0, ymode, &ns, &set);
         if (off >= 0) sym = txtype_to_sym(set, txtype);
       } else {
         set = w->txc.reduced_tx_set ? 2 : 1;
@@ -754,7 +729,7 @@ template <int CS> struct EntropyLds {
 
 // recbuf: per tile job three record buffers of rec_cap entries (producer -> adapters -> coder, rotating per superblock)
 template <int MAXBS, int NA>
-__global__ __launch_bounds__(MI_K4_THREADS_OF(NA) MI_K4_LB_EXTRA) void tile_entropy_kernel(const FrameDev *__restrict__ frames, const TileJob *__restrict__ jobs, int njobs, uint16_t *precarry, uint32_t pre_cap,
+__global__ __launch_bounds__(MI_K4_THREADS_OF(NA)) void tile_entropy_kernel(const FrameDev *__restrict__ frames, const TileJob *__restrict__ jobs, int njobs, uint16_t *precarry, uint32_t pre_cap,
                                                                    uint32_t *recbuf, uint32_t rec_cap) {
   constexpr int CS = MAXBS <= 2 ? 16 : 32, MI_K4_THREADS = MI_K4_THREADS_OF(NA);
   extern __shared__ __align__(16) uint8_t k4_smem[];            // sizeof(EntropyLds<CS>), passed at launch
@@ -789,7 +764,7 @@ __global__ __launch_bounds__(MI_K4_THREADS_OF(NA) MI_K4_LB_EXTRA) void tile_entr
     w.t.mi_row_start = row0; w.t.mi_row_end = row1; w.t.mi_col_start = col0; w.t.mi_col_end = col1;
     w.qc = (LDS int32_t *)L.qc; w.lev = (LDS uint8_t *)L.lev; w.cdef_pending = 1; w.ls = (LDS uint16_t *)L.scans;
     w.rec_off = (LDS uint16_t *)L.rec_off; w.rec_br = (LDS uint16_t *)L.rec_br; w.rec_lv = (LDS uint32_t *)L.rec_lv;
-    w.lr_ref = (LDS int *)L.lr_ref; w.cap = rec_cap; w.out = bufs; w.n = 0; w.cdf = (LDS uint16_t *)L.cdf; w.own_rows = NA == 2 && MI_K4_SPREAD;
+    w.lr_ref = (LDS int *)L.lr_ref; w.cap = rec_cap; w.out = bufs; w.n = 0;
     w.np = U_(f->np); w.mi_rows = U_(f->mi_rows); w.mi_cols = U_(f->mi_cols); w.ms = U_(f->mi_stride); w.tx_mode_select = U_(f->tx_mode_select);
     w.seg_n = U_(f->seg_n); w.enable_cdef = U_(f->enable_cdef); w.cdef_bits = U_(f->cdef_bits); w.enable_restoration = U_(f->enable_restoration); w.sb_cols = U_(f->sb_cols);
     w.fw = U_(f->w); w.fh = U_(f->h); w.txc.reduced_tx_set = U_(f->reduced_tx_set); w.txc.base_q_idx = U_(f->base_q_idx);
@@ -834,10 +809,6 @@ __global__ __launch_bounds__(MI_K4_THREADS_OF(NA) MI_K4_LB_EXTRA) void tile_entr
         if (t >= 2 && (total < 0 || t - 2 < total)) {
           const uint32_t n = L.nrec[(t - 2) % 3]; if (n > rec_cap) overflow = 1;   // (k4_room keeps n below the capacity: a guard, not a path)
           uint32_t *const buf = bufs + (size_t)((t - 2) % 3) * rec_cap; const int nc = (int)imin_((int)n, (int)rec_cap);
-          if constexpr (NA == 2 && MI_K4_SPREAD) {                // the coder's own rows (owner 3): symbols -> bounds right before they are coded
-            k4_adapt_sb<NA>((LDS uint16_t *)L.cdf, buf, nc, 3);
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); WAVE_SYNC();
-          }
           k4_code_sb(&ec, buf, nc);
         }
       }

@@ -24,31 +24,8 @@
 #define MI_BALLOT64(p) __builtin_amdgcn_ballot_w64(p)
 #endif
 #define MI_K1_TRY_ATTR __attribute__((noinline, not_tail_called))
-#define MI_K1_WALK_INLINE __forceinline__
-// The loop over the four children of a split node: unrolled, the recursion's inlining multiplies the node's code by four per level (64 copies of the 8x8 node's body in the
-// 16x16 class: ~600 KB of code, 1127 SGPR spills in the kernel body); rolled (-DMI_K1_WALK_ROLLED=1), one copy per level.
-#ifndef MI_K1_PAIRED_CHAINS                             /* 0: one row per chain (16 / 4 serial steps per depth), tools/build_variant.sh A/B */
-#define MI_K1_PAIRED_CHAINS 1
-#endif
-#ifndef MI_K1_PAIRED_MIN_N                               /* the smallest block whose trial runs paired chains (8: every trial of the 16x16 class) */
-#define MI_K1_PAIRED_MIN_N 8
-#endif
-#ifndef MI_K1_PAIRED_MAX_HN                              /* the largest sub-block whose chains run paired: 8 = every grouped chain of the 16x16 class.  (With the build flags of the
-                                                           round's first half pairing the 8x8 sub-block chains bought nothing and spilled more -- profiles/r06v_ab_pair_only_4x4.txt --;
-                                                           with -sink-insts-to-avoid-spills / -disable-machine-licm it is worth 0.6 ms: profiles/r06_ab_switches_under_final_flags.txt) */
-#define MI_K1_PAIRED_MAX_HN 8
-#endif
-#ifndef MI_K1_CHAIN_PRIO_WAVES
-#define MI_K1_CHAIN_PRIO_WAVES 0
-#endif
-#ifndef MI_K1_WALK_ROLLED
-#define MI_K1_WALK_ROLLED 1
-#endif
-#if MI_K1_WALK_ROLLED
-#define MI_K1_WALK_SPLIT_LOOP _Pragma("unroll 1")
-#else
-#define MI_K1_WALK_SPLIT_LOOP _Pragma("unroll")
-#endif
+// The loop over the four children of a split node stays rolled (`unroll 1`), one copy of a node's body per level: unrolled, the recursion's inlining multiplies the node's
+// code by four per level (64 copies of the 8x8 node's body in the 16x16 class: ~600 KB of code, 1127 SGPR spills in the kernel body).
 #define MI_K1_WG_PER_CU 4                            /* the 16x16 class: 40.9 KB of LDS and 128 VGPRs per workgroup -> exactly four per CU */
 #define WAVE_ID ((int)(threadIdx.x >> 6))
 #ifndef MI_PROFILE
@@ -153,7 +130,7 @@ template <int N> __device__ __forceinline__ LDS unsigned long long &mi_prof_slot
 // context is two 32-bit LDS pointers passed BY VALUE (registers): the accessors fold into ds_read offsets.  (It used to be a
 // struct on the kernel's stack passed by reference: every use inside the non-inlined block search was a flat load from scratch,
 // ~40 per call, each holding both wait counters.)
-// TS, the tool set a kernel is instantiated for (the host launches the matching instantiation, mi_avif.hip search_mode):
+// TS, the tool set a kernel is instantiated for (the host launches the matching instantiation, host_frames.h search_mode):
 //   bit 0 (FULL)  the full candidate set of speed <= 1 (complex_pred_modes): FULL == f->complex_modes, the kernels read the template parameter
 //   bit 1 (FIXED) the switches of ravif's speed 4 below the high-quality threshold (av1encoder.rs:576-586: rdo_tx_decision, reduced_tx_set, fine_directional_intra,
 //                 hence tx_mode_select; Tune::Psychovisual) are constants of the kernel instead of loads from the frame descriptor: the headline configuration's
@@ -765,7 +742,10 @@ __device__ MI_K1_TRY_ATTR long long try_block(const Ctx<MAXN, NW, TS> k, int r, 
           // 10 slots for the 16 sub-blocks of a 4 x 4 grid; (0), (1, 2), (3) for a 2 x 2 grid whose prediction reads no above-right samples), now inside a chain: the
           // pair's rows share the chain's state, a wave barrier orders the slots.  Types 1, 2 on wave 0, types 3, 4 on wave 1, IDTX on wave 2 (two rows, two idle); the
           // chains' state: types 1..4 in wave 3's scratch, IDTX directly in the block's split buffers.  16 serial steps -> 10 slots, 4 -> 3.
-          const bool paired = MI_K1_PAIRED_CHAINS && MAXN == 16 && sntx == 5 && n >= MI_K1_PAIRED_MIN_N && hn <= MI_K1_PAIRED_MAX_HN;
+          // Every grouped chain of the class runs paired, the 8x8 sub-blocks' chains included: with the build's -sink-insts-to-avoid-spills / -disable-machine-licm that is
+          // worth 0.6 ms over pairing the 4x4 chains only (profiles/r06_ab_switches_under_final_flags.txt; before those flags it bought nothing and spilled more,
+          // profiles/r06v_ab_pair_only_4x4.txt).  Issue priority for the chain-carrying waves was tried and costs 1.4 % (profiles/r06p_ab_chain_priority.txt).
+          const bool paired = MAXN == 16 && sntx == 5 && n >= 8 && hn <= 8;
           const int mem = paired ? (g & 1) : 0;                                                          // which sub-block of a slot this row takes
           const int e = paired ? (W == 0 ? 1 + (g >> 1) : (W == 1 ? 3 + (g >> 1) : ((W == 2 && g < 2) ? 0 : 64)))
                                : (sntx == 5 ? (W == 0 ? g + 1 : ((W == 1 && g == 0) ? 0 : 64)) : W * 4 + g);   // this row's transform type (symbol)
@@ -797,7 +777,6 @@ __device__ MI_K1_TRY_ATTR long long try_block(const Ctx<MAXN, NW, TS> k, int r, 
             const uint16_t *grec = f->rec[0];
             long long jc = has_chain ? j_split : J_INF;
             int any = 0;
-            if (W < MI_K1_CHAIN_PRIO_WAVES) __builtin_amdgcn_s_setprio(3);   // off (0 waves): with chains, issue priority for the chain-carrying waves COSTS 1.4 % (profiles/r06p_ab_chain_priority.txt; it gained 1 % for round 5's slots)
             const bool uses_ar = dirm && pa < 90;
             const int nslot = paired ? (G == 4 ? 10 : (uses_ar ? 4 : 3)) : G * G;
 #pragma unroll 1
@@ -1637,12 +1616,9 @@ template <typename SHT> __device__ __forceinline__ long long part_j(const LDS SH
 // belongs to its own superblock or to one earlier in the work list, so the no-deadlock argument of the list order holds unchanged; the decoded
 // flags stay exact because a later neighbour of a block always waits for it.  Steady state for 16x16 roots: a superblock starts 0.75 of a
 // superblock time after its left neighbour and 1.125 after the one above, against 1 and 2 (profiles/r03m_*).
-// Since round 5 every launch of the 16x16 class runs this way (mi_avif.hip search_enqueue: list order 3 * row + 2 * column), and only the roots that other superblocks
+// Since round 5 every launch of the 16x16 class runs this way (host_frames.h search_enqueue: list order 3 * row + 2 * column), and only the roots that other superblocks
 // read take part: a root waits only if it lies in its superblock's first row or column (the others read nothing outside it), publishes only if it lies in the last row or
-// column (nothing else is ever polled), and a waiting root polls foreign superblocks' bits only -- 7 waits and 7 publishes per 16 roots (MI_K1_ROOT_SKIP=0: all 16).
-#ifndef MI_K1_ROOT_SKIP
-#define MI_K1_ROOT_SKIP 1
-#endif
+// column (nothing else is ever polled), and a waiting root polls foreign superblocks' bits only -- 7 waits and 7 publishes per 16 roots.
 // The acquire after a dependency wait: ONE wavefront invalidates (an agent-scope acquire is `buffer_inv sc1`: the compute unit's vector cache and this XCD's L2 lose their
 // lines, for everybody), the workgroup barrier hands the ordering on to the other three -- four invalidations per wait cost ~1 % of the launch (profiles/r05zn_ab_k1_acquire.txt;
 // the same file: with every L2 writeback / invalidation of the launch removed, which breaks the results across XCDs, the launch is no faster than this).
@@ -1665,7 +1641,7 @@ template <int MAXBS, int MAXN, int NW, int TS> __device__ inline void root_wait(
   const LDS FrameDev *f = k.f(); const LDS TileB *t = k.t();
   // a root below the superblock's first row and right of its first column reads its own superblock only (left, above, above-left, above-right are inside it, the
   // below-left one is inside it or later in coding order): nothing to wait for, nothing to invalidate -- 9 of the 16 roots of a 64x64 superblock
-  if (MI_K1_ROOT_SKIP && ((r >> MAXBS) & (G - 1)) != 0 && ((c >> MAXBS) & (G - 1)) != 0) return;
+  if (((r >> MAXBS) & (G - 1)) != 0 && ((c >> MAXBS) & (G - 1)) != 0) return;
   if (threadIdx.x == 0) {
     const int *mask = f->sb_prog + f->sb_rows * f->tile_cols;
     const int gr = r >> MAXBS, gc = c >> MAXBS, zc = root_z(gr & (G - 1), gc & (G - 1)), sr = r >> 4, sc = c >> 4;
@@ -1673,7 +1649,7 @@ template <int MAXBS, int MAXN, int NW, int TS> __device__ inline void root_wait(
       const int rr = (gr + dr) << MAXBS, cc = (gc + dc) << MAXBS;
       if (rr < t->mi_row_start || rr >= t->mi_row_end || cc < t->mi_col_start || cc >= t->mi_col_end) return;
       const int sr2 = rr >> 4, sc2 = cc >> 4, z2 = root_z((gr + dr) & (G - 1), (gc + dc) & (G - 1));
-      if (MI_K1_ROOT_SKIP && sr2 == sr && sc2 == sc) return;               // a root of this superblock: this workgroup did it (program order), and it may never be published
+      if (sr2 == sr && sc2 == sc) return;               // a root of this superblock: this workgroup did it (program order), and it may never be published
       if (only_if_earlier && !(sr2 < sr || (sr2 == sr && (sc2 < sc || (sc2 == sc && z2 < zc))))) return;
       const int *w = mask + sr2 * f->sb_cols + sc2;
       // Bounded (~2^25 polls are tens of seconds: a protocol error, a preempted or shared device must not hang the GPU), and a wait that gives up marks the frame:
@@ -1697,7 +1673,7 @@ template <int MAXBS, int MAXN, int NW, int TS> __device__ inline void root_publi
   const LDS FrameDev *f = k.f();
   // only the last row and the last column of a superblock's roots are read from outside it (by the superblocks right, below, below-left of it): the other 9 of 16
   // are never polled, and their data is covered by the release of the next root that is
-  if (MI_K1_ROOT_SKIP && ((r >> MAXBS) & (G - 1)) != G - 1 && ((c >> MAXBS) & (G - 1)) != G - 1) return;
+  if (((r >> MAXBS) & (G - 1)) != G - 1 && ((c >> MAXBS) & (G - 1)) != G - 1) return;
   WG_SYNC();                                                               // every wave's stores of this root are issued
   if (threadIdx.x == 0) {
     int *w = f->sb_prog + f->sb_rows * f->tile_cols + (r >> 4) * f->sb_cols + (c >> 4);
@@ -1706,7 +1682,7 @@ template <int MAXBS, int MAXN, int NW, int TS> __device__ inline void root_publi
 }
 
 template <int MAXN, int MAXBS, int BS, int NW> struct RdPart {
-  template <int TS> static __device__ MI_K1_WALK_INLINE int run(const Ctx<MAXN, NW, TS> k, int r, int c, long long known_j) {
+  template <int TS> static __device__ __forceinline__ int run(const Ctx<MAXN, NW, TS> k, int r, int c, long long known_j) {
     const LDS FrameDev *f = k.f();
     if (r >= f->mi_rows || c >= f->mi_cols) return 0;
     constexpr int half = (1 << BS) >> 1, px = 4 << BS, n4 = 1 << BS;
@@ -1764,7 +1740,7 @@ template <int MAXN, int MAXBS, int BS, int NW> struct RdPart {
     }
     if (do_split) {
       int chain = !must_split && !DBG_IS(f, 11);      // the four trial results are in place until a sibling decides to split
-      MI_K1_WALK_SPLIT_LOOP
+#pragma unroll 1
       for (int q = 0; q < 4; q++)
       {
         const int rr = r + (q >> 1) * half, cc = c + (q & 1) * half;
@@ -1779,7 +1755,7 @@ template <int MAXN, int MAXBS, int BS, int NW> struct RdPart {
   }
 };
 template <int MAXN, int MAXBS, int NW> struct RdPart<MAXN, MAXBS, 0, NW> {
-  template <int TS> static __device__ MI_K1_WALK_INLINE int run(const Ctx<MAXN, NW, TS> k, int r, int c, long long known_j) {
+  template <int TS> static __device__ __forceinline__ int run(const Ctx<MAXN, NW, TS> k, int r, int c, long long known_j) {
     const LDS FrameDev *f = k.f();
     if (r >= f->mi_rows || c >= f->mi_cols) return 0;
     if (known_j >= 0) return 0;
@@ -1797,7 +1773,7 @@ template <int MAXN> __device__ __forceinline__ constexpr size_t snap_level_off(i
   return o;
 }
 template <int MAXN, int MAXBS, int BS, int NW> struct RdPartBU {
-  template <int TS> static __device__ MI_K1_WALK_INLINE long long run(const Ctx<MAXN, NW, TS> k, int r, int c) {
+  template <int TS> static __device__ __forceinline__ long long run(const Ctx<MAXN, NW, TS> k, int r, int c) {
     const LDS FrameDev *f = k.f();
     if (r >= f->mi_rows || c >= f->mi_cols) return 0;
     constexpr int half = (1 << BS) >> 1, px = 4 << BS, n4 = 1 << BS;
@@ -1848,7 +1824,7 @@ template <int MAXN, int MAXBS, int BS, int NW> struct RdPartBU {
   }
 };
 template <int MAXN, int MAXBS, int NW> struct RdPartBU<MAXN, MAXBS, 0, NW> {
-  template <int TS> static __device__ MI_K1_WALK_INLINE long long run(const Ctx<MAXN, NW, TS> k, int r, int c) {
+  template <int TS> static __device__ __forceinline__ long long run(const Ctx<MAXN, NW, TS> k, int r, int c) {
     const LDS FrameDev *f = k.f();
     if (r >= f->mi_rows || c >= f->mi_cols) return 0;
     return uni64(blk_eval<MAXN, 0, NW>(k, r, c));

@@ -4,7 +4,6 @@
 // place), the adapters turn buffer t - 1 into bounds, the coder codes buffer t - 2, one workgroup barrier per step; three rotating buffers.
 // Built twice by tests/helpers/k4_harness.py: hipcc for gfx950 with the product's flags, g++ with the SIMT emulator (tests/emu/).
 #include <hip/hip_runtime.h>
-#include "../../cavif_rs_amd/csrc/tile_search.h"          /* what tile_entropy.h uses of the block-size helpers (dev_rect.h), in the product's order */
 #include "../../cavif_rs_amd/csrc/tile_entropy.h"
 
 // per stream: sinfo[8 * s + ...] = first buffer in `bufs`, buffer count, pre-carry capacity, output capacity; bufs[2 * b] = first record, bufs[2 * b + 1] = count
