@@ -5,7 +5,7 @@ There is no CPU fallback: importing works anywhere, encoding requires a HIP devi
 """
 from .encoder import (Encoder, EncodedImage, AvifError, BatchEncoder, quality_to_quantizer, tweaks_from_preset,
                       rgb_to_ycbcr, encode_planes, encode_many, library_path, load_library, device_count,
-                      decode_jpeg, load_rgba)
+                      decode_jpeg, load_rgba, parse_jpeg, JpegCoeffs)
 
 __all__ = ['Encoder', 'EncodedImage', 'AvifError', 'BatchEncoder', 'quality_to_quantizer', 'tweaks_from_preset',
-           'rgb_to_ycbcr', 'encode_planes', 'encode_many', 'library_path', 'load_library', 'device_count', 'decode_jpeg', 'load_rgba']
+           'rgb_to_ycbcr', 'encode_planes', 'encode_many', 'library_path', 'load_library', 'device_count', 'decode_jpeg', 'load_rgba', 'parse_jpeg', 'JpegCoeffs']

@@ -1,9 +1,10 @@
 // cavif_mi -- the cavif command line (src/main.rs) on top of libmi_avif.so: same flags, path rules and report line;
 // the rayon fan-out over files (src/main.rs:223) becomes mi_ravif_encode_batch (one host thread per MI355X).
 //   cavif_mi [-Q n] [-s n] [-j n] [-f] [-o path] [-q] [--dirty-alpha] [--color ycbcr|rgb] [--depth 8|10|auto] IMAGES...
-// Input: PNG and baseline / progressive 8-bit JPEG, told apart by their first bytes as load_image does (mi_image_decode_rgba; a JPEG's Huffman decoding
-// runs in the loader thread, the rest of its decoding on the GPU).  Differences, deliberate: `--devices a,b,..` selects HIP devices (default: all), and
-// there is no CPU fallback -- without a GPU every file fails loudly.
+// Input: PNG and baseline / progressive 8-bit JPEG, told apart by their first bytes as load_image does.  A PNG is decoded in its loader thread
+// (mi_image_decode_rgba); of a JPEG the loader does the Huffman decoding (mi_jpeg_parse) and hands the coefficients to the encoder, which finishes
+// the picture on the GPU inside the batch that encodes it (mi_ravif_encode_sources): the loaders never touch a device.  Differences, deliberate:
+// `--devices a,b,..` selects HIP devices (default: all), and there is no CPU fallback -- without a GPU every file fails loudly.
 #include <sched.h>
 #include <sys/stat.h>
 #include <cerrno>
@@ -201,18 +202,19 @@ int main(int argc, char **argv) {
   enc.threads = threads > 0 ? threads : host_threads();
 
   // load + decide output paths (process(), :169-200); failures are collected per file and reported at the end
-  struct Job { std::string in_name, out_path; bool out_stdio = false; uint8_t *rgba = nullptr; uint32_t w = 0, h = 0; std::string error; };
+  struct Job { std::string in_name, out_path; bool out_stdio = false; uint8_t *rgba = nullptr; mi_jpeg_coeffs *jpeg = nullptr; uint32_t w = 0, h = 0; std::string error; };
   std::vector<Job> jobs(files.size());
-  // the reference loads inside files.into_par_iter() (src/main.rs:223): file reads + PNG / JPEG entropy decodes fan out over the host cores; `dev` is the
-  // HIP device that finishes a JPEG (dequantisation, IDCT, upsampling, colour)
-  auto load = [&](size_t i, int dev) {
+  // the reference loads inside files.into_par_iter() (src/main.rs:223): file reads + PNG / JPEG entropy decodes fan out over the host cores; a JPEG leaves
+  // its loader as coefficients (dequantisation, IDCT, upsampling and colour run on the device that encodes it)
+  auto load = [&](size_t i) {
     Job &j = jobs[i]; const Input &in = files[i];
     j.in_name = in.is_stdio ? "stdin" : in.path;
     std::vector<uint8_t> data;
     if (in.is_stdio) { if (!read_all(stdin, data)) j.error = "Unable to read stdin"; }
     else { FILE *f = fopen(in.path.c_str(), "rb"); if (!f || !read_all(f, data)) j.error = "Unable to read input image " + in.path + ": " + strerror(errno); if (f) fclose(f); }
     if (j.error.empty()) {
-      const int st = mi_image_decode_rgba(data.data(), data.size(), dev, &j.rgba, &j.w, &j.h);
+      const bool is_jpeg = data.size() >= 2 && data[0] == 0xFF && data[1] == 0xD8;
+      const int st = is_jpeg ? mi_jpeg_parse(data.data(), data.size(), &j.jpeg, &j.w, &j.h) : mi_image_decode_rgba(data.data(), data.size(), 0, &j.rgba, &j.w, &j.h);
       if (st) j.error = st == MI_UNSUPPORTED ? "unsupported image format (this build reads PNG and baseline/progressive 8-bit JPEG)" :
                         st == MI_NO_DEVICE ? "no HIP device (this encoder has no CPU fallback)" : "corrupt image data";
     }
@@ -237,45 +239,43 @@ int main(int argc, char **argv) {
   size_t released = 0;                                              // guarded by mu: images the encoder is done reading (or that failed to load)
   std::atomic<size_t> next{ 0 };
   std::vector<std::thread> pool;
-  // loader t decodes its JPEGs on device devices[t % ndev]; without --devices that is device t % (count of visible devices) once the count is known and device 0
-  // until then (the loaders do not wait for the runtime to come up)
-  std::atomic<int> ndev_visible{ 0 };
-  auto loader = [&](size_t t) {
+  auto loader = [&]() {
     for (size_t i; (i = next.fetch_add(1)) < files.size();) {
       { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return i < released + window; }); }
-      const int nv = ndev_visible.load();
-      load(i, !devices.empty() ? devices[t % devices.size()] : nv > 0 ? (int)(t % (size_t)nv) : 0);
+      load(i);
       { std::lock_guard<std::mutex> lk(mu); loaded[i] = 1; if (!jobs[i].error.empty()) released++; }
       cv.notify_all();
     }
   };
-  for (size_t t = 0; t < nw; t++) pool.emplace_back(loader, t);
+  for (size_t t = 0; t < nw; t++) pool.emplace_back(loader);
   struct Ctx { std::vector<Job> *jobs; std::mutex *mu; std::condition_variable *cv; std::vector<char> *loaded; size_t *released; } ctx{ &jobs, &mu, &cv, &loaded, &released };
-  auto fetch = [](void *user, size_t i, mi_image_desc *d) -> int {
+  auto fetch = [](void *user, size_t i, mi_image_source *src) -> int {
     Ctx *c = (Ctx *)user;
     { std::unique_lock<std::mutex> lk(*c->mu); c->cv->wait(lk, [&] { return (*c->loaded)[i] != 0; }); }
     const Job &j = (*c->jobs)[i];
     if (!j.error.empty()) return MI_INVALID_ARGUMENT;           // reported from the job's own message below
-    d->pixels = j.rgba; d->width = j.w; d->height = j.h; d->stride_px = j.w; d->channels = 4;
+    src->kind = j.jpeg ? 1 : 0; src->jpeg = j.jpeg;
+    mi_image_desc *d = &src->desc;
+    d->pixels = j.rgba; d->width = j.w; d->height = j.h; d->stride_px = j.w; d->channels = 4;     // a JPEG into an RGBA slot: the pixels load_rgba gives it
     return MI_OK;
   };
   auto release = [](void *user, size_t i) {
     Ctx *c = (Ctx *)user;
     Job &j = (*c->jobs)[i];
     mi_free(j.rgba); j.rgba = nullptr;
+    mi_jpeg_coeffs_free(j.jpeg); j.jpeg = nullptr;
     { std::lock_guard<std::mutex> lk(*c->mu); (*c->released)++; }
     c->cv->notify_all();
   };
   std::vector<mi_encoded_image> enc_out(jobs.size()); std::vector<int> status(jobs.size(), MI_OK);
   if (timing) fprintf(stderr, "[timing] setup %.3f s (tile target bounded by %d threads)\n", now_s() - t_start, enc.threads);
   const size_t ndev_used = devices.empty() ? (size_t)std::max(1, mi_device_count()) : devices.size();      // brings the HIP runtime up while the loaders run
-  if (devices.empty()) ndev_visible = (int)ndev_used;
   const size_t nw_all = std::min<size_t>(files.size(), std::min<size_t>(loaders_cap, getenv("CAVIF_MI_LOADERS") ? nw : loaders_per_device * (ndev_used + 1)));
   { std::lock_guard<std::mutex> lk(mu); window = 4 * 32 * ndev_used + nw_all; }
-  for (size_t t = nw; t < nw_all; t++) pool.emplace_back(loader, t);
+  for (size_t t = nw; t < nw_all; t++) pool.emplace_back(loader);
   cv.notify_all();
   if (timing) fprintf(stderr, "[timing] HIP runtime up %.3f s\n", now_s() - t_start);
-  const int rc_all = mi_ravif_encode_stream(&enc, jobs.size(), fetch, release, &ctx, enc_out.data(), status.data(), devices.empty() ? nullptr : devices.data(), (int)devices.size());
+  const int rc_all = mi_ravif_encode_sources(&enc, jobs.size(), fetch, release, &ctx, enc_out.data(), status.data(), devices.empty() ? nullptr : devices.data(), (int)devices.size());
   for (auto &t : pool) t.join();
   if (timing) fprintf(stderr, "[timing] encoded %.3f s\n", now_s() - t_start);
   if (rc_all == MI_NO_DEVICE) for (size_t i = 0; i < jobs.size(); i++) if (jobs[i].error.empty()) status[i] = MI_NO_DEVICE;
@@ -302,6 +302,7 @@ int main(int argc, char **argv) {
   int failures = 0;
   for (Job &j : jobs) {
     if (j.rgba) mi_free(j.rgba);
+    mi_jpeg_coeffs_free(j.jpeg);
     if (!j.error.empty()) { failures++; if (!quiet) fprintf(stderr, "error: %s: error: %s\n", j.in_name.c_str(), j.error.c_str()); }
   }
   // every output is on disk: leave without the HIP runtime's teardown (freeing pinned staging and contexts costs ~0.3 s)

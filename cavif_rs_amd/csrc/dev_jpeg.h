@@ -3,12 +3,13 @@
 //   jpeg_idct_kernel  dequantise + the "islow" 8x8 inverse DCT (CONST_BITS 13, PASS1_BITS 2: column pass descaled by 11 bits, row pass by 18, round half
 //                     up, +128, clamp) -> one uint8 plane per component over the MCU-padded block grid
 //   jpeg_rgba_kernel  "fancy" (triangle) chroma upsampling 2x1 / 2x2 with edge samples replicated, then YCbCr -> RGB in 16.16 fixed point
-//                     (or a copy for grey / RGB files), alpha 255
+//                     (or a copy for grey / RGB files), alpha 255; jpeg_rgb_kernel is the same code storing packed RGB8 (3-channel batches)
 // libjpeg computes the IDCT in 64-bit long; here products and sums are uint32_t (wrapping) and only the descale shifts see them as int32_t: identical
 // whenever libjpeg's values fit 32 bits, which they do for every encoder-made file, and some defined value for hostile coefficients.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "dev_ingest.h"
 
 namespace mi {
 
@@ -125,9 +126,10 @@ __device__ __forceinline__ void jpeg_chroma4(const uint8_t *plane, const size_t 
   }
 }
 
-// planes -> RGBA8 rows of stride_px pixels at a device pointer; one thread = four adjacent pixels = one 16-byte store (vec16: the destination rows are
-// 16-byte aligned; otherwise, and for the pixels of a last partial group, 4-byte stores)
-__global__ void __launch_bounds__(64) jpeg_rgba_kernel(const uint8_t *planes, const JpegDevGeom g, uint8_t *rgba, const size_t stride_px, const int vec16) {
+// planes -> RGBA8 (DC 4) or RGB8 (DC 3) rows of stride_px pixels at a device pointer; one thread = four adjacent pixels = one 16-byte store or three
+// dword stores (vec: the destination rows are 16-byte / 4-byte aligned; otherwise, and for the pixels of a last partial group, slot_store4's narrow
+// stores).  The one implementation of the upsampling and colour arithmetic; the two kernels below differ in the store alone.
+template <int DC> __device__ __forceinline__ void jpeg_colour4(const uint8_t *planes, const JpegDevGeom &g, uint8_t *out, const size_t stride_px, const int vec) {
   const uint32_t x0 = (blockIdx.x * 64 + threadIdx.x) * 4, y = blockIdx.y;
   if (x0 >= g.w || y >= g.h) return;
   const uint32_t yv = *(const uint32_t *)(planes + g.plane_off[0] + (size_t)y * ((size_t)g.bw[0] * 8) + x0);
@@ -147,9 +149,14 @@ __global__ void __launch_bounds__(64) jpeg_rgba_kernel(const uint8_t *planes, co
       px[k] = r | (gg << 8) | (b << 16) | 0xFF000000u;
     }
   } else for (int k = 0; k < 4; k++) px[k] = (uint32_t)c0[k] * 0x010101u | 0xFF000000u;
-  uint8_t *dst = rgba + ((size_t)y * stride_px + x0) * 4;
-  if (vec16 && x0 + 3 < g.w) { uint4 v; v.x = px[0]; v.y = px[1]; v.z = px[2]; v.w = px[3]; *(uint4 *)dst = v; }
-  else for (uint32_t k = 0; k < 4 && x0 + k < g.w; k++) ((uint32_t *)dst)[k] = px[k];
+  slot_store4<DC>(out + ((size_t)y * stride_px + x0) * DC, px, g.w - x0 < 4 ? g.w - x0 : 4, vec != 0);
+}
+__global__ void __launch_bounds__(64) jpeg_rgba_kernel(const uint8_t *planes, const JpegDevGeom g, uint8_t *rgba, const size_t stride_px, const int vec16) {
+  jpeg_colour4<4>(planes, g, rgba, stride_px, vec16);
+}
+// the same pixels without their alpha byte, for 3-channel batches: 12 bytes per thread (vec4: every destination row is 4-byte aligned)
+__global__ void __launch_bounds__(64) jpeg_rgb_kernel(const uint8_t *planes, const JpegDevGeom g, uint8_t *rgb, const size_t stride_px, const int vec4) {
+  jpeg_colour4<3>(planes, g, rgb, stride_px, vec4);
 }
 
 }  // namespace mi

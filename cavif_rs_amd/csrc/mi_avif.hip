@@ -53,6 +53,10 @@ struct mi_batch {
   std::vector<std::vector<uint8_t>> files; std::vector<size_t> color_sz, alpha_sz;
   hipEvent_t ev[8]{}; double stage_ms[8]{};
   bool in_flight = false;
+  // device-resident input (made on the first use): the event a producer's stream is joined through, and the JPEG staging -- quantisation tables + coefficients
+  // of the images uploaded since the stream last drained, pinned and on the device, and one image's component planes
+  hipEvent_t ev_src = nullptr;
+  PinBuf<uint8_t> h_jpeg; DevBuf<uint8_t> d_jpeg, d_jpeg_planes; size_t h_jpeg_cap = 0, d_jpeg_cap = 0, d_jpeg_planes_cap = 0, jpeg_used = 0;
 };
 
 static void batch_plan(mi_batch *b) {
@@ -260,6 +264,7 @@ int mi_batch_wait(mi_batch *b) {
   const int njobs = (int)b->fs.jobs.size();
   std::vector<uint32_t> offsets(njobs);
   HIP_OK(hipStreamSynchronize(s));
+  b->jpeg_used = 0;                                            // every JPEG upload of the run has left the pinned staging
   if (b->channels == 4) for (int i = 0; i < b->n; i++) b->alpha_flags[i] = b->h_alpha.get()[i];
   auto idle = [&](const FramePlan &p) { return p.is_alpha && !b->alpha_flags[p.image]; };
   if (int st = b->fs.check_lengths()) return st;
@@ -331,8 +336,10 @@ void mi_batch_destroy(mi_batch *b) {
   (void)hipSetDevice(b->device);
   const hipStream_t stream = b->stream;
   hipEvent_t ev[8]; memcpy(ev, b->ev, sizeof(ev));
+  const hipEvent_t ev_src = b->ev_src;
   delete b;                                                        // the buffers first: hipFree waits for the device, so an abandoned run has let go of the events and the stream
   for (int i = 0; i < 8; i++) if (ev[i]) (void)hipEventDestroy(ev[i]);
+  if (ev_src) (void)hipEventDestroy(ev_src);
   if (stream) (void)hipStreamDestroy(stream);
 }
 
@@ -353,7 +360,7 @@ static PoolKey pool_key(const mi_ravif_encoder *e, int cap, uint32_t w, uint32_t
 }
 static std::mutex g_pool_mu;
 static std::vector<std::pair<PoolKey, mi_batch *>> g_pool;          // oldest first; never destroyed at process exit (the runtime may be gone by then)
-static size_t batch_footprint(const mi_batch *b) { return b->fs.arena_bytes + b->fs.aux_bytes + 3 * b->pixel_bytes + b->packed_cap; }
+static size_t batch_footprint(const mi_batch *b) { return b->fs.arena_bytes + b->fs.aux_bytes + 3 * b->pixel_bytes + b->packed_cap + b->h_jpeg_cap + b->d_jpeg_cap + b->d_jpeg_planes_cap; }
 static constexpr size_t MI_POOL_MAX_ITEMS = 8, MI_POOL_MAX_BYTES = (size_t)32 << 30;     // what the one-call entry points may keep between calls (mi_release_cached() frees it)
 
 static mi_batch *pool_acquire(const mi_ravif_encoder *e, int cap, uint32_t w, uint32_t h, int channels) {
@@ -474,12 +481,14 @@ int mi_png_decode_rgba(const uint8_t *data, size_t len, uint8_t **rgba, uint32_t
   } catch (const std::exception &) { return MI_ENCODING_ERROR; }
 }
 
-// The seam of the JPEG path: coefficients of one parsed file -> RGBA8 rows of stride_px pixels at a DEVICE pointer, on `stream`.  Pinned staging of the
-// quantisation tables + coefficients, one H2D, the two kernels of dev_jpeg.h, no sync (probe builds with MI_AVIF_TIMING sync between the steps to time
-// them).  Its own function so that a caller can point d_rgba at memory that is consumed on the device (a batch's HBM input slot) instead of a buffer
-// that goes back to the host.  The caller has made `device` current and owns ctx until the stream has drained.
-static int jpeg_decode_to_device(const JpegCoeffs &jc, int device, uint8_t *d_rgba, size_t stride_px, hipStream_t stream, JpegCtx &ctx, double *step_ms) {
-  (void)device;
+// The seam of the JPEG path: coefficients of one parsed file -> RGBA8 (channels 4) or RGB8 (channels 3) rows of stride_px pixels at a DEVICE pointer, on
+// `stream`.  h_in (pinned) and d_in hold jpeg_in_bytes(jc), d_planes jpeg_plane_bytes(jc): quantisation tables + coefficients are copied to h_in, then one
+// H2D and the two kernels of dev_jpeg.h, no sync (probe builds with MI_AVIF_TIMING sync between the steps to time them).  Its own function so that d_out
+// can be memory that is consumed on the device (a batch's HBM input slot: mi_batch_upload_jpeg) or a buffer that goes back to the host
+// (mi_jpeg_decode_rgba).  The caller has made the device current and keeps h_in untouched until the stream has passed the copy.
+static size_t jpeg_in_bytes(const JpegCoeffs &jc) { return 3 * 64 * sizeof(uint16_t) + jc.nblocks * 64 * sizeof(int16_t); }
+static size_t jpeg_plane_bytes(const JpegCoeffs &jc) { return jc.nblocks * 64; }
+static int jpeg_decode_to_device(const JpegCoeffs &jc, uint8_t *h_in, uint8_t *d_in, uint8_t *d_planes, uint8_t *d_out, int channels, size_t stride_px, hipStream_t stream, double *step_ms) {
   JpegDevGeom g; memset(&g, 0, sizeof(g));
   g.w = jc.w; g.h = jc.h; g.ncomp = (uint32_t)jc.ncomp; g.color = (uint32_t)jc.color; g.nblocks = (uint32_t)jc.nblocks;
   for (int c = 0; c < 3; c++) {
@@ -490,9 +499,7 @@ static int jpeg_decode_to_device(const JpegCoeffs &jc, int device, uint8_t *d_rg
     g.bw[c] = k.bw; g.bh[c] = k.bh; g.cw[c] = k.cw; g.ch[c] = k.ch;
   }
   g.hr = jc.ncomp == 3 ? (uint32_t)(jc.comp[0].h / jc.comp[1].h) : 1; g.vr = jc.ncomp == 3 ? (uint32_t)(jc.comp[0].v / jc.comp[1].v) : 1;
-  const size_t quant_bytes = 3 * 64 * sizeof(uint16_t), in_bytes = quant_bytes + jc.nblocks * 64 * sizeof(int16_t);
-  if (!jpeg_grow(ctx.h_in, ctx.h_in_cap, in_bytes) || !jpeg_grow(ctx.d_in, ctx.d_in_cap, in_bytes) || !jpeg_grow(ctx.d_planes, ctx.d_planes_cap, jc.nblocks * 64)) return MI_ENCODING_ERROR;
-  uint8_t *const h_in = ctx.h_in.get(), *const d_in = ctx.d_in.get(), *const d_planes = ctx.d_planes.get();
+  const size_t quant_bytes = 3 * 64 * sizeof(uint16_t), in_bytes = jpeg_in_bytes(jc);
   const auto t0 = std::chrono::steady_clock::now();
   memset(h_in, 0, quant_bytes);
   for (int c = 0; c < jc.ncomp; c++) memcpy(h_in + c * 64 * sizeof(uint16_t), jc.comp[c].quant, 64 * sizeof(uint16_t));
@@ -502,8 +509,14 @@ static int jpeg_decode_to_device(const JpegCoeffs &jc, int device, uint8_t *d_rg
   lap(0);
   hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((jc.nblocks + MI_JPEG_IDCT_BLOCKS - 1) / MI_JPEG_IDCT_BLOCKS)), dim3(256), 0, stream,
                      (const int16_t *)(d_in + quant_bytes), (const uint16_t *)d_in, g, d_planes);
-  const int vec16 = (stride_px % 4 == 0 && ((uintptr_t)d_rgba & 15) == 0) ? 1 : 0;
-  hipLaunchKernelGGL(jpeg_rgba_kernel, dim3(((jc.w + 3) / 4 + 63) / 64, jc.h), dim3(64), 0, stream, (const uint8_t *)d_planes, g, d_rgba, stride_px, vec16);
+  const dim3 grid(((jc.w + 3) / 4 + 63) / 64, jc.h);
+  if (channels == 4) {
+    const int vec16 = (stride_px % 4 == 0 && ((uintptr_t)d_out & 15) == 0) ? 1 : 0;
+    hipLaunchKernelGGL(jpeg_rgba_kernel, grid, dim3(64), 0, stream, (const uint8_t *)d_planes, g, d_out, stride_px, vec16);
+  } else {
+    const int vec4 = (stride_px % 4 == 0 && ((uintptr_t)d_out & 3) == 0) ? 1 : 0;        // a row is 3 * stride_px bytes
+    hipLaunchKernelGGL(jpeg_rgb_kernel, grid, dim3(64), 0, stream, (const uint8_t *)d_planes, g, d_out, stride_px, vec4);
+  }
   HIP_OK(hipGetLastError());
   lap(1);
   return MI_OK;
@@ -512,7 +525,8 @@ static int jpeg_decode_to_device(const JpegCoeffs &jc, int device, uint8_t *d_rg
 static int jpeg_decode_with(JpegCtx &ctx, const JpegCoeffs &jc, uint8_t *dst, double *step_ms) {
   const size_t out_bytes = (size_t)jc.w * jc.h * 4;
   if (!jpeg_grow(ctx.d_rgba, ctx.d_rgba_cap, out_bytes) || !jpeg_grow(ctx.h_rgba, ctx.h_rgba_cap, out_bytes)) return MI_ENCODING_ERROR;
-  const int st = jpeg_decode_to_device(jc, ctx.device, ctx.d_rgba.get(), jc.w, ctx.stream, ctx, step_ms);
+  if (!jpeg_grow(ctx.h_in, ctx.h_in_cap, jpeg_in_bytes(jc)) || !jpeg_grow(ctx.d_in, ctx.d_in_cap, jpeg_in_bytes(jc)) || !jpeg_grow(ctx.d_planes, ctx.d_planes_cap, jpeg_plane_bytes(jc))) return MI_ENCODING_ERROR;
+  const int st = jpeg_decode_to_device(jc, ctx.h_in.get(), ctx.d_in.get(), ctx.d_planes.get(), ctx.d_rgba.get(), 4, jc.w, ctx.stream, step_ms);
   if (st) { (void)hipStreamSynchronize(ctx.stream); return st; }
   const auto t0 = std::chrono::steady_clock::now();
   HIP_OK(hipMemcpyAsync(ctx.h_rgba.get(), ctx.d_rgba.get(), out_bytes, hipMemcpyDeviceToHost, ctx.stream));
@@ -560,13 +574,106 @@ int mi_image_decode_rgba(const uint8_t *data, size_t len, int device, uint8_t **
   return MI_UNSUPPORTED;
 }
 
+// ---- device-resident input: a picture reaches a batch's HBM input slot without ever being host pixels ----
+struct mi_jpeg_coeffs { JpegCoeffs jc; };
+
+// jpeg_read_coeffs behind a handle: host work only, the statuses mi_jpeg_decode_rgba gives for the same bytes
+int mi_jpeg_parse(const uint8_t *data, size_t len, mi_jpeg_coeffs **out, uint32_t *w, uint32_t *h) {
+  if (!data || !out || !w || !h) return MI_INVALID_ARGUMENT;
+  *out = nullptr;
+  try {                                                       // nothing may unwind through the C ABI
+    std::unique_ptr<mi_jpeg_coeffs> c(new mi_jpeg_coeffs);
+    if (const int st = jpeg_read_coeffs(data, len, c->jc)) return st;
+    *w = c->jc.w; *h = c->jc.h;
+    *out = c.release();
+    return MI_OK;
+  } catch (const std::exception &) { return MI_ENCODING_ERROR; }
+}
+void mi_jpeg_coeffs_free(mi_jpeg_coeffs *c) { delete c; }
+
+uint8_t *mi_batch_device_input(mi_batch *b, int index) {
+  if (!b || index < 0 || index >= b->cap) return nullptr;
+  return b->d_pixels.get() + (size_t)index * b->w * b->h * b->channels;
+}
+int mi_batch_read_input(mi_batch *b, int index, uint8_t *dst) {
+  if (!b || !dst || index < 0 || index >= b->cap) return MI_INVALID_ARGUMENT;
+  (void)hipSetDevice(b->device);
+  HIP_OK(hipStreamSynchronize(b->stream));
+  HIP_OK(hipMemcpy(dst, mi_batch_device_input(b, index), (size_t)b->w * b->h * b->channels, hipMemcpyDeviceToHost));
+  return MI_OK;
+}
+
+// images [first, first + count) from pictures in the memory of the batch's device: one ingest_kernel launch on the batch's stream, after whatever
+// src->after_stream holds at this moment.  Strides of 0 mean packed; a row must not be shorter than its packed pixels (torch views -- crops, permuted
+// tensors, padded rows -- all satisfy that).
+int mi_batch_upload_device(mi_batch *b, int first, int count, const mi_device_pixels *src) {
+  if (!b || !src || !src->dev || b->in_flight || first < 0 || count < 1 || first > b->cap - count) return MI_INVALID_ARGUMENT;
+  if ((src->layout != 0 && src->layout != 1) || (src->channels != 3 && src->channels != 4) || src->channels > b->channels) return MI_INVALID_ARGUMENT;   // alpha is never dropped
+  IngestSrc s;
+  s.base = (const uint8_t *)src->dev; s.w = b->w; s.h = b->h; s.layout = src->layout; s.channels = src->channels;
+  const size_t packed_row = (size_t)b->w * (s.layout == 0 ? s.channels : 1);
+  s.row_stride = src->row_stride ? src->row_stride : packed_row;
+  s.inner_stride = src->pixel_or_plane_stride ? src->pixel_or_plane_stride : s.layout == 0 ? (size_t)s.channels : s.row_stride * b->h;
+  s.image_stride = src->image_stride ? src->image_stride : s.layout == 0 ? s.row_stride * b->h : s.inner_stride * s.channels;
+  if (s.row_stride < packed_row || s.inner_stride < (s.layout == 0 ? (size_t)s.channels : (size_t)b->w)) return MI_INVALID_ARGUMENT;
+  (void)hipSetDevice(b->device);
+  if (src->after_stream) {
+    if (!b->ev_src) HIP_OK(hipEventCreateWithFlags(&b->ev_src, hipEventDisableTiming));
+    HIP_OK(hipEventRecord(b->ev_src, (hipStream_t)src->after_stream));
+    HIP_OK(hipStreamWaitEvent(b->stream, b->ev_src, 0));
+  }
+  const dim3 grid(((b->w + 3) / 4 + 63) / 64, b->h, (unsigned)count);
+  uint8_t *const slots = mi_batch_device_input(b, first);
+  if (b->channels == 4) hipLaunchKernelGGL((ingest_kernel<4>), grid, dim3(64), 0, b->stream, s, slots);
+  else hipLaunchKernelGGL((ingest_kernel<3>), grid, dim3(64), 0, b->stream, s, slots);
+  HIP_OK(hipGetLastError());
+  return MI_OK;
+}
+
+// One parsed JPEG into the slot of image `index`: tables + coefficients into the batch's own pinned staging, one H2D and the two kernels of
+// jpeg_decode_to_device on the batch's stream, no sync.  The staging keeps the images uploaded since the stream last drained (room for
+// MI_BATCH_JPEG_STAGED of the first one's size; when the next one does not fit, the stream -- which carries nothing but such uploads then -- is waited
+// for and the staging starts over); the plane buffer is one image's, stream order serialises its users.
+static constexpr size_t MI_BATCH_JPEG_STAGED = 4;
+int mi_batch_upload_jpeg(mi_batch *b, int index, const mi_jpeg_coeffs *c) {
+  if (!b || !c || b->in_flight || index < 0 || index >= b->cap) return MI_INVALID_ARGUMENT;
+  const JpegCoeffs &jc = c->jc;
+  if (jc.w != b->w || jc.h != b->h) return MI_INVALID_ARGUMENT;
+  (void)hipSetDevice(b->device);
+  const size_t need = align_up(jpeg_in_bytes(jc), 256);
+  if (b->jpeg_used + need > b->h_jpeg_cap) {
+    HIP_OK(hipStreamSynchronize(b->stream));
+    b->jpeg_used = 0;
+    if (!jpeg_grow(b->h_jpeg, b->h_jpeg_cap, MI_BATCH_JPEG_STAGED * need) || !jpeg_grow(b->d_jpeg, b->d_jpeg_cap, MI_BATCH_JPEG_STAGED * need)) return MI_ENCODING_ERROR;
+  }
+  if (jpeg_plane_bytes(jc) > b->d_jpeg_planes_cap) {
+    HIP_OK(hipStreamSynchronize(b->stream));                  // an earlier image's kernels may still read the buffer that is replaced
+    if (!jpeg_grow(b->d_jpeg_planes, b->d_jpeg_planes_cap, jpeg_plane_bytes(jc))) return MI_ENCODING_ERROR;
+  }
+  const size_t at = b->jpeg_used; b->jpeg_used += need;
+  return jpeg_decode_to_device(jc, b->h_jpeg.get() + at, b->d_jpeg.get() + at, b->d_jpeg_planes.get(), mi_batch_device_input(b, index), b->channels, b->w, b->stream, nullptr);
+}
+
+// ravif::Encoder::encode_rgba / encode_rgb for a picture in the memory of device e->device (channels 4 / 3 as src->channels says)
+int mi_ravif_encode_device(const mi_ravif_encoder *e, const mi_device_pixels *src, uint32_t w, uint32_t h, mi_encoded_image *out) {
+  if (!e || !src || !src->dev || !out || w < 1 || h < 1 || (src->channels != 3 && src->channels != 4)) return MI_INVALID_ARGUMENT;
+  mi_batch *b = pool_acquire(e, 1, w, h, src->channels);
+  if (!b) return mi_device_count() > e->device ? MI_INVALID_ARGUMENT : MI_NO_DEVICE;
+  int st = mi_batch_upload_device(b, 0, 1, src);
+  if (st == MI_OK) st = mi_batch_encode(b);
+  if (st == MI_OK) st = mi_batch_get(b, 0, out);
+  pool_release(b);
+  return st;
+}
+
 // The reference's files.into_par_iter() (src/main.rs:223) over the GPUs of one node: images are independent, so a host
 // thread per device pulls runs of equally-shaped images from a shared cursor and pushes each run through one resident
 // batch (no collective, no cross-device traffic).  status[i] receives the per-image result; returns the first failure.
 // Streaming form of the fan-out: image i is obtained through `fetch(user, i, &desc)` when a worker is about to stage it (the
 // call may block until the pixels exist -- e.g. until a loader thread has decoded the file), so loading, upload, encoding and
-// assembly of consecutive runs overlap.  fetch returns MI_OK or a status that becomes the image's status.
-int mi_ravif_encode_stream(const mi_ravif_encoder *e, size_t n, mi_fetch_fn fetch, mi_release_fn release, void *user, mi_encoded_image *out, int *status, const int *devices, int ndev) {
+// assembly of consecutive runs overlap.  fetch returns MI_OK or a status that becomes the image's status.  An image is host pixels (kind 0) or the
+// coefficients of a parsed JPEG (kind 1), whose pixels come into being in the batch's HBM input slot; mi_ravif_encode_stream is this with kind 0 throughout.
+int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source_fn fetch, mi_release_fn release, void *user, mi_encoded_image *out, int *status, const int *devices, int ndev) {
   if (!e || !fetch || (n && !out)) return MI_INVALID_ARGUMENT;
   const int have = mi_device_count();
   std::vector<int> devs;
@@ -588,6 +695,8 @@ int mi_ravif_encode_stream(const mi_ravif_encoder *e, size_t n, mi_fetch_fn fetc
   // shapes it has not used for the longest time until the total stays under its budget (a share of the device's free memory at the start).
   constexpr size_t MI_SLOT_BYTES = (size_t)8 << 30;
   auto est_bytes = [](uint32_t w, uint32_t h, int ch, size_t images) { return images * (size_t)w * h * (ch == 4 ? 110 : 82) + ((size_t)32 << 20); };   // arena + records + staging per pixel (measured on the planner)
+  // what a batch object adds at its first JPEG image: MI_BATCH_JPEG_STAGED images' coefficients (at most three full planes of int16) pinned and on the device, one image's planes
+  auto est_jpeg_bytes = [](uint32_t w, uint32_t h) { return ((size_t)w + 15) * ((size_t)h + 15) * (2 * MI_BATCH_JPEG_STAGED * 6 + 3) + ((size_t)3 << 20); };
   auto worker = [&](int dev) {
     mi_ravif_encoder enc = *e; enc.device = dev;
     std::future<int> warm = std::async(std::launch::async, [dev]() { return hipSetDevice(dev) == hipSuccess ? ensure_tables(dev) : (int)MI_ENCODING_ERROR; });
@@ -596,7 +705,7 @@ int mi_ravif_encode_stream(const mi_ravif_encoder *e, size_t n, mi_fetch_fn fetc
     { int sharing = 0; for (int d2 : devs) sharing += d2 == dev; budget /= (size_t)std::max(1, sharing); }      // workers on the same ordinal (devices = [0, 0]) split what is free
     static constexpr int NSLOT_MAX = 4;
     const int NSLOT = MI_STREAM_SLOTS_DEFAULT;
-    struct Slot { mi_batch *b = nullptr; std::future<mi_batch *> making; std::vector<size_t> idx; bool busy = false; size_t bytes = 0; };
+    struct Slot { mi_batch *b = nullptr; std::future<mi_batch *> making; std::vector<size_t> idx; bool busy = false, jpeg = false; size_t bytes = 0; };
     struct Shape { uint32_t w, h; int ch; size_t cap; Slot slot[NSLOT_MAX]; int next = 0; size_t runs = 0, last_use = 0; };
     std::vector<std::unique_ptr<Shape>> shapes;
     size_t live_bytes = 0, tick = 0;
@@ -612,7 +721,7 @@ int mi_ravif_encode_stream(const mi_ravif_encoder *e, size_t n, mi_fetch_fn fetc
       collect(sl);
       if (sl.making.valid()) sl.b = sl.making.get();
       if (sl.b) mi_batch_destroy(sl.b);
-      sl.b = nullptr; live_bytes -= std::min(live_bytes, sl.bytes); sl.bytes = 0;
+      sl.b = nullptr; live_bytes -= std::min(live_bytes, sl.bytes); sl.bytes = 0; sl.jpeg = false;
     };
     auto make_room = [&](Shape *keep, size_t need) {
       while (live_bytes + need > budget) {
@@ -639,29 +748,39 @@ int mi_ravif_encode_stream(const mi_ravif_encoder *e, size_t n, mi_fetch_fn fetc
       return shapes.back().get();
     };
     // one run (<= the shape's capacity) through the shape's next slot
-    auto submit = [&](Shape *sh, const std::vector<mi_image_desc> &d, const std::vector<size_t> &run, size_t i0, bool more) {
-      const mi_image_desc &d0 = d[run[0]];
+    auto submit = [&](Shape *sh, const std::vector<mi_image_source> &d, const std::vector<size_t> &run, size_t i0, bool more) {
+      const mi_image_desc &d0 = d[run[0]].desc;
       sh->last_use = ++tick; sh->runs++;
       const int j = sh->next; sh->next = (j + 1) % NSLOT;
       Slot &sl = sh->slot[j];
       collect(sl);                                           // the slot's previous run, if any
       ensure_slot(sh, j);
       if (sl.making.valid()) sl.b = sl.making.get();
-      if (!sl.b) { live_bytes -= std::min(live_bytes, sl.bytes); sl.bytes = 0; }      // the object could not be made: nothing of it is resident
+      if (!sl.b) { live_bytes -= std::min(live_bytes, sl.bytes); sl.bytes = 0; sl.jpeg = false; }      // the object could not be made: nothing of it is resident
       int rc = sl.b ? mi_batch_set_count(sl.b, (int)run.size()) : MI_ENCODING_ERROR;
       if (timing) fprintf(stderr, "[mi_avif %8.1f ms] dev %d: slot %d ready\n", since(), dev, j);
       if (rc == MI_OK) {
+        // host images: pinned staging, then one H2D per stretch of neighbours (never across a JPEG image's slot: the staging there is stale).  JPEG images:
+        // coefficients to the batch's own staging, decoded into the slot on the batch's stream.
         const size_t row = (size_t)d0.width * d0.channels;
-        for (size_t k = 0; k < run.size(); k++) {
-          const mi_image_desc &x = d[run[k]];
+        size_t host_from = 0;
+        auto upload_host = [&](size_t end) { if (rc == MI_OK && end > host_from) rc = mi_batch_upload_async(sl.b, (int)host_from, (int)(end - host_from)); };
+        for (size_t k = 0; k < run.size() && rc == MI_OK; k++) {
+          const mi_image_source &src = d[run[k]];
+          if (src.kind == 1) {
+            upload_host(k); host_from = k + 1;
+            if (!sl.jpeg) { sl.jpeg = true; const size_t extra = est_jpeg_bytes(sh->w, sh->h); sl.bytes += extra; live_bytes += extra; }
+            if (rc == MI_OK) rc = mi_batch_upload_jpeg(sl.b, (int)k, src.jpeg);
+            continue;
+          }
+          const mi_image_desc &x = src.desc;
           uint8_t *dst = mi_batch_input(sl.b, (int)k);
           const size_t sp = x.stride_px ? x.stride_px : x.width;
           if (sp == x.width) memcpy(dst, x.pixels, row * d0.height);
           else for (uint32_t y = 0; y < d0.height; y++) memcpy(dst + y * row, x.pixels + (size_t)y * sp * d0.channels, row);
         }
-        if (timing) fprintf(stderr, "[mi_avif %8.1f ms] dev %d: slot %d staged\n", since(), dev, j);
-        rc = mi_batch_upload_async(sl.b, 0, (int)run.size());
-        if (timing) fprintf(stderr, "[mi_avif %8.1f ms] dev %d: slot %d upload enqueued\n", since(), dev, j);
+        upload_host(run.size());
+        if (timing) fprintf(stderr, "[mi_avif %8.1f ms] dev %d: slot %d staged, uploads enqueued\n", since(), dev, j);
       }
       if (release) for (size_t k : run) release(user, i0 + k);   // staged (or failed): the caller's pixels are no longer read
       if (rc == MI_OK) rc = mi_batch_encode_async(sl.b);
@@ -681,15 +800,17 @@ int mi_ravif_encode_stream(const mi_ravif_encoder *e, size_t n, mi_fetch_fn fetc
       const size_t i0 = cursor.fetch_add(want);                // claim the index range [i0, i1)
       if (i0 >= n) break;
       const size_t i1 = std::min(n, i0 + want);
-      std::vector<mi_image_desc> d(i1 - i0);
+      std::vector<mi_image_source> d(i1 - i0);
       // images are staged in arrival order: a run is handed over as soon as the next image has another shape or the run is full
       std::vector<size_t> run; Shape *run_shape = nullptr;
       auto flush = [&](bool more) { if (!run.empty()) { submit(run_shape, d, run, i0, more); run.clear(); } };
       for (size_t i = i0; i < i1; i++) {
         const int rc = fetch(user, i, &d[i - i0]);
-        const mi_image_desc &x = d[i - i0];
+        const mi_image_source &src = d[i - i0];
+        const mi_image_desc &x = src.desc;
         if (rc != MI_OK) { st[i] = rc; continue; }
-        if (!x.pixels || !x.width || !x.height || (x.channels != 3 && x.channels != 4)) { st[i] = MI_INVALID_ARGUMENT; if (release) release(user, i); continue; }
+        const bool have = src.kind == 0 ? x.pixels != nullptr : src.kind == 1 && src.jpeg && src.jpeg->jc.w == x.width && src.jpeg->jc.h == x.height;
+        if (!have || !x.width || !x.height || (x.channels != 3 && x.channels != 4)) { st[i] = MI_INVALID_ARGUMENT; if (release) release(user, i); continue; }
         Shape *sh = shape_for(x);
         if (sh != run_shape || run.size() >= sh->cap) flush(true);
         run_shape = sh; run.push_back(i - i0);
@@ -713,6 +834,15 @@ int mi_ravif_encode_stream(const mi_ravif_encoder *e, size_t n, mi_fetch_fn fetc
   int first = MI_OK;
   for (size_t i = 0; i < n; i++) { if (status) status[i] = st[i]; if (first == MI_OK && st[i] != MI_OK) first = st[i]; }
   return first;
+}
+// the host-pixel form: every source is kind 0
+struct StreamAdapter { mi_fetch_fn fetch; mi_release_fn release; void *user; };
+static int fetch_host_source(void *user, size_t i, mi_image_source *src) { const StreamAdapter *a = (const StreamAdapter *)user; src->kind = 0; src->jpeg = nullptr; return a->fetch(a->user, i, &src->desc); }
+static void release_host_source(void *user, size_t i) { const StreamAdapter *a = (const StreamAdapter *)user; a->release(a->user, i); }
+int mi_ravif_encode_stream(const mi_ravif_encoder *e, size_t n, mi_fetch_fn fetch, mi_release_fn release, void *user, mi_encoded_image *out, int *status, const int *devices, int ndev) {
+  if (!e || !fetch || (n && !out)) return MI_INVALID_ARGUMENT;
+  StreamAdapter a{ fetch, release, user };
+  return mi_ravif_encode_sources(e, n, fetch_host_source, release ? release_host_source : nullptr, &a, out, status, devices, ndev);
 }
 // The reference's files.into_par_iter() (src/main.rs:223) over the GPUs of one node with every image already in host memory.
 static int fetch_from_array(void *user, size_t i, mi_image_desc *d) { *d = ((const mi_image_desc *)user)[i]; return MI_OK; }

@@ -8,6 +8,7 @@ Out-of-range builder arguments raise (the Rust asserts at :117,146,159,188).
 """
 import ctypes as C
 import os
+import sys
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -42,6 +43,23 @@ class _RavifEncoder(C.Structure):
 
 class _EncodedImage(C.Structure):
     _fields_ = [('avif_file', C.POINTER(C.c_uint8)), ('avif_len', C.c_size_t), ('color_byte_size', C.c_size_t), ('alpha_byte_size', C.c_size_t)]
+
+
+class _ImageDesc(C.Structure):
+    _fields_ = [('pixels', C.c_void_p), ('width', C.c_uint32), ('height', C.c_uint32), ('stride_px', C.c_size_t), ('channels', C.c_int)]
+
+
+class _ImageSource(C.Structure):
+    _fields_ = [('kind', C.c_int), ('desc', _ImageDesc), ('jpeg', C.c_void_p)]
+
+
+class _DevicePixels(C.Structure):
+    _fields_ = [('dev', C.c_void_p), ('layout', C.c_int), ('channels', C.c_int), ('row_stride', C.c_size_t),
+                ('pixel_or_plane_stride', C.c_size_t), ('image_stride', C.c_size_t), ('after_stream', C.c_void_p)]
+
+
+_FETCH_SOURCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.POINTER(_ImageSource))
+_RELEASE = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t)
 
 
 def library_path():
@@ -93,6 +111,17 @@ def load_library():
     L.mi_free.argtypes = [C.c_void_p]
     for fn in (L.mi_jpeg_decode_rgba, L.mi_image_decode_rgba):
         fn.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.mi_jpeg_parse.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.mi_jpeg_coeffs_free.argtypes = [C.c_void_p]
+    L.mi_jpeg_coeffs_free.restype = None
+    L.mi_batch_device_input.argtypes = [C.c_void_p, C.c_int]
+    L.mi_batch_device_input.restype = C.c_void_p
+    L.mi_batch_read_input.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.mi_batch_upload_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(_DevicePixels)]
+    L.mi_batch_upload_jpeg.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.mi_ravif_encode_device.argtypes = [C.POINTER(_RavifEncoder), C.POINTER(_DevicePixels), C.c_uint32, C.c_uint32, C.POINTER(_EncodedImage)]
+    L.mi_ravif_encode_sources.argtypes = [C.POINTER(_RavifEncoder), C.c_size_t, _FETCH_SOURCE, _RELEASE, C.c_void_p, C.POINTER(_EncodedImage),
+                                          C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
     _LIB = L
     return L
 
@@ -142,6 +171,87 @@ def decode_jpeg(data, device=0):
 def load_rgba(data, device=0):
     """load_rgba (src/main.rs:255-283) for the formats this library reads: PNG (host) or JPEG (device `device`) bytes -> uint8 array (h, w, 4)."""
     return _decode(load_library().mi_image_decode_rgba, data, device)
+
+
+class JpegCoeffs:
+    """One parsed JPEG file (mi_jpeg_parse): quantised coefficients in host memory, `width`, `height`.  Feeds BatchEncoder.upload_jpeg and encode_many;
+    its pixels come into being on the device.  close() (or the garbage collector) frees it."""
+
+    def __init__(self, data):
+        L = load_library()
+        data = bytes(data)
+        h = C.c_void_p()
+        w, ht = C.c_uint32(), C.c_uint32()
+        st = L.mi_jpeg_parse(data, len(data), C.byref(h), C.byref(w), C.byref(ht))
+        if st:
+            raise AvifError(st)
+        self._L, self._h, self.width, self.height = L, h.value, w.value, ht.value
+
+    def close(self):
+        if getattr(self, '_h', None):
+            self._L.mi_jpeg_coeffs_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def parse_jpeg(data):
+    """mi_jpeg_parse: JPEG bytes -> JpegCoeffs (host work only: parse + Huffman decoding; raises AvifError as decode_jpeg does for the same bytes)."""
+    return JpegCoeffs(data)
+
+
+def _is_device_array(x):
+    return hasattr(x, '__cuda_array_interface__')
+
+
+def _device_pixels(x, batched=False):
+    """(_DevicePixels, images, height, width, device index or None) of an object with __cuda_array_interface__: uint8, (H, W, C) or (C, H, W) -- with
+    batched=True also (N, H, W, C) / (N, C, H, W) -- where C is 3 or 4 and either the channel or the column stride is one byte: contiguous tensors of
+    both layouts, crops, padded rows and permuted views of them.  (C, H, W) is taken when the first dimension is 3 or 4 and the last is not."""
+    ai = x.__cuda_array_interface__
+    if ai.get('typestr') != '|u1':
+        raise TypeError('device pixels must be uint8 (got typestr %r): rounding floats is the caller\'s decision' % (ai.get('typestr'),))
+    shape = tuple(int(v) for v in ai['shape'])
+    strides = ai.get('strides')
+    if strides is None:
+        strides, acc = [], 1
+        for n in reversed(shape):
+            strides.insert(0, acc); acc *= n
+    strides = tuple(int(v) for v in strides)
+    if len(shape) == 4 and batched:
+        n, img_stride, shape, strides = shape[0], strides[0], shape[1:], strides[1:]
+    elif len(shape) == 3:
+        n, img_stride = 1, 0
+    else:
+        raise AvifError(4)
+    ptr = ai['data'][0]
+    if not ptr or min(strides) < 0 or img_stride < 0 or min(shape) < 1 or n < 1:
+        raise AvifError(4)
+    if shape[0] in (3, 4) and shape[2] not in (3, 4):
+        (c, h, w), (sc, sh, sw) = shape, strides
+    else:
+        (h, w, c), (sh, sw, sc) = shape, strides
+    if c not in (3, 4):
+        raise AvifError(4)
+    d = _DevicePixels()
+    d.dev, d.channels, d.row_stride, d.image_stride = ptr, c, sh, img_stride
+    if sc == 1:
+        d.layout, d.pixel_or_plane_stride = 0, sw                  # interleaved: from pixel to pixel
+    elif sw == 1:
+        d.layout, d.pixel_or_plane_stride = 1, sc                  # planar: from plane to plane
+    else:
+        raise AvifError(4)
+    if n > 1 and img_stride == 0:
+        raise AvifError(4)
+    torch = sys.modules.get('torch')                               # never imported here: only a caller that has torch can hand over torch's work
+    if torch is not None and hasattr(torch, 'cuda') and torch.cuda.is_available():
+        idx = getattr(getattr(x, 'device', None), 'index', None)
+        d.after_stream = torch.cuda.current_stream(idx).cuda_stream or None
+    return d, n, h, w, getattr(getattr(x, 'device', None), 'index', None)
 
 
 class EncodedImage:
@@ -258,7 +368,23 @@ class Encoder:
             e.exif, e.exif_len = C.cast(self._exif_buf, C.c_void_p), len(self.exif)
         return e
 
+    def _encode_device(self, px, channels):
+        L = load_library()
+        d, _, h, w, index = _device_pixels(px)
+        if d.channels != channels:
+            raise AvifError(4)
+        img = _EncodedImage()
+        e = self._c()
+        if index is not None:
+            e.device = index                            # the pointer belongs to that device
+        st = L.mi_ravif_encode_device(C.byref(e), C.byref(d), w, h, C.byref(img))
+        if st:
+            raise AvifError(st)
+        return _take(img)
+
     def _encode(self, px, channels):
+        if _is_device_array(px):                        # pixels in HBM (a torch tensor, ...): never through the host
+            return self._encode_device(px, channels)
         L = load_library()
         a = np.ascontiguousarray(px, dtype=np.uint8)
         if a.ndim != 3 or a.shape[2] != channels:
@@ -302,26 +428,39 @@ class Encoder:
         return self._raw(load_library().mi_ravif_encode_raw_planes_10, np.uint16, planes, alpha, width, height, color_pixel_range, matrix_coefficients)
 
 
-class _ImageDesc(C.Structure):
-    _fields_ = [('pixels', C.c_void_p), ('width', C.c_uint32), ('height', C.c_uint32), ('stride_px', C.c_size_t), ('channels', C.c_int)]
-
-
 def encode_many(encoder, images, devices=None):
-    """mi_ravif_encode_batch: the reference's files.into_par_iter() (src/main.rs:223) over the node's GPUs.
-    images: list of HxWx3 / HxWx4 uint8 arrays (shapes may differ).  Returns a list of EncodedImage."""
+    """mi_ravif_encode_sources: the reference's files.into_par_iter() (src/main.rs:223) over the node's GPUs.
+    images: list of HxWx3 / HxWx4 uint8 arrays (shapes may differ) and JpegCoeffs objects (parse_jpeg; encoded as the RGBA pictures decode_jpeg
+    gives, decoded on the device).  Returns a list of EncodedImage."""
     L = load_library()
-    L.mi_ravif_encode_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    arrs = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
-    desc = (_ImageDesc * len(arrs))()
-    for d, a in zip(desc, arrs):
+    items = []
+    for im in images:
+        if isinstance(im, JpegCoeffs):
+            if not im._h:
+                raise AvifError(4)
+            items.append(im)
+            continue
+        if _is_device_array(im):
+            raise TypeError('encode_many takes host arrays and JpegCoeffs; pixels in device memory go through BatchEncoder.upload_device')
+        a = np.ascontiguousarray(im, dtype=np.uint8)
         if a.ndim != 3 or a.shape[2] not in (3, 4):
             raise AvifError(4)
-        d.pixels, d.width, d.height, d.stride_px, d.channels = a.ctypes.data, a.shape[1], a.shape[0], a.shape[1], a.shape[2]
-    out = (_EncodedImage * len(arrs))()
-    status = (C.c_int * len(arrs))()
+        items.append(a)
+
+    def fetch(_user, i, src):
+        it, s = items[i], src.contents
+        if isinstance(it, JpegCoeffs):
+            s.kind, s.jpeg = 1, it._h
+            s.desc.pixels, s.desc.width, s.desc.height, s.desc.stride_px, s.desc.channels = None, it.width, it.height, it.width, 4
+        else:
+            s.kind, s.jpeg = 0, None
+            s.desc.pixels, s.desc.width, s.desc.height, s.desc.stride_px, s.desc.channels = it.ctypes.data, it.shape[1], it.shape[0], it.shape[1], it.shape[2]
+        return 0
+    out = (_EncodedImage * len(items))()
+    status = (C.c_int * len(items))()
     dev = (C.c_int * len(devices))(*devices) if devices else None
     e = encoder._c()
-    st = L.mi_ravif_encode_batch(C.byref(e), len(arrs), desc, out, status, dev, len(devices) if devices else 0)
+    st = L.mi_ravif_encode_sources(C.byref(e), len(items), _FETCH_SOURCE(fetch), _RELEASE(), None, out, status, dev, len(devices) if devices else 0)
     res = [_take(o) if s == 0 else None for o, s in zip(out, status)]
     if st:
         raise AvifError(st)
@@ -339,6 +478,7 @@ class BatchEncoder:
         if not self._h:
             raise AvifError(5 if self._L.mi_device_count() <= encoder.device else 4)
         self.n, self.w, self.h, self.channels = n_images, width, height, channels
+        self._sources = []                           # device arrays handed to upload_device: alive until the run that reads them has been waited for
 
     def upload(self, index, pixels):
         a = np.ascontiguousarray(pixels, dtype=np.uint8)
@@ -346,6 +486,40 @@ class BatchEncoder:
         st = self._L.mi_batch_upload(self._h, index, a.ctypes.data, self.w)
         if st:
             raise AvifError(st)
+
+    def upload_device(self, first, pixels):
+        """images first.. from an object with __cuda_array_interface__ (a torch tensor of the batch's device): uint8 (H, W, C), (C, H, W), (N, H, W, C) or
+        (N, C, H, W), any strides a view has.  Enqueued on the batch's stream after the work of torch's current stream; the object is kept referenced until wait()."""
+        d, n, h, w, _ = _device_pixels(pixels, batched=True)
+        if (h, w) != (self.h, self.w):
+            raise AvifError(4)
+        st = self._L.mi_batch_upload_device(self._h, first, n, C.byref(d))
+        if st:
+            raise AvifError(st)
+        self._sources.append(pixels)
+
+    def upload_jpeg(self, index, coeffs):
+        """one parsed JPEG (parse_jpeg) of the batch's size into slot `index`: dequantisation, IDCT, upsampling and colour run on the batch's stream"""
+        if not isinstance(coeffs, JpegCoeffs) or not coeffs._h:
+            raise AvifError(4)
+        st = self._L.mi_batch_upload_jpeg(self._h, index, coeffs._h)
+        if st:
+            raise AvifError(st)
+
+    def device_input(self, index):
+        """device address (int) of the HBM input slot of image `index`: h * w * channels bytes, rows packed"""
+        ptr = self._L.mi_batch_device_input(self._h, index)
+        if not ptr:
+            raise AvifError(4)
+        return ptr
+
+    def read_input(self, index):
+        """the slot of image `index` as it is on the device now (blocking D2H): uint8 array (h, w, channels)"""
+        a = np.empty((self.h, self.w, self.channels), np.uint8)
+        st = self._L.mi_batch_read_input(self._h, index, a.ctypes.data)
+        if st:
+            raise AvifError(st)
+        return a
 
     def pinned_input(self, index):
         """numpy view of the batch's PINNED host staging of image `index`: fill it in place, then upload_async()."""
@@ -367,6 +541,7 @@ class BatchEncoder:
 
     def encode(self):
         st = self._L.mi_batch_encode(self._h)
+        self._sources = []
         if st:
             raise AvifError(st)
 
@@ -377,6 +552,7 @@ class BatchEncoder:
 
     def wait(self):
         st = self._L.mi_batch_wait(self._h)
+        self._sources = []
         if st:
             raise AvifError(st)
 

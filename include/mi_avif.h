@@ -104,7 +104,37 @@ typedef int (*mi_fetch_fn)(void *user, size_t index, mi_image_desc *desc);
 typedef void (*mi_release_fn)(void *user, size_t index);
 int  mi_ravif_encode_stream(const mi_ravif_encoder *e, size_t n, mi_fetch_fn fetch, mi_release_fn release, void *user, mi_encoded_image *out, int *status, const int *devices, int ndev);
 
-/* The one-call entry points above (mi_ravif_encode_rgba / _rgb / _batch / _stream) keep their device arenas and pinned staging in
+/* The same fan-out over sources that need not be host pixels.  kind 1: the coefficients of a parsed JPEG file (mi_jpeg_parse below); desc.width / height /
+ * channels name the batch slot the picture is decoded into on the device (width and height must be the file's; channels 4 gives the pixels
+ * mi_jpeg_decode_rgba gives, 3 the same without alpha), desc.pixels is unused.  Images are grouped into runs by (width, height, channels), so a JPEG and a
+ * PNG picture of one size share a run.  `release` is called once the pixels (kind 0) or the coefficients (kind 1) are in pinned staging: the handle may
+ * be freed then.  mi_ravif_encode_stream is this call with kind 0 throughout.  Pictures in device memory are not a kind here (a pointer belongs to one
+ * device, the shared cursor hands images to any): they enter through mi_ravif_encode_device and mi_batch_upload_device. */
+typedef struct mi_jpeg_coeffs mi_jpeg_coeffs;   /* opaque: one parsed file, host memory only */
+typedef struct mi_image_source {
+  int kind;                   /* 0 host pixels (desc), 1 JPEG coefficients (jpeg; desc.width/height/channels say the slot) */
+  mi_image_desc desc;
+  const mi_jpeg_coeffs *jpeg;
+} mi_image_source;
+typedef int (*mi_fetch_source_fn)(void *user, size_t index, mi_image_source *src);
+int  mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source_fn fetch, mi_release_fn release, void *user, mi_encoded_image *out,
+                             int *status, const int *devices, int ndev);
+
+/* A picture in the memory of a HIP device: uint8 samples, interleaved (HWC) or planar (CHW), any byte strides that do not make rows overlap their own
+ * pixels (row_stride >= the packed row, pixel stride >= channels, plane stride >= width): crops, permuted views and padded rows of a tensor all fit.
+ * 3 channels into an RGBA batch get alpha 255 (as load_rgba gives RGB files); 4 channels into an RGB batch are MI_INVALID_ARGUMENT. */
+typedef struct mi_device_pixels {
+  const void *dev;
+  int layout;        /* 0 = HWC, 1 = CHW */
+  int channels;      /* 3 | 4 */
+  size_t row_stride, pixel_or_plane_stride, image_stride;   /* bytes; 0 = packed */
+  void *after_stream; /* hipStream_t the pixels were produced on, or NULL = already complete */
+} mi_device_pixels;
+/* ravif::Encoder::encode_rgb / encode_rgba (by src->channels) of a w x h picture in the memory of device e->device.  The pointer must belong to that
+ * device (not detected).  Blocking, through the pooled batch objects like mi_ravif_encode_rgba. */
+int  mi_ravif_encode_device(const mi_ravif_encoder *e, const mi_device_pixels *src, uint32_t w, uint32_t h, mi_encoded_image *out);
+
+/* The one-call entry points above (mi_ravif_encode_rgba / _rgb / _device / _batch / _stream / _sources) keep their device arenas and pinned staging in
  * a process-wide pool keyed by (device, shape, settings), so a loop of calls with the same settings pays the allocation once
  * (what a long-lived rav1e thread pool is to the reference).  At most 12 objects / 96 GB are retained; this frees them now, and the idle JPEG
  * decode contexts (at most 8 exist per device) with them. */
@@ -121,6 +151,11 @@ int  mi_png_decode_rgba(const uint8_t *data, size_t len, uint8_t **rgba, uint32_
  * MI_NO_DEVICE when there is no such device: no CPU fallback.  *rgba is malloc'd (mi_free), w*h*4 bytes.  Calls from many threads share a pool of at most 8
  * decode contexts per device (stream + staging; a call that finds all of them busy waits for one) that mi_release_cached() frees. */
 int  mi_jpeg_decode_rgba(const uint8_t *data, size_t len, int device, uint8_t **rgba, uint32_t *w, uint32_t *h);
+/* The host half of mi_jpeg_decode_rgba on its own: parse + Huffman decoding into a handle (quantised coefficients and tables, host memory).  Never touches a
+ * device; the statuses are the ones mi_jpeg_decode_rgba gives for the same bytes' data errors.  The handle feeds mi_batch_upload_jpeg and
+ * mi_ravif_encode_sources any number of times, from any thread, and is released with mi_jpeg_coeffs_free (NULL is fine). */
+int  mi_jpeg_parse(const uint8_t *data, size_t len, mi_jpeg_coeffs **out, uint32_t *w, uint32_t *h);
+void mi_jpeg_coeffs_free(mi_jpeg_coeffs *c);
 /* load_rgba (src/main.rs:255-283) over both: the first bytes decide -- PNG -> mi_png_decode_rgba (host, `device` unused), FF D8 -> mi_jpeg_decode_rgba,
  * anything else MI_UNSUPPORTED. */
 int  mi_image_decode_rgba(const uint8_t *data, size_t len, int device, uint8_t **rgba, uint32_t *w, uint32_t *h);
@@ -134,6 +169,19 @@ int  mi_batch_upload(mi_batch *b, int index, const uint8_t *pixels, size_t strid
  * the H2D of a range of images on the batch's stream (returns at once; ordered before the next mi_batch_encode[_async]) */
 uint8_t *mi_batch_input(mi_batch *b, int index);
 int  mi_batch_upload_async(mi_batch *b, int first, int count);
+/* device-resident input: the picture reaches the slot without ever being host pixels.
+ * mi_batch_device_input: the HBM input slot of image `index` (w*h*channels bytes, rows packed): a HIP caller may write it directly, ordered before the
+ * next encode by its own means.  mi_batch_read_input: D2H of that slot into dst (w*h*channels bytes), blocking; tests and debugging, like mi_batch_get_recon.
+ * mi_batch_upload_device: images [first, first+count) from memory of the batch's own device (documented, not detected), image k at
+ * dev + k * image_stride; enqueued on the batch's stream -- after the work src->after_stream holds at the time of the call, if given -- and returns
+ * at once: the source must stay valid until the next mi_batch_wait.
+ * mi_batch_upload_jpeg: one parsed JPEG of the batch's width and height (else MI_INVALID_ARGUMENT) into slot `index`: coefficients into pinned staging
+ * the batch owns, H2D, dequantisation + IDCT + upsampling + colour on the batch's stream, no sync; the handle may be freed when the call returns.
+ * Both upload calls return MI_INVALID_ARGUMENT between mi_batch_encode_async and mi_batch_wait. */
+uint8_t *mi_batch_device_input(mi_batch *b, int index);
+int  mi_batch_read_input(mi_batch *b, int index, uint8_t *dst);
+int  mi_batch_upload_device(mi_batch *b, int first, int count, const mi_device_pixels *src);
+int  mi_batch_upload_jpeg(mi_batch *b, int index, const mi_jpeg_coeffs *c);
 int  mi_batch_set_count(mi_batch *b, int n_images);                                       /* images of the next run (<= the count the batch was created for) */
 int  mi_batch_encode(mi_batch *b);                                                        /* the hot path over all resident images */
 /* split form: enqueue the GPU work and return; wait = sync + one packed D2H + OBU/container assembly.  Two batches
