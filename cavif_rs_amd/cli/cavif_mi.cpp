@@ -1,9 +1,9 @@
 // cavif_mi -- the cavif command line (src/main.rs) on top of libmi_avif.so: same flags, path rules and report line;
 // the rayon fan-out over files (src/main.rs:223) becomes mi_ravif_encode_batch (one host thread per MI355X).
 //   cavif_mi [-Q n] [-s n] [-j n] [-f] [-o path] [-q] [--dirty-alpha] [--color ycbcr|rgb] [--depth 8|10|auto] IMAGES...
-// Input: PNG and baseline / progressive 8-bit JPEG, told apart by their first bytes as load_image does.  A PNG is decoded in its loader thread
-// (mi_image_decode_rgba); of a JPEG the loader does the Huffman decoding (mi_jpeg_parse) and hands the coefficients to the encoder, which finishes
-// the picture on the GPU inside the batch that encodes it (mi_ravif_encode_sources): the loaders never touch a device.  Differences, deliberate:
+// Input: PNG and baseline / progressive 8-bit JPEG, told apart by their first bytes as load_image does.  A loader thread does the serial half of the
+// decode -- inflate of a PNG (mi_png_parse), Huffman decoding of a JPEG (mi_jpeg_parse) -- and hands scanlines or coefficients to the encoder, which
+// finishes the picture on the GPU inside the batch that encodes it (mi_ravif_encode_sources): the loaders never touch a device.  Differences, deliberate:
 // `--devices a,b,..` selects HIP devices (default: all), and there is no CPU fallback -- without a GPU every file fails loudly.
 #include <sched.h>
 #include <sys/stat.h>
@@ -100,7 +100,7 @@ int usage(const char *msg) {
 static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 int main(int argc, char **argv) {
   const double t_start = now_s(); const bool timing = getenv("CAVIF_MI_TIMING") != nullptr;
-  // The loaders' buffers (file, inflate output, RGBA: ~8 MB each) come from the heap arenas and stay there: as anonymous mappings every one of them is an
+  // The loaders' buffers (file, inflate output: ~6 MB each) come from the heap arenas and stay there: as anonymous mappings every one of them is an
   // mmap + page faults + munmap (a TLB shootdown across the loader threads), all under the address-space lock the HIP runtime needs while it starts.
   mallopt(M_MMAP_THRESHOLD, 32 << 20); mallopt(M_TRIM_THRESHOLD, 1 << 30);
   // CAVIF_MI_BACKGROUND_EXIT=1 (opt-in): device teardown off the caller's clock.  The work runs in a child; once every output is on disk the child reports its
@@ -202,10 +202,11 @@ int main(int argc, char **argv) {
   enc.threads = threads > 0 ? threads : host_threads();
 
   // load + decide output paths (process(), :169-200); failures are collected per file and reported at the end
-  struct Job { std::string in_name, out_path; bool out_stdio = false; uint8_t *rgba = nullptr; mi_jpeg_coeffs *jpeg = nullptr; uint32_t w = 0, h = 0; std::string error; };
+  struct Job { std::string in_name, out_path; bool out_stdio = false; mi_jpeg_coeffs *jpeg = nullptr; mi_png_scanlines *png = nullptr; uint32_t w = 0, h = 0; std::string error; };
   std::vector<Job> jobs(files.size());
-  // the reference loads inside files.into_par_iter() (src/main.rs:223): file reads + PNG / JPEG entropy decodes fan out over the host cores; a JPEG leaves
-  // its loader as coefficients (dequantisation, IDCT, upsampling and colour run on the device that encodes it)
+  // the reference loads inside files.into_par_iter() (src/main.rs:223): file reads + PNG inflate / JPEG entropy decodes fan out over the host cores; a JPEG leaves
+  // its loader as coefficients (dequantisation, IDCT, upsampling and colour run on the device that encodes it), a PNG as filtered scanlines (unfiltered and
+  // expanded to RGBA there)
   auto load = [&](size_t i) {
     Job &j = jobs[i]; const Input &in = files[i];
     j.in_name = in.is_stdio ? "stdin" : in.path;
@@ -213,8 +214,9 @@ int main(int argc, char **argv) {
     if (in.is_stdio) { if (!read_all(stdin, data)) j.error = "Unable to read stdin"; }
     else { FILE *f = fopen(in.path.c_str(), "rb"); if (!f || !read_all(f, data)) j.error = "Unable to read input image " + in.path + ": " + strerror(errno); if (f) fclose(f); }
     if (j.error.empty()) {
-      const bool is_jpeg = data.size() >= 2 && data[0] == 0xFF && data[1] == 0xD8;
-      const int st = is_jpeg ? mi_jpeg_parse(data.data(), data.size(), &j.jpeg, &j.w, &j.h) : mi_image_decode_rgba(data.data(), data.size(), 0, &j.rgba, &j.w, &j.h);
+      static const uint8_t png_sig[8] = { 0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A };
+      const bool is_jpeg = data.size() >= 2 && data[0] == 0xFF && data[1] == 0xD8, is_png = data.size() >= 8 && !memcmp(data.data(), png_sig, 8);
+      const int st = is_jpeg ? mi_jpeg_parse(data.data(), data.size(), &j.jpeg, &j.w, &j.h) : is_png ? mi_png_parse(data.data(), data.size(), &j.png, &j.w, &j.h, nullptr) : (int)MI_UNSUPPORTED;
       if (st) j.error = st == MI_UNSUPPORTED ? "unsupported image format (this build reads PNG and baseline/progressive 8-bit JPEG)" :
                         st == MI_NO_DEVICE ? "no HIP device (this encoder has no CPU fallback)" : "corrupt image data";
     }
@@ -226,10 +228,10 @@ int main(int argc, char **argv) {
   };
   // loaders (host cores) and the encoder (GPUs) run concurrently: the encoder pulls image i through fetch(), which waits for
   // loader i -- the reference gets the same overlap from rayon's work stealing over process() (src/main.rs:179-223).  Loaders
-  // stay at most `window` images ahead of the images the encoder has released (pixels copied to its staging and freed here), so
+  // stay at most `window` images ahead of the images the encoder has released (scanlines / coefficients copied to its staging and freed here), so
   // host memory is bounded for any number of files.
   std::mutex mu; std::condition_variable cv; std::vector<char> loaded(files.size(), 0);
-  // A 1080p PNG decodes in ~25 ms and one GPU takes an image every ~4 ms: a dozen loaders per GPU keep up with room to spare, and 24 hand the first run
+  // A 1080p PNG inflates in 15 - 21 ms (profiles/png_input.md) and one GPU takes an image every ~4 ms: a dozen loaders per GPU keep up with room to spare, and 24 hand the first run
   // over in one round.  More of them only contend with the HIP runtime's start (64 loaders: runtime + first batch object up after 0.55 s instead of 0.2 s,
   // profiles/r05zk_e2e_knobs.txt).  The pool starts before the device count is known and grows once it is.
   const unsigned loaders_per_device = 12, loaders_first = getenv("CAVIF_MI_LOADERS") ? (unsigned)atoi(getenv("CAVIF_MI_LOADERS")) : 2 * loaders_per_device;
@@ -254,16 +256,16 @@ int main(int argc, char **argv) {
     { std::unique_lock<std::mutex> lk(*c->mu); c->cv->wait(lk, [&] { return (*c->loaded)[i] != 0; }); }
     const Job &j = (*c->jobs)[i];
     if (!j.error.empty()) return MI_INVALID_ARGUMENT;           // reported from the job's own message below
-    src->kind = j.jpeg ? 1 : 0; src->jpeg = j.jpeg;
+    src->kind = j.jpeg ? 1 : j.png ? 2 : 0; src->jpeg = j.jpeg; src->png = j.png;
     mi_image_desc *d = &src->desc;
-    d->pixels = j.rgba; d->width = j.w; d->height = j.h; d->stride_px = j.w; d->channels = 4;     // a JPEG into an RGBA slot: the pixels load_rgba gives it
+    d->pixels = nullptr; d->width = j.w; d->height = j.h; d->stride_px = j.w; d->channels = 4;     // a JPEG or PNG into an RGBA slot: the pixels load_rgba gives it
     return MI_OK;
   };
   auto release = [](void *user, size_t i) {
     Ctx *c = (Ctx *)user;
     Job &j = (*c->jobs)[i];
-    mi_free(j.rgba); j.rgba = nullptr;
     mi_jpeg_coeffs_free(j.jpeg); j.jpeg = nullptr;
+    mi_png_scanlines_free(j.png); j.png = nullptr;
     { std::lock_guard<std::mutex> lk(*c->mu); (*c->released)++; }
     c->cv->notify_all();
   };
@@ -301,8 +303,8 @@ int main(int argc, char **argv) {
   if (timing) fprintf(stderr, "[timing] written %.3f s\n", now_s() - t_start);
   int failures = 0;
   for (Job &j : jobs) {
-    if (j.rgba) mi_free(j.rgba);
     mi_jpeg_coeffs_free(j.jpeg);
+    mi_png_scanlines_free(j.png);
     if (!j.error.empty()) { failures++; if (!quiet) fprintf(stderr, "error: %s: error: %s\n", j.in_name.c_str(), j.error.c_str()); }
   }
   // every output is on disk: leave without the HIP runtime's teardown (freeing pinned staging and contexts costs ~0.3 s)

@@ -18,6 +18,7 @@
 #include "png_reader.h"
 #include "jpeg_reader.h"
 #include "dev_jpeg.h"
+#include "dev_png.h"
 #include "host_frames.h"
 
 // The product library reads no environment variables; probe builds (tools/) get MI_AVIF_TIMING=1 (-DMI_TUNING_KNOBS: host-side timeline on stderr)
@@ -45,7 +46,8 @@ struct mi_batch {
   hipStream_t stream = nullptr;
   int cap = 0;                                                     // images the batch was created for (n = images of the current run <= cap)
   DevBuf<uint8_t> d_pixels; size_t pixel_bytes = 0;               // cap * w*h*channels
-  PinBuf<uint8_t> h_pixels;                                        // pinned staging of the same size: the H2D source (async, no pageable copies)
+  std::mutex staging_mu; PinBuf<uint8_t> h_pixels;                                        // pinned staging of the same size: the H2D source (async, no pageable copies); made by the first mi_batch_input (a batch fed
+                                                                   // JPEG coefficients, PNG scanlines or device pixels alone never pins it: pinning and unpinning 265 MB costs ~0.1 s)
   DevBuf<int> d_alpha_flags; PinBuf<int> h_alpha; std::vector<int> alpha_flags;      // h_alpha: pinned D2H target
   DevBuf<uint8_t> d_clean, d_clean_tmp; DevBuf<unsigned long long> d_alpha_acc;       // dirty-alpha cleaner (RGBA, UnassociatedClean)
   FrameSet fs;                                                     // frames: colour frames [0..n), alpha frames after
@@ -57,6 +59,8 @@ struct mi_batch {
   // of the images uploaded since the stream last drained, pinned and on the device, and one image's component planes
   hipEvent_t ev_src = nullptr;
   PinBuf<uint8_t> h_jpeg; DevBuf<uint8_t> d_jpeg, d_jpeg_planes; size_t h_jpeg_cap = 0, d_jpeg_cap = 0, d_jpeg_planes_cap = 0, jpeg_used = 0;
+  // PNG staging: descriptors + palettes + inflated scanlines of the mi_batch_upload_png calls since the stream last drained, pinned and on the device (unfiltered there in place)
+  PinBuf<uint8_t> h_png; DevBuf<uint8_t> d_png; size_t h_png_cap = 0, d_png_cap = 0, png_used = 0;
 };
 
 static void batch_plan(mi_batch *b) {
@@ -135,7 +139,7 @@ mi_batch *mi_batch_create(const mi_ravif_encoder *e, int n_images, uint32_t w, u
   b->enc.exif = b->exif.empty() ? nullptr : b->exif.data(); b->enc.exif_len = b->exif.size();
   b->alpha_flags.assign(n_images, 0);
   b->pixel_bytes = (size_t)n_images * w * h * channels;
-  bool ok = hipStreamCreate(&b->stream) == hipSuccess && b->d_pixels.alloc(b->pixel_bytes) == hipSuccess && b->h_pixels.alloc(b->pixel_bytes) == hipSuccess &&
+  bool ok = hipStreamCreate(&b->stream) == hipSuccess && b->d_pixels.alloc(b->pixel_bytes) == hipSuccess &&
             b->d_alpha_flags.alloc(n_images) == hipSuccess;
   if (ok && channels == 4 && e->alpha_mode == 1)
     ok = b->d_clean.alloc(b->pixel_bytes) == hipSuccess && b->d_clean_tmp.alloc((size_t)w * h * 4) == hipSuccess && b->d_alpha_acc.alloc((size_t)4 * n_images) == hipSuccess;
@@ -154,6 +158,10 @@ mi_batch *mi_batch_create(const mi_ravif_encoder *e, int n_images, uint32_t w, u
 // The batch owns a pinned host staging area laid out like its HBM input slot; H2D always starts from there.
 uint8_t *mi_batch_input(mi_batch *b, int index) {
   if (!b || index < 0 || index >= b->cap) return nullptr;
+  {                                                           // made once, by whichever thread asks first (callers may fill different slots from different threads)
+    std::lock_guard<std::mutex> lk(b->staging_mu);
+    if (!b->h_pixels.get()) { (void)hipSetDevice(b->device); if (b->h_pixels.alloc(b->pixel_bytes) != hipSuccess) return nullptr; }
+  }
   return b->h_pixels.get() + (size_t)index * b->w * b->h * b->channels;
 }
 int mi_batch_set_count(mi_batch *b, int n_images) {
@@ -163,7 +171,7 @@ int mi_batch_set_count(mi_batch *b, int n_images) {
 }
 // enqueue the H2D of images [first, first + count) from the pinned staging on the batch's stream; returns at once
 int mi_batch_upload_async(mi_batch *b, int first, int count) {
-  if (!b || first < 0 || count < 1 || first + count > b->cap) return MI_INVALID_ARGUMENT;
+  if (!b || first < 0 || count < 1 || first + count > b->cap || !mi_batch_input(b, first)) return MI_INVALID_ARGUMENT;
   (void)hipSetDevice(b->device);
   const size_t img = (size_t)b->w * b->h * b->channels;
   HIP_OK(hipMemcpyAsync(b->d_pixels.get() + first * img, b->h_pixels.get() + first * img, count * img, hipMemcpyHostToDevice, b->stream));
@@ -173,6 +181,7 @@ int mi_batch_upload(mi_batch *b, int index, const uint8_t *pixels, size_t stride
   if (!b || index < 0 || index >= b->cap || !pixels) return MI_INVALID_ARGUMENT;
   const size_t row = (size_t)b->w * b->channels;
   uint8_t *dst = mi_batch_input(b, index);
+  if (!dst) return MI_ENCODING_ERROR;
   for (uint32_t y = 0; y < b->h; y++) memcpy(dst + y * row, pixels + (size_t)y * stride_px * b->channels, row);
   if (int st = mi_batch_upload_async(b, index, 1)) return st;
   HIP_OK(hipStreamSynchronize(b->stream));
@@ -264,7 +273,7 @@ int mi_batch_wait(mi_batch *b) {
   const int njobs = (int)b->fs.jobs.size();
   std::vector<uint32_t> offsets(njobs);
   HIP_OK(hipStreamSynchronize(s));
-  b->jpeg_used = 0;                                            // every JPEG upload of the run has left the pinned staging
+  b->jpeg_used = 0; b->png_used = 0;                           // every JPEG / PNG upload of the run has left the pinned staging
   if (b->channels == 4) for (int i = 0; i < b->n; i++) b->alpha_flags[i] = b->h_alpha.get()[i];
   auto idle = [&](const FramePlan &p) { return p.is_alpha && !b->alpha_flags[p.image]; };
   if (int st = b->fs.check_lengths()) return st;
@@ -360,7 +369,7 @@ static PoolKey pool_key(const mi_ravif_encoder *e, int cap, uint32_t w, uint32_t
 }
 static std::mutex g_pool_mu;
 static std::vector<std::pair<PoolKey, mi_batch *>> g_pool;          // oldest first; never destroyed at process exit (the runtime may be gone by then)
-static size_t batch_footprint(const mi_batch *b) { return b->fs.arena_bytes + b->fs.aux_bytes + 3 * b->pixel_bytes + b->packed_cap + b->h_jpeg_cap + b->d_jpeg_cap + b->d_jpeg_planes_cap; }
+static size_t batch_footprint(const mi_batch *b) { return b->fs.arena_bytes + b->fs.aux_bytes + 3 * b->pixel_bytes + b->packed_cap + b->h_jpeg_cap + b->d_jpeg_cap + b->d_jpeg_planes_cap + b->h_png_cap + b->d_png_cap; }
 static constexpr size_t MI_POOL_MAX_ITEMS = 8, MI_POOL_MAX_BYTES = (size_t)32 << 30;     // what the one-call entry points may keep between calls (mi_release_cached() frees it)
 
 static mi_batch *pool_acquire(const mi_ravif_encoder *e, int cap, uint32_t w, uint32_t h, int channels) {
@@ -437,7 +446,7 @@ static void jpeg_ctx_release(JpegCtx *c) {
   g_jpeg_cv.notify_one();
 }
 // the buffer holds at least `need` bytes afterwards (the context is idle whenever this runs: every public call ends with a stream sync)
-static const auto jpeg_grow = [](auto &buf /* DevBuf or PinBuf */, size_t &cap, size_t need) {
+static const auto staging_grow = [](auto &buf /* DevBuf or PinBuf */, size_t &cap, size_t need) {
   if (need <= cap) return true;
   need = (need + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
   cap = 0;
@@ -524,8 +533,8 @@ static int jpeg_decode_to_device(const JpegCoeffs &jc, uint8_t *h_in, uint8_t *d
 
 static int jpeg_decode_with(JpegCtx &ctx, const JpegCoeffs &jc, uint8_t *dst, double *step_ms) {
   const size_t out_bytes = (size_t)jc.w * jc.h * 4;
-  if (!jpeg_grow(ctx.d_rgba, ctx.d_rgba_cap, out_bytes) || !jpeg_grow(ctx.h_rgba, ctx.h_rgba_cap, out_bytes)) return MI_ENCODING_ERROR;
-  if (!jpeg_grow(ctx.h_in, ctx.h_in_cap, jpeg_in_bytes(jc)) || !jpeg_grow(ctx.d_in, ctx.d_in_cap, jpeg_in_bytes(jc)) || !jpeg_grow(ctx.d_planes, ctx.d_planes_cap, jpeg_plane_bytes(jc))) return MI_ENCODING_ERROR;
+  if (!staging_grow(ctx.d_rgba, ctx.d_rgba_cap, out_bytes) || !staging_grow(ctx.h_rgba, ctx.h_rgba_cap, out_bytes)) return MI_ENCODING_ERROR;
+  if (!staging_grow(ctx.h_in, ctx.h_in_cap, jpeg_in_bytes(jc)) || !staging_grow(ctx.d_in, ctx.d_in_cap, jpeg_in_bytes(jc)) || !staging_grow(ctx.d_planes, ctx.d_planes_cap, jpeg_plane_bytes(jc))) return MI_ENCODING_ERROR;
   const int st = jpeg_decode_to_device(jc, ctx.h_in.get(), ctx.d_in.get(), ctx.d_planes.get(), ctx.d_rgba.get(), 4, jc.w, ctx.stream, step_ms);
   if (st) { (void)hipStreamSynchronize(ctx.stream); return st; }
   const auto t0 = std::chrono::steady_clock::now();
@@ -644,14 +653,107 @@ int mi_batch_upload_jpeg(mi_batch *b, int index, const mi_jpeg_coeffs *c) {
   if (b->jpeg_used + need > b->h_jpeg_cap) {
     HIP_OK(hipStreamSynchronize(b->stream));
     b->jpeg_used = 0;
-    if (!jpeg_grow(b->h_jpeg, b->h_jpeg_cap, MI_BATCH_JPEG_STAGED * need) || !jpeg_grow(b->d_jpeg, b->d_jpeg_cap, MI_BATCH_JPEG_STAGED * need)) return MI_ENCODING_ERROR;
+    if (!staging_grow(b->h_jpeg, b->h_jpeg_cap, MI_BATCH_JPEG_STAGED * need) || !staging_grow(b->d_jpeg, b->d_jpeg_cap, MI_BATCH_JPEG_STAGED * need)) return MI_ENCODING_ERROR;
   }
   if (jpeg_plane_bytes(jc) > b->d_jpeg_planes_cap) {
     HIP_OK(hipStreamSynchronize(b->stream));                  // an earlier image's kernels may still read the buffer that is replaced
-    if (!jpeg_grow(b->d_jpeg_planes, b->d_jpeg_planes_cap, jpeg_plane_bytes(jc))) return MI_ENCODING_ERROR;
+    if (!staging_grow(b->d_jpeg_planes, b->d_jpeg_planes_cap, jpeg_plane_bytes(jc))) return MI_ENCODING_ERROR;
   }
   const size_t at = b->jpeg_used; b->jpeg_used += need;
   return jpeg_decode_to_device(jc, b->h_jpeg.get() + at, b->d_jpeg.get() + at, b->d_jpeg_planes.get(), mi_batch_device_input(b, index), b->channels, b->w, b->stream, nullptr);
+}
+
+// ---- PNG input: the host half behind a handle, the device half on the batch's stream ----
+struct mi_png_scanlines { PngScanlines sl; };
+
+// png_read_scanlines behind a handle: host work only (chunk walk, inflate, filter-byte and palette-index checks), the statuses of mi_png_decode_rgba
+int mi_png_parse(const uint8_t *data, size_t len, mi_png_scanlines **out, uint32_t *w, uint32_t *h, int *has_alpha) {
+  if (!data || !out || !w || !h) return MI_INVALID_ARGUMENT;
+  *out = nullptr;
+  try {                                                       // nothing may unwind through the C ABI
+    std::unique_ptr<mi_png_scanlines> p(new mi_png_scanlines);
+    if (const int st = png_read_scanlines(data, len, p->sl)) return st;
+    *w = p->sl.w; *h = p->sl.h;
+    if (has_alpha) *has_alpha = p->sl.has_alpha() ? 1 : 0;
+    *out = p.release();
+    return MI_OK;
+  } catch (const std::exception &) { return MI_ENCODING_ERROR; }
+}
+void mi_png_scanlines_free(mi_png_scanlines *p) { delete p; }
+
+// what one call stages: pass descriptors of the passes that have a filtered row, one image descriptor per image, then per image its palette (colour type 3)
+// and its scanlines, 16-byte aligned; 16 spare bytes at the end
+static size_t png_call_bytes(int count, const mi_png_scanlines *const *png) {
+  size_t n = align_up((size_t)count * 7 * sizeof(PngPassDev), 16) + align_up((size_t)count * sizeof(PngImageDev), 16);
+  for (int i = 0; i < count; i++) n += (png[i]->sl.ctype == 3 ? 1024 : 0) + align_up(png[i]->sl.raw.size(), 16);
+  return align_up(n + 16, 256);
+}
+
+// room for `bytes` of PNG staging, pinned and on the device, made ahead of the first mi_batch_upload_png (the stream worker does this on the thread that creates the batch
+// object, beside the loaders: on the worker's own thread the 35 - 55 ms of a first call's allocation delay the first run); idle batches only, false = could not
+static bool batch_reserve_png(mi_batch *b, size_t bytes) {
+  if (!b || b->in_flight || b->png_used) return false;
+  if (bytes <= b->h_png_cap && bytes <= b->d_png_cap) return true;
+  (void)hipSetDevice(b->device);
+  if (hipStreamSynchronize(b->stream) != hipSuccess) return false;
+  return staging_grow(b->h_png, b->h_png_cap, bytes) && staging_grow(b->d_png, b->d_png_cap, bytes);
+}
+
+// images [first, first + count) from parsed PNG files of the batch's size: descriptors, palettes and scanlines into the batch's pinned staging, one H2D, then
+// png_unfilter_kernel (one workgroup per pass that has a filtered row, all images in one launch) and png_expand_kernel on the batch's stream, no sync.
+// The staging keeps the calls since the stream last drained; when the next one does not fit, the stream is waited for and the staging starts over, grown to the call.
+int mi_batch_upload_png(mi_batch *b, int first, int count, const mi_png_scanlines *const *png) {
+  if (!b || !png || b->in_flight || first < 0 || count < 1 || first > b->cap - count) return MI_INVALID_ARGUMENT;
+  for (int i = 0; i < count; i++) {
+    if (!png[i] || png[i]->sl.w != b->w || png[i]->sl.h != b->h) return MI_INVALID_ARGUMENT;
+    if (b->channels == 3 && png[i]->sl.has_alpha()) return MI_INVALID_ARGUMENT;      // alpha is never dropped
+  }
+  (void)hipSetDevice(b->device);
+  const size_t need = png_call_bytes(count, png);
+  if (b->png_used + need > b->h_png_cap || b->png_used + need > b->d_png_cap) {
+    HIP_OK(hipStreamSynchronize(b->stream));                  // earlier calls' copies and kernels may still use the buffers that start over or are replaced
+    b->png_used = 0;
+    if (!staging_grow(b->h_png, b->h_png_cap, need) || !staging_grow(b->d_png, b->d_png_cap, need)) return MI_ENCODING_ERROR;
+  }
+  const size_t at = b->png_used; b->png_used += need;
+  uint8_t *const hb = b->h_png.get() + at;
+  PngPassDev *passes = (PngPassDev *)hb;
+  const size_t img_at = align_up((size_t)count * 7 * sizeof(PngPassDev), 16);
+  PngImageDev *imgs = (PngImageDev *)(hb + img_at);
+  size_t pos = img_at + align_up((size_t)count * sizeof(PngImageDev), 16);
+  uint32_t npass = 0, max_rows = 0;
+  for (int i = 0; i < count; i++) {
+    const PngScanlines &sl = png[i]->sl;
+    PngImageDev &im = imgs[i]; memset(&im, 0, sizeof(im));
+    im.depth = (uint32_t)sl.depth; im.ctype = (uint32_t)sl.ctype; im.interlace = (uint32_t)sl.interlace; im.has_key = sl.has_key ? 1 : 0;
+    for (int c = 0; c < 3; c++) im.key[c] = sl.key[c];
+    if (sl.ctype == 3) { im.palette_off = at + pos; memcpy(hb + pos, sl.palette, 1024); pos += 1024; }
+    memcpy(hb + pos, sl.raw.data(), sl.raw.size());
+    for (int p = 0; p < sl.npass; p++) {
+      const PngPass &ps = sl.pass[p];
+      // the Adam7 pass this is: dx, dy and x0 tell (a non-interlaced file has the one pass 0)
+      const int id = !sl.interlace ? 0 : ps.dy == 8 ? (ps.dx == 4 ? 2 : ps.x0 ? 1 : 0) : ps.dy == 4 ? (ps.dx == 4 ? 3 : 4) : ps.dx == 2 ? 5 : 6;
+      im.pass_off[id] = at + pos + ps.off; im.pass_rowbytes[id] = ps.rowbytes;
+      bool filtered = false;
+      for (uint32_t y = 0; y < ps.rows && !filtered; y++) filtered = sl.raw[ps.off + (size_t)y * (ps.rowbytes + 1)] != 0;
+      if (!filtered) continue;                                // nothing to undo
+      passes[npass++] = PngPassDev{ at + pos + ps.off, ps.rows, ps.rowbytes, (uint32_t)sl.bpp, 0 };
+      max_rows = std::max(max_rows, ps.rows);
+    }
+    pos += align_up(sl.raw.size(), 16);
+  }
+  uint8_t *const db = b->d_png.get();
+  HIP_OK(hipMemcpyAsync(db + at, hb, pos, hipMemcpyHostToDevice, b->stream));
+  if (npass) {
+    const unsigned waves = std::min<unsigned>(MI_PNG_WAVES, (max_rows + 63) / 64);
+    hipLaunchKernelGGL(png_unfilter_kernel, dim3(npass), dim3(64 * waves), 0, b->stream, db, (const PngPassDev *)(db + at));
+  }
+  const dim3 grid(((b->w + 3) / 4 + 63) / 64, b->h, (unsigned)count);
+  uint8_t *const slots = mi_batch_device_input(b, first);
+  if (b->channels == 4) hipLaunchKernelGGL((png_expand_kernel<4>), grid, dim3(64), 0, b->stream, (const uint8_t *)db, (const PngImageDev *)(db + at + img_at), b->w, b->h, slots);
+  else hipLaunchKernelGGL((png_expand_kernel<3>), grid, dim3(64), 0, b->stream, (const uint8_t *)db, (const PngImageDev *)(db + at + img_at), b->w, b->h, slots);
+  HIP_OK(hipGetLastError());
+  return MI_OK;
 }
 
 // ravif::Encoder::encode_rgba / encode_rgb for a picture in the memory of device e->device (channels 4 / 3 as src->channels says)
@@ -672,7 +774,8 @@ int mi_ravif_encode_device(const mi_ravif_encoder *e, const mi_device_pixels *sr
 // Streaming form of the fan-out: image i is obtained through `fetch(user, i, &desc)` when a worker is about to stage it (the
 // call may block until the pixels exist -- e.g. until a loader thread has decoded the file), so loading, upload, encoding and
 // assembly of consecutive runs overlap.  fetch returns MI_OK or a status that becomes the image's status.  An image is host pixels (kind 0) or the
-// coefficients of a parsed JPEG (kind 1), whose pixels come into being in the batch's HBM input slot; mi_ravif_encode_stream is this with kind 0 throughout.
+// coefficients of a parsed JPEG (kind 1) or the scanlines of a parsed PNG (kind 2), whose pixels come into being in the batch's HBM input slot; mi_ravif_encode_stream is this
+// with kind 0 throughout.
 int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source_fn fetch, mi_release_fn release, void *user, mi_encoded_image *out, int *status, const int *devices, int ndev) {
   if (!e || !fetch || (n && !out)) return MI_INVALID_ARGUMENT;
   const int have = mi_device_count();
@@ -705,7 +808,7 @@ int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source
     { int sharing = 0; for (int d2 : devs) sharing += d2 == dev; budget /= (size_t)std::max(1, sharing); }      // workers on the same ordinal (devices = [0, 0]) split what is free
     static constexpr int NSLOT_MAX = 4;
     const int NSLOT = MI_STREAM_SLOTS_DEFAULT;
-    struct Slot { mi_batch *b = nullptr; std::future<mi_batch *> making; std::vector<size_t> idx; bool busy = false, jpeg = false; size_t bytes = 0; };
+    struct Slot { mi_batch *b = nullptr; std::future<mi_batch *> making; std::vector<size_t> idx; bool busy = false, jpeg = false; size_t bytes = 0, png_bytes = 0; };
     struct Shape { uint32_t w, h; int ch; size_t cap; Slot slot[NSLOT_MAX]; int next = 0; size_t runs = 0, last_use = 0; };
     std::vector<std::unique_ptr<Shape>> shapes;
     size_t live_bytes = 0, tick = 0;
@@ -721,7 +824,7 @@ int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source
       collect(sl);
       if (sl.making.valid()) sl.b = sl.making.get();
       if (sl.b) mi_batch_destroy(sl.b);
-      sl.b = nullptr; live_bytes -= std::min(live_bytes, sl.bytes); sl.bytes = 0; sl.jpeg = false;
+      sl.b = nullptr; live_bytes -= std::min(live_bytes, sl.bytes); sl.bytes = 0; sl.jpeg = false; sl.png_bytes = 0;
     };
     auto make_room = [&](Shape *keep, size_t need) {
       while (live_bytes + need > budget) {
@@ -731,14 +834,21 @@ int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source
         for (Slot &sl : victim->slot) drop(sl);
       }
     };
-    auto ensure_slot = [&](Shape *sh, int j) {
+    auto ensure_slot = [&](Shape *sh, int j, bool host_staging, size_t png_staging) {
       Slot &sl = sh->slot[j];
       if (sl.b || sl.making.valid()) return;
       const size_t need = est_bytes(sh->w, sh->h, sh->ch, sh->cap);
       make_room(sh, need);
       sl.bytes = need; live_bytes += need;
       const mi_ravif_encoder ec = enc; const uint32_t w = sh->w, h = sh->h; const int ch = sh->ch; const int c = (int)sh->cap;
-      sl.making = std::async(std::launch::async, [ec, c, w, h, ch]() { return pool_acquire(&ec, c, w, h, ch); });
+      // the pinned pixel staging with it when host pixels are coming (a run of JPEG / PNG sources never pins it)
+      // and the PNG staging when scanlines are coming (png_staging: the bytes a full run is expected to need; a call that needs more grows it)
+      sl.making = std::async(std::launch::async, [ec, c, w, h, ch, host_staging, png_staging]() {
+        mi_batch *nb = pool_acquire(&ec, c, w, h, ch);
+        if (nb && host_staging) (void)mi_batch_input(nb, 0);
+        if (nb && png_staging) (void)batch_reserve_png(nb, png_staging);
+        return nb;
+      });
     };
     auto shape_for = [&](const mi_image_desc &x) {
       for (auto &c : shapes) if (c->w == x.width && c->h == x.height && c->ch == x.channels) return c.get();
@@ -754,19 +864,38 @@ int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source
       const int j = sh->next; sh->next = (j + 1) % NSLOT;
       Slot &sl = sh->slot[j];
       collect(sl);                                           // the slot's previous run, if any
-      ensure_slot(sh, j);
+      bool any_host = false; for (size_t k : run) any_host |= d[k].kind == 0;
+      size_t png_run = 0; { std::vector<const mi_png_scanlines *> all; for (size_t k : run) if (d[k].kind == 2) all.push_back(d[k].png); if (!all.empty()) png_run = png_call_bytes((int)all.size(), all.data()); }
+      ensure_slot(sh, j, any_host, png_run);
       if (sl.making.valid()) sl.b = sl.making.get();
-      if (!sl.b) { live_bytes -= std::min(live_bytes, sl.bytes); sl.bytes = 0; sl.jpeg = false; }      // the object could not be made: nothing of it is resident
+      if (!sl.b) { live_bytes -= std::min(live_bytes, sl.bytes); sl.bytes = 0; sl.jpeg = false; sl.png_bytes = 0; }      // the object could not be made: nothing of it is resident
       int rc = sl.b ? mi_batch_set_count(sl.b, (int)run.size()) : MI_ENCODING_ERROR;
       if (timing) fprintf(stderr, "[mi_avif %8.1f ms] dev %d: slot %d ready\n", since(), dev, j);
       if (rc == MI_OK) {
-        // host images: pinned staging, then one H2D per stretch of neighbours (never across a JPEG image's slot: the staging there is stale).  JPEG images:
-        // coefficients to the batch's own staging, decoded into the slot on the batch's stream.
+        // host images: pinned staging, then one H2D per stretch of neighbours (never across a JPEG or PNG image's slot: the staging there is stale).  JPEG images:
+        // coefficients to the batch's own staging, decoded into the slot on the batch's stream.  PNG images: a stretch of neighbours goes up in one
+        // mi_batch_upload_png call (one H2D, one launch per kernel); what the batch's PNG staging holds, pinned and on the device, joins the worker's budget.
         const size_t row = (size_t)d0.width * d0.channels;
         size_t host_from = 0;
         auto upload_host = [&](size_t end) { if (rc == MI_OK && end > host_from) rc = mi_batch_upload_async(sl.b, (int)host_from, (int)(end - host_from)); };
+        std::vector<const mi_png_scanlines *> pngs; size_t png_from = 0;
+        auto upload_png = [&]() {
+          if (rc == MI_OK && !pngs.empty()) {
+            const size_t extra = 2 * (png_call_bytes((int)pngs.size(), pngs.data()) + ((size_t)1 << 20));
+            if (extra > sl.png_bytes) { sl.bytes += extra - sl.png_bytes; live_bytes += extra - sl.png_bytes; sl.png_bytes = extra; }
+            rc = mi_batch_upload_png(sl.b, (int)png_from, (int)pngs.size(), pngs.data());
+          }
+          pngs.clear();
+        };
         for (size_t k = 0; k < run.size() && rc == MI_OK; k++) {
           const mi_image_source &src = d[run[k]];
+          if (src.kind == 2) {
+            upload_host(k); host_from = k + 1;
+            if (pngs.empty()) png_from = k;
+            pngs.push_back(src.png);
+            continue;
+          }
+          upload_png();
           if (src.kind == 1) {
             upload_host(k); host_from = k + 1;
             if (!sl.jpeg) { sl.jpeg = true; const size_t extra = est_jpeg_bytes(sh->w, sh->h); sl.bytes += extra; live_bytes += extra; }
@@ -775,10 +904,12 @@ int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source
           }
           const mi_image_desc &x = src.desc;
           uint8_t *dst = mi_batch_input(sl.b, (int)k);
+          if (!dst) { rc = MI_ENCODING_ERROR; break; }
           const size_t sp = x.stride_px ? x.stride_px : x.width;
           if (sp == x.width) memcpy(dst, x.pixels, row * d0.height);
           else for (uint32_t y = 0; y < d0.height; y++) memcpy(dst + y * row, x.pixels + (size_t)y * sp * d0.channels, row);
         }
+        upload_png();
         upload_host(run.size());
         if (timing) fprintf(stderr, "[mi_avif %8.1f ms] dev %d: slot %d staged, uploads enqueued\n", since(), dev, j);
       }
@@ -790,7 +921,7 @@ int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source
       sl.busy = true;
       // a shape that keeps coming gets its next slot made while the GPU works on this run (not earlier: hipMalloc / hipHostMalloc on another
       // thread hold runtime locks that stall this thread's copies and launches; not for a shape seen once: a directory of differently sized files)
-      if (more && sh->runs >= 2) ensure_slot(sh, sh->next);
+      if (more && sh->runs >= 2) ensure_slot(sh, sh->next, any_host, png_run);
     };
     size_t claims = 0;
     for (;;) {
@@ -809,12 +940,13 @@ int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source
         const mi_image_source &src = d[i - i0];
         const mi_image_desc &x = src.desc;
         if (rc != MI_OK) { st[i] = rc; continue; }
-        const bool have = src.kind == 0 ? x.pixels != nullptr : src.kind == 1 && src.jpeg && src.jpeg->jc.w == x.width && src.jpeg->jc.h == x.height;
+        const bool have = src.kind == 0 ? x.pixels != nullptr : src.kind == 1 ? src.jpeg && src.jpeg->jc.w == x.width && src.jpeg->jc.h == x.height :
+                          src.kind == 2 && src.png && src.png->sl.w == x.width && src.png->sl.h == x.height && !(x.channels == 3 && src.png->sl.has_alpha());
         if (!have || !x.width || !x.height || (x.channels != 3 && x.channels != 4)) { st[i] = MI_INVALID_ARGUMENT; if (release) release(user, i); continue; }
         Shape *sh = shape_for(x);
         if (sh != run_shape || run.size() >= sh->cap) flush(true);
         run_shape = sh; run.push_back(i - i0);
-        if (run.size() == 1) ensure_slot(sh, sh->next);        // made in the background while the rest of the run arrives
+        if (run.size() == 1) ensure_slot(sh, sh->next, src.kind == 0, src.kind == 2 ? sh->cap * png_call_bytes(1, &src.png) : 0);   // made in the background while the rest of the run arrives
       }
       if (timing) fprintf(stderr, "[mi_avif %8.1f ms] dev %d: images %zu..%zu fetched\n", since(), dev, i0, i1);
       flush(cursor.load() < n);
@@ -837,7 +969,7 @@ int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source
 }
 // the host-pixel form: every source is kind 0
 struct StreamAdapter { mi_fetch_fn fetch; mi_release_fn release; void *user; };
-static int fetch_host_source(void *user, size_t i, mi_image_source *src) { const StreamAdapter *a = (const StreamAdapter *)user; src->kind = 0; src->jpeg = nullptr; return a->fetch(a->user, i, &src->desc); }
+static int fetch_host_source(void *user, size_t i, mi_image_source *src) { const StreamAdapter *a = (const StreamAdapter *)user; src->kind = 0; src->jpeg = nullptr; src->png = nullptr; return a->fetch(a->user, i, &src->desc); }
 static void release_host_source(void *user, size_t i) { const StreamAdapter *a = (const StreamAdapter *)user; a->release(a->user, i); }
 int mi_ravif_encode_stream(const mi_ravif_encoder *e, size_t n, mi_fetch_fn fetch, mi_release_fn release, void *user, mi_encoded_image *out, int *status, const int *devices, int ndev) {
   if (!e || !fetch || (n && !out)) return MI_INVALID_ARGUMENT;

@@ -41,11 +41,27 @@ inline bool png_unfilter(uint8_t *data, size_t rows, size_t rowbytes, int bpp) {
   return true;
 }
 
+// One file after inflate: the filtered scanlines (filter byte + filtered bytes per row, pass after pass for Adam7) and what it takes to turn them into
+// pixels.  The host reader below goes on from here with png_unfilter + png_expand_rgba; the device path (dev_png.h, mi_batch_upload_png) uploads `raw`.
+struct PngPass { size_t off; uint32_t rows, rowbytes, pw, x0, y0, dx, dy; };      // off: of the pass's first filter byte in raw; rows x (1 + rowbytes) bytes
+struct PngScanlines {
+  uint32_t w = 0, h = 0;
+  int depth = 0, ctype = 0, interlace = 0, channels = 0, bits_pp = 0, bpp = 0;   // bpp: bytes per complete pixel (>= 1), the filters' distance
+  uint32_t palette[256];                                                          // r | g << 8 | b << 16 | a << 24 with tRNS folded in; entries beyond PLTE are opaque black
+  bool has_key = false, has_trns = false; uint16_t key[3] = { 0, 0, 0 };          // tRNS colour key of gray (key[0]) and truecolour files, compared on all 16 bits
+  int npass = 0; PngPass pass[7];                                                 // the passes that have pixels, in stream order
+  std::vector<uint8_t> raw;
+  bool has_alpha() const { return ctype == 4 || ctype == 6 || has_trns; }
+};
+
+// Chunk walk, IHDR / PLTE / tRNS checks, size guard and inflate; every filter byte is checked (> 4 is an error), and so is every palette index when
+// PLTE is shorter than the index range -- for that the scanlines are unfiltered here and handed on as a filter-0 stream.
 // Returns 0 on success, 2 (MI_UNSUPPORTED) for non-PNG / unsupported data, 3 (MI_ENCODING_ERROR) for corrupt streams.
-inline int png_decode_rgba(const uint8_t *d, size_t len, std::vector<uint8_t> &rgba, uint32_t &w, uint32_t &h) {
+inline int png_read_scanlines(const uint8_t *d, size_t len, PngScanlines &sl) {
   static const uint8_t sig[8] = { 0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A };
   if (len < 8 + 25 || memcmp(d, sig, 8) != 0) return 2;
   size_t pos = 8;
+  uint32_t w = 0, h = 0;
   int depth = 0, ctype = 0, interlace = 0; bool have_ihdr = false;
   std::vector<uint8_t> idat, plte, trns;
   while (pos + 12 <= len) {
@@ -54,6 +70,7 @@ inline int png_decode_rgba(const uint8_t *d, size_t len, std::vector<uint8_t> &r
     if (!memcmp(type, "IHDR", 4)) {
       if (n != 13) return 3;
       w = png_be32(body); h = png_be32(body + 4); depth = body[8]; ctype = body[9]; interlace = body[12];
+      sl.w = w; sl.h = h;
       if (body[10] != 0 || body[11] != 0 || interlace > 1 || w == 0 || h == 0 || w > (1u << 16) || h > (1u << 16)) return 2;
       have_ihdr = true;
     } else if (!memcmp(type, "PLTE", 4)) plte.assign(body, body + n);
@@ -68,21 +85,26 @@ inline int png_decode_rgba(const uint8_t *d, size_t len, std::vector<uint8_t> &r
   if (!(depth == 8 || depth == 16 || ((ctype == 0 || ctype == 3) && (depth == 1 || depth == 2 || depth == 4))) || (ctype == 3 && depth == 16)) return 2;
   if (ctype == 3 && plte.size() < 3) return 3;
   const int bits_pp = channels * depth, bpp = bits_pp >= 8 ? bits_pp / 8 : 1;
+  sl.w = w; sl.h = h; sl.depth = depth; sl.ctype = ctype; sl.interlace = interlace; sl.channels = channels; sl.bits_pp = bits_pp; sl.bpp = bpp;
   // pass geometry: one pass for non-interlaced, seven for Adam7
   struct Pass { uint32_t x0, y0, dx, dy; };
   static const Pass adam7[7] = { { 0, 0, 8, 8 }, { 4, 0, 8, 8 }, { 0, 4, 4, 8 }, { 2, 0, 4, 4 }, { 0, 2, 2, 4 }, { 1, 0, 2, 2 }, { 0, 1, 1, 2 } };
   const Pass whole = { 0, 0, 1, 1 };
-  const int npass = interlace ? 7 : 1;
   size_t total = 0;
-  for (int p = 0; p < npass; p++) {
+  sl.npass = 0;
+  for (int p = 0; p < (interlace ? 7 : 1); p++) {
     const Pass &ps = interlace ? adam7[p] : whole;
+    if (w <= ps.x0 || h <= ps.y0) continue;
     const uint32_t pw = (w - ps.x0 + ps.dx - 1) / ps.dx, ph = (h - ps.y0 + ps.dy - 1) / ps.dy;
-    if (w <= ps.x0 || h <= ps.y0 || !pw || !ph) continue;
-    total += (size_t)ph * (1 + ((size_t)pw * bits_pp + 7) / 8);
+    if (!pw || !ph) continue;
+    const size_t rowbytes = ((size_t)pw * bits_pp + 7) / 8;
+    sl.pass[sl.npass++] = PngPass{ total, ph, (uint32_t)rowbytes, pw, ps.x0, ps.y0, ps.dx, ps.dy };
+    total += (size_t)ph * (1 + rowbytes);
   }
   // a deflate stream expands at most ~1032x: a tiny file that claims a huge canvas is refused before anything is allocated
   if (total > idat.size() * 1040 + 65536) return 3;
-  std::vector<uint8_t> raw(total);
+  std::vector<uint8_t> &raw = sl.raw;
+  raw.assign(total, 0);
   {
     z_stream zs; memset(&zs, 0, sizeof(zs));
     if (inflateInit(&zs) != Z_OK) return 3;
@@ -100,19 +122,49 @@ inline int png_decode_rgba(const uint8_t *d, size_t len, std::vector<uint8_t> &r
     inflateEnd(&zs);
     if ((zr != Z_STREAM_END && zr != Z_OK && zr != Z_BUF_ERROR) || got != total) return 3;
   }
-  rgba.assign((size_t)w * h * 4, 0);
+  // the filter bytes sit at known offsets
+  for (int p = 0; p < sl.npass; p++) {
+    const PngPass &ps = sl.pass[p];
+    for (uint32_t y = 0; y < ps.rows; y++) if (raw[ps.off + (size_t)y * (ps.rowbytes + 1)] > 4) return 3;
+  }
+  // palette (tRNS folded in) and colour key
+  for (int i = 0; i < 256; i++) sl.palette[i] = 0xFF000000u;
+  sl.has_key = sl.has_trns = false; sl.key[0] = sl.key[1] = sl.key[2] = 0;
+  if (ctype == 3) {
+    const size_t entries = std::min<size_t>(plte.size() / 3, 256);
+    for (size_t i = 0; i < entries; i++)
+      sl.palette[i] = (uint32_t)plte[i * 3] | ((uint32_t)plte[i * 3 + 1] << 8) | ((uint32_t)plte[i * 3 + 2] << 16) | ((uint32_t)(i < trns.size() ? trns[i] : 255) << 24);
+    sl.has_trns = !trns.empty();
+    if (entries < ((size_t)1 << depth)) {                      // rare: an index may point beyond PLTE, which only the unfiltered stream can tell
+      for (int p = 0; p < sl.npass; p++) {
+        const PngPass &ps = sl.pass[p];
+        if (!png_unfilter(raw.data() + ps.off, ps.rows, ps.rowbytes, bpp)) return 3;
+        const int mx = (1 << depth) - 1;
+        for (uint32_t y = 0; y < ps.rows; y++) {
+          uint8_t *line = raw.data() + ps.off + (size_t)y * (ps.rowbytes + 1);
+          line[0] = 0;
+          for (uint32_t xx = 0; xx < ps.pw; xx++) {
+            const size_t bit = (size_t)xx * depth;
+            const size_t idx = depth == 8 ? line[1 + (bit >> 3)] : (size_t)((line[1 + (bit >> 3)] >> (8 - depth - (bit & 7))) & mx);
+            if (idx >= entries) return 3;
+          }
+        }
+      }
+    }
+  } else if (ctype == 0 && trns.size() >= 2) { sl.has_key = sl.has_trns = true; sl.key[0] = (uint16_t)((trns[0] << 8) | trns[1]); }
+  else if (ctype == 2 && trns.size() >= 6) { sl.has_key = sl.has_trns = true; for (int c = 0; c < 3; c++) sl.key[c] = (uint16_t)((trns[2 * c] << 8) | trns[2 * c + 1]); }
+  return 0;
+}
+
+// unfiltered scanlines -> RGBA8 (w * h * 4 bytes)
+inline void png_expand_rgba(const PngScanlines &sl, uint8_t *rgba) {
+  const int depth = sl.depth, ctype = sl.ctype, channels = sl.channels;
   const int mx = (1 << (depth > 8 ? 8 : depth)) - 1;
-  size_t off = 0;
-  for (int p = 0; p < npass; p++) {
-    const Pass &ps = interlace ? adam7[p] : whole;
-    if (w <= ps.x0 || h <= ps.y0) continue;
-    const uint32_t pw = (w - ps.x0 + ps.dx - 1) / ps.dx, ph = (h - ps.y0 + ps.dy - 1) / ps.dy;
-    if (!pw || !ph) continue;
-    const size_t rowbytes = ((size_t)pw * bits_pp + 7) / 8;
-    if (!png_unfilter(raw.data() + off, ph, rowbytes, bpp)) return 3;
-    for (uint32_t yy = 0; yy < ph; yy++) {
-      const uint8_t *row = raw.data() + off + (size_t)yy * (rowbytes + 1) + 1;
-      for (uint32_t xx = 0; xx < pw; xx++) {
+  for (int p = 0; p < sl.npass; p++) {
+    const PngPass &ps = sl.pass[p];
+    for (uint32_t yy = 0; yy < ps.rows; yy++) {
+      const uint8_t *row = sl.raw.data() + ps.off + (size_t)yy * (ps.rowbytes + 1) + 1;
+      for (uint32_t xx = 0; xx < ps.pw; xx++) {
         // sample fetch: `depth`-bit big-endian samples, MSB first inside a byte; 16-bit samples keep their high byte
         // (px.map(|c| (c >> 8) as u8), src/main.rs:272-273), sub-byte gray is scaled to 0..255
         int s[4] = { 0, 0, 0, 0 }; int key16[4] = { 0, 0, 0, 0 };
@@ -124,30 +176,37 @@ inline int png_decode_rgba(const uint8_t *d, size_t len, std::vector<uint8_t> &r
         }
         uint8_t r, g, b, a = 255;
         if (ctype == 3) {
-          const size_t idx = (size_t)s[0];
-          if (idx * 3 + 2 >= plte.size()) return 3;
-          r = plte[idx * 3]; g = plte[idx * 3 + 1]; b = plte[idx * 3 + 2];
-          if (idx < trns.size()) a = trns[idx];
+          const uint32_t e = sl.palette[s[0]];
+          r = (uint8_t)e; g = (uint8_t)(e >> 8); b = (uint8_t)(e >> 16); a = (uint8_t)(e >> 24);
         } else if (ctype == 0 || ctype == 4) {
           const int v = depth < 8 ? s[0] * 255 / mx : s[0];
           r = g = b = (uint8_t)v;
           if (ctype == 4) a = (uint8_t)s[1];
-          else if (trns.size() >= 2) { const int key = (trns[0] << 8) | trns[1]; if ((depth == 16 ? key16[0] : s[0]) == key) a = 0; }
+          else if (sl.has_key && (depth == 16 ? key16[0] : s[0]) == sl.key[0]) a = 0;
         } else {
           r = (uint8_t)s[0]; g = (uint8_t)s[1]; b = (uint8_t)s[2];
           if (ctype == 6) a = (uint8_t)s[3];
-          else if (trns.size() >= 6) {
+          else if (sl.has_key) {
             bool eq = true;
-            for (int c = 0; c < 3; c++) { const int key = (trns[2 * c] << 8) | trns[2 * c + 1]; eq = eq && ((depth == 16 ? key16[c] : s[c]) == key); }
+            for (int c = 0; c < 3; c++) eq = eq && ((depth == 16 ? key16[c] : s[c]) == sl.key[c]);
             if (eq) a = 0;
           }
         }
-        uint8_t *o = &rgba[(((size_t)ps.y0 + (size_t)yy * ps.dy) * w + ps.x0 + (size_t)xx * ps.dx) * 4];
+        uint8_t *o = rgba + (((size_t)ps.y0 + (size_t)yy * ps.dy) * sl.w + ps.x0 + (size_t)xx * ps.dx) * 4;
         o[0] = r; o[1] = g; o[2] = b; o[3] = a;
       }
     }
-    off += (size_t)ph * (rowbytes + 1);
   }
+}
+
+// Returns 0 on success, 2 (MI_UNSUPPORTED) for non-PNG / unsupported data, 3 (MI_ENCODING_ERROR) for corrupt streams.
+inline int png_decode_rgba(const uint8_t *d, size_t len, std::vector<uint8_t> &rgba, uint32_t &w, uint32_t &h) {
+  PngScanlines sl;
+  if (const int st = png_read_scanlines(d, len, sl)) { w = sl.w; h = sl.h; return st; }
+  w = sl.w; h = sl.h;
+  for (int p = 0; p < sl.npass; p++) if (!png_unfilter(sl.raw.data() + sl.pass[p].off, sl.pass[p].rows, sl.pass[p].rowbytes, sl.bpp)) return 3;
+  rgba.assign((size_t)w * h * 4, 0);
+  png_expand_rgba(sl, rgba.data());
   return 0;
 }
 

@@ -50,7 +50,7 @@ class _ImageDesc(C.Structure):
 
 
 class _ImageSource(C.Structure):
-    _fields_ = [('kind', C.c_int), ('desc', _ImageDesc), ('jpeg', C.c_void_p)]
+    _fields_ = [('kind', C.c_int), ('desc', _ImageDesc), ('jpeg', C.c_void_p), ('png', C.c_void_p)]
 
 
 class _DevicePixels(C.Structure):
@@ -119,6 +119,10 @@ def load_library():
     L.mi_batch_read_input.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     L.mi_batch_upload_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(_DevicePixels)]
     L.mi_batch_upload_jpeg.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.mi_png_parse.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
+    L.mi_png_scanlines_free.argtypes = [C.c_void_p]
+    L.mi_png_scanlines_free.restype = None
+    L.mi_batch_upload_png.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.mi_ravif_encode_device.argtypes = [C.POINTER(_RavifEncoder), C.POINTER(_DevicePixels), C.c_uint32, C.c_uint32, C.POINTER(_EncodedImage)]
     L.mi_ravif_encode_sources.argtypes = [C.POINTER(_RavifEncoder), C.c_size_t, _FETCH_SOURCE, _RELEASE, C.c_void_p, C.POINTER(_EncodedImage),
                                           C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
@@ -202,6 +206,37 @@ class JpegCoeffs:
 def parse_jpeg(data):
     """mi_jpeg_parse: JPEG bytes -> JpegCoeffs (host work only: parse + Huffman decoding; raises AvifError as decode_jpeg does for the same bytes)."""
     return JpegCoeffs(data)
+
+
+class PngScanlines:
+    """One parsed PNG file (mi_png_parse): the inflated scanlines in host memory, `width`, `height`, `has_alpha` (an alpha channel or a tRNS chunk).  Feeds
+    BatchEncoder.upload_png and encode_many; the filters are undone and the pixels made on the device.  close() (or the garbage collector) frees it."""
+
+    def __init__(self, data):
+        L = load_library()
+        data = bytes(data)
+        h = C.c_void_p()
+        w, ht, alpha = C.c_uint32(), C.c_uint32(), C.c_int()
+        st = L.mi_png_parse(data, len(data), C.byref(h), C.byref(w), C.byref(ht), C.byref(alpha))
+        if st:
+            raise AvifError(st)
+        self._L, self._h, self.width, self.height, self.has_alpha = L, h.value, w.value, ht.value, bool(alpha.value)
+
+    def close(self):
+        if getattr(self, '_h', None):
+            self._L.mi_png_scanlines_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def parse_png(data):
+    """mi_png_parse: PNG bytes -> PngScanlines (host work only: chunks + inflate; raises AvifError as load_rgba does for the same bytes)."""
+    return PngScanlines(data)
 
 
 def _is_device_array(x):
@@ -430,18 +465,19 @@ class Encoder:
 
 def encode_many(encoder, images, devices=None):
     """mi_ravif_encode_sources: the reference's files.into_par_iter() (src/main.rs:223) over the node's GPUs.
-    images: list of HxWx3 / HxWx4 uint8 arrays (shapes may differ) and JpegCoeffs objects (parse_jpeg; encoded as the RGBA pictures decode_jpeg
-    gives, decoded on the device).  Returns a list of EncodedImage."""
+    images: list of HxWx3 / HxWx4 uint8 arrays (shapes may differ), JpegCoeffs objects (parse_jpeg; encoded as the RGBA pictures decode_jpeg
+    gives, decoded on the device) and PngScanlines objects (parse_png; encoded as the RGBA pictures load_rgba gives, unfiltered and expanded on the
+    device).  Returns a list of EncodedImage."""
     L = load_library()
     items = []
     for im in images:
-        if isinstance(im, JpegCoeffs):
+        if isinstance(im, (JpegCoeffs, PngScanlines)):
             if not im._h:
                 raise AvifError(4)
             items.append(im)
             continue
         if _is_device_array(im):
-            raise TypeError('encode_many takes host arrays and JpegCoeffs; pixels in device memory go through BatchEncoder.upload_device')
+            raise TypeError('encode_many takes host arrays, JpegCoeffs and PngScanlines; pixels in device memory go through BatchEncoder.upload_device')
         a = np.ascontiguousarray(im, dtype=np.uint8)
         if a.ndim != 3 or a.shape[2] not in (3, 4):
             raise AvifError(4)
@@ -449,11 +485,14 @@ def encode_many(encoder, images, devices=None):
 
     def fetch(_user, i, src):
         it, s = items[i], src.contents
-        if isinstance(it, JpegCoeffs):
-            s.kind, s.jpeg = 1, it._h
+        if isinstance(it, PngScanlines):
+            s.kind, s.jpeg, s.png = 2, None, it._h
+            s.desc.pixels, s.desc.width, s.desc.height, s.desc.stride_px, s.desc.channels = None, it.width, it.height, it.width, 4
+        elif isinstance(it, JpegCoeffs):
+            s.kind, s.jpeg, s.png = 1, it._h, None
             s.desc.pixels, s.desc.width, s.desc.height, s.desc.stride_px, s.desc.channels = None, it.width, it.height, it.width, 4
         else:
-            s.kind, s.jpeg = 0, None
+            s.kind, s.jpeg, s.png = 0, None, None
             s.desc.pixels, s.desc.width, s.desc.height, s.desc.stride_px, s.desc.channels = it.ctypes.data, it.shape[1], it.shape[0], it.shape[1], it.shape[2]
         return 0
     out = (_EncodedImage * len(items))()
@@ -503,6 +542,17 @@ class BatchEncoder:
         if not isinstance(coeffs, JpegCoeffs) or not coeffs._h:
             raise AvifError(4)
         st = self._L.mi_batch_upload_jpeg(self._h, index, coeffs._h)
+        if st:
+            raise AvifError(st)
+
+    def upload_png(self, first, handles):
+        """parsed PNG files (parse_png) of the batch's size into slots first..: one H2D, the scanline filters and the sample expansion run on the batch's
+        stream, one launch per kernel for all of them.  A file with alpha or tRNS into a 3-channel batch raises InvalidArgument."""
+        handles = [handles] if isinstance(handles, PngScanlines) else list(handles)
+        if not handles or any(not isinstance(p, PngScanlines) or not p._h for p in handles):
+            raise AvifError(4)
+        arr = (C.c_void_p * len(handles))(*[p._h for p in handles])
+        st = self._L.mi_batch_upload_png(self._h, first, len(handles), arr)
         if st:
             raise AvifError(st)
 

@@ -108,13 +108,17 @@ int  mi_ravif_encode_stream(const mi_ravif_encoder *e, size_t n, mi_fetch_fn fet
  * channels name the batch slot the picture is decoded into on the device (width and height must be the file's; channels 4 gives the pixels
  * mi_jpeg_decode_rgba gives, 3 the same without alpha), desc.pixels is unused.  Images are grouped into runs by (width, height, channels), so a JPEG and a
  * PNG picture of one size share a run.  `release` is called once the pixels (kind 0) or the coefficients (kind 1) are in pinned staging: the handle may
- * be freed then.  mi_ravif_encode_stream is this call with kind 0 throughout.  Pictures in device memory are not a kind here (a pointer belongs to one
+ * be freed then.  kind 2: the scanlines of a parsed PNG file (mi_png_parse below), unfiltered and expanded on the device; desc as for kind 1 (channels 3 only
+ * for files without an alpha channel and without tRNS, else the image is MI_INVALID_ARGUMENT), release once the scanlines are in pinned staging.
+ * mi_ravif_encode_stream is this call with kind 0 throughout.  Pictures in device memory are not a kind here (a pointer belongs to one
  * device, the shared cursor hands images to any): they enter through mi_ravif_encode_device and mi_batch_upload_device. */
 typedef struct mi_jpeg_coeffs mi_jpeg_coeffs;   /* opaque: one parsed file, host memory only */
+typedef struct mi_png_scanlines mi_png_scanlines;      /* opaque: one inflated file, host memory only */
 typedef struct mi_image_source {
-  int kind;                   /* 0 host pixels (desc), 1 JPEG coefficients (jpeg; desc.width/height/channels say the slot) */
+  int kind;                   /* 0 host pixels (desc), 1 JPEG coefficients (jpeg; desc.width/height/channels say the slot), 2 PNG scanlines (png; desc likewise) */
   mi_image_desc desc;
   const mi_jpeg_coeffs *jpeg;
+  const mi_png_scanlines *png; /* kind 2 only (the struct grew by this field at its tail: never read for kinds 0 and 1) */
 } mi_image_source;
 typedef int (*mi_fetch_source_fn)(void *user, size_t index, mi_image_source *src);
 int  mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source_fn fetch, mi_release_fn release, void *user, mi_encoded_image *out,
@@ -143,6 +147,12 @@ void mi_release_cached(void);
 /* PNG -> RGBA8 as cavif's load_rgba does (src/main.rs:265-283: RGB gets alpha 255, 16-bit samples keep their high byte, gray is
  * replicated); all colour types, bit depths, tRNS and Adam7.  Host code over zlib.  *rgba is malloc'd (mi_free), w*h*4 bytes. */
 int  mi_png_decode_rgba(const uint8_t *data, size_t len, uint8_t **rgba, uint32_t *w, uint32_t *h);
+/* The host half of a PNG decode on its own: chunk walk, inflate and every check that can fail (filter bytes, palette indices) into a handle that holds the
+ * inflated scanlines.  Never touches a device; the status for any bytes is the one mi_png_decode_rgba gives.  *has_alpha (nullable): the file has an alpha
+ * channel or a tRNS chunk.  The handle feeds mi_batch_upload_png and mi_ravif_encode_sources (kind 2) any number of times, from any thread, and is released
+ * with mi_png_scanlines_free (NULL is fine). */
+int  mi_png_parse(const uint8_t *data, size_t len, mi_png_scanlines **out, uint32_t *w, uint32_t *h, int *has_alpha);
+void mi_png_scanlines_free(mi_png_scanlines *p);
 /* JPEG -> RGBA8, the other format cavif's loader takes (load_image::load_data, src/main.rs:258; load_rgba :265-283: alpha 255, gray replicated).
  * Baseline / extended sequential and progressive Huffman files, 8 bit, one component or three at 4:4:4 / 4:2:2 / 4:2:0; arithmetic coding, lossless,
  * hierarchical, 12-bit, four-component files and other sampling ratios are MI_UNSUPPORTED, broken or incomplete streams MI_ENCODING_ERROR.  Huffman
@@ -166,7 +176,11 @@ typedef struct mi_batch mi_batch;
 mi_batch *mi_batch_create(const mi_ravif_encoder *e, int n_images, uint32_t w, uint32_t h, int channels);
 int  mi_batch_upload(mi_batch *b, int index, const uint8_t *pixels, size_t stride_px);   /* copy into the pinned staging + H2D into the batch's HBM input slot (blocking) */
 /* zero-copy form: fill the batch's PINNED host staging of image `index` (w*h*channels bytes, rows packed) in place, then enqueue
- * the H2D of a range of images on the batch's stream (returns at once; ordered before the next mi_batch_encode[_async]) */
+ * the H2D of a range of images on the batch's stream (returns at once; ordered before the next mi_batch_encode[_async]).
+ * The staging is pinned by the first mi_batch_input / mi_batch_upload of a batch, not by mi_batch_create (a batch fed through the device-resident calls
+ * below never pins it): that first call takes the time of pinning n * w * h * channels bytes, makes the batch's device the calling thread's current HIP
+ * device like the other mi_batch_* calls, and returns NULL (mi_batch_upload[_async]: MI_ENCODING_ERROR / MI_INVALID_ARGUMENT) when the memory cannot be
+ * pinned.  It may come from several threads at once. */
 uint8_t *mi_batch_input(mi_batch *b, int index);
 int  mi_batch_upload_async(mi_batch *b, int first, int count);
 /* device-resident input: the picture reaches the slot without ever being host pixels.
@@ -177,11 +191,16 @@ int  mi_batch_upload_async(mi_batch *b, int first, int count);
  * at once: the source must stay valid until the next mi_batch_wait.
  * mi_batch_upload_jpeg: one parsed JPEG of the batch's width and height (else MI_INVALID_ARGUMENT) into slot `index`: coefficients into pinned staging
  * the batch owns, H2D, dequantisation + IDCT + upsampling + colour on the batch's stream, no sync; the handle may be freed when the call returns.
- * Both upload calls return MI_INVALID_ARGUMENT between mi_batch_encode_async and mi_batch_wait. */
+ * mi_batch_upload_png: images [first, first+count) from parsed PNG files of the batch's width and height (else MI_INVALID_ARGUMENT; so is a file with an
+ * alpha channel or tRNS into a 3-channel batch: alpha is never dropped): scanlines into pinned staging the batch owns, one H2D, the scanline filters undone and
+ * the samples expanded to the slot's pixels -- those of mi_png_decode_rgba -- on the batch's stream, one launch per kernel for the whole call, no sync; the
+ * handles may be freed when the call returns.
+ * The upload calls return MI_INVALID_ARGUMENT between mi_batch_encode_async and mi_batch_wait. */
 uint8_t *mi_batch_device_input(mi_batch *b, int index);
 int  mi_batch_read_input(mi_batch *b, int index, uint8_t *dst);
 int  mi_batch_upload_device(mi_batch *b, int first, int count, const mi_device_pixels *src);
 int  mi_batch_upload_jpeg(mi_batch *b, int index, const mi_jpeg_coeffs *c);
+int  mi_batch_upload_png(mi_batch *b, int first, int count, const mi_png_scanlines *const *png);
 int  mi_batch_set_count(mi_batch *b, int n_images);                                       /* images of the next run (<= the count the batch was created for) */
 int  mi_batch_encode(mi_batch *b);                                                        /* the hot path over all resident images */
 /* split form: enqueue the GPU work and return; wait = sync + one packed D2H + OBU/container assembly.  Two batches
