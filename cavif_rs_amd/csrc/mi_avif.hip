@@ -19,6 +19,7 @@
 #include "jpeg_reader.h"
 #include "dev_jpeg.h"
 #include "dev_png.h"
+#include "dev_resample.h"
 #include "host_frames.h"
 
 // The product library reads no environment variables; probe builds (tools/) get MI_AVIF_TIMING=1 (-DMI_TUNING_KNOBS: host-side timeline on stderr)
@@ -61,6 +62,10 @@ struct mi_batch {
   PinBuf<uint8_t> h_jpeg; DevBuf<uint8_t> d_jpeg, d_jpeg_planes; size_t h_jpeg_cap = 0, d_jpeg_cap = 0, d_jpeg_planes_cap = 0, jpeg_used = 0;
   // PNG staging: descriptors + palettes + inflated scanlines of the mi_batch_upload_png calls since the stream last drained, pinned and on the device (unfiltered there in place)
   PinBuf<uint8_t> h_png; DevBuf<uint8_t> d_png; size_t h_png_cap = 0, d_png_cap = 0, png_used = 0;
+  // resize on input: the per-axis tables (bounds + taps) of the mi_batch_resize_* calls since the stream last drained, pinned and on the device, the last call's
+  // kept for the next one of the same sizes and filter; one device scratch for a decoded JPEG / PNG source and the intermediate of the two passes
+  PinBuf<uint8_t> h_rs; DevBuf<uint8_t> d_rs, d_rs_scratch; size_t h_rs_cap = 0, d_rs_cap = 0, rs_used = 0, d_rs_scratch_cap = 0;
+  uint32_t rs_key[5] = { 0, 0, 0, 0, 0 }; size_t rs_key_at = 0;     // src_w, src_h, dst_w, dst_h, filter + 1 of the tables at rs_key_at (0 in [4]: none)
 };
 
 static void batch_plan(mi_batch *b) {
@@ -273,7 +278,8 @@ int mi_batch_wait(mi_batch *b) {
   const int njobs = (int)b->fs.jobs.size();
   std::vector<uint32_t> offsets(njobs);
   HIP_OK(hipStreamSynchronize(s));
-  b->jpeg_used = 0; b->png_used = 0;                           // every JPEG / PNG upload of the run has left the pinned staging
+  b->jpeg_used = 0; b->png_used = 0; b->rs_used = 0;          // every JPEG / PNG upload and every resize table of the run has left the pinned staging (the last call's
+                                                              // tables stay on the device until the next ones are written: rs_key)
   if (b->channels == 4) for (int i = 0; i < b->n; i++) b->alpha_flags[i] = b->h_alpha.get()[i];
   auto idle = [&](const FramePlan &p) { return p.is_alpha && !b->alpha_flags[p.image]; };
   if (int st = b->fs.check_lengths()) return st;
@@ -369,7 +375,7 @@ static PoolKey pool_key(const mi_ravif_encoder *e, int cap, uint32_t w, uint32_t
 }
 static std::mutex g_pool_mu;
 static std::vector<std::pair<PoolKey, mi_batch *>> g_pool;          // oldest first; never destroyed at process exit (the runtime may be gone by then)
-static size_t batch_footprint(const mi_batch *b) { return b->fs.arena_bytes + b->fs.aux_bytes + 3 * b->pixel_bytes + b->packed_cap + b->h_jpeg_cap + b->d_jpeg_cap + b->d_jpeg_planes_cap + b->h_png_cap + b->d_png_cap; }
+static size_t batch_footprint(const mi_batch *b) { return b->fs.arena_bytes + b->fs.aux_bytes + 3 * b->pixel_bytes + b->packed_cap + b->h_jpeg_cap + b->d_jpeg_cap + b->d_jpeg_planes_cap + b->h_png_cap + b->d_png_cap + b->h_rs_cap + b->d_rs_cap + b->d_rs_scratch_cap; }
 static constexpr size_t MI_POOL_MAX_ITEMS = 8, MI_POOL_MAX_BYTES = (size_t)32 << 30;     // what the one-call entry points may keep between calls (mi_release_cached() frees it)
 
 static mi_batch *pool_acquire(const mi_ravif_encoder *e, int cap, uint32_t w, uint32_t h, int channels) {
@@ -644,11 +650,8 @@ int mi_batch_upload_device(mi_batch *b, int first, int count, const mi_device_pi
 // MI_BATCH_JPEG_STAGED of the first one's size; when the next one does not fit, the stream -- which carries nothing but such uploads then -- is waited
 // for and the staging starts over); the plane buffer is one image's, stream order serialises its users.
 static constexpr size_t MI_BATCH_JPEG_STAGED = 4;
-int mi_batch_upload_jpeg(mi_batch *b, int index, const mi_jpeg_coeffs *c) {
-  if (!b || !c || b->in_flight || index < 0 || index >= b->cap) return MI_INVALID_ARGUMENT;
-  const JpegCoeffs &jc = c->jc;
-  if (jc.w != b->w || jc.h != b->h) return MI_INVALID_ARGUMENT;
-  (void)hipSetDevice(b->device);
+// (the staging half, shared with mi_batch_resize_jpeg: rows of stride_px pixels at any device pointer)
+static int batch_jpeg_decode(mi_batch *b, const JpegCoeffs &jc, uint8_t *d_out, int channels, size_t stride_px) {
   const size_t need = align_up(jpeg_in_bytes(jc), 256);
   if (b->jpeg_used + need > b->h_jpeg_cap) {
     HIP_OK(hipStreamSynchronize(b->stream));
@@ -660,7 +663,14 @@ int mi_batch_upload_jpeg(mi_batch *b, int index, const mi_jpeg_coeffs *c) {
     if (!staging_grow(b->d_jpeg_planes, b->d_jpeg_planes_cap, jpeg_plane_bytes(jc))) return MI_ENCODING_ERROR;
   }
   const size_t at = b->jpeg_used; b->jpeg_used += need;
-  return jpeg_decode_to_device(jc, b->h_jpeg.get() + at, b->d_jpeg.get() + at, b->d_jpeg_planes.get(), mi_batch_device_input(b, index), b->channels, b->w, b->stream, nullptr);
+  return jpeg_decode_to_device(jc, b->h_jpeg.get() + at, b->d_jpeg.get() + at, b->d_jpeg_planes.get(), d_out, channels, stride_px, b->stream, nullptr);
+}
+int mi_batch_upload_jpeg(mi_batch *b, int index, const mi_jpeg_coeffs *c) {
+  if (!b || !c || b->in_flight || index < 0 || index >= b->cap) return MI_INVALID_ARGUMENT;
+  const JpegCoeffs &jc = c->jc;
+  if (jc.w != b->w || jc.h != b->h) return MI_INVALID_ARGUMENT;
+  (void)hipSetDevice(b->device);
+  return batch_jpeg_decode(b, jc, mi_batch_device_input(b, index), b->channels, b->w);
 }
 
 // ---- PNG input: the host half behind a handle, the device half on the batch's stream ----
@@ -702,13 +712,8 @@ static bool batch_reserve_png(mi_batch *b, size_t bytes) {
 // images [first, first + count) from parsed PNG files of the batch's size: descriptors, palettes and scanlines into the batch's pinned staging, one H2D, then
 // png_unfilter_kernel (one workgroup per pass that has a filtered row, all images in one launch) and png_expand_kernel on the batch's stream, no sync.
 // The staging keeps the calls since the stream last drained; when the next one does not fit, the stream is waited for and the staging starts over, grown to the call.
-int mi_batch_upload_png(mi_batch *b, int first, int count, const mi_png_scanlines *const *png) {
-  if (!b || !png || b->in_flight || first < 0 || count < 1 || first > b->cap - count) return MI_INVALID_ARGUMENT;
-  for (int i = 0; i < count; i++) {
-    if (!png[i] || png[i]->sl.w != b->w || png[i]->sl.h != b->h) return MI_INVALID_ARGUMENT;
-    if (b->channels == 3 && png[i]->sl.has_alpha()) return MI_INVALID_ARGUMENT;      // alpha is never dropped
-  }
-  (void)hipSetDevice(b->device);
+// (the body, shared with mi_batch_resize_png: `count` checked files of w x h into packed pictures of `channels` channels, back to back from `slots` on)
+static int batch_png_expand(mi_batch *b, int count, const mi_png_scanlines *const *png, uint32_t w, uint32_t h, int channels, uint8_t *slots) {
   const size_t need = png_call_bytes(count, png);
   if (b->png_used + need > b->h_png_cap || b->png_used + need > b->d_png_cap) {
     HIP_OK(hipStreamSynchronize(b->stream));                  // earlier calls' copies and kernels may still use the buffers that start over or are replaced
@@ -748,12 +753,176 @@ int mi_batch_upload_png(mi_batch *b, int first, int count, const mi_png_scanline
     const unsigned waves = std::min<unsigned>(MI_PNG_WAVES, (max_rows + 63) / 64);
     hipLaunchKernelGGL(png_unfilter_kernel, dim3(npass), dim3(64 * waves), 0, b->stream, db, (const PngPassDev *)(db + at));
   }
-  const dim3 grid(((b->w + 3) / 4 + 63) / 64, b->h, (unsigned)count);
-  uint8_t *const slots = mi_batch_device_input(b, first);
-  if (b->channels == 4) hipLaunchKernelGGL((png_expand_kernel<4>), grid, dim3(64), 0, b->stream, (const uint8_t *)db, (const PngImageDev *)(db + at + img_at), b->w, b->h, slots);
-  else hipLaunchKernelGGL((png_expand_kernel<3>), grid, dim3(64), 0, b->stream, (const uint8_t *)db, (const PngImageDev *)(db + at + img_at), b->w, b->h, slots);
+  const dim3 grid(((w + 3) / 4 + 63) / 64, h, (unsigned)count);
+  if (channels == 4) hipLaunchKernelGGL((png_expand_kernel<4>), grid, dim3(64), 0, b->stream, (const uint8_t *)db, (const PngImageDev *)(db + at + img_at), w, h, slots);
+  else hipLaunchKernelGGL((png_expand_kernel<3>), grid, dim3(64), 0, b->stream, (const uint8_t *)db, (const PngImageDev *)(db + at + img_at), w, h, slots);
   HIP_OK(hipGetLastError());
   return MI_OK;
+}
+int mi_batch_upload_png(mi_batch *b, int first, int count, const mi_png_scanlines *const *png) {
+  if (!b || !png || b->in_flight || first < 0 || count < 1 || first > b->cap - count) return MI_INVALID_ARGUMENT;
+  for (int i = 0; i < count; i++) {
+    if (!png[i] || png[i]->sl.w != b->w || png[i]->sl.h != b->h) return MI_INVALID_ARGUMENT;
+    if (b->channels == 3 && png[i]->sl.has_alpha()) return MI_INVALID_ARGUMENT;      // alpha is never dropped
+  }
+  (void)hipSetDevice(b->device);
+  return batch_png_expand(b, count, png, b->w, b->h, b->channels, mi_batch_device_input(b, first));
+}
+
+// ---- resize on input: a source of any size is resampled on the batch's stream into the slot (kernels: dev_resample.h) ----
+// The filters and the coefficients of one axis, as Pillow computes them for 8-bit pictures (Image.resize, reducing_gap=None): all in double, in this order.
+static double resample_filter(int filter, double x) {
+  switch (filter) {
+    case MI_RESAMPLE_BOX: return x > -0.5 && x <= 0.5 ? 1.0 : 0.0;
+    case MI_RESAMPLE_BILINEAR: if (x < 0.0) x = -x; return x < 1.0 ? 1.0 - x : 0.0;
+    case MI_RESAMPLE_BICUBIC: {
+      const double a = -0.5;
+      if (x < 0.0) x = -x;
+      if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+      if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+      return 0.0;
+    }
+    default: {
+      if (!(-3.0 <= x && x < 3.0)) return 0.0;
+      auto sinc = [](double v) { if (v == 0.0) return 1.0; v = v * 3.14159265358979323846; return sin(v) / v; };
+      return sinc(x) * sinc(x / 3);
+    }
+  }
+}
+static size_t resample_ksize(uint32_t in, uint32_t out, int filter) {
+  if (in == out) return 1;
+  static const double supports[4] = { 0.5, 1.0, 2.0, 3.0 };
+  const double scale = (double)in / out;
+  return (size_t)ceil(supports[filter] * (scale < 1.0 ? 1.0 : scale)) * 2 + 1;
+}
+static size_t resample_axis_bytes(uint32_t in, uint32_t out, int filter) { return align_up((size_t)out * 8, 16) + align_up(resample_ksize(in, out, filter) * out * 4, 16); }
+// bounds[2 i] = first sample, bounds[2 i + 1] = taps of output sample i; tap j of output i at taps[j * out + i], 22 fractional bits (unused ones 0).
+// An axis that keeps its length: the identity (its pass is skipped: the kernel moves the samples unchanged).
+static void resample_axis(uint32_t in, uint32_t out, int filter, uint32_t *bounds, int32_t *taps) {
+  const size_t ksize = resample_ksize(in, out, filter);
+  if (in == out) { for (uint32_t i = 0; i < out; i++) { bounds[2 * i] = i; bounds[2 * i + 1] = 1; taps[i] = 1 << MI_RS_BITS; } return; }
+  static const double supports[4] = { 0.5, 1.0, 2.0, 3.0 };
+  const double scale = (double)in / out, fs = scale < 1.0 ? 1.0 : scale, support = supports[filter] * fs;
+  std::vector<double> k(ksize);
+  memset(taps, 0, ksize * out * sizeof(int32_t));
+  for (uint32_t i = 0; i < out; i++) {
+    const double centre = (i + 0.5) * scale;
+    int xmin = (int)(centre - support + 0.5), xmax = (int)(centre + support + 0.5);
+    if (xmin < 0) xmin = 0;
+    if (xmax > (int)in) xmax = (int)in;
+    const int n = xmax - xmin;
+    double sum = 0.0;
+    for (int j = 0; j < n; j++) { k[j] = resample_filter(filter, (j + xmin - centre + 0.5) / fs); sum += k[j]; }
+    for (int j = 0; j < n; j++) {
+      const double v = sum != 0.0 ? k[j] / sum : k[j];
+      taps[(size_t)j * out + i] = v < 0 ? (int)(-0.5 + v * (1 << MI_RS_BITS)) : (int)(0.5 + v * (1 << MI_RS_BITS));
+    }
+    bounds[2 * i] = (uint32_t)xmin; bounds[2 * i + 1] = (uint32_t)n;
+  }
+}
+
+// the scratch holds `bytes` afterwards; an earlier call's kernels may still use the buffer that is replaced, so the stream is waited for first
+static int batch_reserve_scratch(mi_batch *b, size_t bytes) {
+  if (bytes <= b->d_rs_scratch_cap) return MI_OK;
+  HIP_OK(hipStreamSynchronize(b->stream));
+  return staging_grow(b->d_rs_scratch, b->d_rs_scratch_cap, bytes) ? MI_OK : MI_ENCODING_ERROR;
+}
+
+// The two passes: `count` pictures of s.w x s.h described by s -> slots [first, first + count).  The tables go into the batch's pinned staging and over in
+// one H2D (a call with the sizes and the filter of the one before it finds them on the device); the intermediate lies `inter_at` bytes into the scratch,
+// which the caller has reserved up to inter_at + resample_inter_bytes().  Stream order serialises the users of the scratch.  No sync.
+static size_t resample_inter_bytes(int count, uint32_t src_h, uint32_t dst_w) { return (size_t)count * src_h * align_up(dst_w, 4) * 4; }
+static int batch_resample(mi_batch *b, int first, int count, const IngestSrc &s, int filter, size_t inter_at) {
+  const uint32_t key[5] = { s.w, s.h, b->w, b->h, (uint32_t)filter + 1 };
+  const size_t h_bytes = resample_axis_bytes(s.w, b->w, filter), need = align_up(h_bytes + resample_axis_bytes(s.h, b->h, filter), 256);
+  size_t at = b->rs_key_at;
+  if (memcmp(key, b->rs_key, sizeof(key)) != 0) {
+    if (b->rs_used + need > b->h_rs_cap || b->rs_used + need > b->d_rs_cap) {
+      HIP_OK(hipStreamSynchronize(b->stream));                // earlier calls' copies and kernels may still use the buffers that start over or are replaced
+      b->rs_used = 0; b->rs_key[4] = 0;
+      if (!staging_grow(b->h_rs, b->h_rs_cap, need) || !staging_grow(b->d_rs, b->d_rs_cap, need)) return MI_ENCODING_ERROR;
+    }
+    at = b->rs_used; b->rs_used += need;
+    uint8_t *const hb = b->h_rs.get() + at;
+    resample_axis(s.w, b->w, filter, (uint32_t *)hb, (int32_t *)(hb + align_up((size_t)b->w * 8, 16)));
+    resample_axis(s.h, b->h, filter, (uint32_t *)(hb + h_bytes), (int32_t *)(hb + h_bytes + align_up((size_t)b->h * 8, 16)));
+    HIP_OK(hipMemcpyAsync(b->d_rs.get() + at, hb, need, hipMemcpyHostToDevice, b->stream));
+    memcpy(b->rs_key, key, sizeof(key)); b->rs_key_at = at;
+  }
+  const uint8_t *const db = b->d_rs.get() + at;
+  const uint32_t *const hbounds = (const uint32_t *)db, *const vbounds = (const uint32_t *)(db + h_bytes);
+  const int32_t *const htaps = (const int32_t *)(db + align_up((size_t)b->w * 8, 16)), *const vtaps = (const int32_t *)(db + h_bytes + align_up((size_t)b->h * 8, 16));
+  const uint32_t pitch = (uint32_t)align_up(b->w, 4);
+  uint32_t *const inter = (uint32_t *)(b->d_rs_scratch.get() + inter_at);
+  hipLaunchKernelGGL(resample_h_kernel, dim3((b->w + MI_RS_TW - 1) / MI_RS_TW, (s.h + MI_RS_TH - 1) / MI_RS_TH, (unsigned)count), dim3(64 * MI_RS_TH), 0, b->stream,
+                     s, hbounds, htaps, b->w, pitch, inter);
+  const dim3 grid(((b->w + 3) / 4 + 63) / 64, b->h, (unsigned)count);
+  uint8_t *const slots = mi_batch_device_input(b, first);
+  const int alpha = s.channels == 4 ? 1 : 0;
+  if (b->channels == 4) hipLaunchKernelGGL((resample_v_kernel<4>), grid, dim3(64), 0, b->stream, (const uint32_t *)inter, s.h, pitch, vbounds, vtaps, b->w, b->h, alpha, slots);
+  else hipLaunchKernelGGL((resample_v_kernel<3>), grid, dim3(64), 0, b->stream, (const uint32_t *)inter, s.h, pitch, vbounds, vtaps, b->w, b->h, alpha, slots);
+  HIP_OK(hipGetLastError());
+  return MI_OK;
+}
+static bool resample_filter_known(int filter) { return filter >= MI_RESAMPLE_BOX && filter <= MI_RESAMPLE_LANCZOS3; }
+static bool resample_extent_ok(uint32_t w, uint32_t h) { return w >= 1 && h >= 1 && w <= 65536 && h <= 65536; }     // what a batch may have (the grids and the tables count on it)
+
+// images [first, first + count) from pictures of src_w x src_h in the memory of the batch's device; of the batch's own size: mi_batch_upload_device
+int mi_batch_resize_device(mi_batch *b, int first, int count, const mi_device_pixels *src, uint32_t src_w, uint32_t src_h, int filter) {
+  if (!b || !src || !src->dev || b->in_flight || first < 0 || count < 1 || first > b->cap - count || !resample_filter_known(filter) || !resample_extent_ok(src_w, src_h)) return MI_INVALID_ARGUMENT;
+  if ((src->layout != 0 && src->layout != 1) || (src->channels != 3 && src->channels != 4) || src->channels > b->channels) return MI_INVALID_ARGUMENT;   // alpha is never dropped
+  if (src_w == b->w && src_h == b->h) return mi_batch_upload_device(b, first, count, src);
+  IngestSrc s;
+  s.base = (const uint8_t *)src->dev; s.w = src_w; s.h = src_h; s.layout = src->layout; s.channels = src->channels;
+  const size_t packed_row = (size_t)src_w * (s.layout == 0 ? s.channels : 1);
+  s.row_stride = src->row_stride ? src->row_stride : packed_row;
+  s.inner_stride = src->pixel_or_plane_stride ? src->pixel_or_plane_stride : s.layout == 0 ? (size_t)s.channels : s.row_stride * src_h;
+  s.image_stride = src->image_stride ? src->image_stride : s.layout == 0 ? s.row_stride * src_h : s.inner_stride * s.channels;
+  if (s.row_stride < packed_row || s.inner_stride < (s.layout == 0 ? (size_t)s.channels : (size_t)src_w)) return MI_INVALID_ARGUMENT;
+  (void)hipSetDevice(b->device);
+  if (int st = batch_reserve_scratch(b, resample_inter_bytes(count, src_h, b->w))) return st;
+  if (src->after_stream) {
+    if (!b->ev_src) HIP_OK(hipEventCreateWithFlags(&b->ev_src, hipEventDisableTiming));
+    HIP_OK(hipEventRecord(b->ev_src, (hipStream_t)src->after_stream));
+    HIP_OK(hipStreamWaitEvent(b->stream, b->ev_src, 0));
+  }
+  return batch_resample(b, first, count, s, filter, 0);
+}
+
+// a decoded source at the start of the scratch, packed, `channels` channels: what the two forms below resample
+static IngestSrc resample_scratch_source(const mi_batch *b, uint32_t w, uint32_t h, int channels) {
+  IngestSrc s;
+  s.base = b->d_rs_scratch.get(); s.w = w; s.h = h; s.layout = 0; s.channels = channels;
+  s.inner_stride = (size_t)channels; s.row_stride = (size_t)w * channels; s.image_stride = s.row_stride * h;
+  return s;
+}
+
+// one parsed JPEG of any size into slot `index`: decoded into the scratch as RGB (mi_batch_upload_jpeg's kernels), then the two passes; of the batch's own size: mi_batch_upload_jpeg
+int mi_batch_resize_jpeg(mi_batch *b, int index, const mi_jpeg_coeffs *c, int filter) {
+  if (!b || !c || b->in_flight || index < 0 || index >= b->cap || !resample_filter_known(filter)) return MI_INVALID_ARGUMENT;
+  const JpegCoeffs &jc = c->jc;
+  if (jc.w == b->w && jc.h == b->h) return mi_batch_upload_jpeg(b, index, c);
+  if (!resample_extent_ok(jc.w, jc.h)) return MI_INVALID_ARGUMENT;
+  (void)hipSetDevice(b->device);
+  const size_t inter_at = align_up((size_t)jc.w * jc.h * 3, 256);
+  if (int st = batch_reserve_scratch(b, inter_at + resample_inter_bytes(1, jc.h, b->w))) return st;
+  if (int st = batch_jpeg_decode(b, jc, b->d_rs_scratch.get(), 3, jc.w)) return st;
+  return batch_resample(b, index, 1, resample_scratch_source(b, jc.w, jc.h, 3), filter, inter_at);
+}
+
+// one parsed PNG of any size into slot `index`: unfiltered and expanded into the scratch (RGBA when the file has alpha or tRNS, else RGB), then the two passes; of
+// the batch's own size: mi_batch_upload_png
+int mi_batch_resize_png(mi_batch *b, int index, const mi_png_scanlines *p, int filter) {
+  if (!b || !p || b->in_flight || index < 0 || index >= b->cap || !resample_filter_known(filter)) return MI_INVALID_ARGUMENT;
+  const int channels = p->sl.has_alpha() ? 4 : 3;
+  if (channels > b->channels) return MI_INVALID_ARGUMENT;     // alpha is never dropped
+  if (p->sl.w == b->w && p->sl.h == b->h) return mi_batch_upload_png(b, index, 1, &p);
+  if (!resample_extent_ok(p->sl.w, p->sl.h)) return MI_INVALID_ARGUMENT;
+  (void)hipSetDevice(b->device);
+  const size_t inter_at = align_up((size_t)p->sl.w * p->sl.h * channels, 256);
+  if (int st = batch_reserve_scratch(b, inter_at + resample_inter_bytes(1, p->sl.h, b->w))) return st;
+  if (int st = batch_png_expand(b, 1, &p, p->sl.w, p->sl.h, channels, b->d_rs_scratch.get())) return st;
+  return batch_resample(b, index, 1, resample_scratch_source(b, p->sl.w, p->sl.h, channels), filter, inter_at);
 }
 
 // ravif::Encoder::encode_rgba / encode_rgb for a picture in the memory of device e->device (channels 4 / 3 as src->channels says)
@@ -762,6 +931,17 @@ int mi_ravif_encode_device(const mi_ravif_encoder *e, const mi_device_pixels *sr
   mi_batch *b = pool_acquire(e, 1, w, h, src->channels);
   if (!b) return mi_device_count() > e->device ? MI_INVALID_ARGUMENT : MI_NO_DEVICE;
   int st = mi_batch_upload_device(b, 0, 1, src);
+  if (st == MI_OK) st = mi_batch_encode(b);
+  if (st == MI_OK) st = mi_batch_get(b, 0, out);
+  pool_release(b);
+  return st;
+}
+// the same for a picture of src_w x src_h that is resampled to w x h on the way in
+int mi_ravif_encode_device_resized(const mi_ravif_encoder *e, const mi_device_pixels *src, uint32_t src_w, uint32_t src_h, uint32_t w, uint32_t h, int filter, mi_encoded_image *out) {
+  if (!e || !src || !src->dev || !out || w < 1 || h < 1 || (src->channels != 3 && src->channels != 4)) return MI_INVALID_ARGUMENT;
+  mi_batch *b = pool_acquire(e, 1, w, h, src->channels);
+  if (!b) return mi_device_count() > e->device ? MI_INVALID_ARGUMENT : MI_NO_DEVICE;
+  int st = mi_batch_resize_device(b, 0, 1, src, src_w, src_h, filter);
   if (st == MI_OK) st = mi_batch_encode(b);
   if (st == MI_OK) st = mi_batch_get(b, 0, out);
   pool_release(b);

@@ -124,6 +124,10 @@ def load_library():
     L.mi_png_scanlines_free.restype = None
     L.mi_batch_upload_png.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.mi_ravif_encode_device.argtypes = [C.POINTER(_RavifEncoder), C.POINTER(_DevicePixels), C.c_uint32, C.c_uint32, C.POINTER(_EncodedImage)]
+    L.mi_batch_resize_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(_DevicePixels), C.c_uint32, C.c_uint32, C.c_int]
+    L.mi_batch_resize_jpeg.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    L.mi_batch_resize_png.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    L.mi_ravif_encode_device_resized.argtypes = [C.POINTER(_RavifEncoder), C.POINTER(_DevicePixels), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_EncodedImage)]
     L.mi_ravif_encode_sources.argtypes = [C.POINTER(_RavifEncoder), C.c_size_t, _FETCH_SOURCE, _RELEASE, C.c_void_p, C.POINTER(_EncodedImage),
                                           C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
     _LIB = L
@@ -237,6 +241,15 @@ class PngScanlines:
 def parse_png(data):
     """mi_png_parse: PNG bytes -> PngScanlines (host work only: chunks + inflate; raises AvifError as load_rgba does for the same bytes)."""
     return PngScanlines(data)
+
+
+RESAMPLE_FILTERS = {'box': 0, 'bilinear': 1, 'bicubic': 2, 'lanczos': 3}       # MI_RESAMPLE_*: Pillow's filters of the same names
+
+
+def _resample_filter(name):
+    if name not in RESAMPLE_FILTERS:
+        raise AvifError(4)
+    return RESAMPLE_FILTERS[name]
 
 
 def _is_device_array(x):
@@ -433,6 +446,40 @@ class Encoder:
             raise AvifError(st)
         return _take(img)
 
+    def encode_resized(self, source, size, filter='lanczos'):
+        """`source` resampled to size = (width, height) on the device, then encoded: the file of encode_rgb / encode_rgba over the pixels Pillow's
+        Image.resize(size, resample=filter, reducing_gap=None) gives.  source: an object with __cuda_array_interface__ (uint8, (H, W, C) or (C, H, W), any
+        size; encoded as RGB or RGBA by its channels), a JpegCoeffs (RGB) or a PngScanlines (RGBA when the file has alpha or tRNS, else RGB).
+        filter: 'box', 'bilinear', 'bicubic' or 'lanczos'."""
+        L = load_library()
+        f = _resample_filter(filter)
+        w, h = int(size[0]), int(size[1])
+        if w < 1 or h < 1:
+            raise AvifError(4)
+        if _is_device_array(source):
+            d, _, sh, sw, index = _device_pixels(source)
+            img = _EncodedImage()
+            e = self._c()
+            if index is not None:
+                e.device = index                        # the pointer belongs to that device
+            st = L.mi_ravif_encode_device_resized(C.byref(e), C.byref(d), sw, sh, w, h, f, C.byref(img))
+            if st:
+                raise AvifError(st)
+            return _take(img)
+        if isinstance(source, JpegCoeffs):
+            channels = 3
+        elif isinstance(source, PngScanlines):
+            channels = 4 if source.has_alpha else 3
+        else:
+            raise TypeError('encode_resized takes a device array, a JpegCoeffs or a PngScanlines (host pixels: resize them where they are)')
+        b = BatchEncoder(self, 1, w, h, channels)       # the handle forms go through a one-image batch
+        try:
+            (b.resize_jpeg if isinstance(source, JpegCoeffs) else b.resize_png)(0, source, filter)
+            b.encode()
+            return b.get(0)
+        finally:
+            b.close()
+
     def encode_rgba(self, rgba):                        # :243
         return self._encode(rgba, 4)
 
@@ -553,6 +600,32 @@ class BatchEncoder:
             raise AvifError(4)
         arr = (C.c_void_p * len(handles))(*[p._h for p in handles])
         st = self._L.mi_batch_upload_png(self._h, first, len(handles), arr)
+        if st:
+            raise AvifError(st)
+
+    def resize_device(self, first, pixels, filter='lanczos'):
+        """upload_device for pictures of any size (taken from the array): resampled into the slots on the batch's stream, the pixels of Pillow's
+        Image.resize((w, h), resample=filter, reducing_gap=None); filter: 'box', 'bilinear', 'bicubic' or 'lanczos'"""
+        d, n, h, w, _ = _device_pixels(pixels, batched=True)
+        st = self._L.mi_batch_resize_device(self._h, first, n, C.byref(d), w, h, _resample_filter(filter))
+        if st:
+            raise AvifError(st)
+        self._sources.append(pixels)
+
+    def resize_jpeg(self, index, coeffs, filter='lanczos'):
+        """upload_jpeg for a file of any size: decoded and resampled into slot `index` on the batch's stream"""
+        if not isinstance(coeffs, JpegCoeffs) or not coeffs._h:
+            raise AvifError(4)
+        st = self._L.mi_batch_resize_jpeg(self._h, index, coeffs._h, _resample_filter(filter))
+        if st:
+            raise AvifError(st)
+
+    def resize_png(self, index, scanlines, filter='lanczos'):
+        """upload_png for one file of any size: unfiltered, expanded and resampled into slot `index` on the batch's stream.  A file with alpha or tRNS into
+        a 3-channel batch raises InvalidArgument."""
+        if not isinstance(scanlines, PngScanlines) or not scanlines._h:
+            raise AvifError(4)
+        st = self._L.mi_batch_resize_png(self._h, index, scanlines._h, _resample_filter(filter))
         if st:
             raise AvifError(st)
 

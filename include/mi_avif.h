@@ -137,6 +137,10 @@ typedef struct mi_device_pixels {
 /* ravif::Encoder::encode_rgb / encode_rgba (by src->channels) of a w x h picture in the memory of device e->device.  The pointer must belong to that
  * device (not detected).  Blocking, through the pooled batch objects like mi_ravif_encode_rgba. */
 int  mi_ravif_encode_device(const mi_ravif_encoder *e, const mi_device_pixels *src, uint32_t w, uint32_t h, mi_encoded_image *out);
+/* The same for a picture of src_w x src_h that is resampled to w x h on the device on the way in (mi_batch_resize_device below: `filter` is one of
+ * MI_RESAMPLE_*, the pixels are specified exactly).  Blocking, pooled by (w, h, channels) like mi_ravif_encode_device. */
+int  mi_ravif_encode_device_resized(const mi_ravif_encoder *e, const mi_device_pixels *src, uint32_t src_w, uint32_t src_h, uint32_t w, uint32_t h, int filter,
+                                    mi_encoded_image *out);
 
 /* The one-call entry points above (mi_ravif_encode_rgba / _rgb / _device / _batch / _stream / _sources) keep their device arenas and pinned staging in
  * a process-wide pool keyed by (device, shape, settings), so a loop of calls with the same settings pays the allocation once
@@ -201,6 +205,21 @@ int  mi_batch_read_input(mi_batch *b, int index, uint8_t *dst);
 int  mi_batch_upload_device(mi_batch *b, int first, int count, const mi_device_pixels *src);
 int  mi_batch_upload_jpeg(mi_batch *b, int index, const mi_jpeg_coeffs *c);
 int  mi_batch_upload_png(mi_batch *b, int first, int count, const mi_png_scanlines *const *png);
+/* resize on input: the source has any size and is resampled into the slot on the batch's stream, no sync.  The pixels are exactly those of Pillow's
+ * Image.resize((w, h), resample=filter, reducing_gap=None) on 8-bit pictures: coefficients in double on the host, 22-bit fixed-point taps, horizontal pass
+ * first into an 8-bit intermediate, then the vertical one, a pass whose axis keeps its length skipped; 4-channel sources are premultiplied before the passes and
+ * un-premultiplied after them, 3 channels into an RGBA batch get alpha 255 and no premultiplication.  A source of the batch's own size takes the upload call
+ * of its kind above and gives that call's bytes.  The tables go through pinned staging the batch owns (one H2D per call), a decoded JPEG / PNG source and the
+ * intermediate live in one device scratch of the batch, grown on demand.
+ * mi_batch_resize_device: images [first, first+count) from pictures of src_w x src_h, described and ordered (after_stream) as for mi_batch_upload_device.
+ * mi_batch_resize_jpeg / _png: one parsed file into slot `index`; a PNG with an alpha channel or tRNS into a 3-channel batch is MI_INVALID_ARGUMENT.
+ * MI_INVALID_ARGUMENT as well: an unknown filter, a zero extent (or one above 65536), strides below the packed row, a range past the capacity, a call between
+ * mi_batch_encode_async and mi_batch_wait, 4 channels into a 3-channel batch; MI_ENCODING_ERROR when staging or scratch cannot be allocated.  Lifetimes as for
+ * the upload calls: the device source until the next mi_batch_wait, the handles until the call returns. */
+enum { MI_RESAMPLE_BOX = 0, MI_RESAMPLE_BILINEAR = 1, MI_RESAMPLE_BICUBIC = 2, MI_RESAMPLE_LANCZOS3 = 3 };
+int  mi_batch_resize_device(mi_batch *b, int first, int count, const mi_device_pixels *src, uint32_t src_w, uint32_t src_h, int filter);
+int  mi_batch_resize_jpeg(mi_batch *b, int index, const mi_jpeg_coeffs *c, int filter);
+int  mi_batch_resize_png(mi_batch *b, int index, const mi_png_scanlines *p, int filter);
 int  mi_batch_set_count(mi_batch *b, int n_images);                                       /* images of the next run (<= the count the batch was created for) */
 int  mi_batch_encode(mi_batch *b);                                                        /* the hot path over all resident images */
 /* split form: enqueue the GPU work and return; wait = sync + one packed D2H + OBU/container assembly.  Two batches
