@@ -380,6 +380,7 @@ static int search_enqueue(SearchQueue &q, const std::vector<FramePlan> &frames, 
   return search_launch(q, mode, class_begin, d_frames, d_jobs, device, s);
 }
 
+#define MI_FRAME_RECORD_BYTES 32          /* reserved per (frame, plane) behind the frames' arenas (FrameSet::d_records) */
 // ---- a set of frames on one device, ready to run: what mi_batch and mi_av1_encode_planes share ----
 // reserve() once for the worst case, then per encode: fill `frames` (plan_geometry), place(), write the source planes, stage(), enqueue_chain(),
 // enqueue_readback(), wait for the stream, check_lengths(), assemble().
@@ -393,6 +394,8 @@ struct FrameSet {
   PinBuf<FrameDev> h_frames; PinBuf<TileJob> h_jobs; PinBuf<uint32_t> h_lens; PinBuf<int> h_lf;   // pinned: H2D sources; tile lengths, deblock levels + segment indices (13 per frame)
   SearchQueue queue;
   size_t tiles_cap = 0, payload_worst = 0;                              // reserved: tile jobs, the sum of their output capacities
+  uint8_t *d_records = nullptr; size_t records_cap = 0;                 // MI_FRAME_RECORD_BYTES per (frame, plane) of the worst case, behind the frames' arenas: what a stage outside
+                                                                        // the chain reports per plane (the quality metrics, dev_quality.h); never touched by an encode
   int max_mi_cells = 0, max_sb = 0, max_lr = 0, max_cells = 0, max_tiles = 1;   // launch maxima of the placed frames
 
   // allocates everything for the worst case `worst` (geometry planned): no (device-synchronising) reallocation inside an encode
@@ -406,9 +409,12 @@ struct FrameSet {
       payload_worst += (size_t)p.ntiles * cap;
     }
     pre_cap = max_cap; rec_cap = MI_K4_SB_RECORDS(max_np);
+    const size_t records_off = total;
+    records_cap = worst.size() * 3; total += align_up(records_cap * MI_FRAME_RECORD_BYTES, 4096);
     arena_bytes = total; aux_bytes = tiles_cap * (size_t)max_cap * 2 + tiles_cap * 3 * (size_t)rec_cap * 4;
     const size_t prof_words = std::max<size_t>(tiles_cap, 2048) * 128;
     HIP_OK(d_arena.alloc(total));
+    d_records = d_arena.get() + records_off;
     HIP_OK(d_frames.alloc(worst.size()));
     HIP_OK(d_jobs.alloc(tiles_cap));
     HIP_OK(d_precarry.alloc(tiles_cap * (size_t)max_cap));

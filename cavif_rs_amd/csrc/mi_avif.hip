@@ -20,6 +20,7 @@
 #include "dev_jpeg.h"
 #include "dev_png.h"
 #include "dev_resample.h"
+#include "dev_quality.h"
 #include "host_frames.h"
 
 // The product library reads no environment variables; probe builds (tools/) get MI_AVIF_TIMING=1 (-DMI_TUNING_KNOBS: host-side timeline on stderr)
@@ -66,7 +67,12 @@ struct mi_batch {
   // kept for the next one of the same sizes and filter; one device scratch for a decoded JPEG / PNG source and the intermediate of the two passes
   PinBuf<uint8_t> h_rs; DevBuf<uint8_t> d_rs, d_rs_scratch; size_t h_rs_cap = 0, d_rs_cap = 0, rs_used = 0, d_rs_scratch_cap = 0;
   uint32_t rs_key[5] = { 0, 0, 0, 0, 0 }; size_t rs_key_at = 0;     // src_w, src_h, dst_w, dst_h, filter + 1 of the tables at rs_key_at (0 in [4]: none)
+  // quality metrics (mi_batch_measure): `encoded` = the planes of a completed encode of the current image count are on the device, `measured` = h_quality holds
+  // that encode's records.  The records live at the end of the arena (FrameSet::d_records); their pinned D2H target is made by the first measure.
+  bool encoded = false, measured = false;
+  PinBuf<QualityRec> h_quality; size_t h_quality_bytes = 0;
 };
+static_assert(sizeof(QualityRec) <= MI_FRAME_RECORD_BYTES, "FrameSet reserves MI_FRAME_RECORD_BYTES per (frame, plane)");
 
 static void batch_plan(mi_batch *b) {
   // (re)build frame plans: colour for every image [0, n), then (RGBA input) one alpha frame per image [n, 2n) -- whether an alpha
@@ -172,6 +178,7 @@ uint8_t *mi_batch_input(mi_batch *b, int index) {
 int mi_batch_set_count(mi_batch *b, int n_images) {
   if (!b || b->in_flight || n_images < 1 || n_images > b->cap) return MI_INVALID_ARGUMENT;
   b->n = n_images; b->alpha_flags.assign(n_images, 0);
+  b->encoded = b->measured = false;
   return MI_OK;
 }
 // enqueue the H2D of images [first, first + count) from the pinned staging on the batch's stream; returns at once
@@ -214,6 +221,7 @@ double mi_batch_stage_ms(const mi_batch *b, int stage) { return (b && stage >= 0
 int mi_batch_encode_async(mi_batch *b) {
   if (!b) return MI_INVALID_ARGUMENT;
   if (b->in_flight) return MI_INVALID_ARGUMENT;
+  b->encoded = b->measured = false;
   (void)hipSetDevice(b->device);
   hipStream_t s = b->stream;
   uint8_t *const d_pixels = b->d_pixels.get(), *const d_clean = b->d_clean.get(), *const d_clean_tmp = b->d_clean_tmp.get();
@@ -316,6 +324,7 @@ int mi_batch_wait(mi_batch *b) {
   HIP_OK(hipEventRecord(b->ev[7], s));
   HIP_OK(hipEventSynchronize(b->ev[7]));
   for (int i = 0; i < 7; i++) { float ms = 0; (void)hipEventElapsedTime(&ms, b->ev[i], b->ev[i + 1]); b->stage_ms[i] = ms; }
+  b->encoded = true;
   return MI_OK;
 }
 
@@ -344,6 +353,68 @@ int mi_batch_get_recon(mi_batch *b, int index, int alpha, uint16_t *planes[3]) {
     HIP_OK(hipMemcpy2D(planes[i], (size_t)b->w * 2, p->cfg.lrf ? p->dev.lrp[i] : p->dev.fin[i], (size_t)p->pw * 2, (size_t)b->w * 2, b->h, hipMemcpyDeviceToHost));
   }
   return MI_OK;
+}
+
+int mi_batch_get_source(mi_batch *b, int index, int alpha, uint16_t *planes[3]) {
+  if (!b || !planes || index < 0 || index >= b->n || !b->encoded) return MI_INVALID_ARGUMENT;
+  (void)hipSetDevice(b->device);
+  const FramePlan *p = nullptr;
+  if (!alpha) p = &b->fs.frames[index]; else if (b->channels == 4 && b->alpha_flags[index]) p = &b->fs.frames[b->n + index];
+  if (!p) return MI_INVALID_ARGUMENT;
+  for (int i = 0; i < 3; i++) planes[i] = nullptr;
+  for (int i = 0; i < p->np; i++) {
+    planes[i] = (uint16_t *)malloc((size_t)b->w * b->h * 2);
+    HIP_OK(hipMemcpy2D(planes[i], (size_t)b->w * 2, p->dev.src[i], (size_t)p->pw * 2, (size_t)b->w * 2, b->h, hipMemcpyDeviceToHost));
+  }
+  return MI_OK;
+}
+
+// ---- quality metrics of the last completed encode (dev_quality.h) ----
+// One launch over the frame descriptors the encode staged (still on the device: nothing after mi_batch_wait writes them or the planes until the next encode),
+// the records zeroed in front of it and copied to the pinned mirror behind it, one sync.
+int mi_batch_measure(mi_batch *b) {
+  if (!b || b->in_flight || !b->encoded) return MI_INVALID_ARGUMENT;
+  (void)hipSetDevice(b->device);
+  hipStream_t s = b->stream;
+  const size_t nrec = b->fs.frames.size() * 3;
+  if (nrec == 0 || nrec > b->fs.records_cap) return MI_INVALID_ARGUMENT;
+  if (!b->h_quality.get()) { HIP_OK(b->h_quality.alloc(b->fs.records_cap)); b->h_quality_bytes = b->fs.records_cap * sizeof(QualityRec); }
+  b->measured = false;
+  QualityRec *const d_rec = (QualityRec *)b->fs.d_records;
+  unsigned tiles = 0;
+  for (const FramePlan &p : b->fs.frames) tiles = std::max(tiles, (unsigned)((p.pw / MI_Q_TILE) * (p.ph / MI_Q_TILE)));
+  HIP_OK(hipMemsetAsync(d_rec, 0, nrec * sizeof(QualityRec), s));
+  hipLaunchKernelGGL(quality_kernel, dim3(tiles, 3, (unsigned)b->fs.frames.size()), dim3(256), 0, s, (const FrameDev *)b->fs.d_frames.get(), d_rec);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(b->h_quality.get(), d_rec, nrec * sizeof(QualityRec), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  b->measured = true;
+  return MI_OK;
+}
+int mi_batch_get_quality(mi_batch *b, int index, mi_image_quality *out) {
+  if (!b || !out || index < 0 || index >= b->n || !b->encoded || !b->measured) return MI_INVALID_ARGUMENT;
+  memset(out, 0, sizeof(*out));
+  out->width = b->w; out->height = b->h; out->depth = (uint8_t)b->depth; out->color_planes = (uint8_t)b->fs.frames[index].np;
+  out->has_alpha = (b->channels == 4 && b->alpha_flags[index]) ? 1 : 0;
+  auto put = [&](mi_plane_quality &q, size_t frame, int plane) {
+    const QualityRec &r = b->h_quality.get()[3 * frame + plane];
+    q.sse = r.sse; q.ssim_sum = (int64_t)r.ssim_sum; q.ssim_windows = r.ssim_windows;
+  };
+  for (int p = 0; p < out->color_planes; p++) put(out->color[p], (size_t)index, p);
+  if (out->has_alpha) put(out->alpha, (size_t)b->n + index, 0);
+  return MI_OK;
+}
+double mi_quality_psnr_db(const mi_image_quality *q) {
+  if (!q) return NAN;
+  double sse = 0; for (int p = 0; p < q->color_planes && p < 3; p++) sse += (double)q->color[p].sse;
+  if (sse == 0) return INFINITY;
+  const double peak = (double)((1 << q->depth) - 1), n = (double)q->color_planes * q->width * q->height;
+  return 10.0 * log10(peak * peak * n / sse);
+}
+double mi_quality_ssim_db(const mi_image_quality *q) {
+  if (!q || q->color[0].ssim_windows == 0) return NAN;
+  const double mean = (double)q->color[0].ssim_sum / MI_Q_ONE / (double)q->color[0].ssim_windows;
+  return mean >= 1.0 ? INFINITY : -10.0 * log10(1.0 - mean);
 }
 
 void mi_batch_destroy(mi_batch *b) {
@@ -375,7 +446,7 @@ static PoolKey pool_key(const mi_ravif_encoder *e, int cap, uint32_t w, uint32_t
 }
 static std::mutex g_pool_mu;
 static std::vector<std::pair<PoolKey, mi_batch *>> g_pool;          // oldest first; never destroyed at process exit (the runtime may be gone by then)
-static size_t batch_footprint(const mi_batch *b) { return b->fs.arena_bytes + b->fs.aux_bytes + 3 * b->pixel_bytes + b->packed_cap + b->h_jpeg_cap + b->d_jpeg_cap + b->d_jpeg_planes_cap + b->h_png_cap + b->d_png_cap + b->h_rs_cap + b->d_rs_cap + b->d_rs_scratch_cap; }
+static size_t batch_footprint(const mi_batch *b) { return b->fs.arena_bytes + b->fs.aux_bytes + 3 * b->pixel_bytes + b->packed_cap + b->h_jpeg_cap + b->d_jpeg_cap + b->d_jpeg_planes_cap + b->h_png_cap + b->d_png_cap + b->h_rs_cap + b->d_rs_cap + b->d_rs_scratch_cap + b->h_quality_bytes; }     // (the quality records themselves are part of the arena)
 static constexpr size_t MI_POOL_MAX_ITEMS = 8, MI_POOL_MAX_BYTES = (size_t)32 << 30;     // what the one-call entry points may keep between calls (mi_release_cached() frees it)
 
 static mi_batch *pool_acquire(const mi_ravif_encoder *e, int cap, uint32_t w, uint32_t h, int channels) {
@@ -390,6 +461,7 @@ static mi_batch *pool_acquire(const mi_ravif_encoder *e, int cap, uint32_t w, ui
   if (e->exif && e->exif_len) b->exif.assign(e->exif, e->exif + e->exif_len);
   b->enc.exif = b->exif.empty() ? nullptr : b->exif.data(); b->enc.exif_len = b->exif.size();
   b->n = b->cap; b->alpha_flags.assign(b->cap, 0);
+  b->encoded = b->measured = false;
   return b;
 }
 static void pool_release(mi_batch *b) {

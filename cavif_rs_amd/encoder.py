@@ -7,6 +7,7 @@ Names, argument meaning and error behaviour follow the reference: builder method
 Out-of-range builder arguments raise (the Rust asserts at :117,146,159,188).
 """
 import ctypes as C
+import math
 import os
 import sys
 import numpy as np
@@ -56,6 +57,15 @@ class _ImageSource(C.Structure):
 class _DevicePixels(C.Structure):
     _fields_ = [('dev', C.c_void_p), ('layout', C.c_int), ('channels', C.c_int), ('row_stride', C.c_size_t),
                 ('pixel_or_plane_stride', C.c_size_t), ('image_stride', C.c_size_t), ('after_stream', C.c_void_p)]
+
+
+class _PlaneQuality(C.Structure):
+    _fields_ = [('sse', C.c_uint64), ('ssim_sum', C.c_int64), ('ssim_windows', C.c_uint64)]
+
+
+class _ImageQuality(C.Structure):
+    _fields_ = [('width', C.c_uint32), ('height', C.c_uint32), ('depth', C.c_uint8), ('color_planes', C.c_uint8), ('has_alpha', C.c_uint8), ('pad_', C.c_uint8),
+                ('color', _PlaneQuality * 3), ('alpha', _PlaneQuality)]
 
 
 _FETCH_SOURCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.POINTER(_ImageSource))
@@ -128,6 +138,12 @@ def load_library():
     L.mi_batch_resize_jpeg.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     L.mi_batch_resize_png.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     L.mi_ravif_encode_device_resized.argtypes = [C.POINTER(_RavifEncoder), C.POINTER(_DevicePixels), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_EncodedImage)]
+    L.mi_batch_measure.argtypes = [C.c_void_p]
+    L.mi_batch_get_quality.argtypes = [C.c_void_p, C.c_int, C.POINTER(_ImageQuality)]
+    L.mi_batch_get_source.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.POINTER(C.c_uint16))]
+    for fn in (L.mi_quality_psnr_db, L.mi_quality_ssim_db):
+        fn.argtypes = [C.POINTER(_ImageQuality)]
+        fn.restype = C.c_double
     L.mi_ravif_encode_sources.argtypes = [C.POINTER(_RavifEncoder), C.c_size_t, _FETCH_SOURCE, _RELEASE, C.c_void_p, C.POINTER(_EncodedImage),
                                           C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
     _LIB = L
@@ -311,6 +327,79 @@ class EncodedImage:
         self.alpha_byte_size = alpha_byte_size
 
 
+class PlaneQuality:
+    """mi_plane_quality: `sse` (exact), `ssim_sum` (2^-30 fixed point, summed over the windows), `ssim_windows` of one plane of one frame"""
+
+    def __init__(self, sse, ssim_sum, ssim_windows):
+        self.sse, self.ssim_sum, self.ssim_windows = int(sse), int(ssim_sum), int(ssim_windows)
+
+    @property
+    def ssim(self):
+        """mean SSIM over the windows, None when the plane is too small for one"""
+        return self.ssim_sum / 2.0 ** 30 / self.ssim_windows if self.ssim_windows else None
+
+    def __eq__(self, other):
+        return isinstance(other, PlaneQuality) and (self.sse, self.ssim_sum, self.ssim_windows) == (other.sse, other.ssim_sum, other.ssim_windows)
+
+    def __repr__(self):
+        return 'PlaneQuality(sse=%d, ssim_sum=%d, ssim_windows=%d)' % (self.sse, self.ssim_sum, self.ssim_windows)
+
+
+class ImageQuality:
+    """mi_image_quality of one encoded image: `planes` (a PlaneQuality per colour plane; `sse`, `ssim_sum`, `ssim_windows` list them plane by plane), `alpha`
+    (a PlaneQuality, None when the image has no alpha frame), `width`, `height`, `depth`.  The conversions mirror mi_quality_psnr_db / mi_quality_ssim_db."""
+
+    def __init__(self, width, height, depth, planes, alpha=None):
+        self.width, self.height, self.depth, self.planes, self.alpha = width, height, depth, list(planes), alpha
+
+    sse = property(lambda self: [p.sse for p in self.planes])
+    ssim_sum = property(lambda self: [p.ssim_sum for p in self.planes])
+    ssim_windows = property(lambda self: [p.ssim_windows for p in self.planes])
+
+    @property
+    def psnr_db(self):
+        """10 log10(peak^2 N / sum of sse) over the colour planes; inf when they are identical"""
+        sse = sum(self.sse)
+        if sse == 0:
+            return math.inf
+        peak = float((1 << self.depth) - 1)
+        return 10.0 * math.log10(peak * peak * float(len(self.planes) * self.width * self.height) / float(sse))
+
+    @property
+    def ssim(self):
+        """mean SSIM of plane 0 (Y, or G under the RGB colour model); None when the picture holds no window"""
+        return self.planes[0].ssim
+
+    @property
+    def ssim_db(self):
+        """-10 log10(1 - ssim); inf when ssim >= 1, None when the picture holds no window"""
+        m = self.ssim
+        if m is None:
+            return None
+        return math.inf if m >= 1.0 else -10.0 * math.log10(1.0 - m)
+
+    def _c(self):
+        q = _ImageQuality()
+        q.width, q.height, q.depth, q.color_planes, q.has_alpha = self.width, self.height, self.depth, len(self.planes), int(self.alpha is not None)
+        for dst, src in list(zip(q.color, self.planes)) + ([(q.alpha, self.alpha)] if self.alpha is not None else []):
+            dst.sse, dst.ssim_sum, dst.ssim_windows = src.sse, src.ssim_sum, src.ssim_windows
+        return q
+
+    def __eq__(self, other):
+        return isinstance(other, ImageQuality) and (self.width, self.height, self.depth, self.planes, self.alpha) == (other.width, other.height, other.depth, other.planes, other.alpha)
+
+    def __repr__(self):
+        return 'ImageQuality(%dx%d, %d bit, %r, alpha=%r)' % (self.width, self.height, self.depth, self.planes, self.alpha)
+
+
+class TargetResult:
+    """Encoder.encode_to_target: `image` (EncodedImage) and `quality_report` (ImageQuality) of the encode at `quality`, `reached` (False: even the highest
+    quality stays below the target), `tried`: the (quality, metric) pairs in the order they were encoded"""
+
+    def __init__(self, image, quality_report, quality, reached, tried):
+        self.image, self.quality_report, self.quality, self.reached, self.tried = image, quality_report, quality, reached, tried
+
+
 def _take(img):
     L = load_library()
     data = bytes(bytearray(img.avif_file[:img.avif_len]))
@@ -480,6 +569,58 @@ class Encoder:
         finally:
             b.close()
 
+    def encode_measured(self, pixels):
+        """(EncodedImage, ImageQuality) of an RGB or RGBA picture (host array or device array, by its channels): the file of encode_rgb / encode_rgba and the
+        quality metrics of its reconstruction against the planes the encoder saw, computed on the device (mi_batch_measure); through a one-image batch"""
+        if _is_device_array(pixels):
+            d, _, h, w, index = _device_pixels(pixels)
+            channels, enc = d.channels, (self if index is None else self.with_device(index))
+        else:
+            pixels = np.ascontiguousarray(pixels, dtype=np.uint8)
+            if pixels.ndim != 3 or pixels.shape[2] not in (3, 4):
+                raise AvifError(4)
+            (h, w, channels), enc = pixels.shape, self
+        b = BatchEncoder(enc, 1, w, h, channels)
+        try:
+            (b.upload_device if _is_device_array(pixels) else b.upload)(0, pixels)
+            b.encode()
+            return b.get(0), b.measure()[0]
+        finally:
+            b.close()
+
+    def encode_to_target(self, pixels, target_db, metric='ssim', lo=1, hi=100):
+        """The smallest integer quality in [lo, hi] whose encode reaches `target_db` in `metric`: 'ssim' (ImageQuality.ssim_db) or 'psnr' (ImageQuality.psnr_db).
+        The encode at `hi` comes first; below the target it is returned with reached=False.  Otherwise a bisection over l, h = lo, hi: mid = (l + h) // 2,
+        h = mid when metric(mid) >= target, else l = mid + 1, until l == h (at most 8 encodes).  The returned file is the one with_quality(q).encode_rgb /
+        encode_rgba gives; alpha_quality stays as this encoder has it.  Returns a TargetResult."""
+        if metric not in ('ssim', 'psnr'):
+            raise ValueError('metric must be \'ssim\' or \'psnr\'')
+        lo, hi = int(lo), int(hi)
+        if not 1 <= lo <= hi <= 100:
+            raise ValueError('1 <= lo <= hi <= 100')
+        if metric == 'ssim' and not _is_device_array(pixels) and min(np.shape(pixels)[:2]) < 8:
+            raise ValueError('a picture below 8 x 8 holds no SSIM window')
+        done, tried = {}, []
+
+        def at(q):
+            if q not in done:
+                img, rep = self.with_quality(q).encode_measured(pixels)
+                m = rep.ssim_db if metric == 'ssim' else rep.psnr_db
+                if m is None:
+                    raise ValueError('the picture holds no SSIM window')
+                done[q] = (img, rep, m)
+                tried.append((q, m))
+            return done[q][2]
+        reached = at(hi) >= target_db
+        l, h = lo, hi
+        while reached and l < h:
+            mid = (l + h) // 2
+            if at(mid) >= target_db:
+                h = mid
+            else:
+                l = mid + 1
+        return TargetResult(done[h][0], done[h][1], h, reached, tried)      # h is hi or a mid that reached the target: always encoded
+
     def encode_rgba(self, rgba):                        # :243
         return self._encode(rgba, 4)
 
@@ -564,6 +705,7 @@ class BatchEncoder:
         if not self._h:
             raise AvifError(5 if self._L.mi_device_count() <= encoder.device else 4)
         self.n, self.w, self.h, self.channels = n_images, width, height, channels
+        self.count = n_images                        # images of the next run (set_count)
         self._sources = []                           # device arrays handed to upload_device: alive until the run that reads them has been waited for
 
     def upload(self, index, pixels):
@@ -661,6 +803,7 @@ class BatchEncoder:
         st = self._L.mi_batch_set_count(self._h, n_images)
         if st:
             raise AvifError(st)
+        self.count = n_images
 
     def encode(self):
         st = self._L.mi_batch_encode(self._h)
@@ -696,6 +839,34 @@ class BatchEncoder:
             if rec[i]:
                 out.append(np.ctypeslib.as_array(rec[i], shape=(self.h, self.w)).copy())
                 self._L.mi_free(rec[i])
+        return out
+
+    def source(self, index, alpha=False):
+        """the planes the encoder saw (mi_batch_get_source): what recon() is compared with"""
+        src = (C.POINTER(C.c_uint16) * 3)()
+        st = self._L.mi_batch_get_source(self._h, index, int(alpha), src)
+        if st:
+            raise AvifError(st)
+        out = []
+        for i in range(3):
+            if src[i]:
+                out.append(np.ctypeslib.as_array(src[i], shape=(self.h, self.w)).copy())
+                self._L.mi_free(src[i])
+        return out
+
+    def measure(self):
+        """mi_batch_measure + mi_batch_get_quality: the ImageQuality of every image of the last encode, computed on the device"""
+        st = self._L.mi_batch_measure(self._h)
+        if st:
+            raise AvifError(st)
+        out = []
+        for i in range(self.count):
+            q = _ImageQuality()
+            st = self._L.mi_batch_get_quality(self._h, i, C.byref(q))
+            if st:
+                raise AvifError(st)
+            pq = lambda p: PlaneQuality(p.sse, p.ssim_sum, p.ssim_windows)
+            out.append(ImageQuality(q.width, q.height, q.depth, [pq(q.color[p]) for p in range(q.color_planes)], pq(q.alpha) if q.has_alpha else None))
         return out
 
     def stage_ms(self):

@@ -228,6 +228,31 @@ int  mi_batch_encode_async(mi_batch *b);
 int  mi_batch_wait(mi_batch *b);
 int  mi_batch_get(mi_batch *b, int index, mi_encoded_image *out);                         /* copies; caller frees avif_file */
 int  mi_batch_get_recon(mi_batch *b, int index, int alpha, uint16_t *planes[3]);          /* malloc'd w*h uint16 planes (tests) */
+/* ---- quality metrics of the last completed encode, computed on the device from the planes it left there (opt-in: an encode that is never measured does
+ * nothing for them).  Per frame -- the colour frame of an image, its alpha frame when the image uses alpha -- and per plane, over the visible w x h samples,
+ * between the uint16 source samples the encoder saw (mi_batch_get_source) and the final reconstruction (mi_batch_get_recon), bd = the batch's bit depth:
+ *   sse           sum of (s - r)^2, exact.
+ *   ssim_windows  ((w - 8) / 4 + 1) * ((h - 8) / 4 + 1) in integer division, 0 when w < 8 or h < 8: the 8 x 8 windows with their top-left corner at
+ *                 (4 i, 4 j) that lie wholly inside the picture.
+ *   ssim_sum      the sum over those windows of (long long)floor(q * 2^30 + 0.5).  With the window's integer sums S, R, SS, RR, SR of s, r, s^2, r^2, s r and
+ *                 c1 = 26634, c2 = 239708 at 8 bit, c1 = 428658, c2 = 3857925 at 10 bit (4096 (0.01 peak)^2, 4096 (0.03 peak)^2, rounded):
+ *                 a = 2 S R + c1, b = 128 SR - 2 S R + c2, c = S S + R R + c1, d = 64 SS - S S + 64 RR - R R + c2 as exact int64, each converted to double
+ *                 (exact), q = (a * b) / (c * d): three IEEE double operations, no contraction.  Identical planes give ssim_sum == ssim_windows << 30.
+ * Being sums of integers the three numbers do not depend on any order of evaluation; they equal a float64 restatement bit for bit.
+ * mi_batch_measure: after mi_batch_wait and before the next encode: zeroes the records (they live in the batch's arena), one kernel launch for all frames
+ * and planes, one D2H into pinned memory the batch owns, one sync.  MI_INVALID_ARGUMENT when no encode of the current image count has completed or one is
+ * in flight.  mi_batch_get_quality: MI_INVALID_ARGUMENT until a measure of the current encode exists.  mi_batch_get_source: mi_batch_get_recon for the source
+ * planes (tests and debugging).  The conversions are host arithmetic and not part of the exactness contract: mi_quality_psnr_db = 10 log10(peak^2 N / sum of
+ * sse) over the colour planes (N their samples, peak = 2^bd - 1; +inf when the sum is 0); mi_quality_ssim_db = -10 log10(1 - mean) of plane 0 (Y, or G under
+ * the RGB colour model) with mean = ssim_sum / 2^30 / ssim_windows, +inf when mean >= 1, NaN when there is no window. */
+typedef struct mi_plane_quality { uint64_t sse; int64_t ssim_sum; uint64_t ssim_windows; } mi_plane_quality;
+typedef struct mi_image_quality { uint32_t width, height; uint8_t depth, color_planes, has_alpha, pad_;
+                                  mi_plane_quality color[3], alpha; } mi_image_quality;
+int  mi_batch_measure(mi_batch *b);
+int  mi_batch_get_quality(mi_batch *b, int index, mi_image_quality *out);
+int  mi_batch_get_source(mi_batch *b, int index, int alpha, uint16_t *planes[3]);
+double mi_quality_psnr_db(const mi_image_quality *q);
+double mi_quality_ssim_db(const mi_image_quality *q);
 /* per-kernel HIP-event time (ms) of the last mi_batch_encode: 0 front-end, 1 tile search, 2 deblock, 3 cdef, 4 entropy, 5 pack+D2H, 6 host assembly */
 double mi_batch_stage_ms(const mi_batch *b, int stage);
 int  mi_batch_num_tiles(const mi_batch *b);
