@@ -21,6 +21,7 @@
 #include "dev_png.h"
 #include "dev_resample.h"
 #include "dev_quality.h"
+#include "dev_decoded.h"
 #include "host_frames.h"
 
 // The product library reads no environment variables; probe builds (tools/) get MI_AVIF_TIMING=1 (-DMI_TUNING_KNOBS: host-side timeline on stderr)
@@ -71,6 +72,8 @@ struct mi_batch {
   // that encode's records.  The records live at the end of the arena (FrameSet::d_records); their pinned D2H target is made by the first measure.
   bool encoded = false, measured = false;
   PinBuf<QualityRec> h_quality; size_t h_quality_bytes = 0;
+  // decoded pixels (mi_batch_decode): one image of w*h*4 bytes on the device, made by the first call that decodes into host memory
+  DevBuf<uint8_t> d_decoded; size_t d_decoded_cap = 0;
 };
 static_assert(sizeof(QualityRec) <= MI_FRAME_RECORD_BYTES, "FrameSet reserves MI_FRAME_RECORD_BYTES per (frame, plane)");
 
@@ -446,7 +449,7 @@ static PoolKey pool_key(const mi_ravif_encoder *e, int cap, uint32_t w, uint32_t
 }
 static std::mutex g_pool_mu;
 static std::vector<std::pair<PoolKey, mi_batch *>> g_pool;          // oldest first; never destroyed at process exit (the runtime may be gone by then)
-static size_t batch_footprint(const mi_batch *b) { return b->fs.arena_bytes + b->fs.aux_bytes + 3 * b->pixel_bytes + b->packed_cap + b->h_jpeg_cap + b->d_jpeg_cap + b->d_jpeg_planes_cap + b->h_png_cap + b->d_png_cap + b->h_rs_cap + b->d_rs_cap + b->d_rs_scratch_cap + b->h_quality_bytes; }     // (the quality records themselves are part of the arena)
+static size_t batch_footprint(const mi_batch *b) { return b->fs.arena_bytes + b->fs.aux_bytes + 3 * b->pixel_bytes + b->packed_cap + b->h_jpeg_cap + b->d_jpeg_cap + b->d_jpeg_planes_cap + b->h_png_cap + b->d_png_cap + b->h_rs_cap + b->d_rs_cap + b->d_rs_scratch_cap + b->h_quality_bytes + b->d_decoded_cap; }     // (the quality records themselves are part of the arena)
 static constexpr size_t MI_POOL_MAX_ITEMS = 8, MI_POOL_MAX_BYTES = (size_t)32 << 30;     // what the one-call entry points may keep between calls (mi_release_cached() frees it)
 
 static mi_batch *pool_acquire(const mi_ravif_encoder *e, int cap, uint32_t w, uint32_t h, int channels) {
@@ -714,6 +717,62 @@ int mi_batch_upload_device(mi_batch *b, int first, int count, const mi_device_pi
   if (b->channels == 4) hipLaunchKernelGGL((ingest_kernel<4>), grid, dim3(64), 0, b->stream, s, slots);
   else hipLaunchKernelGGL((ingest_kernel<3>), grid, dim3(64), 0, b->stream, s, slots);
   HIP_OK(hipGetLastError());
+  return MI_OK;
+}
+
+// ---- decoded pixels of the last completed encode (dev_decoded.h) ----
+int mi_batch_uses_alpha(mi_batch *b, int index, int *uses_alpha) {
+  if (!b || !uses_alpha || b->in_flight || !b->encoded || index < 0 || index >= b->n) return MI_INVALID_ARGUMENT;
+  *uses_alpha = (b->channels == 4 && b->alpha_flags[index]) ? 1 : 0;
+  return MI_OK;
+}
+// One decoded_kernel launch over the frame descriptors the encode staged (still on the device, like the planes: nothing after mi_batch_wait writes them until
+// the next encode), after whatever dst->after_stream holds at this moment, then the batch's stream is waited for.  Strides of 0 mean packed.
+int mi_batch_decode_device(mi_batch *b, int first, int count, int which, const mi_device_target *dst) {
+  if (!b || !dst || !dst->dev || b->in_flight || !b->encoded || first < 0 || count < 1 || first > b->n - count) return MI_INVALID_ARGUMENT;
+  if ((which != MI_DECODED_RECON && which != MI_DECODED_SOURCE) || (dst->layout != 0 && dst->layout != 1) || (dst->channels != 3 && dst->channels != 4)) return MI_INVALID_ARGUMENT;
+  if ((size_t)b->n * (b->channels == 4 ? 2 : 1) != b->fs.frames.size()) return MI_INVALID_ARGUMENT;
+  if (dst->channels == 3 && b->channels == 4)
+    for (int i = first; i < first + count; i++) if (b->alpha_flags[i]) return MI_INVALID_ARGUMENT;      // alpha is never dropped
+  DecodedDst d;
+  d.base = (uint8_t *)dst->dev; d.layout = dst->layout; d.channels = dst->channels; d.first = first; d.n = b->n; d.alpha_frames = b->channels == 4; d.source = which == MI_DECODED_SOURCE;
+  const size_t packed_row = (size_t)b->w * (d.layout == 0 ? d.channels : 1);
+  d.row_stride = dst->row_stride ? dst->row_stride : packed_row;
+  d.inner_stride = dst->pixel_or_plane_stride ? dst->pixel_or_plane_stride : d.layout == 0 ? (size_t)d.channels : d.row_stride * b->h;
+  d.image_stride = dst->image_stride ? dst->image_stride : d.layout == 0 ? d.row_stride * b->h : d.inner_stride * d.channels;
+  if (d.row_stride < packed_row || d.inner_stride < (d.layout == 0 ? (size_t)d.channels : (size_t)b->w)) return MI_INVALID_ARGUMENT;
+  if (d.layout == 0 && d.row_stride < (size_t)(b->w - 1) * d.inner_stride + d.channels) return MI_INVALID_ARGUMENT;     // a written row must end before the next one starts
+  (void)hipSetDevice(b->device);
+  if (dst->after_stream) {
+    if (!b->ev_src) HIP_OK(hipEventCreateWithFlags(&b->ev_src, hipEventDisableTiming));
+    HIP_OK(hipEventRecord(b->ev_src, (hipStream_t)dst->after_stream));
+    HIP_OK(hipStreamWaitEvent(b->stream, b->ev_src, 0));
+  }
+  const dim3 grid(((b->w + 3) / 4 + 63) / 64, b->h, (unsigned)count);
+  const FrameDev *const frames = b->fs.d_frames.get();
+  const bool rgb_model = b->fs.frames[first].cfg.matrix == 0;
+  if (b->depth == 8) {
+    if (rgb_model) hipLaunchKernelGGL((decoded_kernel<8, 1>), grid, dim3(64), 0, b->stream, frames, d);
+    else hipLaunchKernelGGL((decoded_kernel<8, 0>), grid, dim3(64), 0, b->stream, frames, d);
+  } else {
+    if (rgb_model) hipLaunchKernelGGL((decoded_kernel<10, 1>), grid, dim3(64), 0, b->stream, frames, d);
+    else hipLaunchKernelGGL((decoded_kernel<10, 0>), grid, dim3(64), 0, b->stream, frames, d);
+  }
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipStreamSynchronize(b->stream));
+  return MI_OK;
+}
+// One image into host memory: the same launch into the batch's own one-image scratch (never the input slot), one D2H.
+int mi_batch_decode(mi_batch *b, int index, int which, int channels, uint8_t *dst) {
+  if (!b || !dst || b->in_flight || !b->encoded || index < 0 || index >= b->n || (channels != 3 && channels != 4)) return MI_INVALID_ARGUMENT;
+  if ((which != MI_DECODED_RECON && which != MI_DECODED_SOURCE) || (channels == 3 && b->channels == 4 && b->alpha_flags[index])) return MI_INVALID_ARGUMENT;   // before the scratch exists: a refused call allocates nothing
+  (void)hipSetDevice(b->device);
+  if (!staging_grow(b->d_decoded, b->d_decoded_cap, (size_t)b->w * b->h * 4)) return MI_ENCODING_ERROR;
+  mi_device_target t;
+  memset(&t, 0, sizeof(t));
+  t.dev = b->d_decoded.get(); t.layout = 0; t.channels = channels;
+  if (const int st = mi_batch_decode_device(b, index, 1, which, &t)) return st;
+  HIP_OK(hipMemcpy(dst, b->d_decoded.get(), (size_t)b->w * b->h * channels, hipMemcpyDeviceToHost));
   return MI_OK;
 }
 

@@ -59,6 +59,10 @@ class _DevicePixels(C.Structure):
                 ('pixel_or_plane_stride', C.c_size_t), ('image_stride', C.c_size_t), ('after_stream', C.c_void_p)]
 
 
+class _DeviceTarget(C.Structure):                      # mi_device_target: _DevicePixels with a writable pointer
+    _fields_ = _DevicePixels._fields_
+
+
 class _PlaneQuality(C.Structure):
     _fields_ = [('sse', C.c_uint64), ('ssim_sum', C.c_int64), ('ssim_windows', C.c_uint64)]
 
@@ -144,6 +148,9 @@ def load_library():
     for fn in (L.mi_quality_psnr_db, L.mi_quality_ssim_db):
         fn.argtypes = [C.POINTER(_ImageQuality)]
         fn.restype = C.c_double
+    L.mi_batch_uses_alpha.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.mi_batch_decode_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(_DeviceTarget)]
+    L.mi_batch_decode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
     L.mi_ravif_encode_sources.argtypes = [C.POINTER(_RavifEncoder), C.c_size_t, _FETCH_SOURCE, _RELEASE, C.c_void_p, C.POINTER(_EncodedImage),
                                           C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
     _LIB = L
@@ -272,11 +279,23 @@ def _is_device_array(x):
     return hasattr(x, '__cuda_array_interface__')
 
 
-def _device_pixels(x, batched=False):
+DECODED_WHICH = {'recon': 0, 'source': 1}                   # MI_DECODED_*
+
+
+def _decoded_which(name):
+    if name not in DECODED_WHICH:
+        raise AvifError(4)
+    return DECODED_WHICH[name]
+
+
+def _device_pixels(x, batched=False, writable=False):
     """(_DevicePixels, images, height, width, device index or None) of an object with __cuda_array_interface__: uint8, (H, W, C) or (C, H, W) -- with
     batched=True also (N, H, W, C) / (N, C, H, W) -- where C is 3 or 4 and either the channel or the column stride is one byte: contiguous tensors of
-    both layouts, crops, padded rows and permuted views of them.  (C, H, W) is taken when the first dimension is 3 or 4 and the last is not."""
+    both layouts, crops, padded rows and permuted views of them.  (C, H, W) is taken when the first dimension is 3 or 4 and the last is not.
+    writable=True: a destination (_DeviceTarget: the same fields, the stream is the one whose work must finish first); a read-only array is refused."""
     ai = x.__cuda_array_interface__
+    if writable and ai['data'][1]:
+        raise ValueError('the target array is read-only')
     if ai.get('typestr') != '|u1':
         raise TypeError('device pixels must be uint8 (got typestr %r): rounding floats is the caller\'s decision' % (ai.get('typestr'),))
     shape = tuple(int(v) for v in ai['shape'])
@@ -301,7 +320,9 @@ def _device_pixels(x, batched=False):
         (h, w, c), (sh, sw, sc) = shape, strides
     if c not in (3, 4):
         raise AvifError(4)
-    d = _DevicePixels()
+    if writable and (any(n_ > 1 and s_ == 0 for n_, s_ in zip(shape, strides)) or (n > 1 and img_stride == 0)):
+        raise ValueError('the target array is an expanded (stride 0) view: its elements share memory')
+    d = _DeviceTarget() if writable else _DevicePixels()
     d.dev, d.channels, d.row_stride, d.image_stride = ptr, c, sh, img_stride
     if sc == 1:
         d.layout, d.pixel_or_plane_stride = 0, sw                  # interleaved: from pixel to pixel
@@ -316,6 +337,19 @@ def _device_pixels(x, batched=False):
         idx = getattr(getattr(x, 'device', None), 'index', None)
         d.after_stream = torch.cuda.current_stream(idx).cuda_stream or None
     return d, n, h, w, getattr(getattr(x, 'device', None), 'index', None)
+
+
+def _empty_like_device(x, shape):
+    """an uninitialised uint8 device array of `shape` from the library `x` comes from, on x's device"""
+    mod = type(x).__module__.split('.')[0]
+    if mod == 'torch':
+        import torch
+        return torch.empty(shape, dtype=torch.uint8, device=x.device)
+    if mod == 'cupy':
+        import cupy
+        with x.device:
+            return cupy.empty(shape, dtype=cupy.uint8)
+    raise TypeError('encode_decoded cannot allocate a device array of %s: decode into an array of your own with BatchEncoder.decode_into' % type(x).__module__)
 
 
 class EncodedImage:
@@ -588,6 +622,34 @@ class Encoder:
         finally:
             b.close()
 
+    def encode_decoded(self, pixels):
+        """(EncodedImage, decoded, premultiplied) of an RGB or RGBA picture (host array or device array, by its channels): the file of encode_rgb / encode_rgba
+        and the pixels a viewer's decoder reconstructs from it, (h, w, c) uint8 with c = 4 when the image uses alpha, else 3, made on the device from the final
+        reconstruction (mi_batch_decode / _decode_device).  A numpy array in gives a numpy array out; a device array in gives a device array of
+        the same library (torch, cupy) on the same device out, and only the file crosses to the host.  `premultiplied`: the colours are stored premultiplied
+        by alpha (the file says so); nothing here undoes that.  Through a one-image batch."""
+        if _is_device_array(pixels):
+            d, _, h, w, index = _device_pixels(pixels)
+            channels, enc = d.channels, (self if index is None else self.with_device(index))
+        else:
+            pixels = np.ascontiguousarray(pixels, dtype=np.uint8)
+            if pixels.ndim != 3 or pixels.shape[2] not in (3, 4):
+                raise AvifError(4)
+            (h, w, channels), enc = pixels.shape, self
+        b = BatchEncoder(enc, 1, w, h, channels)
+        try:
+            (b.upload_device if _is_device_array(pixels) else b.upload)(0, pixels)
+            b.encode()
+            alpha = b.uses_alpha(0)
+            if _is_device_array(pixels):
+                out = _empty_like_device(pixels, (h, w, 4 if alpha else 3))
+                b.decode_into(0, out)
+            else:
+                out = b.decoded(0)
+            return b.get(0), out, bool(alpha and self.alpha_mode == 2)
+        finally:
+            b.close()
+
     def encode_to_target(self, pixels, target_db, metric='ssim', lo=1, hi=100):
         """The smallest integer quality in [lo, hi] whose encode reaches `target_db` in `metric`: 'ssim' (ImageQuality.ssim_db) or 'psnr' (ImageQuality.psnr_db).
         The encode at `hi` comes first; below the target it is returned with reached=False.  Otherwise a bisection over l, h = lo, hi: mid = (l + h) // 2,
@@ -853,6 +915,40 @@ class BatchEncoder:
                 out.append(np.ctypeslib.as_array(src[i], shape=(self.h, self.w)).copy())
                 self._L.mi_free(src[i])
         return out
+
+    def uses_alpha(self, index):
+        """whether image `index` of the last encode carries an alpha frame (an RGBA batch's image that is not fully opaque)"""
+        v = C.c_int()
+        st = self._L.mi_batch_uses_alpha(self._h, index, C.byref(v))
+        if st:
+            raise AvifError(st)
+        return bool(v.value)
+
+    def decoded(self, index, channels=None, which='recon'):
+        """image `index` of the last encode as 8-bit pixels, uint8 array (h, w, c): the final reconstruction (which='recon': what a decoder of the file shows)
+        or the source planes (which='source': what the encoder saw) through the inverse colour transform, on the device, then one D2H.
+        channels: 3, 4 (A = 255 for an opaque image) or None = 4 if the image uses alpha, else 3; 3 for an image that uses alpha raises InvalidArgument."""
+        w = _decoded_which(which)
+        if channels is None:
+            channels = 4 if self.uses_alpha(index) else 3
+        if channels not in (3, 4):
+            raise AvifError(4)
+        a = np.empty((self.h, self.w, channels), np.uint8)
+        st = self._L.mi_batch_decode(self._h, index, w, channels, a.ctypes.data)
+        if st:
+            raise AvifError(st)
+        return a
+
+    def decode_into(self, first, target, which='recon'):
+        """decoded() for images first.. into an object with __cuda_array_interface__ (a torch tensor of the batch's device), writable, uint8 (H, W, C),
+        (C, H, W), (N, H, W, C) or (N, C, H, W), C = 3 or 4, any strides a view has: bytes the view does not address are left alone.  The write is ordered
+        after the work of torch's current stream; the pixels are in place when the call returns."""
+        d, n, h, w, _ = _device_pixels(target, batched=True, writable=True)
+        if (h, w) != (self.h, self.w):
+            raise AvifError(4)
+        st = self._L.mi_batch_decode_device(self._h, first, n, _decoded_which(which), C.byref(d))
+        if st:
+            raise AvifError(st)
 
     def measure(self):
         """mi_batch_measure + mi_batch_get_quality: the ImageQuality of every image of the last encode, computed on the device"""

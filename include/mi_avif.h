@@ -253,6 +253,36 @@ int  mi_batch_get_quality(mi_batch *b, int index, mi_image_quality *out);
 int  mi_batch_get_source(mi_batch *b, int index, int alpha, uint16_t *planes[3]);
 double mi_quality_psnr_db(const mi_image_quality *q);
 double mi_quality_ssim_db(const mi_image_quality *q);
+/* ---- decoded pixels of the last completed encode: the final reconstruction (MI_DECODED_RECON, the planes of mi_batch_get_recon) or the source planes
+ * (MI_DECODED_SOURCE, those of mi_batch_get_source) as 8-bit RGB or RGBA, made on the device by one kernel launch per call (opt-in: an encode that never asks
+ * allocates and launches nothing for it).  The pixels are specified exactly.  bd = the batch's bit depth, peak = 2^bd - 1, half = 2^(bd-1),
+ * p0 p1 p2 the colour frame's samples at (x, y), a plane 0 of the image's alpha frame there, and for exact integers n, d > 0
+ *   q(n, d) = clamp(floor((2 * 255 * n + d * peak) / (2 * d * peak)), 0, 255)          (0 whenever the numerator is negative):
+ *   YCbCr model:  cb = p1 - half, cr = p2 - half;  R = q(1000 p0 + 1402 cr, 1000),  G = q(587000 p0 - 202008 cb - 419198 cr, 587000),
+ *                 B = q(1000 p0 + 1772 cb, 1000)          (matrix 6, full range: the exact BT.601 inverse)
+ *   RGB model:    G = q(p0, 1), B = q(p1, 1), R = q(p2, 1)
+ *   alpha:        A = q(a, 1) when the image uses alpha (mi_batch_uses_alpha), else 255.
+ * There is no alpha association step: with the premultiplied alpha mode the output holds the stored (premultiplied) colours, with the clean mode the cleaned
+ * ones.  Only the visible w x h pixels are read and written; bytes of the destination that its layout does not address are left alone.
+ * All three calls are valid after mi_batch_wait and before the next encode or mi_batch_set_count (the state rule of mi_batch_measure), else
+ * MI_INVALID_ARGUMENT.  mi_batch_decode_device: images [first, first + count) into memory of the batch's own device (documented, not detected), image k at
+ * dev + k * image_stride, strides under mi_device_pixels' rules (0 = packed) and, being written, an interleaved row stride of at least (w - 1) * pixel stride +
+ * channels; beyond that, that rows, planes and images of the destination do not overlap one another is the caller's promise (not detected); the launch is ordered after the work dst->after_stream holds at the time of the
+ * call, the batch's stream is waited for, and the pixels are in place when the call returns.  mi_batch_decode: one image into host memory (w * h * channels
+ * bytes, rows packed) through a one-image device scratch the batch makes on first use; the input slot is never touched.  MI_INVALID_ARGUMENT as well: null
+ * pointers, a range outside the images of the run or an empty one, `which` not 0 or 1, channels not 3 or 4, a layout not 0 or 1, strides below the packed
+ * extent, and 3 channels when any image of the range uses alpha (alpha is never dropped).  4 channels for an opaque image or a 3-channel batch give A = 255. */
+enum { MI_DECODED_RECON = 0, MI_DECODED_SOURCE = 1 };
+typedef struct mi_device_target {          /* mi_device_pixels with a writable pointer; same stride rules, 0 = packed */
+  void *dev;
+  int layout;        /* 0 = HWC, 1 = CHW */
+  int channels;      /* 3 | 4 */
+  size_t row_stride, pixel_or_plane_stride, image_stride;   /* bytes; 0 = packed */
+  void *after_stream; /* hipStream_t whose queued work must finish before dst is written, or NULL */
+} mi_device_target;
+int  mi_batch_uses_alpha(mi_batch *b, int index, int *uses_alpha);
+int  mi_batch_decode_device(mi_batch *b, int first, int count, int which, const mi_device_target *dst);
+int  mi_batch_decode(mi_batch *b, int index, int which, int channels, uint8_t *dst);
 /* per-kernel HIP-event time (ms) of the last mi_batch_encode: 0 front-end, 1 tile search, 2 deblock, 3 cdef, 4 entropy, 5 pack+D2H, 6 host assembly */
 double mi_batch_stage_ms(const mi_batch *b, int stage);
 int  mi_batch_num_tiles(const mi_batch *b);
