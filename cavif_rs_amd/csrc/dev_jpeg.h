@@ -4,6 +4,7 @@
 //                     up, +128, clamp) -> one uint8 plane per component over the MCU-padded block grid
 //   jpeg_rgba_kernel  "fancy" (triangle) chroma upsampling 2x1 / 2x2 with edge samples replicated, then YCbCr -> RGB in 16.16 fixed point
 //                     (or a copy for grey / RGB files), alpha 255; jpeg_rgb_kernel is the same code storing packed RGB8 (3-channel batches)
+//   jpeg_ycc_kernel   the same upsampling and no colour arithmetic: (Y, Cb, Cr) as the file holds them, for slots of input kind MI_INPUT_YCBCR
 // libjpeg computes the IDCT in 64-bit long; here products and sums are uint32_t (wrapping) and only the descale shifts see them as int32_t: identical
 // whenever libjpeg's values fit 32 bits, which they do for every encoder-made file, and some defined value for hostile coefficients.
 #pragma once
@@ -94,19 +95,28 @@ __global__ void __launch_bounds__(256) jpeg_idct_kernel(const int16_t *coef, con
 
 // four horizontally adjacent samples x0..x0+3 of row y of a chroma plane brought to luma resolution (libjpeg's h2v1 / h2v2 fancy upsampling: weights 3:1
 // towards the nearer sample in each direction, neighbours outside the plane's cw x ch extent replaced by the nearest one inside; plain replication in
-// both directions when the plane is one or two samples wide, as libjpeg does)
-__device__ __forceinline__ void jpeg_chroma4(const uint8_t *plane, const size_t stride, const uint32_t cw, const uint32_t ch, const uint32_t hr, const uint32_t vr,
-                                             const uint32_t x0, const uint32_t y, int out[4]) {
+// both directions when the plane is one or two samples wide, as libjpeg does).  The one implementation of the upsampling: the JPEG kernels below and
+// planes_ingest_kernel (dev_planes.h) call it.  PS = bytes from one sample of the plane to the next (1; 2 for interleaved (Cb, Cr) pairs).  PADDED: every
+// row holds whole aligned dwords past cw (the MCU-padded planes of jpeg_idct_kernel), so a plane at luma resolution is read as one dword; otherwise a
+// dword where the address allows it and n = 4, bytes for the n (1..4) samples that exist else (out[k] for k >= n is 0 then).
+template <int PS, bool PADDED> __device__ __forceinline__ void jpeg_chroma4(const uint8_t *plane, const size_t stride, const uint32_t cw, const uint32_t ch, const uint32_t hr,
+                                                                            const uint32_t vr, const uint32_t x0, const uint32_t y, const uint32_t n, int out[4]) {
   if (hr == 1) {
-    const uint32_t v = *(const uint32_t *)(plane + (size_t)y * stride + x0);
-    out[0] = v & 255; out[1] = (v >> 8) & 255; out[2] = (v >> 16) & 255; out[3] = v >> 24;
+    const uint8_t *q = plane + (size_t)y * stride + (size_t)x0 * PS;
+    if (PS == 1 && (PADDED || (n == 4 && ((uintptr_t)q & 3) == 0))) {
+      const uint32_t v = *(const uint32_t *)q;
+      out[0] = v & 255; out[1] = (v >> 8) & 255; out[2] = (v >> 16) & 255; out[3] = v >> 24;
+    } else {
+#pragma unroll
+      for (uint32_t k = 0; k < 4; k++) out[k] = k < n ? q[(size_t)k * PS] : 0;
+    }
     return;
   }
   const uint32_t yn = vr == 2 ? y >> 1 : y;
   if (cw <= 2) {                                                 // libjpeg takes the triangle filter only for planes wider than two samples and replicates otherwise
     const uint8_t *row = plane + (size_t)yn * stride;
     const uint32_t i0 = x0 >> 1, i1 = i0 + 1 < cw ? i0 + 1 : cw - 1;
-    out[0] = out[1] = row[i0]; out[2] = out[3] = row[i1];
+    out[0] = out[1] = row[(size_t)i0 * PS]; out[2] = out[3] = row[(size_t)i1 * PS];
     return;
   }
   const uint32_t yf = vr == 2 ? ((y & 1) ? (yn + 1 < ch ? yn + 1 : ch - 1) : (yn > 0 ? yn - 1 : 0)) : yn;
@@ -115,7 +125,7 @@ __device__ __forceinline__ void jpeg_chroma4(const uint8_t *plane, const size_t 
   int s[4];
   for (int k = 0; k < 4; k++) {
     uint32_t i = i0 + k; i = i > 0 ? i - 1 : 0; i = i < cw ? i : cw - 1;
-    s[k] = vr == 2 ? 3 * near[i] + far[i] : near[i];
+    s[k] = vr == 2 ? 3 * near[(size_t)i * PS] + far[(size_t)i * PS] : near[(size_t)i * PS];
   }
   if (vr == 2) {
     out[0] = (3 * s[1] + s[0] + 8) >> 4; out[1] = (3 * s[1] + s[2] + 7) >> 4;
@@ -126,18 +136,27 @@ __device__ __forceinline__ void jpeg_chroma4(const uint8_t *plane, const size_t 
   }
 }
 
+// the component samples of pixels x0..x0+3 of row y at luma resolution: c0 from plane 0, c1 / c2 the upsampled planes 1 / 2 of a three-component file
+// (a one-component file leaves them as they are).  What the colour kernels and jpeg_ycc_kernel start from.
+__device__ __forceinline__ void jpeg_samples4(const uint8_t *planes, const JpegDevGeom &g, const uint32_t x0, const uint32_t y, int c0[4], int c1[4], int c2[4]) {
+  const uint32_t yv = *(const uint32_t *)(planes + g.plane_off[0] + (size_t)y * ((size_t)g.bw[0] * 8) + x0);
+  c0[0] = (int)(yv & 255); c0[1] = (int)((yv >> 8) & 255); c0[2] = (int)((yv >> 16) & 255); c0[3] = (int)(yv >> 24);
+  if (g.ncomp == 3) {
+    jpeg_chroma4<1, true>(planes + g.plane_off[1], (size_t)g.bw[1] * 8, g.cw[1], g.ch[1], g.hr, g.vr, x0, y, 4, c1);
+    jpeg_chroma4<1, true>(planes + g.plane_off[2], (size_t)g.bw[2] * 8, g.cw[2], g.ch[2], g.hr, g.vr, x0, y, 4, c2);
+  }
+}
+
 // planes -> RGBA8 (DC 4) or RGB8 (DC 3) rows of stride_px pixels at a device pointer; one thread = four adjacent pixels = one 16-byte store or three
 // dword stores (vec: the destination rows are 16-byte / 4-byte aligned; otherwise, and for the pixels of a last partial group, slot_store4's narrow
-// stores).  The one implementation of the upsampling and colour arithmetic; the two kernels below differ in the store alone.
+// stores).  The one implementation of the colour arithmetic; the two kernels below differ in the store alone.
 template <int DC> __device__ __forceinline__ void jpeg_colour4(const uint8_t *planes, const JpegDevGeom &g, uint8_t *out, const size_t stride_px, const int vec) {
   const uint32_t x0 = (blockIdx.x * 64 + threadIdx.x) * 4, y = blockIdx.y;
   if (x0 >= g.w || y >= g.h) return;
-  const uint32_t yv = *(const uint32_t *)(planes + g.plane_off[0] + (size_t)y * ((size_t)g.bw[0] * 8) + x0);
-  int c0[4] = { (int)(yv & 255), (int)((yv >> 8) & 255), (int)((yv >> 16) & 255), (int)(yv >> 24) }, c1[4], c2[4];
+  int c0[4], c1[4], c2[4];
+  jpeg_samples4(planes, g, x0, y, c0, c1, c2);
   uint32_t px[4];
   if (g.ncomp == 3) {
-    jpeg_chroma4(planes + g.plane_off[1], (size_t)g.bw[1] * 8, g.cw[1], g.ch[1], g.hr, g.vr, x0, y, c1);
-    jpeg_chroma4(planes + g.plane_off[2], (size_t)g.bw[2] * 8, g.cw[2], g.ch[2], g.hr, g.vr, x0, y, c2);
     for (int k = 0; k < 4; k++) {
       uint32_t r, gg, b;
       if (g.color == 1) {                                        // YCbCr: 1.40200, 0.34414, 0.71414, 1.77200 in 16.16
@@ -157,6 +176,17 @@ __global__ void __launch_bounds__(64) jpeg_rgba_kernel(const uint8_t *planes, co
 // the same pixels without their alpha byte, for 3-channel batches: 12 bytes per thread (vec4: every destination row is 4-byte aligned)
 __global__ void __launch_bounds__(64) jpeg_rgb_kernel(const uint8_t *planes, const JpegDevGeom g, uint8_t *rgb, const size_t stride_px, const int vec4) {
   jpeg_colour4<3>(planes, g, rgb, stride_px, vec4);
+}
+// planes -> the file's own samples, no colour arithmetic: (Y, Cb, Cr, 255) of a three-component YCbCr file (chroma upsampled as above), (Y, 128, 128, 255)
+// of a grey one, into a slot of DC channels (DC 3: without the fourth byte).  Thread shape, store and `vec` as for the colour kernels.
+template <int DC> __global__ void __launch_bounds__(64) jpeg_ycc_kernel(const uint8_t *planes, const JpegDevGeom g, uint8_t *out, const size_t stride_px, const int vec) {
+  const uint32_t x0 = (blockIdx.x * 64 + threadIdx.x) * 4, y = blockIdx.y;
+  if (x0 >= g.w || y >= g.h) return;
+  int c0[4], c1[4] = { 128, 128, 128, 128 }, c2[4] = { 128, 128, 128, 128 };
+  jpeg_samples4(planes, g, x0, y, c0, c1, c2);
+  uint32_t px[4];
+  for (int k = 0; k < 4; k++) px[k] = (uint32_t)c0[k] | ((uint32_t)c1[k] << 8) | ((uint32_t)c2[k] << 16) | 0xFF000000u;
+  slot_store4<DC>(out + ((size_t)y * stride_px + x0) * DC, px, g.w - x0 < 4 ? g.w - x0 : 4, vec != 0);
 }
 
 }  // namespace mi

@@ -637,16 +637,26 @@ __global__ __launch_bounds__(256) void segment_kernel(FrameDev *frames) {
 // RGBA8/RGB8 (HBM) -> planar Y,Cb,Cr (BT.601 full range, f32 FMA exactly as ravif rgb_to_ycbcr,
 // av1encoder.rs:504-524) or G,B,R, 8->10 bit expansion, optional alpha plane, edge replication into the
 // 64-aligned padding.  One thread per output pixel of the padded plane; 4 B read, 3*2 (+2) B written.
-struct FrontParams { float sy_r, sy_g, sy_b, scale, kcb, kcr, shift; int depth, color_model, bpp; };
+// ycc (an image whose slot is of input kind MI_INPUT_YCBCR: the bytes are (Y, Cb, Cr[, x]) already, BT.601 full range): the planes are the bytes, no matrix --
+// at 8 bit as they are, at 10 bit scaled by 1023/255 about the centres (0 for Y, 128 -> 512 for chroma), rounded half up: rgb_to_ycbcr's convention at
+// depth 10 and the one decoded_kernel's q() inverts.  Such an image is opaque whatever its fourth byte holds.
+struct FrontParams { float sy_r, sy_g, sy_b, scale, kcb, kcr, shift; int depth, color_model, bpp, ycc; };
 __global__ __launch_bounds__(256) void frontend_kernel(const uint8_t *pix, int w, int h, int stride_px, FrontParams fp,
                                                        uint16_t *p0, uint16_t *p1, uint16_t *p2, uint16_t *pa, int pw, int ph, int *alpha_flag) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
   if (x >= pw || y >= ph) return;
   const int sx = imin_(x, w - 1), sy = imin_(y, h - 1);
   const uint8_t *p = pix + ((size_t)sy * stride_px + sx) * fp.bpp;
-  const int R = p[0], G = p[1], B = p[2], A = fp.bpp == 4 ? p[3] : 255;
+  const int R = p[0], G = p[1], B = p[2], A = (fp.bpp == 4 && !fp.ycc) ? p[3] : 255;
   uint16_t o0, o1, o2;
-  if (fp.color_model == 1) {
+  if (fp.ycc) {
+    if (fp.depth == 8) { o0 = (uint16_t)R; o1 = (uint16_t)G; o2 = (uint16_t)B; }
+    else {                                                       // floor((2046 v + 255) / 510) for v = Y, Cb - 128, Cr - 128; 1024 * 510 keeps the dividend positive
+      o0 = (uint16_t)((2046 * R + 255) / 510);
+      o1 = (uint16_t)iclamp_((2046 * (G - 128) + 255 + 1024 * 510) / 510 - 512, 0, 1023);
+      o2 = (uint16_t)iclamp_((2046 * (B - 128) + 255 + 1024 * 510) / 510 - 512, 0, 1023);
+    }
+  } else if (fp.color_model == 1) {
     if (fp.depth == 8) { o0 = (uint16_t)G; o1 = (uint16_t)B; o2 = (uint16_t)R; }
     else { o0 = (uint16_t)((G << 2) | (G >> 6)); o1 = (uint16_t)((B << 2) | (B >> 6)); o2 = (uint16_t)((R << 2) | (R >> 6)); }
   } else {

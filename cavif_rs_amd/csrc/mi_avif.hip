@@ -19,6 +19,7 @@
 #include "jpeg_reader.h"
 #include "dev_jpeg.h"
 #include "dev_png.h"
+#include "dev_planes.h"
 #include "dev_resample.h"
 #include "dev_quality.h"
 #include "dev_decoded.h"
@@ -74,7 +75,13 @@ struct mi_batch {
   PinBuf<QualityRec> h_quality; size_t h_quality_bytes = 0;
   // decoded pixels (mi_batch_decode): one image of w*h*4 bytes on the device, made by the first call that decodes into host memory
   DevBuf<uint8_t> d_decoded; size_t d_decoded_cap = 0;
+  // what the bytes of each input slot mean (MI_INPUT_RGB / MI_INPUT_YCBCR): host state, set by whichever call last filled the slot, kept across encodes and
+  // mi_batch_set_count like the slot's contents
+  std::vector<uint8_t> kinds;
 };
+static void batch_tag(mi_batch *b, int first, int count, int kind) { std::fill(b->kinds.begin() + first, b->kinds.begin() + first + count, (uint8_t)kind); }
+// MI_INPUT_YCBCR needs the YCbCr colour model (the planes are the slot's bytes) and, in a 4-channel batch, an alpha mode that leaves opaque pixels alone
+static bool batch_takes_ycbcr(const mi_batch *b) { return b->enc.color_model != 1 && !(b->channels == 4 && b->enc.alpha_mode == 2); }
 static_assert(sizeof(QualityRec) <= MI_FRAME_RECORD_BYTES, "FrameSet reserves MI_FRAME_RECORD_BYTES per (frame, plane)");
 
 static void batch_plan(mi_batch *b) {
@@ -152,6 +159,7 @@ mi_batch *mi_batch_create(const mi_ravif_encoder *e, int n_images, uint32_t w, u
   if (e->exif && e->exif_len) b->exif.assign(e->exif, e->exif + e->exif_len);
   b->enc.exif = b->exif.empty() ? nullptr : b->exif.data(); b->enc.exif_len = b->exif.size();
   b->alpha_flags.assign(n_images, 0);
+  b->kinds.assign(n_images, MI_INPUT_RGB);
   b->pixel_bytes = (size_t)n_images * w * h * channels;
   bool ok = hipStreamCreate(&b->stream) == hipSuccess && b->d_pixels.alloc(b->pixel_bytes) == hipSuccess &&
             b->d_alpha_flags.alloc(n_images) == hipSuccess;
@@ -190,6 +198,18 @@ int mi_batch_upload_async(mi_batch *b, int first, int count) {
   (void)hipSetDevice(b->device);
   const size_t img = (size_t)b->w * b->h * b->channels;
   HIP_OK(hipMemcpyAsync(b->d_pixels.get() + first * img, b->h_pixels.get() + first * img, count * img, hipMemcpyHostToDevice, b->stream));
+  batch_tag(b, first, count, MI_INPUT_RGB);
+  return MI_OK;
+}
+int mi_batch_set_input_kind(mi_batch *b, int first, int count, int kind) {
+  if (!b || b->in_flight || first < 0 || count < 1 || first > b->cap - count || (kind != MI_INPUT_RGB && kind != MI_INPUT_YCBCR)) return MI_INVALID_ARGUMENT;
+  if (kind == MI_INPUT_YCBCR && !batch_takes_ycbcr(b)) return MI_INVALID_ARGUMENT;
+  batch_tag(b, first, count, kind);
+  return MI_OK;
+}
+int mi_batch_input_kind(mi_batch *b, int index, int *kind) {
+  if (!b || !kind || index < 0 || index >= b->cap) return MI_INVALID_ARGUMENT;
+  *kind = b->kinds[index];
   return MI_OK;
 }
 int mi_batch_upload(mi_batch *b, int index, const uint8_t *pixels, size_t stride_px) {
@@ -236,7 +256,7 @@ int mi_batch_encode_async(mi_batch *b) {
   HIP_OK(hipEventRecord(b->ev[0], s));
   HIP_OK(hipMemsetAsync(d_alpha_flags, 0, sizeof(int) * b->n, s));
   const FrontConsts fc = front_consts(b->depth);
-  FrontParams fp{ fc.sy_r, fc.sy_g, fc.sy_b, fc.scale, fc.kcb, fc.kcr, fc.shift, b->depth, b->enc.color_model, b->channels };
+  FrontParams fp{ fc.sy_r, fc.sy_g, fc.sy_b, fc.scale, fc.kcb, fc.kcr, fc.shift, b->depth, b->enc.color_model, b->channels, 0 };
   const uint8_t *front_src = d_pixels;
   if (d_clean && b->enc.alpha_mode == 2) {                  // convert_alpha_8bit: Premultiplied (av1encoder.rs:282-296)
     const size_t npx = (size_t)b->n * b->w * b->h;
@@ -247,6 +267,7 @@ int mi_batch_encode_async(mi_batch *b) {
     HIP_OK(hipMemsetAsync(d_alpha_acc, 0, sizeof(unsigned long long) * 4 * b->n, s));
     const dim3 g((b->w + 255) / 256, b->h), blk(256);
     for (int i = 0; i < b->n; i++) {
+      if (b->kinds[i] == MI_INPUT_YCBCR) continue;              // opaque: the passes would be copies; the front end reads the slot itself
       const uint8_t *in = d_pixels + (size_t)i * b->w * b->h * 4; uint8_t *outp = d_clean + (size_t)i * b->w * b->h * 4;
       hipLaunchKernelGGL(alpha_scan_kernel, g, blk, 0, s, in, (int)b->w, (int)b->h, d_alpha_acc + 4 * i);
       hipLaunchKernelGGL(alpha_rewrite_kernel, g, blk, 0, s, in, d_clean_tmp, (int)b->w, (int)b->h, d_alpha_acc + 4 * i, 0);
@@ -258,8 +279,9 @@ int mi_batch_encode_async(mi_batch *b) {
   for (int i = 0; i < b->n; i++) {
     FramePlan &p = b->fs.frames[i];
     uint16_t *alpha_stage = b->channels == 4 ? p.dev.fin[0] : nullptr;      // fin[0] is free until CDEF runs
+    fp.ycc = b->kinds[i] == MI_INPUT_YCBCR;
     hipLaunchKernelGGL(frontend_kernel, dim3((p.pw + 255) / 256, p.ph), dim3(256), 0, s,
-                       front_src + (size_t)i * b->w * b->h * b->channels, (int)b->w, (int)b->h, (int)b->w, fp,
+                       (fp.ycc ? d_pixels : front_src) + (size_t)i * b->w * b->h * b->channels, (int)b->w, (int)b->h, (int)b->w, fp,
                        p.dev.src[0], p.dev.src[1], p.dev.src[2], alpha_stage, p.pw, p.ph, d_alpha_flags + i);
   }
   HIP_OK(hipGetLastError());
@@ -578,7 +600,7 @@ int mi_png_decode_rgba(const uint8_t *data, size_t len, uint8_t **rgba, uint32_t
 // (mi_jpeg_decode_rgba).  The caller has made the device current and keeps h_in untouched until the stream has passed the copy.
 static size_t jpeg_in_bytes(const JpegCoeffs &jc) { return 3 * 64 * sizeof(uint16_t) + jc.nblocks * 64 * sizeof(int16_t); }
 static size_t jpeg_plane_bytes(const JpegCoeffs &jc) { return jc.nblocks * 64; }
-static int jpeg_decode_to_device(const JpegCoeffs &jc, uint8_t *h_in, uint8_t *d_in, uint8_t *d_planes, uint8_t *d_out, int channels, size_t stride_px, hipStream_t stream, double *step_ms) {
+static int jpeg_decode_to_device(const JpegCoeffs &jc, uint8_t *h_in, uint8_t *d_in, uint8_t *d_planes, uint8_t *d_out, int channels, size_t stride_px, hipStream_t stream, double *step_ms, bool ycc = false) {
   JpegDevGeom g; memset(&g, 0, sizeof(g));
   g.w = jc.w; g.h = jc.h; g.ncomp = (uint32_t)jc.ncomp; g.color = (uint32_t)jc.color; g.nblocks = (uint32_t)jc.nblocks;
   for (int c = 0; c < 3; c++) {
@@ -602,10 +624,12 @@ static int jpeg_decode_to_device(const JpegCoeffs &jc, uint8_t *h_in, uint8_t *d
   const dim3 grid(((jc.w + 3) / 4 + 63) / 64, jc.h);
   if (channels == 4) {
     const int vec16 = (stride_px % 4 == 0 && ((uintptr_t)d_out & 15) == 0) ? 1 : 0;
-    hipLaunchKernelGGL(jpeg_rgba_kernel, grid, dim3(64), 0, stream, (const uint8_t *)d_planes, g, d_out, stride_px, vec16);
+    if (ycc) hipLaunchKernelGGL((jpeg_ycc_kernel<4>), grid, dim3(64), 0, stream, (const uint8_t *)d_planes, g, d_out, stride_px, vec16);
+    else hipLaunchKernelGGL(jpeg_rgba_kernel, grid, dim3(64), 0, stream, (const uint8_t *)d_planes, g, d_out, stride_px, vec16);
   } else {
     const int vec4 = (stride_px % 4 == 0 && ((uintptr_t)d_out & 3) == 0) ? 1 : 0;        // a row is 3 * stride_px bytes
-    hipLaunchKernelGGL(jpeg_rgb_kernel, grid, dim3(64), 0, stream, (const uint8_t *)d_planes, g, d_out, stride_px, vec4);
+    if (ycc) hipLaunchKernelGGL((jpeg_ycc_kernel<3>), grid, dim3(64), 0, stream, (const uint8_t *)d_planes, g, d_out, stride_px, vec4);
+    else hipLaunchKernelGGL(jpeg_rgb_kernel, grid, dim3(64), 0, stream, (const uint8_t *)d_planes, g, d_out, stride_px, vec4);
   }
   HIP_OK(hipGetLastError());
   lap(1);
@@ -717,6 +741,35 @@ int mi_batch_upload_device(mi_batch *b, int first, int count, const mi_device_pi
   if (b->channels == 4) hipLaunchKernelGGL((ingest_kernel<4>), grid, dim3(64), 0, b->stream, s, slots);
   else hipLaunchKernelGGL((ingest_kernel<3>), grid, dim3(64), 0, b->stream, s, slots);
   HIP_OK(hipGetLastError());
+  batch_tag(b, first, count, MI_INPUT_RGB);
+  return MI_OK;
+}
+// images [first, first + count) from 8-bit YCbCr planes in the memory of the batch's device: one planes_ingest_kernel launch on the batch's stream, after
+// whatever src->after_stream holds at this moment; the slots are tagged MI_INPUT_YCBCR.  Strides of 0 mean packed.
+int mi_batch_upload_device_ycbcr(mi_batch *b, int first, int count, const mi_device_planes *src) {
+  if (!b || !src || !src->y || !src->cb || b->in_flight || first < 0 || count < 1 || first > b->cap - count || !batch_takes_ycbcr(b)) return MI_INVALID_ARGUMENT;
+  if (!((src->hsub == 1 && src->vsub == 1) || (src->hsub == 2 && (src->vsub == 1 || src->vsub == 2)))) return MI_INVALID_ARGUMENT;
+  PlanesSrc s;
+  s.w = b->w; s.h = b->h; s.hsub = (uint32_t)src->hsub; s.vsub = (uint32_t)src->vsub;
+  s.cw = (b->w + s.hsub - 1) / s.hsub; s.ch = (b->h + s.vsub - 1) / s.vsub;
+  s.cpitch = src->cr ? 1 : 2;
+  s.y = (const uint8_t *)src->y; s.cb = (const uint8_t *)src->cb; s.cr = src->cr ? (const uint8_t *)src->cr : s.cb + 1;
+  const size_t packed_c = (size_t)s.cw * s.cpitch;
+  s.y_row = src->y_row_stride ? src->y_row_stride : b->w; s.c_row = src->c_row_stride ? src->c_row_stride : packed_c;
+  s.y_image = src->y_image_stride ? src->y_image_stride : s.y_row * b->h; s.c_image = src->c_image_stride ? src->c_image_stride : s.c_row * s.ch;
+  if (s.y_row < b->w || s.c_row < packed_c) return MI_INVALID_ARGUMENT;
+  (void)hipSetDevice(b->device);
+  if (src->after_stream) {
+    if (!b->ev_src) HIP_OK(hipEventCreateWithFlags(&b->ev_src, hipEventDisableTiming));
+    HIP_OK(hipEventRecord(b->ev_src, (hipStream_t)src->after_stream));
+    HIP_OK(hipStreamWaitEvent(b->stream, b->ev_src, 0));
+  }
+  const dim3 grid(((b->w + 3) / 4 + 63) / 64, b->h, (unsigned)count);
+  uint8_t *const slots = mi_batch_device_input(b, first);
+  if (b->channels == 4) hipLaunchKernelGGL((planes_ingest_kernel<4>), grid, dim3(64), 0, b->stream, s, slots);
+  else hipLaunchKernelGGL((planes_ingest_kernel<3>), grid, dim3(64), 0, b->stream, s, slots);
+  HIP_OK(hipGetLastError());
+  batch_tag(b, first, count, MI_INPUT_YCBCR);
   return MI_OK;
 }
 
@@ -782,7 +835,7 @@ int mi_batch_decode(mi_batch *b, int index, int which, int channels, uint8_t *ds
 // for and the staging starts over); the plane buffer is one image's, stream order serialises its users.
 static constexpr size_t MI_BATCH_JPEG_STAGED = 4;
 // (the staging half, shared with mi_batch_resize_jpeg: rows of stride_px pixels at any device pointer)
-static int batch_jpeg_decode(mi_batch *b, const JpegCoeffs &jc, uint8_t *d_out, int channels, size_t stride_px) {
+static int batch_jpeg_decode(mi_batch *b, const JpegCoeffs &jc, uint8_t *d_out, int channels, size_t stride_px, bool ycc = false) {
   const size_t need = align_up(jpeg_in_bytes(jc), 256);
   if (b->jpeg_used + need > b->h_jpeg_cap) {
     HIP_OK(hipStreamSynchronize(b->stream));
@@ -794,14 +847,35 @@ static int batch_jpeg_decode(mi_batch *b, const JpegCoeffs &jc, uint8_t *d_out, 
     if (!staging_grow(b->d_jpeg_planes, b->d_jpeg_planes_cap, jpeg_plane_bytes(jc))) return MI_ENCODING_ERROR;
   }
   const size_t at = b->jpeg_used; b->jpeg_used += need;
-  return jpeg_decode_to_device(jc, b->h_jpeg.get() + at, b->d_jpeg.get() + at, b->d_jpeg_planes.get(), d_out, channels, stride_px, b->stream, nullptr);
+  return jpeg_decode_to_device(jc, b->h_jpeg.get() + at, b->d_jpeg.get() + at, b->d_jpeg_planes.get(), d_out, channels, stride_px, b->stream, nullptr, ycc);
 }
 int mi_batch_upload_jpeg(mi_batch *b, int index, const mi_jpeg_coeffs *c) {
   if (!b || !c || b->in_flight || index < 0 || index >= b->cap) return MI_INVALID_ARGUMENT;
   const JpegCoeffs &jc = c->jc;
   if (jc.w != b->w || jc.h != b->h) return MI_INVALID_ARGUMENT;
   (void)hipSetDevice(b->device);
-  return batch_jpeg_decode(b, jc, mi_batch_device_input(b, index), b->channels, b->w);
+  if (int st = batch_jpeg_decode(b, jc, mi_batch_device_input(b, index), b->channels, b->w)) return st;
+  batch_tag(b, index, 1, MI_INPUT_RGB);
+  return MI_OK;
+}
+// the same staging, copy and IDCT, then jpeg_ycc_kernel instead of a colour kernel: the slot holds the file's own (Y, Cb, Cr) and is tagged MI_INPUT_YCBCR
+int mi_batch_upload_jpeg_ycbcr(mi_batch *b, int index, const mi_jpeg_coeffs *c) {
+  if (!b || !c || b->in_flight || index < 0 || index >= b->cap) return MI_INVALID_ARGUMENT;
+  const JpegCoeffs &jc = c->jc;
+  if (jc.w != b->w || jc.h != b->h || !batch_takes_ycbcr(b)) return MI_INVALID_ARGUMENT;
+  if (jc.color == JPEG_RGB) return MI_UNSUPPORTED;
+  (void)hipSetDevice(b->device);
+  if (int st = batch_jpeg_decode(b, jc, mi_batch_device_input(b, index), b->channels, b->w, true)) return st;
+  batch_tag(b, index, 1, MI_INPUT_YCBCR);
+  return MI_OK;
+}
+int mi_jpeg_coeffs_info(const mi_jpeg_coeffs *c, int *color, int *hsub, int *vsub) {
+  if (!c) return MI_INVALID_ARGUMENT;
+  const JpegCoeffs &jc = c->jc;
+  if (color) *color = jc.color == JPEG_GREY ? 0 : jc.color == JPEG_YCBCR ? 1 : 2;
+  if (hsub) *hsub = jc.ncomp == 3 ? jc.comp[0].h / jc.comp[1].h : 1;
+  if (vsub) *vsub = jc.ncomp == 3 ? jc.comp[0].v / jc.comp[1].v : 1;
+  return MI_OK;
 }
 
 // ---- PNG input: the host half behind a handle, the device half on the batch's stream ----
@@ -897,7 +971,9 @@ int mi_batch_upload_png(mi_batch *b, int first, int count, const mi_png_scanline
     if (b->channels == 3 && png[i]->sl.has_alpha()) return MI_INVALID_ARGUMENT;      // alpha is never dropped
   }
   (void)hipSetDevice(b->device);
-  return batch_png_expand(b, count, png, b->w, b->h, b->channels, mi_batch_device_input(b, first));
+  if (int st = batch_png_expand(b, count, png, b->w, b->h, b->channels, mi_batch_device_input(b, first))) return st;
+  batch_tag(b, first, count, MI_INPUT_RGB);
+  return MI_OK;
 }
 
 // ---- resize on input: a source of any size is resampled on the batch's stream into the slot (kernels: dev_resample.h) ----
@@ -993,6 +1069,7 @@ static int batch_resample(mi_batch *b, int first, int count, const IngestSrc &s,
   if (b->channels == 4) hipLaunchKernelGGL((resample_v_kernel<4>), grid, dim3(64), 0, b->stream, (const uint32_t *)inter, s.h, pitch, vbounds, vtaps, b->w, b->h, alpha, slots);
   else hipLaunchKernelGGL((resample_v_kernel<3>), grid, dim3(64), 0, b->stream, (const uint32_t *)inter, s.h, pitch, vbounds, vtaps, b->w, b->h, alpha, slots);
   HIP_OK(hipGetLastError());
+  batch_tag(b, first, count, MI_INPUT_RGB);
   return MI_OK;
 }
 static bool resample_filter_known(int filter) { return filter >= MI_RESAMPLE_BOX && filter <= MI_RESAMPLE_LANCZOS3; }
@@ -1067,6 +1144,17 @@ int mi_ravif_encode_device(const mi_ravif_encoder *e, const mi_device_pixels *sr
   pool_release(b);
   return st;
 }
+// the same for YCbCr planes in the memory of device e->device: the file of a 3-channel batch fed through mi_batch_upload_device_ycbcr
+int mi_ravif_encode_device_ycbcr(const mi_ravif_encoder *e, const mi_device_planes *src, uint32_t w, uint32_t h, mi_encoded_image *out) {
+  if (!e || !src || !src->y || !src->cb || !out || w < 1 || h < 1) return MI_INVALID_ARGUMENT;
+  mi_batch *b = pool_acquire(e, 1, w, h, 3);
+  if (!b) return mi_device_count() > e->device ? MI_INVALID_ARGUMENT : MI_NO_DEVICE;
+  int st = mi_batch_upload_device_ycbcr(b, 0, 1, src);
+  if (st == MI_OK) st = mi_batch_encode(b);
+  if (st == MI_OK) st = mi_batch_get(b, 0, out);
+  pool_release(b);
+  return st;
+}
 // the same for a picture of src_w x src_h that is resampled to w x h on the way in
 int mi_ravif_encode_device_resized(const mi_ravif_encoder *e, const mi_device_pixels *src, uint32_t src_w, uint32_t src_h, uint32_t w, uint32_t h, int filter, mi_encoded_image *out) {
   if (!e || !src || !src->dev || !out || w < 1 || h < 1 || (src->channels != 3 && src->channels != 4)) return MI_INVALID_ARGUMENT;
@@ -1085,7 +1173,7 @@ int mi_ravif_encode_device_resized(const mi_ravif_encoder *e, const mi_device_pi
 // Streaming form of the fan-out: image i is obtained through `fetch(user, i, &desc)` when a worker is about to stage it (the
 // call may block until the pixels exist -- e.g. until a loader thread has decoded the file), so loading, upload, encoding and
 // assembly of consecutive runs overlap.  fetch returns MI_OK or a status that becomes the image's status.  An image is host pixels (kind 0) or the
-// coefficients of a parsed JPEG (kind 1) or the scanlines of a parsed PNG (kind 2), whose pixels come into being in the batch's HBM input slot; mi_ravif_encode_stream is this
+// coefficients of a parsed JPEG (kind 1; kind 3: the same, kept as the file's own YCbCr) or the scanlines of a parsed PNG (kind 2), whose pixels come into being in the batch's HBM input slot; mi_ravif_encode_stream is this
 // with kind 0 throughout.
 int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source_fn fetch, mi_release_fn release, void *user, mi_encoded_image *out, int *status, const int *devices, int ndev) {
   if (!e || !fetch || (n && !out)) return MI_INVALID_ARGUMENT;
@@ -1207,10 +1295,10 @@ int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source
             continue;
           }
           upload_png();
-          if (src.kind == 1) {
+          if (src.kind == 1 || src.kind == 3) {
             upload_host(k); host_from = k + 1;
             if (!sl.jpeg) { sl.jpeg = true; const size_t extra = est_jpeg_bytes(sh->w, sh->h); sl.bytes += extra; live_bytes += extra; }
-            if (rc == MI_OK) rc = mi_batch_upload_jpeg(sl.b, (int)k, src.jpeg);
+            if (rc == MI_OK) rc = src.kind == 3 ? mi_batch_upload_jpeg_ycbcr(sl.b, (int)k, src.jpeg) : mi_batch_upload_jpeg(sl.b, (int)k, src.jpeg);
             continue;
           }
           const mi_image_desc &x = src.desc;
@@ -1251,9 +1339,15 @@ int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source
         const mi_image_source &src = d[i - i0];
         const mi_image_desc &x = src.desc;
         if (rc != MI_OK) { st[i] = rc; continue; }
-        const bool have = src.kind == 0 ? x.pixels != nullptr : src.kind == 1 ? src.jpeg && src.jpeg->jc.w == x.width && src.jpeg->jc.h == x.height :
+        const bool have = src.kind == 0 ? x.pixels != nullptr : (src.kind == 1 || src.kind == 3) ? src.jpeg && src.jpeg->jc.w == x.width && src.jpeg->jc.h == x.height :
                           src.kind == 2 && src.png && src.png->sl.w == x.width && src.png->sl.h == x.height && !(x.channels == 3 && src.png->sl.has_alpha());
         if (!have || !x.width || !x.height || (x.channels != 3 && x.channels != 4)) { st[i] = MI_INVALID_ARGUMENT; if (release) release(user, i); continue; }
+        // a kind-3 source that its upload call would refuse fails alone, not with its run
+        if (src.kind == 3 && (src.jpeg->jc.color == JPEG_RGB || e->color_model == 1 || (x.channels == 4 && e->alpha_mode == 2))) {
+          st[i] = src.jpeg->jc.color == JPEG_RGB && e->color_model != 1 && !(x.channels == 4 && e->alpha_mode == 2) ? MI_UNSUPPORTED : MI_INVALID_ARGUMENT;
+          if (release) release(user, i);
+          continue;
+        }
         Shape *sh = shape_for(x);
         if (sh != run_shape || run.size() >= sh->cap) flush(true);
         run_shape = sh; run.push_back(i - i0);

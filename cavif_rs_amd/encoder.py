@@ -59,6 +59,11 @@ class _DevicePixels(C.Structure):
                 ('pixel_or_plane_stride', C.c_size_t), ('image_stride', C.c_size_t), ('after_stream', C.c_void_p)]
 
 
+class _DevicePlanes(C.Structure):                      # mi_device_planes
+    _fields_ = [('y', C.c_void_p), ('cb', C.c_void_p), ('cr', C.c_void_p), ('hsub', C.c_int), ('vsub', C.c_int), ('y_row_stride', C.c_size_t),
+                ('c_row_stride', C.c_size_t), ('y_image_stride', C.c_size_t), ('c_image_stride', C.c_size_t), ('after_stream', C.c_void_p)]
+
+
 class _DeviceTarget(C.Structure):                      # mi_device_target: _DevicePixels with a writable pointer
     _fields_ = _DevicePixels._fields_
 
@@ -153,6 +158,12 @@ def load_library():
     L.mi_batch_decode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
     L.mi_ravif_encode_sources.argtypes = [C.POINTER(_RavifEncoder), C.c_size_t, _FETCH_SOURCE, _RELEASE, C.c_void_p, C.POINTER(_EncodedImage),
                                           C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
+    L.mi_batch_set_input_kind.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    L.mi_batch_input_kind.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.mi_batch_upload_jpeg_ycbcr.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.mi_jpeg_coeffs_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.mi_batch_upload_device_ycbcr.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(_DevicePlanes)]
+    L.mi_ravif_encode_device_ycbcr.argtypes = [C.POINTER(_RavifEncoder), C.POINTER(_DevicePlanes), C.c_uint32, C.c_uint32, C.POINTER(_EncodedImage)]
     _LIB = L
     return L
 
@@ -205,8 +216,10 @@ def load_rgba(data, device=0):
 
 
 class JpegCoeffs:
-    """One parsed JPEG file (mi_jpeg_parse): quantised coefficients in host memory, `width`, `height`.  Feeds BatchEncoder.upload_jpeg and encode_many;
-    its pixels come into being on the device.  close() (or the garbage collector) frees it."""
+    """One parsed JPEG file (mi_jpeg_parse): quantised coefficients in host memory, `width`, `height`, `color` ('grey', 'ycbcr' or 'rgb': what the file's
+    components are) and `subsampling` ((hsub, vsub): luma samples per chroma sample).  Feeds BatchEncoder.upload_jpeg and encode_many; its pixels come
+    into being on the device.  close() (or the garbage collector) frees it."""
+    COLORS = ('grey', 'ycbcr', 'rgb')
 
     def __init__(self, data):
         L = load_library()
@@ -217,6 +230,11 @@ class JpegCoeffs:
         if st:
             raise AvifError(st)
         self._L, self._h, self.width, self.height = L, h.value, w.value, ht.value
+        color, hs, vs = C.c_int(), C.c_int(), C.c_int()
+        st = L.mi_jpeg_coeffs_info(self._h, C.byref(color), C.byref(hs), C.byref(vs))
+        if st:
+            raise AvifError(st)
+        self.color, self.subsampling = self.COLORS[color.value], (hs.value, vs.value)
 
     def close(self):
         if getattr(self, '_h', None):
@@ -337,6 +355,64 @@ def _device_pixels(x, batched=False, writable=False):
         idx = getattr(getattr(x, 'device', None), 'index', None)
         d.after_stream = torch.cuda.current_stream(idx).cuda_stream or None
     return d, n, h, w, getattr(getattr(x, 'device', None), 'index', None)
+
+
+def _plane_view(x, what):
+    """(pointer, shape, byte strides, device index or None) of a uint8 object with __cuda_array_interface__"""
+    ai = x.__cuda_array_interface__
+    if ai.get('typestr') != '|u1':
+        raise TypeError('%s must be uint8 (got typestr %r)' % (what, ai.get('typestr')))
+    shape = tuple(int(v) for v in ai['shape'])
+    strides = ai.get('strides')
+    if strides is None:
+        strides, acc = [], 1
+        for n in reversed(shape):
+            strides.insert(0, acc); acc *= n
+    strides = tuple(int(v) for v in strides)
+    if not ai['data'][0] or not shape or min(shape) < 1 or min(strides) < 0:
+        raise AvifError(4)
+    return ai['data'][0], shape, strides, getattr(getattr(x, 'device', None), 'index', None)
+
+
+def _device_planes(y, cb, cr, subsampling):
+    """(_DevicePlanes, images, height, width, device index or None) of uint8 device arrays: y (N, H, W) or (H, W); cb and cr of the chroma extent
+    ceil(H / vsub) x ceil(W / hsub) with the same leading dimension, or cr=None and cb of shape (..., ch, cw, 2): interleaved (Cb, Cr) pairs.  Columns one byte
+    apart (pairs two); Cb and Cr share their row and image strides."""
+    hsub, vsub = (int(v) for v in subsampling)
+    yp, ys, yst, index = _plane_view(y, 'y')
+    if len(ys) not in (2, 3):
+        raise AvifError(4)
+    n = ys[0] if len(ys) == 3 else 1
+    h, w = ys[-2:]
+    if hsub < 1 or vsub < 1:
+        raise AvifError(4)
+    cdims = ((h + vsub - 1) // vsub, (w + hsub - 1) // hsub)
+    lead = ys[:-2]
+    cp, cs, cst, _ = _plane_view(cb, 'cb')
+    d = _DevicePlanes()
+    if cr is None:
+        if cs != lead + cdims + (2,) or cst[-1] != 1 or (cst[-2] != 2 and cdims[1] > 1):
+            raise AvifError(4)
+        cst = cst[:-1]
+        d.cr = None
+    else:
+        rp, rs, rst, _ = _plane_view(cr, 'cr')
+        if cs != lead + cdims or rs != cs or (cst[-1] != 1 and cdims[1] > 1):
+            raise AvifError(4)
+        if any(a != b_ for a, b_, m in zip(cst[:-1], rst[:-1], cs[:-1]) if m > 1) or (rst[-1] != 1 and cdims[1] > 1):
+            raise AvifError(4)                                     # one c_row_stride / c_image_stride serves both planes
+        d.cr = rp
+    if yst[-1] != 1 and w > 1:
+        raise AvifError(4)
+    if n > 1 and (yst[0] == 0 or cst[0] == 0):
+        raise AvifError(4)
+    d.y, d.cb, d.hsub, d.vsub = yp, cp, hsub, vsub
+    d.y_row_stride, d.c_row_stride = (yst[-2] if h > 1 else 0), (cst[-2] if cdims[0] > 1 else 0)
+    d.y_image_stride, d.c_image_stride = (yst[0] if n > 1 else 0), (cst[0] if n > 1 else 0)
+    torch = sys.modules.get('torch')                               # never imported here: only a caller that has torch can hand over torch's work
+    if torch is not None and hasattr(torch, 'cuda') and torch.cuda.is_available():
+        d.after_stream = torch.cuda.current_stream(index).cuda_stream or None
+    return d, n, h, w, index
 
 
 def _empty_like_device(x, shape):
@@ -683,6 +759,31 @@ class Encoder:
                 l = mid + 1
         return TargetResult(done[h][0], done[h][1], h, reached, tried)      # h is hi or a mid that reached the target: always encoded
 
+    def encode_jpeg(self, coeffs_or_bytes, ycbcr=True):
+        """a JPEG file (bytes or a JpegCoeffs) as an opaque picture, decoded on the device.  ycbcr=True: the frame is coded from the file's own Y, Cb, Cr
+        (mi_batch_upload_jpeg_ycbcr: no conversion to RGB and back; a file whose colour is RGB raises Unsupported); ycbcr=False: from the RGB pixels
+        decode_jpeg gives, the file of encode_rgb over them.  One source of kind 3 or 1 through mi_ravif_encode_sources (a 3-channel slot)."""
+        c = coeffs_or_bytes if isinstance(coeffs_or_bytes, JpegCoeffs) else JpegCoeffs(coeffs_or_bytes)
+        if not c._h:
+            raise AvifError(4)
+        return _encode_sources(self, [(3 if ycbcr else 1, c, 3)], None)[0]
+
+    def encode_ycbcr_device(self, y, cb, cr=None, subsampling=(2, 2)):
+        """8-bit BT.601 full-range planes in device memory (objects with __cuda_array_interface__; see BatchEncoder.upload_device_ycbcr for the shapes) as
+        one opaque picture: mi_ravif_encode_device_ycbcr"""
+        L = load_library()
+        d, n, h, w, index = _device_planes(y, cb, cr, subsampling)
+        if n != 1:
+            raise AvifError(4)
+        img = _EncodedImage()
+        e = self._c()
+        if index is not None:
+            e.device = index                            # the pointers belong to that device
+        st = L.mi_ravif_encode_device_ycbcr(C.byref(e), C.byref(d), w, h, C.byref(img))
+        if st:
+            raise AvifError(st)
+        return _take(img)
+
     def encode_rgba(self, rgba):                        # :243
         return self._encode(rgba, 4)
 
@@ -713,37 +814,44 @@ class Encoder:
         return self._raw(load_library().mi_ravif_encode_raw_planes_10, np.uint16, planes, alpha, width, height, color_pixel_range, matrix_coefficients)
 
 
-def encode_many(encoder, images, devices=None):
+def encode_many(encoder, images, devices=None, jpeg_ycbcr=False):
     """mi_ravif_encode_sources: the reference's files.into_par_iter() (src/main.rs:223) over the node's GPUs.
     images: list of HxWx3 / HxWx4 uint8 arrays (shapes may differ), JpegCoeffs objects (parse_jpeg; encoded as the RGBA pictures decode_jpeg
     gives, decoded on the device) and PngScanlines objects (parse_png; encoded as the RGBA pictures load_rgba gives, unfiltered and expanded on the
-    device).  Returns a list of EncodedImage."""
-    L = load_library()
+    device).  jpeg_ycbcr=True: a JpegCoeffs whose colour is not RGB is coded from the file's own Y, Cb, Cr (source kind 3) instead.
+    Returns a list of EncodedImage."""
     items = []
     for im in images:
         if isinstance(im, (JpegCoeffs, PngScanlines)):
             if not im._h:
                 raise AvifError(4)
-            items.append(im)
+            items.append((2, im, 4) if isinstance(im, PngScanlines) else (3 if jpeg_ycbcr and im.color != 'rgb' else 1, im, 4))
             continue
         if _is_device_array(im):
             raise TypeError('encode_many takes host arrays, JpegCoeffs and PngScanlines; pixels in device memory go through BatchEncoder.upload_device')
         a = np.ascontiguousarray(im, dtype=np.uint8)
         if a.ndim != 3 or a.shape[2] not in (3, 4):
             raise AvifError(4)
-        items.append(a)
+        items.append((0, a, a.shape[2]))
+    return _encode_sources(encoder, items, devices)
+
+
+def _encode_sources(encoder, items, devices):
+    """mi_ravif_encode_sources over (kind, object, channels of the slot) triples: kind 0 a contiguous uint8 array, 1 / 3 a JpegCoeffs, 2 a PngScanlines"""
+    L = load_library()
 
     def fetch(_user, i, src):
-        it, s = items[i], src.contents
-        if isinstance(it, PngScanlines):
-            s.kind, s.jpeg, s.png = 2, None, it._h
-            s.desc.pixels, s.desc.width, s.desc.height, s.desc.stride_px, s.desc.channels = None, it.width, it.height, it.width, 4
-        elif isinstance(it, JpegCoeffs):
-            s.kind, s.jpeg, s.png = 1, it._h, None
-            s.desc.pixels, s.desc.width, s.desc.height, s.desc.stride_px, s.desc.channels = None, it.width, it.height, it.width, 4
+        (kind, it, channels), s = items[i], src.contents
+        s.kind = kind
+        if kind == 2:
+            s.jpeg, s.png = None, it._h
+            s.desc.pixels, s.desc.width, s.desc.height, s.desc.stride_px, s.desc.channels = None, it.width, it.height, it.width, channels
+        elif kind in (1, 3):
+            s.jpeg, s.png = it._h, None
+            s.desc.pixels, s.desc.width, s.desc.height, s.desc.stride_px, s.desc.channels = None, it.width, it.height, it.width, channels
         else:
-            s.kind, s.jpeg, s.png = 0, None, None
-            s.desc.pixels, s.desc.width, s.desc.height, s.desc.stride_px, s.desc.channels = it.ctypes.data, it.shape[1], it.shape[0], it.shape[1], it.shape[2]
+            s.jpeg, s.png = None, None
+            s.desc.pixels, s.desc.width, s.desc.height, s.desc.stride_px, s.desc.channels = it.ctypes.data, it.shape[1], it.shape[0], it.shape[1], channels
         return 0
     out = (_EncodedImage * len(items))()
     status = (C.c_int * len(items))()
@@ -788,11 +896,39 @@ class BatchEncoder:
             raise AvifError(st)
         self._sources.append(pixels)
 
-    def upload_jpeg(self, index, coeffs):
-        """one parsed JPEG (parse_jpeg) of the batch's size into slot `index`: dequantisation, IDCT, upsampling and colour run on the batch's stream"""
+    def upload_jpeg(self, index, coeffs, ycbcr=False):
+        """one parsed JPEG (parse_jpeg) of the batch's size into slot `index`: dequantisation, IDCT, upsampling and colour run on the batch's stream.
+        ycbcr=True: no colour step, the slot holds the file's own (Y, Cb, Cr) and is of input kind 1 (a file whose colour is RGB raises Unsupported)"""
         if not isinstance(coeffs, JpegCoeffs) or not coeffs._h:
             raise AvifError(4)
-        st = self._L.mi_batch_upload_jpeg(self._h, index, coeffs._h)
+        st = (self._L.mi_batch_upload_jpeg_ycbcr if ycbcr else self._L.mi_batch_upload_jpeg)(self._h, index, coeffs._h)
+        if st:
+            raise AvifError(st)
+
+    def upload_device_ycbcr(self, first, y, cb, cr=None, subsampling=(2, 2)):
+        """images first.. from 8-bit BT.601 full-range planes in device memory (objects with __cuda_array_interface__): y (N, H, W) or (H, W), cb and cr of
+        ceil(H / vsub) x ceil(W / hsub) samples with subsampling = (hsub, vsub) one of (1, 1), (2, 1), (2, 2); cb of shape (..., ch, cw, 2) with cr=None:
+        interleaved (Cb, Cr) pairs (NV12-style).  Chroma is upsampled as libjpeg does (centred siting); the slots are of input kind 1.  Enqueued on the
+        batch's stream after the work of torch's current stream; the objects are kept referenced until wait()."""
+        d, n, h, w, _ = _device_planes(y, cb, cr, subsampling)
+        if (h, w) != (self.h, self.w):
+            raise AvifError(4)
+        st = self._L.mi_batch_upload_device_ycbcr(self._h, first, n, C.byref(d))
+        if st:
+            raise AvifError(st)
+        self._sources.append((y, cb, cr))
+
+    def input_kind(self, index):
+        """what the bytes of slot `index` mean: 0 RGB(A), 1 (Y, Cb, Cr[, 255]); set by whichever call last filled the slot"""
+        v = C.c_int()
+        st = self._L.mi_batch_input_kind(self._h, index, C.byref(v))
+        if st:
+            raise AvifError(st)
+        return v.value
+
+    def set_input_kind(self, first, count, kind):
+        """mi_batch_set_input_kind: for callers that write device_input() themselves"""
+        st = self._L.mi_batch_set_input_kind(self._h, first, count, int(kind))
         if st:
             raise AvifError(st)
 

@@ -110,12 +110,16 @@ int  mi_ravif_encode_stream(const mi_ravif_encoder *e, size_t n, mi_fetch_fn fet
  * PNG picture of one size share a run.  `release` is called once the pixels (kind 0) or the coefficients (kind 1) are in pinned staging: the handle may
  * be freed then.  kind 2: the scanlines of a parsed PNG file (mi_png_parse below), unfiltered and expanded on the device; desc as for kind 1 (channels 3 only
  * for files without an alpha channel and without tRNS, else the image is MI_INVALID_ARGUMENT), release once the scanlines are in pinned staging.
+ * kind 3: a parsed JPEG file as for kind 1, uploaded through mi_batch_upload_jpeg_ycbcr: the frame is coded from the file's own (Y, Cb, Cr) without the detour over
+ * RGB.  A file whose colour is RGB gets MI_UNSUPPORTED, and an encoder with the RGB colour model or (channels 4) the premultiplied alpha mode
+ * MI_INVALID_ARGUMENT, for that image alone.  Runs are grouped by (width, height, channels) as before, so kinds 0 to 3 mix in one run.
  * mi_ravif_encode_stream is this call with kind 0 throughout.  Pictures in device memory are not a kind here (a pointer belongs to one
  * device, the shared cursor hands images to any): they enter through mi_ravif_encode_device and mi_batch_upload_device. */
 typedef struct mi_jpeg_coeffs mi_jpeg_coeffs;   /* opaque: one parsed file, host memory only */
 typedef struct mi_png_scanlines mi_png_scanlines;      /* opaque: one inflated file, host memory only */
 typedef struct mi_image_source {
-  int kind;                   /* 0 host pixels (desc), 1 JPEG coefficients (jpeg; desc.width/height/channels say the slot), 2 PNG scanlines (png; desc likewise) */
+  int kind;                   /* 0 host pixels (desc), 1 JPEG coefficients (jpeg; desc.width/height/channels say the slot), 2 PNG scanlines (png; desc likewise),
+                                 3 JPEG coefficients kept as the file's own YCbCr (jpeg; desc as for kind 1; mi_batch_upload_jpeg_ycbcr below) */
   mi_image_desc desc;
   const mi_jpeg_coeffs *jpeg;
   const mi_png_scanlines *png; /* kind 2 only (the struct grew by this field at its tail: never read for kinds 0 and 1) */
@@ -137,6 +141,17 @@ typedef struct mi_device_pixels {
 /* ravif::Encoder::encode_rgb / encode_rgba (by src->channels) of a w x h picture in the memory of device e->device.  The pointer must belong to that
  * device (not detected).  Blocking, through the pooled batch objects like mi_ravif_encode_rgba. */
 int  mi_ravif_encode_device(const mi_ravif_encoder *e, const mi_device_pixels *src, uint32_t w, uint32_t h, mi_encoded_image *out);
+/* 8-bit YCbCr planes in the memory of a HIP device, BT.601 full range (JFIF's matrix: the one the colour frames signal): what rocJPEG / rocDecode deliver.
+ * Chroma is subsampled by (hsub, vsub) luma samples per chroma sample and has ceil(w / hsub) x ceil(h / vsub) samples, sited at the centre of the luma
+ * samples it covers (JPEG's siting, not MPEG-2's co-sited columns).  See mi_batch_upload_device_ycbcr below for the exact bytes. */
+typedef struct mi_device_planes {
+  const void *y, *cb, *cr;   /* cr == NULL: cb points at interleaved (Cb, Cr) byte pairs (NV12-style) */
+  int hsub, vsub;            /* luma samples per chroma sample: (1,1), (2,1) or (2,2); anything else MI_INVALID_ARGUMENT */
+  size_t y_row_stride, c_row_stride, y_image_stride, c_image_stride;   /* bytes; 0 = packed; same for Cb and Cr */
+  void *after_stream;        /* hipStream_t the planes were produced on, or NULL = already complete */
+} mi_device_planes;
+/* mi_ravif_encode_device for such planes: the file of a 3-channel batch of one image fed through mi_batch_upload_device_ycbcr.  Blocking, pooled. */
+int  mi_ravif_encode_device_ycbcr(const mi_ravif_encoder *e, const mi_device_planes *src, uint32_t w, uint32_t h, mi_encoded_image *out);
 /* The same for a picture of src_w x src_h that is resampled to w x h on the device on the way in (mi_batch_resize_device below: `filter` is one of
  * MI_RESAMPLE_*, the pixels are specified exactly).  Blocking, pooled by (w, h, channels) like mi_ravif_encode_device. */
 int  mi_ravif_encode_device_resized(const mi_ravif_encoder *e, const mi_device_pixels *src, uint32_t src_w, uint32_t src_h, uint32_t w, uint32_t h, int filter,
@@ -200,6 +215,41 @@ int  mi_batch_upload_async(mi_batch *b, int first, int count);
  * the samples expanded to the slot's pixels -- those of mi_png_decode_rgba -- on the batch's stream, one launch per kernel for the whole call, no sync; the
  * handles may be freed when the call returns.
  * The upload calls return MI_INVALID_ARGUMENT between mi_batch_encode_async and mi_batch_wait. */
+/* ---- input kinds: what the bytes of a slot mean.  MI_INPUT_RGB: (R, G, B[, A]), converted by the front end (BT.601 full range, rgb_to_ycbcr).
+ * MI_INPUT_YCBCR: (Y, Cb, Cr) in a 3-channel batch, (Y, Cb, Cr, 255) in a 4-channel one, BT.601 full range already.  With (Y, C1, C2) the slot bytes of a
+ * pixel the planes of the colour frame are, without any matrix,
+ *   8 bit:   p0 = Y, p1 = C1, p2 = C2
+ *   10 bit:  p0 = floor((2046 Y + 255) / 510),  p_k = clamp(512 + floor((2046 (C_k - 128) + 255) / 510), 0, 1023)      (floor towards -inf)
+ * i.e. the scale 1023/255 about the centres (128 -> 512), rounded half up: the convention of rgb_to_ycbcr at depth 10 and the one mi_batch_decode's q() inverts
+ * (bit replication would map neutral chroma 128 to 514).  Samples past the picture replicate its edge as for RGB.  Such an image is opaque: its fourth byte
+ * is not read, it never gets an alpha frame (mi_batch_uses_alpha 0), and the clean alpha mode leaves it as it is.  mi_batch_get_source, mi_batch_measure and
+ * mi_batch_decode* (MI_DECODED_SOURCE: through the exact inverse) then speak about the YCbCr the source held.
+ * The kind is host state per slot, set by whichever call last filled the slot: every upload / resize call above and below tags its slots MI_INPUT_RGB, the
+ * three *_ycbcr calls tag theirs MI_INPUT_YCBCR; it survives encodes and mi_batch_set_count as the slot's contents do.  mi_batch_set_input_kind is for HIP
+ * callers that write mi_batch_device_input themselves.  MI_INPUT_YCBCR is refused with MI_INVALID_ARGUMENT (by the set call and the *_ycbcr uploads alike)
+ * when the encoder's colour model is RGB (color_model 1) and when the batch has 4 channels and alpha_mode 2 (premultiplied: defined on RGB colours).
+ * mi_batch_set_input_kind: MI_INVALID_ARGUMENT as well for a range past the capacity, a kind not 0 or 1, a call between mi_batch_encode_async and mi_batch_wait.
+ * mi_batch_upload_jpeg_ycbcr: mi_batch_upload_jpeg (staging, H2D, IDCT, ordering, lifetimes) ending in jpeg_ycc_kernel: the slot's pixels are
+ * (Y, Cb', Cr') of a three-component YCbCr file, Cb' Cr' libjpeg's fancy-upsampled chroma -- exactly the triples whose 16.16 conversion mi_batch_upload_jpeg
+ * stores -- and (Y, 128, 128) of a grey file.  A file whose colour is RGB (Adobe transform 0, or components named R G B): MI_UNSUPPORTED; a size mismatch, an
+ * encode in flight or a refusal of the kind: MI_INVALID_ARGUMENT (checked first).
+ * mi_jpeg_coeffs_info: *color 0 grey, 1 YCbCr, 2 RGB; *hsub, *vsub luma samples per chroma sample (1, 1 for grey); any of the three may be NULL.
+ * mi_batch_upload_device_ycbcr: images [first, first + count) from mi_device_planes of the batch's own device, image k's planes at y + k * y_image_stride and
+ * cb / cr + k * c_image_stride; one launch on the batch's stream, ordered after src->after_stream, returns at once; the source must stay valid until the next
+ * mi_batch_wait.  Pixel (x, y) gets Y = y[y][x] and chroma upsampled as libjpeg's h2v1 / h2v2 "fancy" upsampling does, with c[j][i] the chroma sample of row j,
+ * column i, indices clamped to the plane (edges replicated), cw = ceil(w / hsub), i = floor(x / 2), j = floor(y / 2):
+ *   (1,1)  c[y][x]
+ *   (2,1)  cw <= 2: c[y][i];  else x even: (3 c[y][i] + c[y][i-1] + 1) >> 2,  x odd: (3 c[y][i] + c[y][i+1] + 2) >> 2
+ *   (2,2)  cw <= 2: c[j][i];  else with v(i) = 3 c[j][i] + c[j'][i], j' = j - 1 for even y and j + 1 for odd y:
+ *          x even: (3 v(i) + v(i-1) + 8) >> 4,  x odd: (3 v(i) + v(i+1) + 7) >> 4
+ * MI_INVALID_ARGUMENT: null b / src / y / cb, another (hsub, vsub), a row stride below the packed row (w for y; cw, or 2 cw interleaved, for chroma), a
+ * range past the capacity, a refusal of the kind, a call between mi_batch_encode_async and mi_batch_wait. */
+enum { MI_INPUT_RGB = 0, MI_INPUT_YCBCR = 1 };
+int  mi_batch_set_input_kind(mi_batch *b, int first, int count, int kind);
+int  mi_batch_input_kind(mi_batch *b, int index, int *kind);
+int  mi_batch_upload_jpeg_ycbcr(mi_batch *b, int index, const mi_jpeg_coeffs *c);
+int  mi_jpeg_coeffs_info(const mi_jpeg_coeffs *c, int *color, int *hsub, int *vsub);
+int  mi_batch_upload_device_ycbcr(mi_batch *b, int first, int count, const mi_device_planes *src);
 uint8_t *mi_batch_device_input(mi_batch *b, int index);
 int  mi_batch_read_input(mi_batch *b, int index, uint8_t *dst);
 int  mi_batch_upload_device(mi_batch *b, int first, int count, const mi_device_pixels *src);
