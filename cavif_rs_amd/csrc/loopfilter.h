@@ -351,7 +351,8 @@ __device__ __forceinline__ void cdef_strengths(const FrameDev *f, int plane, int
 
 // grid.x = sb index, grid.y = frame; 256 threads = 4 waves, wave w handles 8x8 blocks w, w+4, ...
 // Every strength index >= 1 of the fixed list has a non-zero primary strength, so the filter direction of a block is
-// its luma direction for all candidates and the 12 tap samples per pixel and plane are loaded once.
+// its luma direction for all candidates and the 12 tap samples per pixel and plane are loaded once (a list entry with primary code 0 and a
+// secondary strength -- direction 0 -- is searched on a slow path of its own, cdef_y / cdef_uv are honoured whatever they hold).
 // (three waves per SIMD: at four the packed strength search spills 40 VGPRs -- 0.13 ms faster, and 5.7 GB of scratch traffic per launch on top of the 2.7 GB the planes cost)
 __global__ __launch_bounds__(256, 3) void cdef_kernel(const FrameDev *__restrict__ frames, int write_final) {
   const FrameDev *f = frames + blockIdx.y;
@@ -374,6 +375,9 @@ __global__ __launch_bounds__(256, 3) void cdef_kernel(const FrameDev *__restrict
     // (< 1024 + 256) all fit 16 bits.  Same filter as cdef_apply_taps / cdef_pri_sum / cdef_sec_sum, sample for sample; a block's sums land on its own half's lanes.
     const int hs = lane >> 5, l32 = lane & 31, py2 = l32 >> 2, px2 = (l32 & 3) * 2;
     const int st = f->stride, fw = f->mi_cols * 4, fh = f->mi_rows * 4;
+    int dir0_planes = 0;                          // bit 0 / 1: the luma / chroma list holds an entry with primary code 0 and a secondary strength (the fixed list: neither)
+    for (int idx = 0; idx < 8; idx++) dir0_planes |= (int)((f->cdef_y[idx] >> 2) == 0 && (f->cdef_y[idx] & 3) != 0) | ((int)((f->cdef_uv[idx] >> 2) == 0 && (f->cdef_uv[idx] & 3) != 0) << 1);
+    dir0_planes = uni32(dir0_planes);
     for (int it = 0; it < 8; it++) {
       const int bA = wave + 8 * it, bB = bA + 4;
       const int rA = sr * 16 + (bA >> 3) * 2, cA = sc * 16 + (bA & 7) * 2, rB = sr * 16 + (bB >> 3) * 2, cB = sc * 16 + (bB & 7) * 2;
@@ -428,6 +432,20 @@ __global__ __launch_bounds__(256, 3) void cdef_kernel(const FrameDev *__restrict
         const bool psy = p == 0 && !f->tune_psnr;
         uint32_t my_sse = 0, my_s = 0, my_q = 0;
         int ssec = -1; pk16 ssum = pk_splat(0);
+        // books candidate idx's filtered pair v: the block's SSE (and sums, for the psychovisual distortion) land on lane idx of the block's half
+        auto book = [&](int idx, pk16 v) {
+          const pk16 d = v - sv;
+          int e = pk_dot2(d, d, 0);                                                     // 32 lanes x 2 samples x 1023^2 < 2^26 per block
+          e = half_sum_i32(e);
+          const uint32_t eA = (uint32_t)__builtin_amdgcn_readlane(e, 31), eB = (uint32_t)__builtin_amdgcn_readlane(e, 63);
+          if (l32 == idx) my_sse = hs ? eB : eA;
+          if (psy) {
+            int s1 = half_sum_i32(pk_dot2(v, pk_splat(1), 0)), s2 = half_sum_i32(pk_dot2(v, v, 0));
+            const uint32_t s1A = (uint32_t)__builtin_amdgcn_readlane(s1, 31), s1B = (uint32_t)__builtin_amdgcn_readlane(s1, 63);
+            const uint32_t s2A = (uint32_t)__builtin_amdgcn_readlane(s2, 31), s2B = (uint32_t)__builtin_amdgcn_readlane(s2, 63);
+            if (l32 == idx) { my_s = hs ? s1B : s1A; my_q = hs ? s2B : s2A; }
+          }
+        };
 #pragma unroll
         for (int idx = 0; idx < 8; idx++) {
           int priA, priB, sec, damping, sec2, damping2;
@@ -457,17 +475,26 @@ __global__ __launch_bounds__(256, 3) void cdef_kernel(const FrameDev *__restrict
             }
           }
           // cdef_finish: x + ((8 + sum - (sum < 0)) >> 4), clamped to the taps' range (no strength at all leaves x: sum = 0, mn <= x <= mx)
-          const pk16 v = pk_min(pk_max(un + ((pk_splat(8) + sum + (sum >> pk_splat(15))) >> pk_splat(4)), mn), mx);
-          const pk16 d = v - sv;
-          int e = pk_dot2(d, d, 0);                                                     // 32 lanes x 2 samples x 1023^2 < 2^26 per block
-          e = half_sum_i32(e);
-          const uint32_t eA = (uint32_t)__builtin_amdgcn_readlane(e, 31), eB = (uint32_t)__builtin_amdgcn_readlane(e, 63);
-          if (l32 == idx) my_sse = hs ? eB : eA;
-          if (psy) {
-            int s1 = half_sum_i32(pk_dot2(v, pk_splat(1), 0)), s2 = half_sum_i32(pk_dot2(v, v, 0));
-            const uint32_t s1A = (uint32_t)__builtin_amdgcn_readlane(s1, 31), s1B = (uint32_t)__builtin_amdgcn_readlane(s1, 63);
-            const uint32_t s2A = (uint32_t)__builtin_amdgcn_readlane(s2, 31), s2B = (uint32_t)__builtin_amdgcn_readlane(s2, 63);
-            if (l32 == idx) { my_s = hs ? s1B : s1A; my_q = hs ? s2B : s2A; }
+          book(idx, pk_min(pk_max(un + ((pk_splat(8) + sum + (sum >> pk_splat(15))) >> pk_splat(4)), mn), mx));
+        }
+        // A strength with primary code 0 and a secondary strength is filtered along direction 0, not the block's (spec 7.15.1: dir = priStr == 0 ? 0 : yDir, before the
+        // variance adjustment).  The fixed list has none, so this never runs for the product's frames: such candidates are filtered again, sample by sample, and rebooked.
+        if ((dir0_planes >> (p != 0)) & 1) {
+#pragma unroll 1
+          for (int idx = 0; idx < 8; idx++) {
+            const int code = p == 0 ? f->cdef_y[idx] : f->cdef_uv[idx];
+            if ((code >> 2) != 0 || (code & 3) == 0) continue;
+            int pri, sec, damping;
+            cdef_strengths(f, p, idx, 0, &pri, &sec, &damping);
+            uint32_t pair = 0;
+#pragma unroll 1
+            for (int k = 0; k < 2; k++) {
+              int t[12];
+              const int xv = in[y * st + x + k];
+              cdef_load_taps(f, in, y, x + k, 0, xv, t, false);
+              pair |= (uint32_t)cdef_apply_taps(xv, t, 0, sec, damping, cs) << (16 * k);
+            }
+            book(idx, pk_from_u32(pair));
           }
         }
         // Tune::Psychovisual (rav1e rdo_loop_plane_error): luma through the cdef-dist kernel of the 8x8 block, chroma SSE x activity
@@ -494,14 +521,15 @@ __global__ __launch_bounds__(256, 3) void cdef_kernel(const FrameDev *__restrict
     const int r = sr * 16 + (b >> 3) * 2, c = sc * 16 + (b & 7) * 2;
     if (r >= f->mi_rows || c >= f->mi_cols) continue;
     const int sk = f->m_skip[r * ms + c] & f->m_skip[(r + 1) * ms + c] & f->m_skip[r * ms + c + 1] & f->m_skip[(r + 1) * ms + c + 1] & 1;      // bit 0 of the map (the rest is the segment id)
-    const int filt = best > 0 && !sk;                    // index 0 of the list is (0, 0): nothing to filter
+    const int filt = best >= 0 && !sk;                   // (index 0 of the fixed list is (0, 0): nothing to filter, found below)
     const int ydir = filt ? dirvar[b][0] : 0, var = filt ? dirvar[b][1] : 0;
     for (int p = 0; p < f->np; p++) {
       const int y = r * 4 + py_l, x = c * 4 + px_l;
       int v = f->rec[p][(size_t)y * f->stride + x];
       if (filt) {
         int pri, sec, damping; cdef_strengths(f, p, best, var, &pri, &sec, &damping);
-        if (pri || sec) { int tap[12]; cdef_load_taps(f, f->rec[p], y, x, ydir, v, tap, r * 4 >= 2 && c * 4 >= 2 && r * 4 + 10 <= f->mi_rows * 4 && c * 4 + 10 <= f->mi_cols * 4); v = cdef_apply_taps(v, tap, pri, sec, damping, cs); }
+        const int pdir = ((p == 0 ? f->cdef_y[best] : f->cdef_uv[best]) >> 2) ? ydir : 0;      // primary code 0: direction 0 (spec 7.15.1)
+        if (pri || sec) { int tap[12]; cdef_load_taps(f, f->rec[p], y, x, pdir, v, tap, r * 4 >= 2 && c * 4 >= 2 && r * 4 + 10 <= f->mi_rows * 4 && c * 4 + 10 <= f->mi_cols * 4); v = cdef_apply_taps(v, tap, pri, sec, damping, cs); }
       }
       f->fin[p][(size_t)y * f->stride + x] = (uint16_t)v;
     }

@@ -167,11 +167,17 @@ void av1o_txb_ctx(const Av1oFrame *f, const TileB *t, int plane, int r4, int c4,
 void *av1o_live_open(Av1oFrame *f, int tile_row, int tile_col); void av1o_live_sb(void *w, int r, int c, uint32_t *cost_out); void av1o_live_close(void *w);   /* AV1O_LIVE_CDF experiment */
 /* loop filters (spec 7.14, 7.15) */
 void av1o_deblock_frame(Av1oFrame *f);
+void av1o_deblock_search(Av1oFrame *f, int64_t tally[3][2][64]);   /* prefix-summed SSE change per (plane, pass, level) */
 void av1o_cdef_search_and_apply(Av1oFrame *f);
 /* loop restoration (spec 7.17) */
 void av1o_lr_search_and_apply(Av1oFrame *f);
 int  av1o_lr_units(int size);
 void av1o_write_lr_sb(Av1oFrame *f, int r, int c, int ref_xqd[3][2], void (*sym)(void *, int, int), void (*lit)(void *, uint32_t, int), void *u);
+
+/* tests only: the three stages above on a caller-supplied frame (av1o_test_filters.c) */
+int av1o_test_loop_filters(const int *par, int64_t rdmult, uint16_t *const src[3], uint16_t *const rec[3], uint16_t *const fin[3], uint16_t *const lrp[3],
+                           const uint8_t *m_txsize, const uint8_t *m_bsize, const uint8_t *m_skip, int64_t *tally, int *lf_level, int8_t *cdef_idx,
+                           uint32_t *act, uint32_t *svar8, uint8_t *lr_type, uint8_t *lr_set, int8_t *lr_xqd);
 
 /* headers */
 size_t av1o_write_obus(Av1oFrame *f, uint8_t **tile_data, size_t *tile_len, uint8_t **out);

@@ -1,61 +1,24 @@
 """Build and call tests/kernels/k4_coder_harness.hip (the entropy kernel's coder on given record streams) -- test infrastructure only.
 
-Two builds, each stamped with a digest of its sources and flags and rebuilt when stale: hipcc with the product's flags (the GPU library) and g++ with the SIMT
-emulator's shim (tests/emu/, the same command as tests/emu/__init__.py).  `run` pads every output buffer with a guard zone of sentinels behind the capacity it
+Two builds (tests/helpers/kernel_build.py): hipcc with the product's flags (the GPU library) and g++ with the SIMT emulator's shim.  `run` pads every output buffer with a guard zone of sentinels behind the capacity it
 passes, and reports whether the zones came back untouched."""
 import ctypes as C
-import hashlib
 import os
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-KDIR = os.path.join(ROOT, 'tests', 'kernels')
-SRC = os.path.join(KDIR, 'k4_coder_harness.hip')
-OUT = os.path.join(KDIR, '_build')
-GPU_LIB = os.path.join(OUT, 'libk4_harness.so')
-EMU_LIB = os.path.join(OUT, 'libk4_harness_emu.so')
+from tests.helpers import kernel_build
+
+ROOT = kernel_build.ROOT
+KDIR = kernel_build.KDIR
+SRC = kernel_build.source('k4_coder_harness.hip')
+OUT = kernel_build.OUT
+GPU_LIB = kernel_build.target('k4_harness', emu=False)
+EMU_LIB = kernel_build.target('k4_harness', emu=True)
 GUARD = 64                       # entries of sentinel behind every capacity
 SENT8, SENT16 = 0xA7, 0xBEEF
 
 
-def _sources(emu):
-    csrc = os.path.join(ROOT, 'cavif_rs_amd', 'csrc')
-    srcs = [SRC] + [os.path.join(csrc, f) for f in sorted(os.listdir(csrc))]
-    if emu:
-        srcs += [os.path.join(ROOT, 'tests', 'emu', 'emu_runtime.cpp'), os.path.join(ROOT, 'tests', 'emu', 'include', 'hip', 'hip_runtime.h')]
-    return srcs
-
-
-def _command(emu, target):
-    if emu:
-        return ['g++', '-O2', '-g', '-rdynamic', '-fno-extern-tls-init', '-std=c++17', '-ffp-contract=off', '-fPIC', '-shared', '-w',
-                '-I', os.path.join(ROOT, 'tests', 'emu', 'include'), '-I', os.path.join(ROOT, 'include'), '-x', 'c++',
-                SRC, os.path.join(ROOT, 'tests', 'emu', 'emu_runtime.cpp'), '-o', target, '-lz', '-lpthread', '-ldl']
-    import __graft_entry__
-    hipcc = 'hipcc' if subprocess.call(['which', 'hipcc'], stdout=subprocess.DEVNULL) == 0 else '/opt/rocm/bin/hipcc'
-    return [hipcc] + __graft_entry__.HIPCC_FLAGS + ['-o', target, SRC]
-
-
-def _digest(cmd, srcs):
-    h = hashlib.sha256(' '.join(os.path.relpath(c, ROOT) if c.startswith(ROOT) else c for c in cmd).encode())
-    for s in srcs:
-        with open(s, 'rb') as fh:
-            h.update(os.path.basename(s).encode() + b'\0' + fh.read())
-    return h.hexdigest()
-
-
 def build(emu, force=False):
-    target = EMU_LIB if emu else GPU_LIB
-    cmd = _command(emu, target)
-    want = _digest(cmd, _sources(emu))
-    stamp = target + '.stamp'
-    have = open(stamp).read().strip() if os.path.exists(stamp) and os.path.exists(target) else ''
-    if force or have != want:
-        os.makedirs(OUT, exist_ok=True)
-        subprocess.check_call(cmd)
-        with open(stamp, 'w') as fh:
-            fh.write(want + '\n')
-    return target
+    return kernel_build.build(SRC, EMU_LIB if emu else GPU_LIB, emu, force=force)
 
 
 def build_all(force=False):
