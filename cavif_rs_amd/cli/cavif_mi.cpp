@@ -1,12 +1,14 @@
 // cavif_mi -- the cavif command line (src/main.rs) on top of libmi_avif.so: same flags, path rules and report line;
 // the rayon fan-out over files (src/main.rs:223) becomes mi_ravif_encode_batch (one host thread per MI355X).
-//   cavif_mi [-Q n] [-s n] [-j n] [-f] [-o path] [-q] [--dirty-alpha] [--color ycbcr|rgb] [--depth 8|10|auto] [--jpeg-ycbcr] IMAGES...
+//   cavif_mi [-Q n] [-s n] [-j n] [-f] [-o path] [-q] [--dirty-alpha] [--color ycbcr|rgb] [--depth 8|10|auto] [--jpeg-ycbcr] [--deep-png] IMAGES...
 // Input: PNG and baseline / progressive 8-bit JPEG, told apart by their first bytes as load_image does.  A loader thread does the serial half of the
 // decode -- inflate of a PNG (mi_png_parse), Huffman decoding of a JPEG (mi_jpeg_parse) -- and hands scanlines or coefficients to the encoder, which
 // finishes the picture on the GPU inside the batch that encodes it (mi_ravif_encode_sources): the loaders never touch a device.  Differences, deliberate:
 // `--devices a,b,..` selects HIP devices (default: all), and there is no CPU fallback -- without a GPU every file fails loudly.  `--jpeg-ycbcr` (off by
 // default) codes a grey or YCbCr JPEG from the file's own Y, Cb, Cr instead of the RGB pixels a decoder makes of them; RGB-coloured JPEG files, PNG files and
-// everything under --color rgb go as without it.
+// everything under --color rgb go as without it.  `--deep-png` (off by default) codes a PNG file of bit depth 16 from all 16 bits of its samples instead of
+// their high bytes; a file with an alpha channel or tRNS goes that way only together with --dirty-alpha (the alpha cleaner is defined on 8-bit samples), every
+// other file as without the flag.
 #include <sched.h>
 #include <sys/stat.h>
 #include <cerrno>
@@ -87,7 +89,7 @@ int host_threads() {
 }
 int usage(const char *msg) {
   fprintf(stderr, "error: %s\nusage: cavif_mi [-Q quality 1-100] [-s speed 1-10] [-j threads] [-f|--overwrite] [-o path] [-q] [--dirty-alpha]\n"
-                  "                [--color ycbcr|rgb] [--depth 8|10|auto] [--devices 0,1,..] [--rdo-passes 1|2] [--jpeg-ycbcr] IMAGES...   (\"-\" = stdin/stdout)\n", msg);
+                  "                [--color ycbcr|rgb] [--depth 8|10|auto] [--devices 0,1,..] [--rdo-passes 1|2] [--jpeg-ycbcr] [--deep-png] IMAGES...   (\"-\" = stdin/stdout)\n", msg);
   return 1;
 }
 
@@ -132,7 +134,7 @@ int main(int argc, char **argv) {
     }
   }
   float quality = 80.f; int speed = 4, threads = 0, depth = 0, color_model = 0, rdo_passes = 1;
-  bool overwrite = false, quiet = false, dirty_alpha = false, have_output = false, output_stdio = false, jpeg_ycbcr = false;
+  bool overwrite = false, quiet = false, dirty_alpha = false, have_output = false, output_stdio = false, jpeg_ycbcr = false, deep_png = false;
   std::string output; std::vector<std::string> images; std::vector<int> devices;
   // clap syntax (src/main.rs:45-110): --name value, --name=value, -n value, -nvalue, -n=value, combined short flags (-fq)
   std::vector<std::string> args;
@@ -168,6 +170,7 @@ int main(int argc, char **argv) {
     else if (a == "-q" || a == "--quiet") quiet = true;
     else if (a == "--dirty-alpha") dirty_alpha = true;
     else if (a == "--jpeg-ycbcr") jpeg_ycbcr = true;                                                                                                   // extension: not a cavif flag
+    else if (a == "--deep-png") deep_png = true;                                                                                                       // extension: not a cavif flag
     else if (a == "--color") { const std::string v = value("--color"); if (v == "ycbcr") color_model = 0; else if (v == "rgb") color_model = 1; else return usage("bad color type"); }
     else if (a == "--rdo-passes") { rdo_passes = atoi(value("--rdo-passes")); if (rdo_passes < 1 || rdo_passes > 2) return usage("bad --rdo-passes (1 or 2)"); }   // extension: not a cavif flag
     else if (a == "--depth") { const std::string v = value("--depth"); depth = v == "8" ? 8 : v == "10" ? 10 : 0; if (v != "8" && v != "10" && v != "auto") return usage("bad depth"); }
@@ -205,7 +208,7 @@ int main(int argc, char **argv) {
   enc.threads = threads > 0 ? threads : host_threads();
 
   // load + decide output paths (process(), :169-200); failures are collected per file and reported at the end
-  struct Job { std::string in_name, out_path; bool out_stdio = false; mi_jpeg_coeffs *jpeg = nullptr; mi_png_scanlines *png = nullptr; uint32_t w = 0, h = 0; bool ycbcr = false; std::string error; };
+  struct Job { std::string in_name, out_path; bool out_stdio = false; mi_jpeg_coeffs *jpeg = nullptr; mi_png_scanlines *png = nullptr; uint32_t w = 0, h = 0; bool ycbcr = false, deep = false; std::string error; };
   std::vector<Job> jobs(files.size());
   // the reference loads inside files.into_par_iter() (src/main.rs:223): file reads + PNG inflate / JPEG entropy decodes fan out over the host cores; a JPEG leaves
   // its loader as coefficients (dequantisation, IDCT, upsampling and colour run on the device that encodes it), a PNG as filtered scanlines (unfiltered and
@@ -218,9 +221,11 @@ int main(int argc, char **argv) {
     else { FILE *f = fopen(in.path.c_str(), "rb"); if (!f || !read_all(f, data)) j.error = "Unable to read input image " + in.path + ": " + strerror(errno); if (f) fclose(f); }
     if (j.error.empty()) {
       static const uint8_t png_sig[8] = { 0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A };
+      int png_alpha = 0;
       const bool is_jpeg = data.size() >= 2 && data[0] == 0xFF && data[1] == 0xD8, is_png = data.size() >= 8 && !memcmp(data.data(), png_sig, 8);
-      const int st = is_jpeg ? mi_jpeg_parse(data.data(), data.size(), &j.jpeg, &j.w, &j.h) : is_png ? mi_png_parse(data.data(), data.size(), &j.png, &j.w, &j.h, nullptr) : (int)MI_UNSUPPORTED;
-      int color = 2;
+      const int st = is_jpeg ? mi_jpeg_parse(data.data(), data.size(), &j.jpeg, &j.w, &j.h) : is_png ? mi_png_parse(data.data(), data.size(), &j.png, &j.w, &j.h, &png_alpha) : (int)MI_UNSUPPORTED;
+      int color = 2, png_depth = 0;
+      if (!st && is_png && deep_png && mi_png_scanlines_info(j.png, nullptr, &png_depth) == MI_OK) j.deep = png_depth == 16 && (!png_alpha || dirty_alpha);
       if (!st && is_jpeg && jpeg_ycbcr && color_model == 0 && mi_jpeg_coeffs_info(j.jpeg, &color, nullptr, nullptr) == MI_OK) j.ycbcr = color != 2;
       if (st) j.error = st == MI_UNSUPPORTED ? "unsupported image format (this build reads PNG and baseline/progressive 8-bit JPEG)" :
                         st == MI_NO_DEVICE ? "no HIP device (this encoder has no CPU fallback)" : "corrupt image data";
@@ -261,7 +266,7 @@ int main(int argc, char **argv) {
     { std::unique_lock<std::mutex> lk(*c->mu); c->cv->wait(lk, [&] { return (*c->loaded)[i] != 0; }); }
     const Job &j = (*c->jobs)[i];
     if (!j.error.empty()) return MI_INVALID_ARGUMENT;           // reported from the job's own message below
-    src->kind = j.jpeg ? (j.ycbcr ? 3 : 1) : j.png ? 2 : 0; src->jpeg = j.jpeg; src->png = j.png;
+    src->kind = j.jpeg ? (j.ycbcr ? 3 : 1) : j.png ? (j.deep ? 4 : 2) : 0; src->jpeg = j.jpeg; src->png = j.png;
     mi_image_desc *d = &src->desc;
     d->pixels = nullptr; d->width = j.w; d->height = j.h; d->stride_px = j.w; d->channels = 4;     // a JPEG or PNG into an RGBA slot: the pixels load_rgba gives it
     return MI_OK;

@@ -23,6 +23,7 @@
 #include "dev_resample.h"
 #include "dev_quality.h"
 #include "dev_decoded.h"
+#include "dev_deep.h"
 #include "host_frames.h"
 
 // The product library reads no environment variables; probe builds (tools/) get MI_AVIF_TIMING=1 (-DMI_TUNING_KNOBS: host-side timeline on stderr)
@@ -78,10 +79,30 @@ struct mi_batch {
   // what the bytes of each input slot mean (MI_INPUT_RGB / MI_INPUT_YCBCR): host state, set by whichever call last filled the slot, kept across encodes and
   // mi_batch_set_count like the slot's contents
   std::vector<uint8_t> kinds;
+  // deep input: the slots of kind MI_INPUT_RGB16, cap * w*h*channels uint16 samples laid out like d_pixels; made by the first call that needs
+  // them (under staging_mu), never by a batch that sees no 16-bit source
+  DevBuf<uint16_t> d_pixels16; size_t deep_bytes = 0;
 };
 static void batch_tag(mi_batch *b, int first, int count, int kind) { std::fill(b->kinds.begin() + first, b->kinds.begin() + first + count, (uint8_t)kind); }
 // MI_INPUT_YCBCR needs the YCbCr colour model (the planes are the slot's bytes) and, in a 4-channel batch, an alpha mode that leaves opaque pixels alone
 static bool batch_takes_ycbcr(const mi_batch *b) { return b->enc.color_model != 1 && !(b->channels == 4 && b->enc.alpha_mode == 2); }
+// MI_INPUT_RGB16: the dirty-alpha cleaner and the premultiply branch are defined on 8-bit samples, so a 4-channel batch takes a deep source with an alpha channel
+// under UnassociatedDirty alone and an opaque one (A = 65535: the cleaner skips it as it skips MI_INPUT_YCBCR) under both unassociated modes; a 3-channel batch takes 3 channels
+static bool batch_takes_deep(const mi_batch *b, int src_channels) {
+  if (src_channels != 3 && src_channels != 4) return false;
+  if (b->channels == 3) return src_channels == 3;
+  return src_channels == 4 ? b->enc.alpha_mode == 0 : b->enc.alpha_mode != 2;
+}
+// the deep slots, made on first use; nullptr = could not be allocated
+static uint16_t *batch_deep(mi_batch *b) {
+  std::lock_guard<std::mutex> lk(b->staging_mu);
+  if (!b->d_pixels16.get()) {
+    (void)hipSetDevice(b->device);
+    if (b->d_pixels16.alloc(b->pixel_bytes) != hipSuccess) return nullptr;
+    b->deep_bytes = b->pixel_bytes * sizeof(uint16_t);
+  }
+  return b->d_pixels16.get();
+}
 static_assert(sizeof(QualityRec) <= MI_FRAME_RECORD_BYTES, "FrameSet reserves MI_FRAME_RECORD_BYTES per (frame, plane)");
 
 static void batch_plan(mi_batch *b) {
@@ -202,8 +223,15 @@ int mi_batch_upload_async(mi_batch *b, int first, int count) {
   return MI_OK;
 }
 int mi_batch_set_input_kind(mi_batch *b, int first, int count, int kind) {
-  if (!b || b->in_flight || first < 0 || count < 1 || first > b->cap - count || (kind != MI_INPUT_RGB && kind != MI_INPUT_YCBCR)) return MI_INVALID_ARGUMENT;
+  if (!b || b->in_flight || first < 0 || count < 1 || first > b->cap - count || (kind != MI_INPUT_RGB && kind != MI_INPUT_YCBCR && kind != MI_INPUT_RGB16)) return MI_INVALID_ARGUMENT;
   if (kind == MI_INPUT_YCBCR && !batch_takes_ycbcr(b)) return MI_INVALID_ARGUMENT;
+  // kind 2 tags what a HIP caller wrote through mi_batch_device_input16, the call that makes the deep slots: a batch without them has nothing to tag (and the
+  // set call allocates nothing); the slot may hold any alpha
+  if (kind == MI_INPUT_RGB16) {
+    if (!batch_takes_deep(b, b->channels)) return MI_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lk(b->staging_mu);
+    if (!b->d_pixels16.get()) return MI_INVALID_ARGUMENT;
+  }
   batch_tag(b, first, count, kind);
   return MI_OK;
 }
@@ -267,7 +295,7 @@ int mi_batch_encode_async(mi_batch *b) {
     HIP_OK(hipMemsetAsync(d_alpha_acc, 0, sizeof(unsigned long long) * 4 * b->n, s));
     const dim3 g((b->w + 255) / 256, b->h), blk(256);
     for (int i = 0; i < b->n; i++) {
-      if (b->kinds[i] == MI_INPUT_YCBCR) continue;              // opaque: the passes would be copies; the front end reads the slot itself
+      if (b->kinds[i] != MI_INPUT_RGB) continue;                // opaque (YCbCr, or a deep image with A = 65535): the passes would be copies; the front end reads the slot itself
       const uint8_t *in = d_pixels + (size_t)i * b->w * b->h * 4; uint8_t *outp = d_clean + (size_t)i * b->w * b->h * 4;
       hipLaunchKernelGGL(alpha_scan_kernel, g, blk, 0, s, in, (int)b->w, (int)b->h, d_alpha_acc + 4 * i);
       hipLaunchKernelGGL(alpha_rewrite_kernel, g, blk, 0, s, in, d_clean_tmp, (int)b->w, (int)b->h, d_alpha_acc + 4 * i, 0);
@@ -279,6 +307,17 @@ int mi_batch_encode_async(mi_batch *b) {
   for (int i = 0; i < b->n; i++) {
     FramePlan &p = b->fs.frames[i];
     uint16_t *alpha_stage = b->channels == 4 ? p.dev.fin[0] : nullptr;      // fin[0] is free until CDEF runs
+    if (b->kinds[i] == MI_INPUT_RGB16) {                        // its deep slot, through the 16-bit front end
+      const uint16_t *deep = b->d_pixels16.get();
+      if (!deep) return MI_INVALID_ARGUMENT;
+      deep += (size_t)i * b->w * b->h * b->channels;
+      const FrontDeepParams dp{ b->depth, b->enc.color_model };
+      if (b->channels == 4) hipLaunchKernelGGL((frontend_deep_kernel<4>), dim3((p.pw + 255) / 256, p.ph), dim3(256), 0, s, deep, (int)b->w, (int)b->h, dp,
+                                               p.dev.src[0], p.dev.src[1], p.dev.src[2], alpha_stage, p.pw, p.ph, d_alpha_flags + i);
+      else hipLaunchKernelGGL((frontend_deep_kernel<3>), dim3((p.pw + 255) / 256, p.ph), dim3(256), 0, s, deep, (int)b->w, (int)b->h, dp,
+                              p.dev.src[0], p.dev.src[1], p.dev.src[2], alpha_stage, p.pw, p.ph, d_alpha_flags + i);
+      continue;
+    }
     fp.ycc = b->kinds[i] == MI_INPUT_YCBCR;
     hipLaunchKernelGGL(frontend_kernel, dim3((p.pw + 255) / 256, p.ph), dim3(256), 0, s,
                        (fp.ycc ? d_pixels : front_src) + (size_t)i * b->w * b->h * b->channels, (int)b->w, (int)b->h, (int)b->w, fp,
@@ -471,7 +510,7 @@ static PoolKey pool_key(const mi_ravif_encoder *e, int cap, uint32_t w, uint32_t
 }
 static std::mutex g_pool_mu;
 static std::vector<std::pair<PoolKey, mi_batch *>> g_pool;          // oldest first; never destroyed at process exit (the runtime may be gone by then)
-static size_t batch_footprint(const mi_batch *b) { return b->fs.arena_bytes + b->fs.aux_bytes + 3 * b->pixel_bytes + b->packed_cap + b->h_jpeg_cap + b->d_jpeg_cap + b->d_jpeg_planes_cap + b->h_png_cap + b->d_png_cap + b->h_rs_cap + b->d_rs_cap + b->d_rs_scratch_cap + b->h_quality_bytes + b->d_decoded_cap; }     // (the quality records themselves are part of the arena)
+static size_t batch_footprint(const mi_batch *b) { return b->fs.arena_bytes + b->fs.aux_bytes + 3 * b->pixel_bytes + b->packed_cap + b->h_jpeg_cap + b->d_jpeg_cap + b->d_jpeg_planes_cap + b->h_png_cap + b->d_png_cap + b->h_rs_cap + b->d_rs_cap + b->d_rs_scratch_cap + b->h_quality_bytes + b->d_decoded_cap + b->deep_bytes; }     // (the quality records themselves are part of the arena)
 static constexpr size_t MI_POOL_MAX_ITEMS = 8, MI_POOL_MAX_BYTES = (size_t)32 << 30;     // what the one-call entry points may keep between calls (mi_release_cached() frees it)
 
 static mi_batch *pool_acquire(const mi_ravif_encoder *e, int cap, uint32_t w, uint32_t h, int channels) {
@@ -773,6 +812,78 @@ int mi_batch_upload_device_ycbcr(mi_batch *b, int first, int count, const mi_dev
   return MI_OK;
 }
 
+// ---- deep input: 16-bit sources into the deep slots (dev_deep.h) ----
+uint16_t *mi_batch_device_input16(mi_batch *b, int index) {
+  if (!b || index < 0 || index >= b->cap) return nullptr;
+  uint16_t *const deep = batch_deep(b);
+  return deep ? deep + (size_t)index * b->w * b->h * b->channels : nullptr;
+}
+int mi_batch_read_input16(mi_batch *b, int index, uint16_t *dst) {
+  if (!b || !dst || index < 0 || index >= b->cap) return MI_INVALID_ARGUMENT;
+  const uint16_t *const src = mi_batch_device_input16(b, index);
+  if (!src) return MI_ENCODING_ERROR;
+  (void)hipSetDevice(b->device);
+  HIP_OK(hipStreamSynchronize(b->stream));
+  HIP_OK(hipMemcpy(dst, src, (size_t)b->w * b->h * b->channels * sizeof(uint16_t), hipMemcpyDeviceToHost));
+  return MI_OK;
+}
+size_t mi_batch_footprint(const mi_batch *b) { return b ? batch_footprint(b) : 0; }
+
+// images [first, first + count) from uint16 pictures in the memory of the batch's device: one ingest16_kernel launch on the batch's stream, after whatever
+// src->after_stream holds at this moment; the slots are tagged MI_INPUT_RGB16.  Every check comes before the deep slots are made: a refused call allocates nothing.
+int mi_batch_upload_device16(mi_batch *b, int first, int count, const mi_device_pixels16 *src) {
+  if (!b || !src || !src->dev || b->in_flight || first < 0 || count < 1 || first > b->cap - count) return MI_INVALID_ARGUMENT;
+  if ((src->layout != 0 && src->layout != 1) || !batch_takes_deep(b, src->channels)) return MI_INVALID_ARGUMENT;   // alpha is never dropped; the alpha rules of the kind
+  if (src->bits < 8 || src->bits > 16 || (src->msb_aligned != 0 && src->msb_aligned != 1)) return MI_INVALID_ARGUMENT;
+  if (((uintptr_t)src->dev | src->row_stride | src->pixel_or_plane_stride | src->image_stride) & 1) return MI_INVALID_ARGUMENT;   // uint16 samples
+  Ingest16Src s;
+  s.base = (const uint8_t *)src->dev; s.w = b->w; s.h = b->h; s.layout = src->layout; s.channels = src->channels; s.bits = src->bits; s.msb_aligned = src->msb_aligned;
+  const size_t packed_row = (size_t)b->w * (s.layout == 0 ? s.channels : 1) * 2;
+  s.row_stride = src->row_stride ? src->row_stride : packed_row;
+  s.inner_stride = src->pixel_or_plane_stride ? src->pixel_or_plane_stride : s.layout == 0 ? (size_t)s.channels * 2 : s.row_stride * b->h;
+  s.image_stride = src->image_stride ? src->image_stride : s.layout == 0 ? s.row_stride * b->h : s.inner_stride * s.channels;
+  if (s.row_stride < packed_row || s.inner_stride < (s.layout == 0 ? (size_t)s.channels * 2 : (size_t)b->w * 2)) return MI_INVALID_ARGUMENT;
+  uint16_t *const slots = mi_batch_device_input16(b, first);
+  if (!slots) return MI_ENCODING_ERROR;
+  (void)hipSetDevice(b->device);
+  if (src->after_stream) {
+    if (!b->ev_src) HIP_OK(hipEventCreateWithFlags(&b->ev_src, hipEventDisableTiming));
+    HIP_OK(hipEventRecord(b->ev_src, (hipStream_t)src->after_stream));
+    HIP_OK(hipStreamWaitEvent(b->stream, b->ev_src, 0));
+  }
+  const dim3 grid(((b->w + 3) / 4 + 63) / 64, b->h, (unsigned)count);
+  if (b->channels == 4) hipLaunchKernelGGL((ingest16_kernel<4>), grid, dim3(64), 0, b->stream, s, slots);
+  else hipLaunchKernelGGL((ingest16_kernel<3>), grid, dim3(64), 0, b->stream, s, slots);
+  HIP_OK(hipGetLastError());
+  batch_tag(b, first, count, MI_INPUT_RGB16);
+  return MI_OK;
+}
+// one image of full-scale uint16 host pixels into the deep slot of `index`: a 2-D copy on the batch's stream (3 channels into a 4-channel batch: through a host
+// copy that carries A = 65535), then the stream is waited for.  No pinned staging of its own.
+int mi_batch_upload16(mi_batch *b, int index, const uint16_t *pixels, size_t stride_px, int channels) {
+  if (!b || !pixels || b->in_flight || index < 0 || index >= b->cap || !batch_takes_deep(b, channels)) return MI_INVALID_ARGUMENT;
+  if (stride_px == 0) stride_px = b->w;
+  if (stride_px < b->w) return MI_INVALID_ARGUMENT;
+  uint16_t *const slot = mi_batch_device_input16(b, index);
+  if (!slot) return MI_ENCODING_ERROR;
+  (void)hipSetDevice(b->device);
+  const size_t row = (size_t)b->w * b->channels * sizeof(uint16_t);
+  try {                                                       // nothing may unwind through the C ABI
+    std::vector<uint16_t> wide;
+    if (channels != b->channels) {
+      wide.resize((size_t)b->w * b->h * 4);
+      for (uint32_t y = 0; y < b->h; y++) for (uint32_t x = 0; x < b->w; x++) {
+        const uint16_t *q = pixels + ((size_t)y * stride_px + x) * 3; uint16_t *o = wide.data() + ((size_t)y * b->w + x) * 4;
+        o[0] = q[0]; o[1] = q[1]; o[2] = q[2]; o[3] = 65535;
+      }
+      HIP_OK(hipMemcpyAsync(slot, wide.data(), row * b->h, hipMemcpyHostToDevice, b->stream));
+    } else HIP_OK(hipMemcpy2DAsync(slot, row, pixels, stride_px * channels * sizeof(uint16_t), row, b->h, hipMemcpyHostToDevice, b->stream));
+    HIP_OK(hipStreamSynchronize(b->stream));
+  } catch (const std::exception &) { return MI_ENCODING_ERROR; }
+  batch_tag(b, index, 1, MI_INPUT_RGB16);
+  return MI_OK;
+}
+
 // ---- decoded pixels of the last completed encode (dev_decoded.h) ----
 int mi_batch_uses_alpha(mi_batch *b, int index, int *uses_alpha) {
   if (!b || !uses_alpha || b->in_flight || !b->encoded || index < 0 || index >= b->n) return MI_INVALID_ARGUMENT;
@@ -918,7 +1029,7 @@ static bool batch_reserve_png(mi_batch *b, size_t bytes) {
 // png_unfilter_kernel (one workgroup per pass that has a filtered row, all images in one launch) and png_expand_kernel on the batch's stream, no sync.
 // The staging keeps the calls since the stream last drained; when the next one does not fit, the stream is waited for and the staging starts over, grown to the call.
 // (the body, shared with mi_batch_resize_png: `count` checked files of w x h into packed pictures of `channels` channels, back to back from `slots` on)
-static int batch_png_expand(mi_batch *b, int count, const mi_png_scanlines *const *png, uint32_t w, uint32_t h, int channels, uint8_t *slots) {
+static int batch_png_expand(mi_batch *b, int count, const mi_png_scanlines *const *png, uint32_t w, uint32_t h, int channels, void *slots, bool deep = false) {
   const size_t need = png_call_bytes(count, png);
   if (b->png_used + need > b->h_png_cap || b->png_used + need > b->d_png_cap) {
     HIP_OK(hipStreamSynchronize(b->stream));                  // earlier calls' copies and kernels may still use the buffers that start over or are replaced
@@ -959,8 +1070,11 @@ static int batch_png_expand(mi_batch *b, int count, const mi_png_scanlines *cons
     hipLaunchKernelGGL(png_unfilter_kernel, dim3(npass), dim3(64 * waves), 0, b->stream, db, (const PngPassDev *)(db + at));
   }
   const dim3 grid(((w + 3) / 4 + 63) / 64, h, (unsigned)count);
-  if (channels == 4) hipLaunchKernelGGL((png_expand_kernel<4>), grid, dim3(64), 0, b->stream, (const uint8_t *)db, (const PngImageDev *)(db + at + img_at), w, h, slots);
-  else hipLaunchKernelGGL((png_expand_kernel<3>), grid, dim3(64), 0, b->stream, (const uint8_t *)db, (const PngImageDev *)(db + at + img_at), w, h, slots);
+  if (deep) {                                                 // files of bit depth 16 into deep slots: both bytes of every sample
+    if (channels == 4) hipLaunchKernelGGL((png_expand16_kernel<4>), grid, dim3(64), 0, b->stream, (const uint8_t *)db, (const PngImageDev *)(db + at + img_at), w, h, (uint16_t *)slots);
+    else hipLaunchKernelGGL((png_expand16_kernel<3>), grid, dim3(64), 0, b->stream, (const uint8_t *)db, (const PngImageDev *)(db + at + img_at), w, h, (uint16_t *)slots);
+  } else if (channels == 4) hipLaunchKernelGGL((png_expand_kernel<4>), grid, dim3(64), 0, b->stream, (const uint8_t *)db, (const PngImageDev *)(db + at + img_at), w, h, (uint8_t *)slots);
+  else hipLaunchKernelGGL((png_expand_kernel<3>), grid, dim3(64), 0, b->stream, (const uint8_t *)db, (const PngImageDev *)(db + at + img_at), w, h, (uint8_t *)slots);
   HIP_OK(hipGetLastError());
   return MI_OK;
 }
@@ -973,6 +1087,38 @@ int mi_batch_upload_png(mi_batch *b, int first, int count, const mi_png_scanline
   (void)hipSetDevice(b->device);
   if (int st = batch_png_expand(b, count, png, b->w, b->h, b->channels, mi_batch_device_input(b, first))) return st;
   batch_tag(b, first, count, MI_INPUT_RGB);
+  return MI_OK;
+}
+
+// mi_batch_upload_png for 16-bit masters: a handle of bit depth 16 is unfiltered as above and expanded by png_expand16_kernel into its deep slot (kind
+// MI_INPUT_RGB16), every other handle goes exactly the way mi_batch_upload_png sends it (kind MI_INPUT_RGB).  Neighbours that go the same way share one call's
+// staging, copy and launches.  Every handle is checked before anything is staged or allocated.
+static bool png_goes_deep(const mi_png_scanlines *p) { return p->sl.depth == 16 && p->sl.ctype != 3; }
+int mi_png_scanlines_info(const mi_png_scanlines *p, int *color_type, int *bit_depth) {
+  if (!p) return MI_INVALID_ARGUMENT;
+  if (color_type) *color_type = p->sl.ctype;
+  if (bit_depth) *bit_depth = p->sl.depth;
+  return MI_OK;
+}
+int mi_batch_upload_png_deep(mi_batch *b, int first, int count, const mi_png_scanlines *const *png) {
+  if (!b || !png || b->in_flight || first < 0 || count < 1 || first > b->cap - count) return MI_INVALID_ARGUMENT;
+  bool any_deep = false;
+  for (int i = 0; i < count; i++) {
+    if (!png[i] || png[i]->sl.w != b->w || png[i]->sl.h != b->h) return MI_INVALID_ARGUMENT;
+    if (b->channels == 3 && png[i]->sl.has_alpha()) return MI_INVALID_ARGUMENT;      // alpha is never dropped
+    if (png_goes_deep(png[i])) { any_deep = true; if (!batch_takes_deep(b, png[i]->sl.has_alpha() ? 4 : 3)) return MI_INVALID_ARGUMENT; }
+  }
+  if (any_deep && !batch_deep(b)) return MI_ENCODING_ERROR;
+  (void)hipSetDevice(b->device);
+  for (int i = 0; i < count;) {
+    const bool deep = png_goes_deep(png[i]);
+    int j = i + 1;
+    while (j < count && png_goes_deep(png[j]) == deep) j++;
+    void *const slots = deep ? (void *)mi_batch_device_input16(b, first + i) : (void *)mi_batch_device_input(b, first + i);
+    if (int st = batch_png_expand(b, j - i, png + i, b->w, b->h, b->channels, slots, deep)) return st;
+    batch_tag(b, first + i, j - i, deep ? MI_INPUT_RGB16 : MI_INPUT_RGB);
+    i = j;
+  }
   return MI_OK;
 }
 
@@ -1144,6 +1290,17 @@ int mi_ravif_encode_device(const mi_ravif_encoder *e, const mi_device_pixels *sr
   pool_release(b);
   return st;
 }
+// the same for a uint16 picture in the memory of device e->device (mi_batch_upload_device16)
+int mi_ravif_encode_device16(const mi_ravif_encoder *e, const mi_device_pixels16 *src, uint32_t w, uint32_t h, mi_encoded_image *out) {
+  if (!e || !src || !src->dev || !out || w < 1 || h < 1 || (src->channels != 3 && src->channels != 4)) return MI_INVALID_ARGUMENT;
+  mi_batch *b = pool_acquire(e, 1, w, h, src->channels);
+  if (!b) return mi_device_count() > e->device ? MI_INVALID_ARGUMENT : MI_NO_DEVICE;
+  int st = mi_batch_upload_device16(b, 0, 1, src);
+  if (st == MI_OK) st = mi_batch_encode(b);
+  if (st == MI_OK) st = mi_batch_get(b, 0, out);
+  pool_release(b);
+  return st;
+}
 // the same for YCbCr planes in the memory of device e->device: the file of a 3-channel batch fed through mi_batch_upload_device_ycbcr
 int mi_ravif_encode_device_ycbcr(const mi_ravif_encoder *e, const mi_device_planes *src, uint32_t w, uint32_t h, mi_encoded_image *out) {
   if (!e || !src || !src->y || !src->cb || !out || w < 1 || h < 1) return MI_INVALID_ARGUMENT;
@@ -1173,7 +1330,7 @@ int mi_ravif_encode_device_resized(const mi_ravif_encoder *e, const mi_device_pi
 // Streaming form of the fan-out: image i is obtained through `fetch(user, i, &desc)` when a worker is about to stage it (the
 // call may block until the pixels exist -- e.g. until a loader thread has decoded the file), so loading, upload, encoding and
 // assembly of consecutive runs overlap.  fetch returns MI_OK or a status that becomes the image's status.  An image is host pixels (kind 0) or the
-// coefficients of a parsed JPEG (kind 1; kind 3: the same, kept as the file's own YCbCr) or the scanlines of a parsed PNG (kind 2), whose pixels come into being in the batch's HBM input slot; mi_ravif_encode_stream is this
+// coefficients of a parsed JPEG (kind 1; kind 3: the same, kept as the file's own YCbCr) or the scanlines of a parsed PNG (kind 2; kind 4: the same, a file of bit depth 16 through its deep slot), whose pixels come into being in the batch's HBM input slot; mi_ravif_encode_stream is this
 // with kind 0 throughout.
 int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source_fn fetch, mi_release_fn release, void *user, mi_encoded_image *out, int *status, const int *devices, int ndev) {
   if (!e || !fetch || (n && !out)) return MI_INVALID_ARGUMENT;
@@ -1207,7 +1364,7 @@ int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source
     { int sharing = 0; for (int d2 : devs) sharing += d2 == dev; budget /= (size_t)std::max(1, sharing); }      // workers on the same ordinal (devices = [0, 0]) split what is free
     static constexpr int NSLOT_MAX = 4;
     const int NSLOT = MI_STREAM_SLOTS_DEFAULT;
-    struct Slot { mi_batch *b = nullptr; std::future<mi_batch *> making; std::vector<size_t> idx; bool busy = false, jpeg = false; size_t bytes = 0, png_bytes = 0; };
+    struct Slot { mi_batch *b = nullptr; std::future<mi_batch *> making; std::vector<size_t> idx; bool busy = false, jpeg = false, deep = false; size_t bytes = 0, png_bytes = 0; };
     struct Shape { uint32_t w, h; int ch; size_t cap; Slot slot[NSLOT_MAX]; int next = 0; size_t runs = 0, last_use = 0; };
     std::vector<std::unique_ptr<Shape>> shapes;
     size_t live_bytes = 0, tick = 0;
@@ -1223,7 +1380,7 @@ int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source
       collect(sl);
       if (sl.making.valid()) sl.b = sl.making.get();
       if (sl.b) mi_batch_destroy(sl.b);
-      sl.b = nullptr; live_bytes -= std::min(live_bytes, sl.bytes); sl.bytes = 0; sl.jpeg = false; sl.png_bytes = 0;
+      sl.b = nullptr; live_bytes -= std::min(live_bytes, sl.bytes); sl.bytes = 0; sl.jpeg = false; sl.deep = false; sl.png_bytes = 0;
     };
     auto make_room = [&](Shape *keep, size_t need) {
       while (live_bytes + need > budget) {
@@ -1264,10 +1421,10 @@ int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source
       Slot &sl = sh->slot[j];
       collect(sl);                                           // the slot's previous run, if any
       bool any_host = false; for (size_t k : run) any_host |= d[k].kind == 0;
-      size_t png_run = 0; { std::vector<const mi_png_scanlines *> all; for (size_t k : run) if (d[k].kind == 2) all.push_back(d[k].png); if (!all.empty()) png_run = png_call_bytes((int)all.size(), all.data()); }
+      size_t png_run = 0; { std::vector<const mi_png_scanlines *> all; for (size_t k : run) if (d[k].kind == 2 || d[k].kind == 4) all.push_back(d[k].png); if (!all.empty()) png_run = png_call_bytes((int)all.size(), all.data()); }
       ensure_slot(sh, j, any_host, png_run);
       if (sl.making.valid()) sl.b = sl.making.get();
-      if (!sl.b) { live_bytes -= std::min(live_bytes, sl.bytes); sl.bytes = 0; sl.jpeg = false; sl.png_bytes = 0; }      // the object could not be made: nothing of it is resident
+      if (!sl.b) { live_bytes -= std::min(live_bytes, sl.bytes); sl.bytes = 0; sl.jpeg = false; sl.deep = false; sl.png_bytes = 0; }      // the object could not be made: nothing of it is resident
       int rc = sl.b ? mi_batch_set_count(sl.b, (int)run.size()) : MI_ENCODING_ERROR;
       if (timing) fprintf(stderr, "[mi_avif %8.1f ms] dev %d: slot %d ready\n", since(), dev, j);
       if (rc == MI_OK) {
@@ -1277,20 +1434,22 @@ int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source
         const size_t row = (size_t)d0.width * d0.channels;
         size_t host_from = 0;
         auto upload_host = [&](size_t end) { if (rc == MI_OK && end > host_from) rc = mi_batch_upload_async(sl.b, (int)host_from, (int)(end - host_from)); };
-        std::vector<const mi_png_scanlines *> pngs; size_t png_from = 0;
+        std::vector<const mi_png_scanlines *> pngs; size_t png_from = 0; int png_kind = 2;       // a stretch holds one kind: 2 goes through mi_batch_upload_png, 4 through _png_deep
         auto upload_png = [&]() {
           if (rc == MI_OK && !pngs.empty()) {
             const size_t extra = 2 * (png_call_bytes((int)pngs.size(), pngs.data()) + ((size_t)1 << 20));
             if (extra > sl.png_bytes) { sl.bytes += extra - sl.png_bytes; live_bytes += extra - sl.png_bytes; sl.png_bytes = extra; }
-            rc = mi_batch_upload_png(sl.b, (int)png_from, (int)pngs.size(), pngs.data());
+            if (png_kind == 4 && !sl.deep) { sl.deep = true; const size_t deep = sh->cap * (size_t)sh->w * sh->h * sh->ch * 2; sl.bytes += deep; live_bytes += deep; }   // the deep slots join the worker's budget
+            rc = png_kind == 4 ? mi_batch_upload_png_deep(sl.b, (int)png_from, (int)pngs.size(), pngs.data()) : mi_batch_upload_png(sl.b, (int)png_from, (int)pngs.size(), pngs.data());
           }
           pngs.clear();
         };
         for (size_t k = 0; k < run.size() && rc == MI_OK; k++) {
           const mi_image_source &src = d[run[k]];
-          if (src.kind == 2) {
+          if (src.kind == 2 || src.kind == 4) {
             upload_host(k); host_from = k + 1;
-            if (pngs.empty()) png_from = k;
+            if (!pngs.empty() && png_kind != src.kind) upload_png();
+            if (pngs.empty()) { png_from = k; png_kind = src.kind; }
             pngs.push_back(src.png);
             continue;
           }
@@ -1340,7 +1499,7 @@ int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source
         const mi_image_desc &x = src.desc;
         if (rc != MI_OK) { st[i] = rc; continue; }
         const bool have = src.kind == 0 ? x.pixels != nullptr : (src.kind == 1 || src.kind == 3) ? src.jpeg && src.jpeg->jc.w == x.width && src.jpeg->jc.h == x.height :
-                          src.kind == 2 && src.png && src.png->sl.w == x.width && src.png->sl.h == x.height && !(x.channels == 3 && src.png->sl.has_alpha());
+                          (src.kind == 2 || src.kind == 4) && src.png && src.png->sl.w == x.width && src.png->sl.h == x.height && !(x.channels == 3 && src.png->sl.has_alpha());
         if (!have || !x.width || !x.height || (x.channels != 3 && x.channels != 4)) { st[i] = MI_INVALID_ARGUMENT; if (release) release(user, i); continue; }
         // a kind-3 source that its upload call would refuse fails alone, not with its run
         if (src.kind == 3 && (src.jpeg->jc.color == JPEG_RGB || e->color_model == 1 || (x.channels == 4 && e->alpha_mode == 2))) {
@@ -1348,10 +1507,16 @@ int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source
           if (release) release(user, i);
           continue;
         }
+        // so does a kind-4 source of bit depth 16 under an alpha mode that takes no deep image of its channels (batch_takes_deep)
+        if (src.kind == 4 && png_goes_deep(src.png) && x.channels == 4 && (src.png->sl.has_alpha() ? e->alpha_mode != 0 : e->alpha_mode == 2)) {
+          st[i] = MI_INVALID_ARGUMENT;
+          if (release) release(user, i);
+          continue;
+        }
         Shape *sh = shape_for(x);
         if (sh != run_shape || run.size() >= sh->cap) flush(true);
         run_shape = sh; run.push_back(i - i0);
-        if (run.size() == 1) ensure_slot(sh, sh->next, src.kind == 0, src.kind == 2 ? sh->cap * png_call_bytes(1, &src.png) : 0);   // made in the background while the rest of the run arrives
+        if (run.size() == 1) ensure_slot(sh, sh->next, src.kind == 0, src.kind == 2 || src.kind == 4 ? sh->cap * png_call_bytes(1, &src.png) : 0);   // made in the background while the rest of the run arrives
       }
       if (timing) fprintf(stderr, "[mi_avif %8.1f ms] dev %d: images %zu..%zu fetched\n", since(), dev, i0, i1);
       flush(cursor.load() < n);

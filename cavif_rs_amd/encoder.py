@@ -59,6 +59,10 @@ class _DevicePixels(C.Structure):
                 ('pixel_or_plane_stride', C.c_size_t), ('image_stride', C.c_size_t), ('after_stream', C.c_void_p)]
 
 
+class _DevicePixels16(C.Structure):                    # mi_device_pixels16: _DevicePixels for uint16 samples + the bits of a sample that count
+    _fields_ = _DevicePixels._fields_ + [('bits', C.c_int), ('msb_aligned', C.c_int)]
+
+
 class _DevicePlanes(C.Structure):                      # mi_device_planes
     _fields_ = [('y', C.c_void_p), ('cb', C.c_void_p), ('cr', C.c_void_p), ('hsub', C.c_int), ('vsub', C.c_int), ('y_row_stride', C.c_size_t),
                 ('c_row_stride', C.c_size_t), ('y_image_stride', C.c_size_t), ('c_image_stride', C.c_size_t), ('after_stream', C.c_void_p)]
@@ -163,6 +167,16 @@ def load_library():
     L.mi_batch_upload_jpeg_ycbcr.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     L.mi_jpeg_coeffs_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.mi_batch_upload_device_ycbcr.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(_DevicePlanes)]
+    L.mi_batch_device_input16.argtypes = [C.c_void_p, C.c_int]
+    L.mi_batch_device_input16.restype = C.c_void_p
+    L.mi_batch_read_input16.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.mi_batch_footprint.argtypes = [C.c_void_p]
+    L.mi_batch_footprint.restype = C.c_size_t
+    L.mi_batch_upload_device16.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(_DevicePixels16)]
+    L.mi_batch_upload16.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int]
+    L.mi_batch_upload_png_deep.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    L.mi_png_scanlines_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.mi_ravif_encode_device16.argtypes = [C.POINTER(_RavifEncoder), C.POINTER(_DevicePixels16), C.c_uint32, C.c_uint32, C.POINTER(_EncodedImage)]
     L.mi_ravif_encode_device_ycbcr.argtypes = [C.POINTER(_RavifEncoder), C.POINTER(_DevicePlanes), C.c_uint32, C.c_uint32, C.POINTER(_EncodedImage)]
     _LIB = L
     return L
@@ -254,7 +268,8 @@ def parse_jpeg(data):
 
 
 class PngScanlines:
-    """One parsed PNG file (mi_png_parse): the inflated scanlines in host memory, `width`, `height`, `has_alpha` (an alpha channel or a tRNS chunk).  Feeds
+    """One parsed PNG file (mi_png_parse): the inflated scanlines in host memory, `width`, `height`, `has_alpha` (an alpha channel or a tRNS chunk),
+    `color_type` and `bit_depth` of the file (bit depth 16 is what upload_png(deep=True) sends through the deep slots).  Feeds
     BatchEncoder.upload_png and encode_many; the filters are undone and the pixels made on the device.  close() (or the garbage collector) frees it."""
 
     def __init__(self, data):
@@ -266,6 +281,9 @@ class PngScanlines:
         if st:
             raise AvifError(st)
         self._L, self._h, self.width, self.height, self.has_alpha = L, h.value, w.value, ht.value, bool(alpha.value)
+        ct, bd = C.c_int(), C.c_int()
+        L.mi_png_scanlines_info(self._h, C.byref(ct), C.byref(bd))
+        self.color_type, self.bit_depth = ct.value, bd.value
 
     def close(self):
         if getattr(self, '_h', None):
@@ -306,20 +324,23 @@ def _decoded_which(name):
     return DECODED_WHICH[name]
 
 
-def _device_pixels(x, batched=False, writable=False):
-    """(_DevicePixels, images, height, width, device index or None) of an object with __cuda_array_interface__: uint8, (H, W, C) or (C, H, W) -- with
+def _device_pixels(x, batched=False, writable=False, deep_ok=False):
+    """(_DevicePixels, images, height, width, device index or None) of an object with __cuda_array_interface__: uint8 -- or little-endian uint16, which gives
+    a _DevicePixels16 whose bits / msb_aligned the caller fills in, for the callers that pass deep_ok -- (H, W, C) or (C, H, W), with
     batched=True also (N, H, W, C) / (N, C, H, W) -- where C is 3 or 4 and either the channel or the column stride is one byte: contiguous tensors of
     both layouts, crops, padded rows and permuted views of them.  (C, H, W) is taken when the first dimension is 3 or 4 and the last is not.
     writable=True: a destination (_DeviceTarget: the same fields, the stream is the one whose work must finish first); a read-only array is refused."""
     ai = x.__cuda_array_interface__
     if writable and ai['data'][1]:
         raise ValueError('the target array is read-only')
-    if ai.get('typestr') != '|u1':
-        raise TypeError('device pixels must be uint8 (got typestr %r): rounding floats is the caller\'s decision' % (ai.get('typestr'),))
+    deep = ai.get('typestr') == '<u2' and deep_ok and not writable
+    if ai.get('typestr') != '|u1' and not deep:
+        raise TypeError('device pixels must be uint8%s (got typestr %r): rounding floats is the caller\'s decision' % (' or uint16' if deep_ok else '', ai.get('typestr'),))
+    item = 2 if deep else 1
     shape = tuple(int(v) for v in ai['shape'])
     strides = ai.get('strides')
     if strides is None:
-        strides, acc = [], 1
+        strides, acc = [], item
         for n in reversed(shape):
             strides.insert(0, acc); acc *= n
     strides = tuple(int(v) for v in strides)
@@ -340,11 +361,13 @@ def _device_pixels(x, batched=False, writable=False):
         raise AvifError(4)
     if writable and (any(n_ > 1 and s_ == 0 for n_, s_ in zip(shape, strides)) or (n > 1 and img_stride == 0)):
         raise ValueError('the target array is an expanded (stride 0) view: its elements share memory')
-    d = _DeviceTarget() if writable else _DevicePixels()
+    d = _DeviceTarget() if writable else _DevicePixels16() if deep else _DevicePixels()
     d.dev, d.channels, d.row_stride, d.image_stride = ptr, c, sh, img_stride
-    if sc == 1:
+    if deep:
+        d.bits, d.msb_aligned = 16, 0
+    if sc == item:
         d.layout, d.pixel_or_plane_stride = 0, sw                  # interleaved: from pixel to pixel
-    elif sw == 1:
+    elif sw == item:
         d.layout, d.pixel_or_plane_stride = 1, sc                  # planar: from plane to plane
     else:
         raise AvifError(4)
@@ -355,6 +378,18 @@ def _device_pixels(x, batched=False, writable=False):
         idx = getattr(getattr(x, 'device', None), 'index', None)
         d.after_stream = torch.cuda.current_stream(idx).cuda_stream or None
     return d, n, h, w, getattr(getattr(x, 'device', None), 'index', None)
+
+
+def _widen16(a, bits=16, msb_aligned=False):
+    """uint16 samples of `bits` significant bits (8..16; low bits, or high bits when msb_aligned) at full scale: reduced to `bits`, then widened by bit
+    replication -- what mi_batch_upload_device16 does on the device"""
+    bits = int(bits)
+    if a.dtype != np.uint16 or not 8 <= bits <= 16:
+        raise AvifError(4)
+    if bits == 16:
+        return a
+    v = (a >> (16 - bits)) if msb_aligned else (a & ((1 << bits) - 1))
+    return ((v << (16 - bits)) | (v >> (2 * bits - 16))).astype(np.uint16)
 
 
 def _plane_view(x, what):
@@ -615,23 +650,38 @@ class Encoder:
             e.exif, e.exif_len = C.cast(self._exif_buf, C.c_void_p), len(self.exif)
         return e
 
-    def _encode_device(self, px, channels):
+    def _encode_device(self, px, channels, bits=16, msb_aligned=False):
         L = load_library()
-        d, _, h, w, index = _device_pixels(px)
+        d, _, h, w, index = _device_pixels(px, deep_ok=True)
         if d.channels != channels:
             raise AvifError(4)
         img = _EncodedImage()
         e = self._c()
         if index is not None:
             e.device = index                            # the pointer belongs to that device
-        st = L.mi_ravif_encode_device(C.byref(e), C.byref(d), w, h, C.byref(img))
+        if isinstance(d, _DevicePixels16):              # uint16 samples: through the deep slot
+            d.bits, d.msb_aligned = int(bits), int(bool(msb_aligned))
+            st = L.mi_ravif_encode_device16(C.byref(e), C.byref(d), w, h, C.byref(img))
+        else:
+            st = L.mi_ravif_encode_device(C.byref(e), C.byref(d), w, h, C.byref(img))
         if st:
             raise AvifError(st)
         return _take(img)
 
-    def _encode(self, px, channels):
+    def _encode(self, px, channels, bits=16, msb_aligned=False):
         if _is_device_array(px):                        # pixels in HBM (a torch tensor, ...): never through the host
-            return self._encode_device(px, channels)
+            return self._encode_device(px, channels, bits, msb_aligned)
+        if getattr(px, 'dtype', None) == np.uint16:     # 16-bit host pixels: a one-image batch whose deep slot they fill
+            a = _widen16(np.ascontiguousarray(px), bits, msb_aligned)
+            if a.ndim != 3 or a.shape[2] != channels:
+                raise AvifError(4)
+            b = BatchEncoder(self, 1, a.shape[1], a.shape[0], channels)
+            try:
+                b.upload(0, a)
+                b.encode()
+                return b.get(0)
+            finally:
+                b.close()
         L = load_library()
         a = np.ascontiguousarray(px, dtype=np.uint8)
         if a.ndim != 3 or a.shape[2] != channels:
@@ -784,11 +834,11 @@ class Encoder:
             raise AvifError(st)
         return _take(img)
 
-    def encode_rgba(self, rgba):                        # :243
-        return self._encode(rgba, 4)
+    def encode_rgba(self, rgba, bits=16, msb_aligned=False):   # :243; uint16 arrays (host or device) are coded from all `bits` of their samples (deep input)
+        return self._encode(rgba, 4, bits, msb_aligned)
 
-    def encode_rgb(self, rgb):                          # :318
-        return self._encode(rgb, 3)
+    def encode_rgb(self, rgb, bits=16, msb_aligned=False):     # :318
+        return self._encode(rgb, 3, bits, msb_aligned)
 
     def _raw(self, fn, dt, yuv, alpha, width, height, color_pixel_range, matrix_coefficients):
         L = load_library()
@@ -814,18 +864,19 @@ class Encoder:
         return self._raw(load_library().mi_ravif_encode_raw_planes_10, np.uint16, planes, alpha, width, height, color_pixel_range, matrix_coefficients)
 
 
-def encode_many(encoder, images, devices=None, jpeg_ycbcr=False):
+def encode_many(encoder, images, devices=None, jpeg_ycbcr=False, png_deep=False):
     """mi_ravif_encode_sources: the reference's files.into_par_iter() (src/main.rs:223) over the node's GPUs.
     images: list of HxWx3 / HxWx4 uint8 arrays (shapes may differ), JpegCoeffs objects (parse_jpeg; encoded as the RGBA pictures decode_jpeg
     gives, decoded on the device) and PngScanlines objects (parse_png; encoded as the RGBA pictures load_rgba gives, unfiltered and expanded on the
     device).  jpeg_ycbcr=True: a JpegCoeffs whose colour is not RGB is coded from the file's own Y, Cb, Cr (source kind 3) instead.
+    png_deep=True: a PngScanlines goes as source kind 4: a file of bit depth 16 is coded from all 16 bits of its samples.
     Returns a list of EncodedImage."""
     items = []
     for im in images:
         if isinstance(im, (JpegCoeffs, PngScanlines)):
             if not im._h:
                 raise AvifError(4)
-            items.append((2, im, 4) if isinstance(im, PngScanlines) else (3 if jpeg_ycbcr and im.color != 'rgb' else 1, im, 4))
+            items.append((4 if png_deep else 2, im, 4) if isinstance(im, PngScanlines) else (3 if jpeg_ycbcr and im.color != 'rgb' else 1, im, 4))
             continue
         if _is_device_array(im):
             raise TypeError('encode_many takes host arrays, JpegCoeffs and PngScanlines; pixels in device memory go through BatchEncoder.upload_device')
@@ -837,13 +888,13 @@ def encode_many(encoder, images, devices=None, jpeg_ycbcr=False):
 
 
 def _encode_sources(encoder, items, devices):
-    """mi_ravif_encode_sources over (kind, object, channels of the slot) triples: kind 0 a contiguous uint8 array, 1 / 3 a JpegCoeffs, 2 a PngScanlines"""
+    """mi_ravif_encode_sources over (kind, object, channels of the slot) triples: kind 0 a contiguous uint8 array, 1 / 3 a JpegCoeffs, 2 / 4 a PngScanlines"""
     L = load_library()
 
     def fetch(_user, i, src):
         (kind, it, channels), s = items[i], src.contents
         s.kind = kind
-        if kind == 2:
+        if kind in (2, 4):
             s.jpeg, s.png = None, it._h
             s.desc.pixels, s.desc.width, s.desc.height, s.desc.stride_px, s.desc.channels = None, it.width, it.height, it.width, channels
         elif kind in (1, 3):
@@ -878,20 +929,35 @@ class BatchEncoder:
         self.count = n_images                        # images of the next run (set_count)
         self._sources = []                           # device arrays handed to upload_device: alive until the run that reads them has been waited for
 
-    def upload(self, index, pixels):
+    def upload(self, index, pixels, bits=16, msb_aligned=False):
+        """host pixels (h, w, channels) uint8 into the slot of `index`; a uint16 array -- (h, w, 3) or (h, w, 4), `bits` significant bits -- into its deep slot
+        (input kind 2: coded from all 16 bits)"""
+        if getattr(pixels, 'dtype', None) == np.uint16:
+            a = _widen16(np.ascontiguousarray(pixels), bits, msb_aligned)
+            if a.ndim != 3 or a.shape[:2] != (self.h, self.w) or a.shape[2] not in (3, 4):
+                raise AvifError(4)
+            st = self._L.mi_batch_upload16(self._h, index, a.ctypes.data, self.w, a.shape[2])
+            if st:
+                raise AvifError(st)
+            return
         a = np.ascontiguousarray(pixels, dtype=np.uint8)
         assert a.shape == (self.h, self.w, self.channels)
         st = self._L.mi_batch_upload(self._h, index, a.ctypes.data, self.w)
         if st:
             raise AvifError(st)
 
-    def upload_device(self, first, pixels):
+    def upload_device(self, first, pixels, bits=16, msb_aligned=False):
         """images first.. from an object with __cuda_array_interface__ (a torch tensor of the batch's device): uint8 (H, W, C), (C, H, W), (N, H, W, C) or
-        (N, C, H, W), any strides a view has.  Enqueued on the batch's stream after the work of torch's current stream; the object is kept referenced until wait()."""
-        d, n, h, w, _ = _device_pixels(pixels, batched=True)
+        (N, C, H, W), any strides a view has.  Enqueued on the batch's stream after the work of torch's current stream; the object is kept referenced until wait().
+        uint16 arrays of the same shapes fill the deep slots (input kind 2); `bits` (8..16) of a sample count, its low ones or (msb_aligned) its high ones."""
+        d, n, h, w, _ = _device_pixels(pixels, batched=True, deep_ok=True)
         if (h, w) != (self.h, self.w):
             raise AvifError(4)
-        st = self._L.mi_batch_upload_device(self._h, first, n, C.byref(d))
+        if isinstance(d, _DevicePixels16):
+            d.bits, d.msb_aligned = int(bits), int(bool(msb_aligned))
+            st = self._L.mi_batch_upload_device16(self._h, first, n, C.byref(d))
+        else:
+            st = self._L.mi_batch_upload_device(self._h, first, n, C.byref(d))
         if st:
             raise AvifError(st)
         self._sources.append(pixels)
@@ -919,7 +985,7 @@ class BatchEncoder:
         self._sources.append((y, cb, cr))
 
     def input_kind(self, index):
-        """what the bytes of slot `index` mean: 0 RGB(A), 1 (Y, Cb, Cr[, 255]); set by whichever call last filled the slot"""
+        """what the bytes of slot `index` mean: 0 RGB(A), 1 (Y, Cb, Cr[, 255]), 2 16-bit RGB(A) in the deep slot; set by whichever call last filled the slot"""
         v = C.c_int()
         st = self._L.mi_batch_input_kind(self._h, index, C.byref(v))
         if st:
@@ -932,14 +998,15 @@ class BatchEncoder:
         if st:
             raise AvifError(st)
 
-    def upload_png(self, first, handles):
+    def upload_png(self, first, handles, deep=False):
         """parsed PNG files (parse_png) of the batch's size into slots first..: one H2D, the scanline filters and the sample expansion run on the batch's
-        stream, one launch per kernel for all of them.  A file with alpha or tRNS into a 3-channel batch raises InvalidArgument."""
+        stream, one launch per kernel for all of them.  A file with alpha or tRNS into a 3-channel batch raises InvalidArgument.
+        deep=True: files of bit depth 16 fill their deep slots with both bytes of every sample (input kind 2); every other file goes as before."""
         handles = [handles] if isinstance(handles, PngScanlines) else list(handles)
         if not handles or any(not isinstance(p, PngScanlines) or not p._h for p in handles):
             raise AvifError(4)
         arr = (C.c_void_p * len(handles))(*[p._h for p in handles])
-        st = self._L.mi_batch_upload_png(self._h, first, len(handles), arr)
+        st = (self._L.mi_batch_upload_png_deep if deep else self._L.mi_batch_upload_png)(self._h, first, len(handles), arr)
         if st:
             raise AvifError(st)
 
@@ -980,6 +1047,14 @@ class BatchEncoder:
         """the slot of image `index` as it is on the device now (blocking D2H): uint8 array (h, w, channels)"""
         a = np.empty((self.h, self.w, self.channels), np.uint8)
         st = self._L.mi_batch_read_input(self._h, index, a.ctypes.data)
+        if st:
+            raise AvifError(st)
+        return a
+
+    def read_input16(self, index):
+        """the deep slot of image `index` as it is on the device now (blocking D2H): uint16 array (h, w, channels), full scale"""
+        a = np.empty((self.h, self.w, self.channels), np.uint16)
+        st = self._L.mi_batch_read_input16(self._h, index, a.ctypes.data)
         if st:
             raise AvifError(st)
         return a

@@ -113,16 +113,20 @@ int  mi_ravif_encode_stream(const mi_ravif_encoder *e, size_t n, mi_fetch_fn fet
  * kind 3: a parsed JPEG file as for kind 1, uploaded through mi_batch_upload_jpeg_ycbcr: the frame is coded from the file's own (Y, Cb, Cr) without the detour over
  * RGB.  A file whose colour is RGB gets MI_UNSUPPORTED, and an encoder with the RGB colour model or (channels 4) the premultiplied alpha mode
  * MI_INVALID_ARGUMENT, for that image alone.  Runs are grouped by (width, height, channels) as before, so kinds 0 to 3 mix in one run.
+ * kind 4: a parsed PNG file as for kind 2, uploaded through mi_batch_upload_png_deep (below): a file of bit depth 16 is coded from all 16 bits of its samples, any
+ * other file exactly as kind 2.  A 16-bit file that the alpha rules of deep input refuse (4 channels: alpha or tRNS unless alpha_mode is 0; any under
+ * alpha_mode 2) gets MI_INVALID_ARGUMENT, for that image alone.
  * mi_ravif_encode_stream is this call with kind 0 throughout.  Pictures in device memory are not a kind here (a pointer belongs to one
  * device, the shared cursor hands images to any): they enter through mi_ravif_encode_device and mi_batch_upload_device. */
 typedef struct mi_jpeg_coeffs mi_jpeg_coeffs;   /* opaque: one parsed file, host memory only */
 typedef struct mi_png_scanlines mi_png_scanlines;      /* opaque: one inflated file, host memory only */
 typedef struct mi_image_source {
   int kind;                   /* 0 host pixels (desc), 1 JPEG coefficients (jpeg; desc.width/height/channels say the slot), 2 PNG scanlines (png; desc likewise),
-                                 3 JPEG coefficients kept as the file's own YCbCr (jpeg; desc as for kind 1; mi_batch_upload_jpeg_ycbcr below) */
+                                 3 JPEG coefficients kept as the file's own YCbCr (jpeg; desc as for kind 1; mi_batch_upload_jpeg_ycbcr below),
+                                 4 PNG scanlines, 16-bit files through their deep slot (png; desc as for kind 2; mi_batch_upload_png_deep below) */
   mi_image_desc desc;
   const mi_jpeg_coeffs *jpeg;
-  const mi_png_scanlines *png; /* kind 2 only (the struct grew by this field at its tail: never read for kinds 0 and 1) */
+  const mi_png_scanlines *png; /* kinds 2 and 4 only (the struct grew by this field at its tail: never read for kinds 0 and 1) */
 } mi_image_source;
 typedef int (*mi_fetch_source_fn)(void *user, size_t index, mi_image_source *src);
 int  mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source_fn fetch, mi_release_fn release, void *user, mi_encoded_image *out,
@@ -228,7 +232,8 @@ int  mi_batch_upload_async(mi_batch *b, int first, int count);
  * three *_ycbcr calls tag theirs MI_INPUT_YCBCR; it survives encodes and mi_batch_set_count as the slot's contents do.  mi_batch_set_input_kind is for HIP
  * callers that write mi_batch_device_input themselves.  MI_INPUT_YCBCR is refused with MI_INVALID_ARGUMENT (by the set call and the *_ycbcr uploads alike)
  * when the encoder's colour model is RGB (color_model 1) and when the batch has 4 channels and alpha_mode 2 (premultiplied: defined on RGB colours).
- * mi_batch_set_input_kind: MI_INVALID_ARGUMENT as well for a range past the capacity, a kind not 0 or 1, a call between mi_batch_encode_async and mi_batch_wait.
+ * mi_batch_set_input_kind: MI_INVALID_ARGUMENT as well for a range past the capacity, a kind not 0, 1 or 2 (MI_INPUT_RGB16: deep input, below; refused while the
+ * batch has no deep slots), a call between mi_batch_encode_async and mi_batch_wait.
  * mi_batch_upload_jpeg_ycbcr: mi_batch_upload_jpeg (staging, H2D, IDCT, ordering, lifetimes) ending in jpeg_ycc_kernel: the slot's pixels are
  * (Y, Cb', Cr') of a three-component YCbCr file, Cb' Cr' libjpeg's fancy-upsampled chroma -- exactly the triples whose 16.16 conversion mi_batch_upload_jpeg
  * stores -- and (Y, 128, 128) of a grey file.  A file whose colour is RGB (Adobe transform 0, or components named R G B): MI_UNSUPPORTED; a size mismatch, an
@@ -244,7 +249,7 @@ int  mi_batch_upload_async(mi_batch *b, int first, int count);
  *          x even: (3 v(i) + v(i-1) + 8) >> 4,  x odd: (3 v(i) + v(i+1) + 7) >> 4
  * MI_INVALID_ARGUMENT: null b / src / y / cb, another (hsub, vsub), a row stride below the packed row (w for y; cw, or 2 cw interleaved, for chroma), a
  * range past the capacity, a refusal of the kind, a call between mi_batch_encode_async and mi_batch_wait. */
-enum { MI_INPUT_RGB = 0, MI_INPUT_YCBCR = 1 };
+enum { MI_INPUT_RGB = 0, MI_INPUT_YCBCR = 1, MI_INPUT_RGB16 = 2 };
 int  mi_batch_set_input_kind(mi_batch *b, int first, int count, int kind);
 int  mi_batch_input_kind(mi_batch *b, int index, int *kind);
 int  mi_batch_upload_jpeg_ycbcr(mi_batch *b, int index, const mi_jpeg_coeffs *c);
@@ -255,6 +260,54 @@ int  mi_batch_read_input(mi_batch *b, int index, uint8_t *dst);
 int  mi_batch_upload_device(mi_batch *b, int first, int count, const mi_device_pixels *src);
 int  mi_batch_upload_jpeg(mi_batch *b, int index, const mi_jpeg_coeffs *c);
 int  mi_batch_upload_png(mi_batch *b, int first, int count, const mi_png_scanlines *const *png);
+/* ---- deep input: 16-bit sources.  MI_INPUT_RGB16: the image is read from its DEEP slot, a second slot array beside the 8-bit one: w*h*channels
+ * uint16 samples per image, rows packed, images back to back, FULL SCALE 0..65535, (R, G, B[, A]).  The array is made by the first call that needs it (any
+ * call below but mi_png_scanlines_info and mi_batch_footprint) and never by a batch that sees no 16-bit source; the 8-bit slot of such an image is ignored.
+ * mi_batch_set_input_kind(.., 2) tags what a HIP caller wrote through mi_batch_device_input16: on a batch whose deep slots do not exist yet it has nothing to
+ * tag, allocates nothing and answers MI_INVALID_ARGUMENT.  Kinds 0, 1 and 2 mix freely in one batch; the kind follows the last call that filled the slot and survives encodes and mi_batch_set_count.
+ * The planes of the colour frame are specified exactly, in integers.  M = 65535, bd = the batch's bit depth (8 | 10), peak = 2^bd - 1, half = 2^(bd-1), floor
+ * division towards minus infinity:
+ *   YCbCr model:  S  = 299 R + 587 G + 114 B
+ *                 Y  = floor((2 peak S + 1000 M) / (2000 M))
+ *                 Cb = clamp(half + floor((2 peak (1000 B - S) + 1772 M) / (3544 M)), 0, peak)
+ *                 Cr = clamp(half + floor((2 peak (1000 R - S) + 1402 M) / (2804 M)), 0, peak)
+ *   RGB model (planes G, B, R) and the alpha plane:  p = floor((2 peak v + M) / (2 M))
+ * i.e. BT.601 with Kr = 0.299, Kb = 0.114 and the scale peak / M, rounded half up: the constants mi_batch_decode's q() inverts; grey gives chroma exactly half.
+ * Samples past the picture replicate its edge.  The image uses alpha when A != 65535 anywhere inside w x h.
+ * Alpha rules (the dirty-alpha cleaner and the premultiplied mode are defined on 8-bit samples and are not generalised): a 3-channel batch takes kind 2 under
+ * every alpha mode.  In a 4-channel batch a 3-channel deep source is stored with A = 65535 -- opaque, skipped by the cleaner as MI_INPUT_YCBCR is -- and is taken
+ * under alpha_mode 0 and 1; a 4-channel deep source and mi_batch_set_input_kind(.., 2) need alpha_mode 0; alpha_mode 2 takes none.  4 channels into a 3-channel
+ * batch are refused.  Every refusal is MI_INVALID_ARGUMENT and allocates nothing.
+ * mi_batch_device_input16: the deep slot of image `index` in device memory (a HIP caller may write it and then tag it with mi_batch_set_input_kind), NULL when
+ * it cannot be made.  mi_batch_read_input16: D2H of that slot (w*h*channels uint16), blocking; tests and debugging.  mi_batch_footprint: the bytes of device
+ * and pinned memory the batch holds now (what the pool of the one-call entry points counts).
+ * mi_batch_upload_device16: mi_batch_upload_device (after_stream, ordering, lifetimes, stride rules in BYTES) for uint16 samples; the pointer and every stride
+ * must be even.  A sample v is first reduced to `bits` (8..16) -- masked to its low bits, or v >> (16 - bits) when msb_aligned -- then widened by bit
+ * replication, (v << (16 - bits)) | (v >> (2 bits - 16)): 16 bits pass unchanged, 8 bits give 257 v, and a 10-bit (8-bit) sample comes back from the RGB-model
+ * formula above at depth 10 (8) as itself.  One launch for all images of the call.
+ * mi_batch_upload16: one image of full-scale host pixels, rows stride_px pixels apart (0 = packed), channels 3 | 4; blocking, on the batch's stream.
+ * mi_batch_upload_png_deep: mi_batch_upload_png where a handle whose file has bit depth 16 (colour types 0, 2, 4, 6; Adam7) fills its deep slot with both
+ * bytes of every sample -- grey replicated, the tRNS colour key compared on all 16 bits (A = 0, else 65535), a file with an alpha channel or tRNS a 4-channel
+ * source under the rules above -- and every other handle goes exactly as mi_batch_upload_png sends it, kind 0.  All handles are checked before any is staged.
+ * mi_png_scanlines_info: the file's colour type and bit depth (either pointer may be NULL): bit depth 16 is what goes deep.
+ * mi_ravif_encode_device16: mi_ravif_encode_device for such a source. */
+typedef struct mi_device_pixels16 {        /* mi_device_pixels for uint16 samples, plus how many bits of a sample count */
+  const void *dev;
+  int layout;        /* 0 = HWC, 1 = CHW */
+  int channels;      /* 3 | 4 */
+  size_t row_stride, pixel_or_plane_stride, image_stride;   /* bytes, even; 0 = packed */
+  void *after_stream; /* hipStream_t the pixels were produced on, or NULL = already complete */
+  int bits;          /* 8..16 significant bits */
+  int msb_aligned;   /* 0: they are the low bits of a sample (bits above them are ignored), 1: the high bits */
+} mi_device_pixels16;
+uint16_t *mi_batch_device_input16(mi_batch *b, int index);
+int  mi_batch_read_input16(mi_batch *b, int index, uint16_t *dst);
+size_t mi_batch_footprint(const mi_batch *b);
+int  mi_batch_upload_device16(mi_batch *b, int first, int count, const mi_device_pixels16 *src);
+int  mi_batch_upload16(mi_batch *b, int index, const uint16_t *pixels, size_t stride_px, int channels);
+int  mi_batch_upload_png_deep(mi_batch *b, int first, int count, const mi_png_scanlines *const *png);
+int  mi_png_scanlines_info(const mi_png_scanlines *p, int *color_type, int *bit_depth);
+int  mi_ravif_encode_device16(const mi_ravif_encoder *e, const mi_device_pixels16 *src, uint32_t w, uint32_t h, mi_encoded_image *out);
 /* resize on input: the source has any size and is resampled into the slot on the batch's stream, no sync.  The pixels are exactly those of Pillow's
  * Image.resize((w, h), resample=filter, reducing_gap=None) on 8-bit pictures: coefficients in double on the host, 22-bit fixed-point taps, horizontal pass
  * first into an 8-bit intermediate, then the vertical one, a pass whose axis keeps its length skipped; 4-channel sources are premultiplied before the passes and
