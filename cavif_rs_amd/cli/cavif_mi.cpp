@@ -266,7 +266,7 @@ int main(int argc, char **argv) {
     { std::unique_lock<std::mutex> lk(*c->mu); c->cv->wait(lk, [&] { return (*c->loaded)[i] != 0; }); }
     const Job &j = (*c->jobs)[i];
     if (!j.error.empty()) return MI_INVALID_ARGUMENT;           // reported from the job's own message below
-    src->kind = j.jpeg ? (j.ycbcr ? 3 : 1) : j.png ? (j.deep ? 4 : 2) : 0; src->jpeg = j.jpeg; src->png = j.png;
+    src->kind = j.jpeg ? (j.ycbcr ? MI_SOURCE_JPEG_YCBCR : MI_SOURCE_JPEG) : j.png ? (j.deep ? MI_SOURCE_PNG_DEEP : MI_SOURCE_PNG) : MI_SOURCE_HOST; src->jpeg = j.jpeg; src->png = j.png;
     mi_image_desc *d = &src->desc;
     d->pixels = nullptr; d->width = j.w; d->height = j.h; d->stride_px = j.w; d->channels = 4;     // a JPEG or PNG into an RGBA slot: the pixels load_rgba gives it
     return MI_OK;

@@ -1,5 +1,6 @@
-// mi_avif.hip -- the entry points of include/mi_avif.h: the batch object (pixels and staging, K0 front end, pack + D2H, AVIF containers, timing), its
-// pool, the JPEG decode contexts, the stream worker and the level-1 plane encoder.  The frame chain they all run (plans, arena, K1 tile search, K2 deblock,
+// mi_avif.hip -- the entry points of include/mi_avif.h: the batch's lifecycle and its encode (K0 front end, pack + D2H, AVIF containers, timing), its
+// pool, the stream worker and the level-1 plane encoder.  Every call through which pixels reach a slot or leave it (host, device,
+// JPEG, PNG, 16-bit, resize, decoded output) is host_input.h, included below the pool.  The frame chain they all run (plans, arena, K1 tile search, K2 deblock,
 // K3 CDEF, K5 restoration, K4 tile entropy coding, readback) is host_frames.h.  One HIP stream per batch, no hidden device syncs
 // other than the two points where the host needs device results (alpha flags, tile lengths).
 #include <hip/hip_runtime.h>
@@ -83,26 +84,6 @@ struct mi_batch {
   // them (under staging_mu), never by a batch that sees no 16-bit source
   DevBuf<uint16_t> d_pixels16; size_t deep_bytes = 0;
 };
-static void batch_tag(mi_batch *b, int first, int count, int kind) { std::fill(b->kinds.begin() + first, b->kinds.begin() + first + count, (uint8_t)kind); }
-// MI_INPUT_YCBCR needs the YCbCr colour model (the planes are the slot's bytes) and, in a 4-channel batch, an alpha mode that leaves opaque pixels alone
-static bool batch_takes_ycbcr(const mi_batch *b) { return b->enc.color_model != 1 && !(b->channels == 4 && b->enc.alpha_mode == 2); }
-// MI_INPUT_RGB16: the dirty-alpha cleaner and the premultiply branch are defined on 8-bit samples, so a 4-channel batch takes a deep source with an alpha channel
-// under UnassociatedDirty alone and an opaque one (A = 65535: the cleaner skips it as it skips MI_INPUT_YCBCR) under both unassociated modes; a 3-channel batch takes 3 channels
-static bool batch_takes_deep(const mi_batch *b, int src_channels) {
-  if (src_channels != 3 && src_channels != 4) return false;
-  if (b->channels == 3) return src_channels == 3;
-  return src_channels == 4 ? b->enc.alpha_mode == 0 : b->enc.alpha_mode != 2;
-}
-// the deep slots, made on first use; nullptr = could not be allocated
-static uint16_t *batch_deep(mi_batch *b) {
-  std::lock_guard<std::mutex> lk(b->staging_mu);
-  if (!b->d_pixels16.get()) {
-    (void)hipSetDevice(b->device);
-    if (b->d_pixels16.alloc(b->pixel_bytes) != hipSuccess) return nullptr;
-    b->deep_bytes = b->pixel_bytes * sizeof(uint16_t);
-  }
-  return b->d_pixels16.get();
-}
 static_assert(sizeof(QualityRec) <= MI_FRAME_RECORD_BYTES, "FrameSet reserves MI_FRAME_RECORD_BYTES per (frame, plane)");
 
 static void batch_plan(mi_batch *b) {
@@ -198,56 +179,10 @@ mi_batch *mi_batch_create(const mi_ravif_encoder *e, int n_images, uint32_t w, u
   return b;
 }
 
-// The batch owns a pinned host staging area laid out like its HBM input slot; H2D always starts from there.
-uint8_t *mi_batch_input(mi_batch *b, int index) {
-  if (!b || index < 0 || index >= b->cap) return nullptr;
-  {                                                           // made once, by whichever thread asks first (callers may fill different slots from different threads)
-    std::lock_guard<std::mutex> lk(b->staging_mu);
-    if (!b->h_pixels.get()) { (void)hipSetDevice(b->device); if (b->h_pixels.alloc(b->pixel_bytes) != hipSuccess) return nullptr; }
-  }
-  return b->h_pixels.get() + (size_t)index * b->w * b->h * b->channels;
-}
 int mi_batch_set_count(mi_batch *b, int n_images) {
   if (!b || b->in_flight || n_images < 1 || n_images > b->cap) return MI_INVALID_ARGUMENT;
   b->n = n_images; b->alpha_flags.assign(n_images, 0);
   b->encoded = b->measured = false;
-  return MI_OK;
-}
-// enqueue the H2D of images [first, first + count) from the pinned staging on the batch's stream; returns at once
-int mi_batch_upload_async(mi_batch *b, int first, int count) {
-  if (!b || first < 0 || count < 1 || first + count > b->cap || !mi_batch_input(b, first)) return MI_INVALID_ARGUMENT;
-  (void)hipSetDevice(b->device);
-  const size_t img = (size_t)b->w * b->h * b->channels;
-  HIP_OK(hipMemcpyAsync(b->d_pixels.get() + first * img, b->h_pixels.get() + first * img, count * img, hipMemcpyHostToDevice, b->stream));
-  batch_tag(b, first, count, MI_INPUT_RGB);
-  return MI_OK;
-}
-int mi_batch_set_input_kind(mi_batch *b, int first, int count, int kind) {
-  if (!b || b->in_flight || first < 0 || count < 1 || first > b->cap - count || (kind != MI_INPUT_RGB && kind != MI_INPUT_YCBCR && kind != MI_INPUT_RGB16)) return MI_INVALID_ARGUMENT;
-  if (kind == MI_INPUT_YCBCR && !batch_takes_ycbcr(b)) return MI_INVALID_ARGUMENT;
-  // kind 2 tags what a HIP caller wrote through mi_batch_device_input16, the call that makes the deep slots: a batch without them has nothing to tag (and the
-  // set call allocates nothing); the slot may hold any alpha
-  if (kind == MI_INPUT_RGB16) {
-    if (!batch_takes_deep(b, b->channels)) return MI_INVALID_ARGUMENT;
-    std::lock_guard<std::mutex> lk(b->staging_mu);
-    if (!b->d_pixels16.get()) return MI_INVALID_ARGUMENT;
-  }
-  batch_tag(b, first, count, kind);
-  return MI_OK;
-}
-int mi_batch_input_kind(mi_batch *b, int index, int *kind) {
-  if (!b || !kind || index < 0 || index >= b->cap) return MI_INVALID_ARGUMENT;
-  *kind = b->kinds[index];
-  return MI_OK;
-}
-int mi_batch_upload(mi_batch *b, int index, const uint8_t *pixels, size_t stride_px) {
-  if (!b || index < 0 || index >= b->cap || !pixels) return MI_INVALID_ARGUMENT;
-  const size_t row = (size_t)b->w * b->channels;
-  uint8_t *dst = mi_batch_input(b, index);
-  if (!dst) return MI_ENCODING_ERROR;
-  for (uint32_t y = 0; y < b->h; y++) memcpy(dst + y * row, pixels + (size_t)y * stride_px * b->channels, row);
-  if (int st = mi_batch_upload_async(b, index, 1)) return st;
-  HIP_OK(hipStreamSynchronize(b->stream));
   return MI_OK;
 }
 
@@ -542,786 +477,71 @@ static void pool_release(mi_batch *b) {
   for (mi_batch *x : evict) mi_batch_destroy(x);
 }
 
-// ---- JPEG input: decode contexts ----
-// mi_jpeg_decode_rgba is called from many loader threads at once (the command line runs a few dozen).  Each call borrows a context -- its own stream, pinned
-// staging and device buffers, all grown on demand and never shrunk -- from a per-device free list and hands it back: no hipMalloc per call in the steady
-// state.  At most MI_JPEG_CTX_MAX contexts exist per device: a caller that finds them all busy waits for one (the device part of a decode is a fraction of
-// the call, the Huffman decoding before it needs no context), because allocating and freeing pinned and device memory per call stalls every other stream of
-// the process (measured: profiles/jpeg_input.md).  mi_release_cached() frees the idle ones.
-struct JpegCtx {
-  int device = 0; hipStream_t stream = nullptr;
-  PinBuf<uint8_t> h_in, h_rgba; DevBuf<uint8_t> d_in, d_planes, d_rgba;
-  size_t h_in_cap = 0, d_in_cap = 0, d_planes_cap = 0, d_rgba_cap = 0, h_rgba_cap = 0;
-};
-static constexpr int MI_JPEG_CTX_MAX = 8;
-static std::mutex g_jpeg_mu;
-static std::condition_variable g_jpeg_cv;
-static std::vector<JpegCtx *> g_jpeg_free;                    // never destroyed at process exit (the runtime may be gone by then)
-static std::vector<int> g_jpeg_live;                          // contexts in existence per device, idle or borrowed
-static void jpeg_ctx_destroy(JpegCtx *c) {
-  (void)hipSetDevice(c->device);
-  const hipStream_t stream = c->stream;
-  delete c;                                                   // the buffers first, then the stream
-  if (stream) (void)hipStreamDestroy(stream);
-}
-static JpegCtx *jpeg_ctx_acquire(int device) {
-  {
-    std::unique_lock<std::mutex> lk(g_jpeg_mu);
-    if ((size_t)device >= g_jpeg_live.size()) g_jpeg_live.resize((size_t)device + 1, 0);
-    for (;;) {
-      for (size_t i = g_jpeg_free.size(); i-- > 0;) if (g_jpeg_free[i]->device == device) { JpegCtx *c = g_jpeg_free[i]; g_jpeg_free.erase(g_jpeg_free.begin() + i); return c; }
-      if (g_jpeg_live[device] < MI_JPEG_CTX_MAX) { g_jpeg_live[device]++; break; }
-      g_jpeg_cv.wait(lk);
-    }
-  }
-  JpegCtx *c = new JpegCtx; c->device = device;
-  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
-    delete c;
-    { std::lock_guard<std::mutex> lk(g_jpeg_mu); g_jpeg_live[device]--; }
-    g_jpeg_cv.notify_one();
-    return nullptr;
-  }
-  return c;
-}
-static void jpeg_ctx_release(JpegCtx *c) {
-  { std::lock_guard<std::mutex> lk(g_jpeg_mu); g_jpeg_free.push_back(c); }
-  g_jpeg_cv.notify_one();
-}
-// the buffer holds at least `need` bytes afterwards (the context is idle whenever this runs: every public call ends with a stream sync)
-static const auto staging_grow = [](auto &buf /* DevBuf or PinBuf */, size_t &cap, size_t need) {
-  if (need <= cap) return true;
-  need = (need + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
-  cap = 0;
-  if (buf.alloc(need) != hipSuccess) return false;
-  cap = need; return true;
-};
+}  // extern "C"
+
+#include "host_input.h"
+
+extern "C" {
 
 void mi_release_cached(void) {
   std::vector<std::pair<PoolKey, mi_batch *>> all;
   { std::lock_guard<std::mutex> lk(g_pool_mu); all.swap(g_pool); }
   for (auto &x : all) mi_batch_destroy(x.second);
-  std::vector<JpegCtx *> ctxs;
-  { std::lock_guard<std::mutex> lk(g_jpeg_mu); ctxs.swap(g_jpeg_free); for (JpegCtx *c : ctxs) g_jpeg_live[c->device]--; }
-  g_jpeg_cv.notify_all();
-  for (JpegCtx *c : ctxs) jpeg_ctx_destroy(c);
-}
-
-static int encode_one(const mi_ravif_encoder *e, const uint8_t *px, int channels, uint32_t w, uint32_t h, size_t stride_px, mi_encoded_image *out) {
-  if (!e || !px || !out || w < 1 || h < 1) return MI_INVALID_ARGUMENT;
-  mi_batch *b = pool_acquire(e, 1, w, h, channels);
-  if (!b) return mi_device_count() > e->device ? MI_INVALID_ARGUMENT : MI_NO_DEVICE;
-  int st = mi_batch_upload(b, 0, px, stride_px);
-  if (st == MI_OK) st = mi_batch_encode(b);
-  if (st == MI_OK) st = mi_batch_get(b, 0, out);
-  pool_release(b);
-  return st;
-}
-int mi_ravif_encode_rgba(const mi_ravif_encoder *e, const uint8_t *rgba, uint32_t w, uint32_t h, size_t stride_px, mi_encoded_image *out) { return encode_one(e, rgba, 4, w, h, stride_px, out); }
-
-// PNG -> RGBA8 (cavif's load_rgba, src/main.rs:265-283); host code, no GPU involved
-int mi_png_decode_rgba(const uint8_t *data, size_t len, uint8_t **rgba, uint32_t *w, uint32_t *h) {
-  if (!data || !rgba || !w || !h) return MI_INVALID_ARGUMENT;
-  try {                                                       // nothing may unwind through the C ABI
-    std::vector<uint8_t> px;
-    const int st = png_decode_rgba(data, len, px, *w, *h);
-    if (st) return st;
-    *rgba = (uint8_t *)malloc(px.size());
-    if (!*rgba) return MI_ENCODING_ERROR;
-    memcpy(*rgba, px.data(), px.size());
-    return MI_OK;
-  } catch (const std::exception &) { return MI_ENCODING_ERROR; }
-}
-
-// The seam of the JPEG path: coefficients of one parsed file -> RGBA8 (channels 4) or RGB8 (channels 3) rows of stride_px pixels at a DEVICE pointer, on
-// `stream`.  h_in (pinned) and d_in hold jpeg_in_bytes(jc), d_planes jpeg_plane_bytes(jc): quantisation tables + coefficients are copied to h_in, then one
-// H2D and the two kernels of dev_jpeg.h, no sync (probe builds with MI_AVIF_TIMING sync between the steps to time them).  Its own function so that d_out
-// can be memory that is consumed on the device (a batch's HBM input slot: mi_batch_upload_jpeg) or a buffer that goes back to the host
-// (mi_jpeg_decode_rgba).  The caller has made the device current and keeps h_in untouched until the stream has passed the copy.
-static size_t jpeg_in_bytes(const JpegCoeffs &jc) { return 3 * 64 * sizeof(uint16_t) + jc.nblocks * 64 * sizeof(int16_t); }
-static size_t jpeg_plane_bytes(const JpegCoeffs &jc) { return jc.nblocks * 64; }
-static int jpeg_decode_to_device(const JpegCoeffs &jc, uint8_t *h_in, uint8_t *d_in, uint8_t *d_planes, uint8_t *d_out, int channels, size_t stride_px, hipStream_t stream, double *step_ms, bool ycc = false) {
-  JpegDevGeom g; memset(&g, 0, sizeof(g));
-  g.w = jc.w; g.h = jc.h; g.ncomp = (uint32_t)jc.ncomp; g.color = (uint32_t)jc.color; g.nblocks = (uint32_t)jc.nblocks;
-  for (int c = 0; c < 3; c++) {
-    g.first_block[c] = g.nblocks;
-    if (c >= jc.ncomp) continue;
-    const JpegComp &k = jc.comp[c];
-    g.first_block[c] = (uint32_t)k.first_block; g.plane_off[c] = (unsigned long long)k.first_block * 64;
-    g.bw[c] = k.bw; g.bh[c] = k.bh; g.cw[c] = k.cw; g.ch[c] = k.ch;
-  }
-  g.hr = jc.ncomp == 3 ? (uint32_t)(jc.comp[0].h / jc.comp[1].h) : 1; g.vr = jc.ncomp == 3 ? (uint32_t)(jc.comp[0].v / jc.comp[1].v) : 1;
-  const size_t quant_bytes = 3 * 64 * sizeof(uint16_t), in_bytes = jpeg_in_bytes(jc);
-  const auto t0 = std::chrono::steady_clock::now();
-  memset(h_in, 0, quant_bytes);
-  for (int c = 0; c < jc.ncomp; c++) memcpy(h_in + c * 64 * sizeof(uint16_t), jc.comp[c].quant, 64 * sizeof(uint16_t));
-  memcpy(h_in + quant_bytes, jc.coef.data(), jc.nblocks * 64 * sizeof(int16_t));
-  auto lap = [&](int i) { if (step_ms) { (void)hipStreamSynchronize(stream); step_ms[i] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); } };
-  HIP_OK(hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, stream));
-  lap(0);
-  hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((jc.nblocks + MI_JPEG_IDCT_BLOCKS - 1) / MI_JPEG_IDCT_BLOCKS)), dim3(256), 0, stream,
-                     (const int16_t *)(d_in + quant_bytes), (const uint16_t *)d_in, g, d_planes);
-  const dim3 grid(((jc.w + 3) / 4 + 63) / 64, jc.h);
-  if (channels == 4) {
-    const int vec16 = (stride_px % 4 == 0 && ((uintptr_t)d_out & 15) == 0) ? 1 : 0;
-    if (ycc) hipLaunchKernelGGL((jpeg_ycc_kernel<4>), grid, dim3(64), 0, stream, (const uint8_t *)d_planes, g, d_out, stride_px, vec16);
-    else hipLaunchKernelGGL(jpeg_rgba_kernel, grid, dim3(64), 0, stream, (const uint8_t *)d_planes, g, d_out, stride_px, vec16);
-  } else {
-    const int vec4 = (stride_px % 4 == 0 && ((uintptr_t)d_out & 3) == 0) ? 1 : 0;        // a row is 3 * stride_px bytes
-    if (ycc) hipLaunchKernelGGL((jpeg_ycc_kernel<3>), grid, dim3(64), 0, stream, (const uint8_t *)d_planes, g, d_out, stride_px, vec4);
-    else hipLaunchKernelGGL(jpeg_rgb_kernel, grid, dim3(64), 0, stream, (const uint8_t *)d_planes, g, d_out, stride_px, vec4);
-  }
-  HIP_OK(hipGetLastError());
-  lap(1);
-  return MI_OK;
-}
-
-static int jpeg_decode_with(JpegCtx &ctx, const JpegCoeffs &jc, uint8_t *dst, double *step_ms) {
-  const size_t out_bytes = (size_t)jc.w * jc.h * 4;
-  if (!staging_grow(ctx.d_rgba, ctx.d_rgba_cap, out_bytes) || !staging_grow(ctx.h_rgba, ctx.h_rgba_cap, out_bytes)) return MI_ENCODING_ERROR;
-  if (!staging_grow(ctx.h_in, ctx.h_in_cap, jpeg_in_bytes(jc)) || !staging_grow(ctx.d_in, ctx.d_in_cap, jpeg_in_bytes(jc)) || !staging_grow(ctx.d_planes, ctx.d_planes_cap, jpeg_plane_bytes(jc))) return MI_ENCODING_ERROR;
-  const int st = jpeg_decode_to_device(jc, ctx.h_in.get(), ctx.d_in.get(), ctx.d_planes.get(), ctx.d_rgba.get(), 4, jc.w, ctx.stream, step_ms);
-  if (st) { (void)hipStreamSynchronize(ctx.stream); return st; }
-  const auto t0 = std::chrono::steady_clock::now();
-  HIP_OK(hipMemcpyAsync(ctx.h_rgba.get(), ctx.d_rgba.get(), out_bytes, hipMemcpyDeviceToHost, ctx.stream));
-  HIP_OK(hipStreamSynchronize(ctx.stream));
-  if (step_ms) step_ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  memcpy(dst, ctx.h_rgba.get(), out_bytes);
-  if (step_ms) step_ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - step_ms[2];
-  return MI_OK;
-}
-
-// JPEG -> RGBA8 (load_image::load_data + load_rgba, src/main.rs:255-283, for JPEG bytes): Huffman decoding on the host, everything after it on the device
-int mi_jpeg_decode_rgba(const uint8_t *data, size_t len, int device, uint8_t **rgba, uint32_t *w, uint32_t *h) {
-  if (!data || !rgba || !w || !h) return MI_INVALID_ARGUMENT;
-  try {                                                       // nothing may unwind through the C ABI
-    const bool timing = mi_timing_enabled();
-    const auto t0 = std::chrono::steady_clock::now();
-    JpegCoeffs jc;
-    int st = jpeg_read_coeffs(data, len, jc);                 // header and stream errors come first: they need no device
-    if (st) return st;
-    const double parse_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (device < 0) return MI_INVALID_ARGUMENT;
-    if (mi_device_count() <= device) return MI_NO_DEVICE;     // no CPU fallback
-    if (hipSetDevice(device) != hipSuccess) return MI_NO_DEVICE;
-    uint8_t *px = (uint8_t *)malloc((size_t)jc.w * jc.h * 4);
-    if (!px) return MI_ENCODING_ERROR;
-    JpegCtx *ctx = jpeg_ctx_acquire(device);
-    if (!ctx) { free(px); return MI_ENCODING_ERROR; }
-    double step_ms[4] = { 0, 0, 0, 0 };
-    st = jpeg_decode_with(*ctx, jc, px, timing ? step_ms : nullptr);
-    jpeg_ctx_release(ctx);
-    if (st) { free(px); return st; }
-    if (timing) fprintf(stderr, "[jpeg] %ux%u %zu bytes: parse+entropy %.3f ms, staging+H2D %.3f ms, kernels %.3f ms, D2H %.3f ms, copy-out %.3f ms\n", jc.w, jc.h, len, parse_ms,
-                        step_ms[0], step_ms[1] - step_ms[0], step_ms[2], step_ms[3]);
-    *rgba = px; *w = jc.w; *h = jc.h;
-    return MI_OK;
-  } catch (const std::exception &) { return MI_ENCODING_ERROR; }
-}
-
-// load_rgba (src/main.rs:255-283) for the formats this library reads, told apart by their first bytes as load_image does
-int mi_image_decode_rgba(const uint8_t *data, size_t len, int device, uint8_t **rgba, uint32_t *w, uint32_t *h) {
-  if (!data || !rgba || !w || !h) return MI_INVALID_ARGUMENT;
-  static const uint8_t png_sig[8] = { 0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A };
-  if (len >= 8 && !memcmp(data, png_sig, 8)) return mi_png_decode_rgba(data, len, rgba, w, h);
-  if (len >= 2 && data[0] == 0xFF && data[1] == 0xD8) return mi_jpeg_decode_rgba(data, len, device, rgba, w, h);
-  return MI_UNSUPPORTED;
-}
-
-// ---- device-resident input: a picture reaches a batch's HBM input slot without ever being host pixels ----
-struct mi_jpeg_coeffs { JpegCoeffs jc; };
-
-// jpeg_read_coeffs behind a handle: host work only, the statuses mi_jpeg_decode_rgba gives for the same bytes
-int mi_jpeg_parse(const uint8_t *data, size_t len, mi_jpeg_coeffs **out, uint32_t *w, uint32_t *h) {
-  if (!data || !out || !w || !h) return MI_INVALID_ARGUMENT;
-  *out = nullptr;
-  try {                                                       // nothing may unwind through the C ABI
-    std::unique_ptr<mi_jpeg_coeffs> c(new mi_jpeg_coeffs);
-    if (const int st = jpeg_read_coeffs(data, len, c->jc)) return st;
-    *w = c->jc.w; *h = c->jc.h;
-    *out = c.release();
-    return MI_OK;
-  } catch (const std::exception &) { return MI_ENCODING_ERROR; }
-}
-void mi_jpeg_coeffs_free(mi_jpeg_coeffs *c) { delete c; }
-
-uint8_t *mi_batch_device_input(mi_batch *b, int index) {
-  if (!b || index < 0 || index >= b->cap) return nullptr;
-  return b->d_pixels.get() + (size_t)index * b->w * b->h * b->channels;
-}
-int mi_batch_read_input(mi_batch *b, int index, uint8_t *dst) {
-  if (!b || !dst || index < 0 || index >= b->cap) return MI_INVALID_ARGUMENT;
-  (void)hipSetDevice(b->device);
-  HIP_OK(hipStreamSynchronize(b->stream));
-  HIP_OK(hipMemcpy(dst, mi_batch_device_input(b, index), (size_t)b->w * b->h * b->channels, hipMemcpyDeviceToHost));
-  return MI_OK;
-}
-
-// images [first, first + count) from pictures in the memory of the batch's device: one ingest_kernel launch on the batch's stream, after whatever
-// src->after_stream holds at this moment.  Strides of 0 mean packed; a row must not be shorter than its packed pixels (torch views -- crops, permuted
-// tensors, padded rows -- all satisfy that).
-int mi_batch_upload_device(mi_batch *b, int first, int count, const mi_device_pixels *src) {
-  if (!b || !src || !src->dev || b->in_flight || first < 0 || count < 1 || first > b->cap - count) return MI_INVALID_ARGUMENT;
-  if ((src->layout != 0 && src->layout != 1) || (src->channels != 3 && src->channels != 4) || src->channels > b->channels) return MI_INVALID_ARGUMENT;   // alpha is never dropped
-  IngestSrc s;
-  s.base = (const uint8_t *)src->dev; s.w = b->w; s.h = b->h; s.layout = src->layout; s.channels = src->channels;
-  const size_t packed_row = (size_t)b->w * (s.layout == 0 ? s.channels : 1);
-  s.row_stride = src->row_stride ? src->row_stride : packed_row;
-  s.inner_stride = src->pixel_or_plane_stride ? src->pixel_or_plane_stride : s.layout == 0 ? (size_t)s.channels : s.row_stride * b->h;
-  s.image_stride = src->image_stride ? src->image_stride : s.layout == 0 ? s.row_stride * b->h : s.inner_stride * s.channels;
-  if (s.row_stride < packed_row || s.inner_stride < (s.layout == 0 ? (size_t)s.channels : (size_t)b->w)) return MI_INVALID_ARGUMENT;
-  (void)hipSetDevice(b->device);
-  if (src->after_stream) {
-    if (!b->ev_src) HIP_OK(hipEventCreateWithFlags(&b->ev_src, hipEventDisableTiming));
-    HIP_OK(hipEventRecord(b->ev_src, (hipStream_t)src->after_stream));
-    HIP_OK(hipStreamWaitEvent(b->stream, b->ev_src, 0));
-  }
-  const dim3 grid(((b->w + 3) / 4 + 63) / 64, b->h, (unsigned)count);
-  uint8_t *const slots = mi_batch_device_input(b, first);
-  if (b->channels == 4) hipLaunchKernelGGL((ingest_kernel<4>), grid, dim3(64), 0, b->stream, s, slots);
-  else hipLaunchKernelGGL((ingest_kernel<3>), grid, dim3(64), 0, b->stream, s, slots);
-  HIP_OK(hipGetLastError());
-  batch_tag(b, first, count, MI_INPUT_RGB);
-  return MI_OK;
-}
-// images [first, first + count) from 8-bit YCbCr planes in the memory of the batch's device: one planes_ingest_kernel launch on the batch's stream, after
-// whatever src->after_stream holds at this moment; the slots are tagged MI_INPUT_YCBCR.  Strides of 0 mean packed.
-int mi_batch_upload_device_ycbcr(mi_batch *b, int first, int count, const mi_device_planes *src) {
-  if (!b || !src || !src->y || !src->cb || b->in_flight || first < 0 || count < 1 || first > b->cap - count || !batch_takes_ycbcr(b)) return MI_INVALID_ARGUMENT;
-  if (!((src->hsub == 1 && src->vsub == 1) || (src->hsub == 2 && (src->vsub == 1 || src->vsub == 2)))) return MI_INVALID_ARGUMENT;
-  PlanesSrc s;
-  s.w = b->w; s.h = b->h; s.hsub = (uint32_t)src->hsub; s.vsub = (uint32_t)src->vsub;
-  s.cw = (b->w + s.hsub - 1) / s.hsub; s.ch = (b->h + s.vsub - 1) / s.vsub;
-  s.cpitch = src->cr ? 1 : 2;
-  s.y = (const uint8_t *)src->y; s.cb = (const uint8_t *)src->cb; s.cr = src->cr ? (const uint8_t *)src->cr : s.cb + 1;
-  const size_t packed_c = (size_t)s.cw * s.cpitch;
-  s.y_row = src->y_row_stride ? src->y_row_stride : b->w; s.c_row = src->c_row_stride ? src->c_row_stride : packed_c;
-  s.y_image = src->y_image_stride ? src->y_image_stride : s.y_row * b->h; s.c_image = src->c_image_stride ? src->c_image_stride : s.c_row * s.ch;
-  if (s.y_row < b->w || s.c_row < packed_c) return MI_INVALID_ARGUMENT;
-  (void)hipSetDevice(b->device);
-  if (src->after_stream) {
-    if (!b->ev_src) HIP_OK(hipEventCreateWithFlags(&b->ev_src, hipEventDisableTiming));
-    HIP_OK(hipEventRecord(b->ev_src, (hipStream_t)src->after_stream));
-    HIP_OK(hipStreamWaitEvent(b->stream, b->ev_src, 0));
-  }
-  const dim3 grid(((b->w + 3) / 4 + 63) / 64, b->h, (unsigned)count);
-  uint8_t *const slots = mi_batch_device_input(b, first);
-  if (b->channels == 4) hipLaunchKernelGGL((planes_ingest_kernel<4>), grid, dim3(64), 0, b->stream, s, slots);
-  else hipLaunchKernelGGL((planes_ingest_kernel<3>), grid, dim3(64), 0, b->stream, s, slots);
-  HIP_OK(hipGetLastError());
-  batch_tag(b, first, count, MI_INPUT_YCBCR);
-  return MI_OK;
-}
-
-// ---- deep input: 16-bit sources into the deep slots (dev_deep.h) ----
-uint16_t *mi_batch_device_input16(mi_batch *b, int index) {
-  if (!b || index < 0 || index >= b->cap) return nullptr;
-  uint16_t *const deep = batch_deep(b);
-  return deep ? deep + (size_t)index * b->w * b->h * b->channels : nullptr;
-}
-int mi_batch_read_input16(mi_batch *b, int index, uint16_t *dst) {
-  if (!b || !dst || index < 0 || index >= b->cap) return MI_INVALID_ARGUMENT;
-  const uint16_t *const src = mi_batch_device_input16(b, index);
-  if (!src) return MI_ENCODING_ERROR;
-  (void)hipSetDevice(b->device);
-  HIP_OK(hipStreamSynchronize(b->stream));
-  HIP_OK(hipMemcpy(dst, src, (size_t)b->w * b->h * b->channels * sizeof(uint16_t), hipMemcpyDeviceToHost));
-  return MI_OK;
+  jpeg_ctx_release_cached();
 }
 size_t mi_batch_footprint(const mi_batch *b) { return b ? batch_footprint(b) : 0; }
 
-// images [first, first + count) from uint16 pictures in the memory of the batch's device: one ingest16_kernel launch on the batch's stream, after whatever
-// src->after_stream holds at this moment; the slots are tagged MI_INPUT_RGB16.  Every check comes before the deep slots are made: a refused call allocates nothing.
-int mi_batch_upload_device16(mi_batch *b, int first, int count, const mi_device_pixels16 *src) {
-  if (!b || !src || !src->dev || b->in_flight || first < 0 || count < 1 || first > b->cap - count) return MI_INVALID_ARGUMENT;
-  if ((src->layout != 0 && src->layout != 1) || !batch_takes_deep(b, src->channels)) return MI_INVALID_ARGUMENT;   // alpha is never dropped; the alpha rules of the kind
-  if (src->bits < 8 || src->bits > 16 || (src->msb_aligned != 0 && src->msb_aligned != 1)) return MI_INVALID_ARGUMENT;
-  if (((uintptr_t)src->dev | src->row_stride | src->pixel_or_plane_stride | src->image_stride) & 1) return MI_INVALID_ARGUMENT;   // uint16 samples
-  Ingest16Src s;
-  s.base = (const uint8_t *)src->dev; s.w = b->w; s.h = b->h; s.layout = src->layout; s.channels = src->channels; s.bits = src->bits; s.msb_aligned = src->msb_aligned;
-  const size_t packed_row = (size_t)b->w * (s.layout == 0 ? s.channels : 1) * 2;
-  s.row_stride = src->row_stride ? src->row_stride : packed_row;
-  s.inner_stride = src->pixel_or_plane_stride ? src->pixel_or_plane_stride : s.layout == 0 ? (size_t)s.channels * 2 : s.row_stride * b->h;
-  s.image_stride = src->image_stride ? src->image_stride : s.layout == 0 ? s.row_stride * b->h : s.inner_stride * s.channels;
-  if (s.row_stride < packed_row || s.inner_stride < (s.layout == 0 ? (size_t)s.channels * 2 : (size_t)b->w * 2)) return MI_INVALID_ARGUMENT;
-  uint16_t *const slots = mi_batch_device_input16(b, first);
-  if (!slots) return MI_ENCODING_ERROR;
-  (void)hipSetDevice(b->device);
-  if (src->after_stream) {
-    if (!b->ev_src) HIP_OK(hipEventCreateWithFlags(&b->ev_src, hipEventDisableTiming));
-    HIP_OK(hipEventRecord(b->ev_src, (hipStream_t)src->after_stream));
-    HIP_OK(hipStreamWaitEvent(b->stream, b->ev_src, 0));
-  }
-  const dim3 grid(((b->w + 3) / 4 + 63) / 64, b->h, (unsigned)count);
-  if (b->channels == 4) hipLaunchKernelGGL((ingest16_kernel<4>), grid, dim3(64), 0, b->stream, s, slots);
-  else hipLaunchKernelGGL((ingest16_kernel<3>), grid, dim3(64), 0, b->stream, s, slots);
-  HIP_OK(hipGetLastError());
-  batch_tag(b, first, count, MI_INPUT_RGB16);
-  return MI_OK;
-}
-// one image of full-scale uint16 host pixels into the deep slot of `index`: a 2-D copy on the batch's stream (3 channels into a 4-channel batch: through a host
-// copy that carries A = 65535), then the stream is waited for.  No pinned staging of its own.
-int mi_batch_upload16(mi_batch *b, int index, const uint16_t *pixels, size_t stride_px, int channels) {
-  if (!b || !pixels || b->in_flight || index < 0 || index >= b->cap || !batch_takes_deep(b, channels)) return MI_INVALID_ARGUMENT;
-  if (stride_px == 0) stride_px = b->w;
-  if (stride_px < b->w) return MI_INVALID_ARGUMENT;
-  uint16_t *const slot = mi_batch_device_input16(b, index);
-  if (!slot) return MI_ENCODING_ERROR;
-  (void)hipSetDevice(b->device);
-  const size_t row = (size_t)b->w * b->channels * sizeof(uint16_t);
-  try {                                                       // nothing may unwind through the C ABI
-    std::vector<uint16_t> wide;
-    if (channels != b->channels) {
-      wide.resize((size_t)b->w * b->h * 4);
-      for (uint32_t y = 0; y < b->h; y++) for (uint32_t x = 0; x < b->w; x++) {
-        const uint16_t *q = pixels + ((size_t)y * stride_px + x) * 3; uint16_t *o = wide.data() + ((size_t)y * b->w + x) * 4;
-        o[0] = q[0]; o[1] = q[1]; o[2] = q[2]; o[3] = 65535;
-      }
-      HIP_OK(hipMemcpyAsync(slot, wide.data(), row * b->h, hipMemcpyHostToDevice, b->stream));
-    } else HIP_OK(hipMemcpy2DAsync(slot, row, pixels, stride_px * channels * sizeof(uint16_t), row, b->h, hipMemcpyHostToDevice, b->stream));
-    HIP_OK(hipStreamSynchronize(b->stream));
-  } catch (const std::exception &) { return MI_ENCODING_ERROR; }
-  batch_tag(b, index, 1, MI_INPUT_RGB16);
-  return MI_OK;
-}
-
-// ---- decoded pixels of the last completed encode (dev_decoded.h) ----
-int mi_batch_uses_alpha(mi_batch *b, int index, int *uses_alpha) {
-  if (!b || !uses_alpha || b->in_flight || !b->encoded || index < 0 || index >= b->n) return MI_INVALID_ARGUMENT;
-  *uses_alpha = (b->channels == 4 && b->alpha_flags[index]) ? 1 : 0;
-  return MI_OK;
-}
-// One decoded_kernel launch over the frame descriptors the encode staged (still on the device, like the planes: nothing after mi_batch_wait writes them until
-// the next encode), after whatever dst->after_stream holds at this moment, then the batch's stream is waited for.  Strides of 0 mean packed.
-int mi_batch_decode_device(mi_batch *b, int first, int count, int which, const mi_device_target *dst) {
-  if (!b || !dst || !dst->dev || b->in_flight || !b->encoded || first < 0 || count < 1 || first > b->n - count) return MI_INVALID_ARGUMENT;
-  if ((which != MI_DECODED_RECON && which != MI_DECODED_SOURCE) || (dst->layout != 0 && dst->layout != 1) || (dst->channels != 3 && dst->channels != 4)) return MI_INVALID_ARGUMENT;
-  if ((size_t)b->n * (b->channels == 4 ? 2 : 1) != b->fs.frames.size()) return MI_INVALID_ARGUMENT;
-  if (dst->channels == 3 && b->channels == 4)
-    for (int i = first; i < first + count; i++) if (b->alpha_flags[i]) return MI_INVALID_ARGUMENT;      // alpha is never dropped
-  DecodedDst d;
-  d.base = (uint8_t *)dst->dev; d.layout = dst->layout; d.channels = dst->channels; d.first = first; d.n = b->n; d.alpha_frames = b->channels == 4; d.source = which == MI_DECODED_SOURCE;
-  const size_t packed_row = (size_t)b->w * (d.layout == 0 ? d.channels : 1);
-  d.row_stride = dst->row_stride ? dst->row_stride : packed_row;
-  d.inner_stride = dst->pixel_or_plane_stride ? dst->pixel_or_plane_stride : d.layout == 0 ? (size_t)d.channels : d.row_stride * b->h;
-  d.image_stride = dst->image_stride ? dst->image_stride : d.layout == 0 ? d.row_stride * b->h : d.inner_stride * d.channels;
-  if (d.row_stride < packed_row || d.inner_stride < (d.layout == 0 ? (size_t)d.channels : (size_t)b->w)) return MI_INVALID_ARGUMENT;
-  if (d.layout == 0 && d.row_stride < (size_t)(b->w - 1) * d.inner_stride + d.channels) return MI_INVALID_ARGUMENT;     // a written row must end before the next one starts
-  (void)hipSetDevice(b->device);
-  if (dst->after_stream) {
-    if (!b->ev_src) HIP_OK(hipEventCreateWithFlags(&b->ev_src, hipEventDisableTiming));
-    HIP_OK(hipEventRecord(b->ev_src, (hipStream_t)dst->after_stream));
-    HIP_OK(hipStreamWaitEvent(b->stream, b->ev_src, 0));
-  }
-  const dim3 grid(((b->w + 3) / 4 + 63) / 64, b->h, (unsigned)count);
-  const FrameDev *const frames = b->fs.d_frames.get();
-  const bool rgb_model = b->fs.frames[first].cfg.matrix == 0;
-  if (b->depth == 8) {
-    if (rgb_model) hipLaunchKernelGGL((decoded_kernel<8, 1>), grid, dim3(64), 0, b->stream, frames, d);
-    else hipLaunchKernelGGL((decoded_kernel<8, 0>), grid, dim3(64), 0, b->stream, frames, d);
-  } else {
-    if (rgb_model) hipLaunchKernelGGL((decoded_kernel<10, 1>), grid, dim3(64), 0, b->stream, frames, d);
-    else hipLaunchKernelGGL((decoded_kernel<10, 0>), grid, dim3(64), 0, b->stream, frames, d);
-  }
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipStreamSynchronize(b->stream));
-  return MI_OK;
-}
-// One image into host memory: the same launch into the batch's own one-image scratch (never the input slot), one D2H.
-int mi_batch_decode(mi_batch *b, int index, int which, int channels, uint8_t *dst) {
-  if (!b || !dst || b->in_flight || !b->encoded || index < 0 || index >= b->n || (channels != 3 && channels != 4)) return MI_INVALID_ARGUMENT;
-  if ((which != MI_DECODED_RECON && which != MI_DECODED_SOURCE) || (channels == 3 && b->channels == 4 && b->alpha_flags[index])) return MI_INVALID_ARGUMENT;   // before the scratch exists: a refused call allocates nothing
-  (void)hipSetDevice(b->device);
-  if (!staging_grow(b->d_decoded, b->d_decoded_cap, (size_t)b->w * b->h * 4)) return MI_ENCODING_ERROR;
-  mi_device_target t;
-  memset(&t, 0, sizeof(t));
-  t.dev = b->d_decoded.get(); t.layout = 0; t.channels = channels;
-  if (const int st = mi_batch_decode_device(b, index, 1, which, &t)) return st;
-  HIP_OK(hipMemcpy(dst, b->d_decoded.get(), (size_t)b->w * b->h * channels, hipMemcpyDeviceToHost));
-  return MI_OK;
-}
-
-// One parsed JPEG into the slot of image `index`: tables + coefficients into the batch's own pinned staging, one H2D and the two kernels of
-// jpeg_decode_to_device on the batch's stream, no sync.  The staging keeps the images uploaded since the stream last drained (room for
-// MI_BATCH_JPEG_STAGED of the first one's size; when the next one does not fit, the stream -- which carries nothing but such uploads then -- is waited
-// for and the staging starts over); the plane buffer is one image's, stream order serialises its users.
-static constexpr size_t MI_BATCH_JPEG_STAGED = 4;
-// (the staging half, shared with mi_batch_resize_jpeg: rows of stride_px pixels at any device pointer)
-static int batch_jpeg_decode(mi_batch *b, const JpegCoeffs &jc, uint8_t *d_out, int channels, size_t stride_px, bool ycc = false) {
-  const size_t need = align_up(jpeg_in_bytes(jc), 256);
-  if (b->jpeg_used + need > b->h_jpeg_cap) {
-    HIP_OK(hipStreamSynchronize(b->stream));
-    b->jpeg_used = 0;
-    if (!staging_grow(b->h_jpeg, b->h_jpeg_cap, MI_BATCH_JPEG_STAGED * need) || !staging_grow(b->d_jpeg, b->d_jpeg_cap, MI_BATCH_JPEG_STAGED * need)) return MI_ENCODING_ERROR;
-  }
-  if (jpeg_plane_bytes(jc) > b->d_jpeg_planes_cap) {
-    HIP_OK(hipStreamSynchronize(b->stream));                  // an earlier image's kernels may still read the buffer that is replaced
-    if (!staging_grow(b->d_jpeg_planes, b->d_jpeg_planes_cap, jpeg_plane_bytes(jc))) return MI_ENCODING_ERROR;
-  }
-  const size_t at = b->jpeg_used; b->jpeg_used += need;
-  return jpeg_decode_to_device(jc, b->h_jpeg.get() + at, b->d_jpeg.get() + at, b->d_jpeg_planes.get(), d_out, channels, stride_px, b->stream, nullptr, ycc);
-}
-int mi_batch_upload_jpeg(mi_batch *b, int index, const mi_jpeg_coeffs *c) {
-  if (!b || !c || b->in_flight || index < 0 || index >= b->cap) return MI_INVALID_ARGUMENT;
-  const JpegCoeffs &jc = c->jc;
-  if (jc.w != b->w || jc.h != b->h) return MI_INVALID_ARGUMENT;
-  (void)hipSetDevice(b->device);
-  if (int st = batch_jpeg_decode(b, jc, mi_batch_device_input(b, index), b->channels, b->w)) return st;
-  batch_tag(b, index, 1, MI_INPUT_RGB);
-  return MI_OK;
-}
-// the same staging, copy and IDCT, then jpeg_ycc_kernel instead of a colour kernel: the slot holds the file's own (Y, Cb, Cr) and is tagged MI_INPUT_YCBCR
-int mi_batch_upload_jpeg_ycbcr(mi_batch *b, int index, const mi_jpeg_coeffs *c) {
-  if (!b || !c || b->in_flight || index < 0 || index >= b->cap) return MI_INVALID_ARGUMENT;
-  const JpegCoeffs &jc = c->jc;
-  if (jc.w != b->w || jc.h != b->h || !batch_takes_ycbcr(b)) return MI_INVALID_ARGUMENT;
-  if (jc.color == JPEG_RGB) return MI_UNSUPPORTED;
-  (void)hipSetDevice(b->device);
-  if (int st = batch_jpeg_decode(b, jc, mi_batch_device_input(b, index), b->channels, b->w, true)) return st;
-  batch_tag(b, index, 1, MI_INPUT_YCBCR);
-  return MI_OK;
-}
-int mi_jpeg_coeffs_info(const mi_jpeg_coeffs *c, int *color, int *hsub, int *vsub) {
-  if (!c) return MI_INVALID_ARGUMENT;
-  const JpegCoeffs &jc = c->jc;
-  if (color) *color = jc.color == JPEG_GREY ? 0 : jc.color == JPEG_YCBCR ? 1 : 2;
-  if (hsub) *hsub = jc.ncomp == 3 ? jc.comp[0].h / jc.comp[1].h : 1;
-  if (vsub) *vsub = jc.ncomp == 3 ? jc.comp[0].v / jc.comp[1].v : 1;
-  return MI_OK;
-}
-
-// ---- PNG input: the host half behind a handle, the device half on the batch's stream ----
-struct mi_png_scanlines { PngScanlines sl; };
-
-// png_read_scanlines behind a handle: host work only (chunk walk, inflate, filter-byte and palette-index checks), the statuses of mi_png_decode_rgba
-int mi_png_parse(const uint8_t *data, size_t len, mi_png_scanlines **out, uint32_t *w, uint32_t *h, int *has_alpha) {
-  if (!data || !out || !w || !h) return MI_INVALID_ARGUMENT;
-  *out = nullptr;
-  try {                                                       // nothing may unwind through the C ABI
-    std::unique_ptr<mi_png_scanlines> p(new mi_png_scanlines);
-    if (const int st = png_read_scanlines(data, len, p->sl)) return st;
-    *w = p->sl.w; *h = p->sl.h;
-    if (has_alpha) *has_alpha = p->sl.has_alpha() ? 1 : 0;
-    *out = p.release();
-    return MI_OK;
-  } catch (const std::exception &) { return MI_ENCODING_ERROR; }
-}
-void mi_png_scanlines_free(mi_png_scanlines *p) { delete p; }
-
-// what one call stages: pass descriptors of the passes that have a filtered row, one image descriptor per image, then per image its palette (colour type 3)
-// and its scanlines, 16-byte aligned; 16 spare bytes at the end
-static size_t png_call_bytes(int count, const mi_png_scanlines *const *png) {
-  size_t n = align_up((size_t)count * 7 * sizeof(PngPassDev), 16) + align_up((size_t)count * sizeof(PngImageDev), 16);
-  for (int i = 0; i < count; i++) n += (png[i]->sl.ctype == 3 ? 1024 : 0) + align_up(png[i]->sl.raw.size(), 16);
-  return align_up(n + 16, 256);
-}
-
-// room for `bytes` of PNG staging, pinned and on the device, made ahead of the first mi_batch_upload_png (the stream worker does this on the thread that creates the batch
-// object, beside the loaders: on the worker's own thread the 35 - 55 ms of a first call's allocation delay the first run); idle batches only, false = could not
-static bool batch_reserve_png(mi_batch *b, size_t bytes) {
-  if (!b || b->in_flight || b->png_used) return false;
-  if (bytes <= b->h_png_cap && bytes <= b->d_png_cap) return true;
-  (void)hipSetDevice(b->device);
-  if (hipStreamSynchronize(b->stream) != hipSuccess) return false;
-  return staging_grow(b->h_png, b->h_png_cap, bytes) && staging_grow(b->d_png, b->d_png_cap, bytes);
-}
-
-// images [first, first + count) from parsed PNG files of the batch's size: descriptors, palettes and scanlines into the batch's pinned staging, one H2D, then
-// png_unfilter_kernel (one workgroup per pass that has a filtered row, all images in one launch) and png_expand_kernel on the batch's stream, no sync.
-// The staging keeps the calls since the stream last drained; when the next one does not fit, the stream is waited for and the staging starts over, grown to the call.
-// (the body, shared with mi_batch_resize_png: `count` checked files of w x h into packed pictures of `channels` channels, back to back from `slots` on)
-static int batch_png_expand(mi_batch *b, int count, const mi_png_scanlines *const *png, uint32_t w, uint32_t h, int channels, void *slots, bool deep = false) {
-  const size_t need = png_call_bytes(count, png);
-  if (b->png_used + need > b->h_png_cap || b->png_used + need > b->d_png_cap) {
-    HIP_OK(hipStreamSynchronize(b->stream));                  // earlier calls' copies and kernels may still use the buffers that start over or are replaced
-    b->png_used = 0;
-    if (!staging_grow(b->h_png, b->h_png_cap, need) || !staging_grow(b->d_png, b->d_png_cap, need)) return MI_ENCODING_ERROR;
-  }
-  const size_t at = b->png_used; b->png_used += need;
-  uint8_t *const hb = b->h_png.get() + at;
-  PngPassDev *passes = (PngPassDev *)hb;
-  const size_t img_at = align_up((size_t)count * 7 * sizeof(PngPassDev), 16);
-  PngImageDev *imgs = (PngImageDev *)(hb + img_at);
-  size_t pos = img_at + align_up((size_t)count * sizeof(PngImageDev), 16);
-  uint32_t npass = 0, max_rows = 0;
-  for (int i = 0; i < count; i++) {
-    const PngScanlines &sl = png[i]->sl;
-    PngImageDev &im = imgs[i]; memset(&im, 0, sizeof(im));
-    im.depth = (uint32_t)sl.depth; im.ctype = (uint32_t)sl.ctype; im.interlace = (uint32_t)sl.interlace; im.has_key = sl.has_key ? 1 : 0;
-    for (int c = 0; c < 3; c++) im.key[c] = sl.key[c];
-    if (sl.ctype == 3) { im.palette_off = at + pos; memcpy(hb + pos, sl.palette, 1024); pos += 1024; }
-    memcpy(hb + pos, sl.raw.data(), sl.raw.size());
-    for (int p = 0; p < sl.npass; p++) {
-      const PngPass &ps = sl.pass[p];
-      // the Adam7 pass this is: dx, dy and x0 tell (a non-interlaced file has the one pass 0)
-      const int id = !sl.interlace ? 0 : ps.dy == 8 ? (ps.dx == 4 ? 2 : ps.x0 ? 1 : 0) : ps.dy == 4 ? (ps.dx == 4 ? 3 : 4) : ps.dx == 2 ? 5 : 6;
-      im.pass_off[id] = at + pos + ps.off; im.pass_rowbytes[id] = ps.rowbytes;
-      bool filtered = false;
-      for (uint32_t y = 0; y < ps.rows && !filtered; y++) filtered = sl.raw[ps.off + (size_t)y * (ps.rowbytes + 1)] != 0;
-      if (!filtered) continue;                                // nothing to undo
-      passes[npass++] = PngPassDev{ at + pos + ps.off, ps.rows, ps.rowbytes, (uint32_t)sl.bpp, 0 };
-      max_rows = std::max(max_rows, ps.rows);
-    }
-    pos += align_up(sl.raw.size(), 16);
-  }
-  uint8_t *const db = b->d_png.get();
-  HIP_OK(hipMemcpyAsync(db + at, hb, pos, hipMemcpyHostToDevice, b->stream));
-  if (npass) {
-    const unsigned waves = std::min<unsigned>(MI_PNG_WAVES, (max_rows + 63) / 64);
-    hipLaunchKernelGGL(png_unfilter_kernel, dim3(npass), dim3(64 * waves), 0, b->stream, db, (const PngPassDev *)(db + at));
-  }
-  const dim3 grid(((w + 3) / 4 + 63) / 64, h, (unsigned)count);
-  if (deep) {                                                 // files of bit depth 16 into deep slots: both bytes of every sample
-    if (channels == 4) hipLaunchKernelGGL((png_expand16_kernel<4>), grid, dim3(64), 0, b->stream, (const uint8_t *)db, (const PngImageDev *)(db + at + img_at), w, h, (uint16_t *)slots);
-    else hipLaunchKernelGGL((png_expand16_kernel<3>), grid, dim3(64), 0, b->stream, (const uint8_t *)db, (const PngImageDev *)(db + at + img_at), w, h, (uint16_t *)slots);
-  } else if (channels == 4) hipLaunchKernelGGL((png_expand_kernel<4>), grid, dim3(64), 0, b->stream, (const uint8_t *)db, (const PngImageDev *)(db + at + img_at), w, h, (uint8_t *)slots);
-  else hipLaunchKernelGGL((png_expand_kernel<3>), grid, dim3(64), 0, b->stream, (const uint8_t *)db, (const PngImageDev *)(db + at + img_at), w, h, (uint8_t *)slots);
-  HIP_OK(hipGetLastError());
-  return MI_OK;
-}
-int mi_batch_upload_png(mi_batch *b, int first, int count, const mi_png_scanlines *const *png) {
-  if (!b || !png || b->in_flight || first < 0 || count < 1 || first > b->cap - count) return MI_INVALID_ARGUMENT;
-  for (int i = 0; i < count; i++) {
-    if (!png[i] || png[i]->sl.w != b->w || png[i]->sl.h != b->h) return MI_INVALID_ARGUMENT;
-    if (b->channels == 3 && png[i]->sl.has_alpha()) return MI_INVALID_ARGUMENT;      // alpha is never dropped
-  }
-  (void)hipSetDevice(b->device);
-  if (int st = batch_png_expand(b, count, png, b->w, b->h, b->channels, mi_batch_device_input(b, first))) return st;
-  batch_tag(b, first, count, MI_INPUT_RGB);
-  return MI_OK;
-}
-
-// mi_batch_upload_png for 16-bit masters: a handle of bit depth 16 is unfiltered as above and expanded by png_expand16_kernel into its deep slot (kind
-// MI_INPUT_RGB16), every other handle goes exactly the way mi_batch_upload_png sends it (kind MI_INPUT_RGB).  Neighbours that go the same way share one call's
-// staging, copy and launches.  Every handle is checked before anything is staged or allocated.
-static bool png_goes_deep(const mi_png_scanlines *p) { return p->sl.depth == 16 && p->sl.ctype != 3; }
-int mi_png_scanlines_info(const mi_png_scanlines *p, int *color_type, int *bit_depth) {
-  if (!p) return MI_INVALID_ARGUMENT;
-  if (color_type) *color_type = p->sl.ctype;
-  if (bit_depth) *bit_depth = p->sl.depth;
-  return MI_OK;
-}
-int mi_batch_upload_png_deep(mi_batch *b, int first, int count, const mi_png_scanlines *const *png) {
-  if (!b || !png || b->in_flight || first < 0 || count < 1 || first > b->cap - count) return MI_INVALID_ARGUMENT;
-  bool any_deep = false;
-  for (int i = 0; i < count; i++) {
-    if (!png[i] || png[i]->sl.w != b->w || png[i]->sl.h != b->h) return MI_INVALID_ARGUMENT;
-    if (b->channels == 3 && png[i]->sl.has_alpha()) return MI_INVALID_ARGUMENT;      // alpha is never dropped
-    if (png_goes_deep(png[i])) { any_deep = true; if (!batch_takes_deep(b, png[i]->sl.has_alpha() ? 4 : 3)) return MI_INVALID_ARGUMENT; }
-  }
-  if (any_deep && !batch_deep(b)) return MI_ENCODING_ERROR;
-  (void)hipSetDevice(b->device);
-  for (int i = 0; i < count;) {
-    const bool deep = png_goes_deep(png[i]);
-    int j = i + 1;
-    while (j < count && png_goes_deep(png[j]) == deep) j++;
-    void *const slots = deep ? (void *)mi_batch_device_input16(b, first + i) : (void *)mi_batch_device_input(b, first + i);
-    if (int st = batch_png_expand(b, j - i, png + i, b->w, b->h, b->channels, slots, deep)) return st;
-    batch_tag(b, first + i, j - i, deep ? MI_INPUT_RGB16 : MI_INPUT_RGB);
-    i = j;
-  }
-  return MI_OK;
-}
-
-// ---- resize on input: a source of any size is resampled on the batch's stream into the slot (kernels: dev_resample.h) ----
-// The filters and the coefficients of one axis, as Pillow computes them for 8-bit pictures (Image.resize, reducing_gap=None): all in double, in this order.
-static double resample_filter(int filter, double x) {
-  switch (filter) {
-    case MI_RESAMPLE_BOX: return x > -0.5 && x <= 0.5 ? 1.0 : 0.0;
-    case MI_RESAMPLE_BILINEAR: if (x < 0.0) x = -x; return x < 1.0 ? 1.0 - x : 0.0;
-    case MI_RESAMPLE_BICUBIC: {
-      const double a = -0.5;
-      if (x < 0.0) x = -x;
-      if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
-      if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
-      return 0.0;
-    }
-    default: {
-      if (!(-3.0 <= x && x < 3.0)) return 0.0;
-      auto sinc = [](double v) { if (v == 0.0) return 1.0; v = v * 3.14159265358979323846; return sin(v) / v; };
-      return sinc(x) * sinc(x / 3);
-    }
-  }
-}
-static size_t resample_ksize(uint32_t in, uint32_t out, int filter) {
-  if (in == out) return 1;
-  static const double supports[4] = { 0.5, 1.0, 2.0, 3.0 };
-  const double scale = (double)in / out;
-  return (size_t)ceil(supports[filter] * (scale < 1.0 ? 1.0 : scale)) * 2 + 1;
-}
-static size_t resample_axis_bytes(uint32_t in, uint32_t out, int filter) { return align_up((size_t)out * 8, 16) + align_up(resample_ksize(in, out, filter) * out * 4, 16); }
-// bounds[2 i] = first sample, bounds[2 i + 1] = taps of output sample i; tap j of output i at taps[j * out + i], 22 fractional bits (unused ones 0).
-// An axis that keeps its length: the identity (its pass is skipped: the kernel moves the samples unchanged).
-static void resample_axis(uint32_t in, uint32_t out, int filter, uint32_t *bounds, int32_t *taps) {
-  const size_t ksize = resample_ksize(in, out, filter);
-  if (in == out) { for (uint32_t i = 0; i < out; i++) { bounds[2 * i] = i; bounds[2 * i + 1] = 1; taps[i] = 1 << MI_RS_BITS; } return; }
-  static const double supports[4] = { 0.5, 1.0, 2.0, 3.0 };
-  const double scale = (double)in / out, fs = scale < 1.0 ? 1.0 : scale, support = supports[filter] * fs;
-  std::vector<double> k(ksize);
-  memset(taps, 0, ksize * out * sizeof(int32_t));
-  for (uint32_t i = 0; i < out; i++) {
-    const double centre = (i + 0.5) * scale;
-    int xmin = (int)(centre - support + 0.5), xmax = (int)(centre + support + 0.5);
-    if (xmin < 0) xmin = 0;
-    if (xmax > (int)in) xmax = (int)in;
-    const int n = xmax - xmin;
-    double sum = 0.0;
-    for (int j = 0; j < n; j++) { k[j] = resample_filter(filter, (j + xmin - centre + 0.5) / fs); sum += k[j]; }
-    for (int j = 0; j < n; j++) {
-      const double v = sum != 0.0 ? k[j] / sum : k[j];
-      taps[(size_t)j * out + i] = v < 0 ? (int)(-0.5 + v * (1 << MI_RS_BITS)) : (int)(0.5 + v * (1 << MI_RS_BITS));
-    }
-    bounds[2 * i] = (uint32_t)xmin; bounds[2 * i + 1] = (uint32_t)n;
-  }
-}
-
-// the scratch holds `bytes` afterwards; an earlier call's kernels may still use the buffer that is replaced, so the stream is waited for first
-static int batch_reserve_scratch(mi_batch *b, size_t bytes) {
-  if (bytes <= b->d_rs_scratch_cap) return MI_OK;
-  HIP_OK(hipStreamSynchronize(b->stream));
-  return staging_grow(b->d_rs_scratch, b->d_rs_scratch_cap, bytes) ? MI_OK : MI_ENCODING_ERROR;
-}
-
-// The two passes: `count` pictures of s.w x s.h described by s -> slots [first, first + count).  The tables go into the batch's pinned staging and over in
-// one H2D (a call with the sizes and the filter of the one before it finds them on the device); the intermediate lies `inter_at` bytes into the scratch,
-// which the caller has reserved up to inter_at + resample_inter_bytes().  Stream order serialises the users of the scratch.  No sync.
-static size_t resample_inter_bytes(int count, uint32_t src_h, uint32_t dst_w) { return (size_t)count * src_h * align_up(dst_w, 4) * 4; }
-static int batch_resample(mi_batch *b, int first, int count, const IngestSrc &s, int filter, size_t inter_at) {
-  const uint32_t key[5] = { s.w, s.h, b->w, b->h, (uint32_t)filter + 1 };
-  const size_t h_bytes = resample_axis_bytes(s.w, b->w, filter), need = align_up(h_bytes + resample_axis_bytes(s.h, b->h, filter), 256);
-  size_t at = b->rs_key_at;
-  if (memcmp(key, b->rs_key, sizeof(key)) != 0) {
-    if (b->rs_used + need > b->h_rs_cap || b->rs_used + need > b->d_rs_cap) {
-      HIP_OK(hipStreamSynchronize(b->stream));                // earlier calls' copies and kernels may still use the buffers that start over or are replaced
-      b->rs_used = 0; b->rs_key[4] = 0;
-      if (!staging_grow(b->h_rs, b->h_rs_cap, need) || !staging_grow(b->d_rs, b->d_rs_cap, need)) return MI_ENCODING_ERROR;
-    }
-    at = b->rs_used; b->rs_used += need;
-    uint8_t *const hb = b->h_rs.get() + at;
-    resample_axis(s.w, b->w, filter, (uint32_t *)hb, (int32_t *)(hb + align_up((size_t)b->w * 8, 16)));
-    resample_axis(s.h, b->h, filter, (uint32_t *)(hb + h_bytes), (int32_t *)(hb + h_bytes + align_up((size_t)b->h * 8, 16)));
-    HIP_OK(hipMemcpyAsync(b->d_rs.get() + at, hb, need, hipMemcpyHostToDevice, b->stream));
-    memcpy(b->rs_key, key, sizeof(key)); b->rs_key_at = at;
-  }
-  const uint8_t *const db = b->d_rs.get() + at;
-  const uint32_t *const hbounds = (const uint32_t *)db, *const vbounds = (const uint32_t *)(db + h_bytes);
-  const int32_t *const htaps = (const int32_t *)(db + align_up((size_t)b->w * 8, 16)), *const vtaps = (const int32_t *)(db + h_bytes + align_up((size_t)b->h * 8, 16));
-  const uint32_t pitch = (uint32_t)align_up(b->w, 4);
-  uint32_t *const inter = (uint32_t *)(b->d_rs_scratch.get() + inter_at);
-  hipLaunchKernelGGL(resample_h_kernel, dim3((b->w + MI_RS_TW - 1) / MI_RS_TW, (s.h + MI_RS_TH - 1) / MI_RS_TH, (unsigned)count), dim3(64 * MI_RS_TH), 0, b->stream,
-                     s, hbounds, htaps, b->w, pitch, inter);
-  const dim3 grid(((b->w + 3) / 4 + 63) / 64, b->h, (unsigned)count);
-  uint8_t *const slots = mi_batch_device_input(b, first);
-  const int alpha = s.channels == 4 ? 1 : 0;
-  if (b->channels == 4) hipLaunchKernelGGL((resample_v_kernel<4>), grid, dim3(64), 0, b->stream, (const uint32_t *)inter, s.h, pitch, vbounds, vtaps, b->w, b->h, alpha, slots);
-  else hipLaunchKernelGGL((resample_v_kernel<3>), grid, dim3(64), 0, b->stream, (const uint32_t *)inter, s.h, pitch, vbounds, vtaps, b->w, b->h, alpha, slots);
-  HIP_OK(hipGetLastError());
-  batch_tag(b, first, count, MI_INPUT_RGB);
-  return MI_OK;
-}
-static bool resample_filter_known(int filter) { return filter >= MI_RESAMPLE_BOX && filter <= MI_RESAMPLE_LANCZOS3; }
-static bool resample_extent_ok(uint32_t w, uint32_t h) { return w >= 1 && h >= 1 && w <= 65536 && h <= 65536; }     // what a batch may have (the grids and the tables count on it)
-
-// images [first, first + count) from pictures of src_w x src_h in the memory of the batch's device; of the batch's own size: mi_batch_upload_device
-int mi_batch_resize_device(mi_batch *b, int first, int count, const mi_device_pixels *src, uint32_t src_w, uint32_t src_h, int filter) {
-  if (!b || !src || !src->dev || b->in_flight || first < 0 || count < 1 || first > b->cap - count || !resample_filter_known(filter) || !resample_extent_ok(src_w, src_h)) return MI_INVALID_ARGUMENT;
-  if ((src->layout != 0 && src->layout != 1) || (src->channels != 3 && src->channels != 4) || src->channels > b->channels) return MI_INVALID_ARGUMENT;   // alpha is never dropped
-  if (src_w == b->w && src_h == b->h) return mi_batch_upload_device(b, first, count, src);
-  IngestSrc s;
-  s.base = (const uint8_t *)src->dev; s.w = src_w; s.h = src_h; s.layout = src->layout; s.channels = src->channels;
-  const size_t packed_row = (size_t)src_w * (s.layout == 0 ? s.channels : 1);
-  s.row_stride = src->row_stride ? src->row_stride : packed_row;
-  s.inner_stride = src->pixel_or_plane_stride ? src->pixel_or_plane_stride : s.layout == 0 ? (size_t)s.channels : s.row_stride * src_h;
-  s.image_stride = src->image_stride ? src->image_stride : s.layout == 0 ? s.row_stride * src_h : s.inner_stride * s.channels;
-  if (s.row_stride < packed_row || s.inner_stride < (s.layout == 0 ? (size_t)s.channels : (size_t)src_w)) return MI_INVALID_ARGUMENT;
-  (void)hipSetDevice(b->device);
-  if (int st = batch_reserve_scratch(b, resample_inter_bytes(count, src_h, b->w))) return st;
-  if (src->after_stream) {
-    if (!b->ev_src) HIP_OK(hipEventCreateWithFlags(&b->ev_src, hipEventDisableTiming));
-    HIP_OK(hipEventRecord(b->ev_src, (hipStream_t)src->after_stream));
-    HIP_OK(hipStreamWaitEvent(b->stream, b->ev_src, 0));
-  }
-  return batch_resample(b, first, count, s, filter, 0);
-}
-
-// a decoded source at the start of the scratch, packed, `channels` channels: what the two forms below resample
-static IngestSrc resample_scratch_source(const mi_batch *b, uint32_t w, uint32_t h, int channels) {
-  IngestSrc s;
-  s.base = b->d_rs_scratch.get(); s.w = w; s.h = h; s.layout = 0; s.channels = channels;
-  s.inner_stride = (size_t)channels; s.row_stride = (size_t)w * channels; s.image_stride = s.row_stride * h;
-  return s;
-}
-
-// one parsed JPEG of any size into slot `index`: decoded into the scratch as RGB (mi_batch_upload_jpeg's kernels), then the two passes; of the batch's own size: mi_batch_upload_jpeg
-int mi_batch_resize_jpeg(mi_batch *b, int index, const mi_jpeg_coeffs *c, int filter) {
-  if (!b || !c || b->in_flight || index < 0 || index >= b->cap || !resample_filter_known(filter)) return MI_INVALID_ARGUMENT;
-  const JpegCoeffs &jc = c->jc;
-  if (jc.w == b->w && jc.h == b->h) return mi_batch_upload_jpeg(b, index, c);
-  if (!resample_extent_ok(jc.w, jc.h)) return MI_INVALID_ARGUMENT;
-  (void)hipSetDevice(b->device);
-  const size_t inter_at = align_up((size_t)jc.w * jc.h * 3, 256);
-  if (int st = batch_reserve_scratch(b, inter_at + resample_inter_bytes(1, jc.h, b->w))) return st;
-  if (int st = batch_jpeg_decode(b, jc, b->d_rs_scratch.get(), 3, jc.w)) return st;
-  return batch_resample(b, index, 1, resample_scratch_source(b, jc.w, jc.h, 3), filter, inter_at);
-}
-
-// one parsed PNG of any size into slot `index`: unfiltered and expanded into the scratch (RGBA when the file has alpha or tRNS, else RGB), then the two passes; of
-// the batch's own size: mi_batch_upload_png
-int mi_batch_resize_png(mi_batch *b, int index, const mi_png_scanlines *p, int filter) {
-  if (!b || !p || b->in_flight || index < 0 || index >= b->cap || !resample_filter_known(filter)) return MI_INVALID_ARGUMENT;
-  const int channels = p->sl.has_alpha() ? 4 : 3;
-  if (channels > b->channels) return MI_INVALID_ARGUMENT;     // alpha is never dropped
-  if (p->sl.w == b->w && p->sl.h == b->h) return mi_batch_upload_png(b, index, 1, &p);
-  if (!resample_extent_ok(p->sl.w, p->sl.h)) return MI_INVALID_ARGUMENT;
-  (void)hipSetDevice(b->device);
-  const size_t inter_at = align_up((size_t)p->sl.w * p->sl.h * channels, 256);
-  if (int st = batch_reserve_scratch(b, inter_at + resample_inter_bytes(1, p->sl.h, b->w))) return st;
-  if (int st = batch_png_expand(b, 1, &p, p->sl.w, p->sl.h, channels, b->d_rs_scratch.get())) return st;
-  return batch_resample(b, index, 1, resample_scratch_source(b, p->sl.w, p->sl.h, channels), filter, inter_at);
-}
-
-// ravif::Encoder::encode_rgba / encode_rgb for a picture in the memory of device e->device (channels 4 / 3 as src->channels says)
-int mi_ravif_encode_device(const mi_ravif_encoder *e, const mi_device_pixels *src, uint32_t w, uint32_t h, mi_encoded_image *out) {
-  if (!e || !src || !src->dev || !out || w < 1 || h < 1 || (src->channels != 3 && src->channels != 4)) return MI_INVALID_ARGUMENT;
-  mi_batch *b = pool_acquire(e, 1, w, h, src->channels);
+// ---- the one-call entry points: a pooled batch of one image of w x h, filled by `fill`, encoded, its file handed out ----
+static const auto encode_pooled = [](const mi_ravif_encoder *e, uint32_t w, uint32_t h, int channels, mi_encoded_image *out, auto fill) -> int {
+  if (!e || !out || w < 1 || h < 1) return MI_INVALID_ARGUMENT;
+  mi_batch *b = pool_acquire(e, 1, w, h, channels);
   if (!b) return mi_device_count() > e->device ? MI_INVALID_ARGUMENT : MI_NO_DEVICE;
-  int st = mi_batch_upload_device(b, 0, 1, src);
+  int st = fill(b);
   if (st == MI_OK) st = mi_batch_encode(b);
   if (st == MI_OK) st = mi_batch_get(b, 0, out);
   pool_release(b);
   return st;
+};
+static int encode_one(const mi_ravif_encoder *e, const uint8_t *px, int channels, uint32_t w, uint32_t h, size_t stride_px, mi_encoded_image *out) {
+  if (!px) return MI_INVALID_ARGUMENT;
+  return encode_pooled(e, w, h, channels, out, [&](mi_batch *b) { return mi_batch_upload(b, 0, px, stride_px); });
+}
+int mi_ravif_encode_rgba(const mi_ravif_encoder *e, const uint8_t *rgba, uint32_t w, uint32_t h, size_t stride_px, mi_encoded_image *out) { return encode_one(e, rgba, 4, w, h, stride_px, out); }
+int mi_ravif_encode_rgb(const mi_ravif_encoder *e, const uint8_t *rgb, uint32_t w, uint32_t h, size_t stride_px, mi_encoded_image *out) { return encode_one(e, rgb, 3, w, h, stride_px, out); }
+// ravif::Encoder::encode_rgba / encode_rgb for a picture in the memory of device e->device (channels 4 / 3 as src->channels says)
+int mi_ravif_encode_device(const mi_ravif_encoder *e, const mi_device_pixels *src, uint32_t w, uint32_t h, mi_encoded_image *out) {
+  if (!src || !src->dev || (src->channels != 3 && src->channels != 4)) return MI_INVALID_ARGUMENT;
+  return encode_pooled(e, w, h, src->channels, out, [&](mi_batch *b) { return mi_batch_upload_device(b, 0, 1, src); });
 }
 // the same for a uint16 picture in the memory of device e->device (mi_batch_upload_device16)
 int mi_ravif_encode_device16(const mi_ravif_encoder *e, const mi_device_pixels16 *src, uint32_t w, uint32_t h, mi_encoded_image *out) {
-  if (!e || !src || !src->dev || !out || w < 1 || h < 1 || (src->channels != 3 && src->channels != 4)) return MI_INVALID_ARGUMENT;
-  mi_batch *b = pool_acquire(e, 1, w, h, src->channels);
-  if (!b) return mi_device_count() > e->device ? MI_INVALID_ARGUMENT : MI_NO_DEVICE;
-  int st = mi_batch_upload_device16(b, 0, 1, src);
-  if (st == MI_OK) st = mi_batch_encode(b);
-  if (st == MI_OK) st = mi_batch_get(b, 0, out);
-  pool_release(b);
-  return st;
+  if (!src || !src->dev || (src->channels != 3 && src->channels != 4)) return MI_INVALID_ARGUMENT;
+  return encode_pooled(e, w, h, src->channels, out, [&](mi_batch *b) { return mi_batch_upload_device16(b, 0, 1, src); });
 }
 // the same for YCbCr planes in the memory of device e->device: the file of a 3-channel batch fed through mi_batch_upload_device_ycbcr
 int mi_ravif_encode_device_ycbcr(const mi_ravif_encoder *e, const mi_device_planes *src, uint32_t w, uint32_t h, mi_encoded_image *out) {
-  if (!e || !src || !src->y || !src->cb || !out || w < 1 || h < 1) return MI_INVALID_ARGUMENT;
-  mi_batch *b = pool_acquire(e, 1, w, h, 3);
-  if (!b) return mi_device_count() > e->device ? MI_INVALID_ARGUMENT : MI_NO_DEVICE;
-  int st = mi_batch_upload_device_ycbcr(b, 0, 1, src);
-  if (st == MI_OK) st = mi_batch_encode(b);
-  if (st == MI_OK) st = mi_batch_get(b, 0, out);
-  pool_release(b);
-  return st;
+  if (!src || !src->y || !src->cb) return MI_INVALID_ARGUMENT;
+  return encode_pooled(e, w, h, 3, out, [&](mi_batch *b) { return mi_batch_upload_device_ycbcr(b, 0, 1, src); });
 }
 // the same for a picture of src_w x src_h that is resampled to w x h on the way in
 int mi_ravif_encode_device_resized(const mi_ravif_encoder *e, const mi_device_pixels *src, uint32_t src_w, uint32_t src_h, uint32_t w, uint32_t h, int filter, mi_encoded_image *out) {
-  if (!e || !src || !src->dev || !out || w < 1 || h < 1 || (src->channels != 3 && src->channels != 4)) return MI_INVALID_ARGUMENT;
-  mi_batch *b = pool_acquire(e, 1, w, h, src->channels);
-  if (!b) return mi_device_count() > e->device ? MI_INVALID_ARGUMENT : MI_NO_DEVICE;
-  int st = mi_batch_resize_device(b, 0, 1, src, src_w, src_h, filter);
-  if (st == MI_OK) st = mi_batch_encode(b);
-  if (st == MI_OK) st = mi_batch_get(b, 0, out);
-  pool_release(b);
-  return st;
+  if (!src || !src->dev || (src->channels != 3 && src->channels != 4)) return MI_INVALID_ARGUMENT;
+  return encode_pooled(e, w, h, src->channels, out, [&](mi_batch *b) { return mi_batch_resize_device(b, 0, 1, src, src_w, src_h, filter); });
+}
+
+// ---- the stream worker: the kinds of source it takes (MI_SOURCE_*) ----
+static bool is_jpeg(int kind) { return kind == MI_SOURCE_JPEG || kind == MI_SOURCE_JPEG_YCBCR; }
+static bool is_png(int kind) { return kind == MI_SOURCE_PNG || kind == MI_SOURCE_PNG_DEEP; }
+// MI_OK, or the status of a fetched source that names nothing usable or that its upload call would refuse: it fails alone, not with its run
+static int source_refusal(const mi_ravif_encoder &e, const mi_image_source &src) {
+  const mi_image_desc &x = src.desc;
+  const bool have = src.kind == MI_SOURCE_HOST ? x.pixels != nullptr : is_jpeg(src.kind) ? src.jpeg && src.jpeg->jc.w == x.width && src.jpeg->jc.h == x.height :
+                    is_png(src.kind) && src.png && src.png->sl.w == x.width && src.png->sl.h == x.height && !(x.channels == 3 && src.png->sl.has_alpha());
+  if (!have || !x.width || !x.height || (x.channels != 3 && x.channels != 4)) return MI_INVALID_ARGUMENT;
+  if (src.kind == MI_SOURCE_JPEG_YCBCR && !batch_takes_ycbcr(e, x.channels)) return MI_INVALID_ARGUMENT;      // the batch's rule first, then the file's colour, as in mi_batch_upload_jpeg_ycbcr
+  if (src.kind == MI_SOURCE_JPEG_YCBCR && src.jpeg->jc.color == JPEG_RGB) return MI_UNSUPPORTED;
+  if (src.kind == MI_SOURCE_PNG_DEEP && png_goes_deep(src.png) && !batch_takes_deep(e, x.channels, src.png->sl.has_alpha() ? 4 : 3)) return MI_INVALID_ARGUMENT;
+  return MI_OK;
 }
 
 // The reference's files.into_par_iter() (src/main.rs:223) over the GPUs of one node: images are independent, so a host
@@ -1329,9 +549,10 @@ int mi_ravif_encode_device_resized(const mi_ravif_encoder *e, const mi_device_pi
 // batch (no collective, no cross-device traffic).  status[i] receives the per-image result; returns the first failure.
 // Streaming form of the fan-out: image i is obtained through `fetch(user, i, &desc)` when a worker is about to stage it (the
 // call may block until the pixels exist -- e.g. until a loader thread has decoded the file), so loading, upload, encoding and
-// assembly of consecutive runs overlap.  fetch returns MI_OK or a status that becomes the image's status.  An image is host pixels (kind 0) or the
-// coefficients of a parsed JPEG (kind 1; kind 3: the same, kept as the file's own YCbCr) or the scanlines of a parsed PNG (kind 2; kind 4: the same, a file of bit depth 16 through its deep slot), whose pixels come into being in the batch's HBM input slot; mi_ravif_encode_stream is this
-// with kind 0 throughout.
+// assembly of consecutive runs overlap.  fetch returns MI_OK or a status that becomes the image's status.  An image is host pixels (MI_SOURCE_HOST) or the
+// coefficients of a parsed JPEG (MI_SOURCE_JPEG; _JPEG_YCBCR: the same, kept as the file's own YCbCr) or the scanlines of a parsed PNG (MI_SOURCE_PNG; _PNG_DEEP: the
+// same, a file of bit depth 16 through its deep slot), whose pixels come into being in the batch's HBM input slot; mi_ravif_encode_stream is this
+// with MI_SOURCE_HOST throughout.
 int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source_fn fetch, mi_release_fn release, void *user, mi_encoded_image *out, int *status, const int *devices, int ndev) {
   if (!e || !fetch || (n && !out)) return MI_INVALID_ARGUMENT;
   const int have = mi_device_count();
@@ -1368,6 +589,8 @@ int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source
     struct Shape { uint32_t w, h; int ch; size_t cap; Slot slot[NSLOT_MAX]; int next = 0; size_t runs = 0, last_use = 0; };
     std::vector<std::unique_ptr<Shape>> shapes;
     size_t live_bytes = 0, tick = 0;
+    auto charge = [&](Slot &sl, size_t extra) { sl.bytes += extra; live_bytes += extra; };      // what a slot's object holds on the device and pinned counts against the worker's budget
+    auto reset_accounting = [&](Slot &sl) { live_bytes -= std::min(live_bytes, sl.bytes); sl.bytes = 0; sl.jpeg = false; sl.deep = false; sl.png_bytes = 0; };
     auto collect = [&](Slot &sl) {
       if (!sl.busy) return;
       const int rc = mi_batch_wait(sl.b);
@@ -1380,7 +603,7 @@ int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source
       collect(sl);
       if (sl.making.valid()) sl.b = sl.making.get();
       if (sl.b) mi_batch_destroy(sl.b);
-      sl.b = nullptr; live_bytes -= std::min(live_bytes, sl.bytes); sl.bytes = 0; sl.jpeg = false; sl.deep = false; sl.png_bytes = 0;
+      sl.b = nullptr; reset_accounting(sl);
     };
     auto make_room = [&](Shape *keep, size_t need) {
       while (live_bytes + need > budget) {
@@ -1420,11 +643,11 @@ int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source
       const int j = sh->next; sh->next = (j + 1) % NSLOT;
       Slot &sl = sh->slot[j];
       collect(sl);                                           // the slot's previous run, if any
-      bool any_host = false; for (size_t k : run) any_host |= d[k].kind == 0;
-      size_t png_run = 0; { std::vector<const mi_png_scanlines *> all; for (size_t k : run) if (d[k].kind == 2 || d[k].kind == 4) all.push_back(d[k].png); if (!all.empty()) png_run = png_call_bytes((int)all.size(), all.data()); }
+      bool any_host = false; for (size_t k : run) any_host |= d[k].kind == MI_SOURCE_HOST;
+      size_t png_run = 0; { std::vector<const mi_png_scanlines *> all; for (size_t k : run) if (is_png(d[k].kind)) all.push_back(d[k].png); if (!all.empty()) png_run = png_call_bytes((int)all.size(), all.data()); }
       ensure_slot(sh, j, any_host, png_run);
       if (sl.making.valid()) sl.b = sl.making.get();
-      if (!sl.b) { live_bytes -= std::min(live_bytes, sl.bytes); sl.bytes = 0; sl.jpeg = false; sl.deep = false; sl.png_bytes = 0; }      // the object could not be made: nothing of it is resident
+      if (!sl.b) reset_accounting(sl);                       // the object could not be made: nothing of it is resident
       int rc = sl.b ? mi_batch_set_count(sl.b, (int)run.size()) : MI_ENCODING_ERROR;
       if (timing) fprintf(stderr, "[mi_avif %8.1f ms] dev %d: slot %d ready\n", since(), dev, j);
       if (rc == MI_OK) {
@@ -1434,19 +657,19 @@ int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source
         const size_t row = (size_t)d0.width * d0.channels;
         size_t host_from = 0;
         auto upload_host = [&](size_t end) { if (rc == MI_OK && end > host_from) rc = mi_batch_upload_async(sl.b, (int)host_from, (int)(end - host_from)); };
-        std::vector<const mi_png_scanlines *> pngs; size_t png_from = 0; int png_kind = 2;       // a stretch holds one kind: 2 goes through mi_batch_upload_png, 4 through _png_deep
+        std::vector<const mi_png_scanlines *> pngs; size_t png_from = 0; int png_kind = MI_SOURCE_PNG;       // a stretch holds one kind: _PNG goes through mi_batch_upload_png, _PNG_DEEP through _png_deep
         auto upload_png = [&]() {
           if (rc == MI_OK && !pngs.empty()) {
             const size_t extra = 2 * (png_call_bytes((int)pngs.size(), pngs.data()) + ((size_t)1 << 20));
-            if (extra > sl.png_bytes) { sl.bytes += extra - sl.png_bytes; live_bytes += extra - sl.png_bytes; sl.png_bytes = extra; }
-            if (png_kind == 4 && !sl.deep) { sl.deep = true; const size_t deep = sh->cap * (size_t)sh->w * sh->h * sh->ch * 2; sl.bytes += deep; live_bytes += deep; }   // the deep slots join the worker's budget
-            rc = png_kind == 4 ? mi_batch_upload_png_deep(sl.b, (int)png_from, (int)pngs.size(), pngs.data()) : mi_batch_upload_png(sl.b, (int)png_from, (int)pngs.size(), pngs.data());
+            if (extra > sl.png_bytes) { charge(sl, extra - sl.png_bytes); sl.png_bytes = extra; }
+            if (png_kind == MI_SOURCE_PNG_DEEP && !sl.deep) { sl.deep = true; charge(sl, sh->cap * (size_t)sh->w * sh->h * sh->ch * 2); }   // the deep slots join the worker's budget
+            rc = png_kind == MI_SOURCE_PNG_DEEP ? mi_batch_upload_png_deep(sl.b, (int)png_from, (int)pngs.size(), pngs.data()) : mi_batch_upload_png(sl.b, (int)png_from, (int)pngs.size(), pngs.data());
           }
           pngs.clear();
         };
         for (size_t k = 0; k < run.size() && rc == MI_OK; k++) {
           const mi_image_source &src = d[run[k]];
-          if (src.kind == 2 || src.kind == 4) {
+          if (is_png(src.kind)) {
             upload_host(k); host_from = k + 1;
             if (!pngs.empty() && png_kind != src.kind) upload_png();
             if (pngs.empty()) { png_from = k; png_kind = src.kind; }
@@ -1454,10 +677,10 @@ int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source
             continue;
           }
           upload_png();
-          if (src.kind == 1 || src.kind == 3) {
+          if (is_jpeg(src.kind)) {
             upload_host(k); host_from = k + 1;
-            if (!sl.jpeg) { sl.jpeg = true; const size_t extra = est_jpeg_bytes(sh->w, sh->h); sl.bytes += extra; live_bytes += extra; }
-            if (rc == MI_OK) rc = src.kind == 3 ? mi_batch_upload_jpeg_ycbcr(sl.b, (int)k, src.jpeg) : mi_batch_upload_jpeg(sl.b, (int)k, src.jpeg);
+            if (!sl.jpeg) { sl.jpeg = true; charge(sl, est_jpeg_bytes(sh->w, sh->h)); }
+            if (rc == MI_OK) rc = src.kind == MI_SOURCE_JPEG_YCBCR ? mi_batch_upload_jpeg_ycbcr(sl.b, (int)k, src.jpeg) : mi_batch_upload_jpeg(sl.b, (int)k, src.jpeg);
             continue;
           }
           const mi_image_desc &x = src.desc;
@@ -1498,25 +721,11 @@ int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source
         const mi_image_source &src = d[i - i0];
         const mi_image_desc &x = src.desc;
         if (rc != MI_OK) { st[i] = rc; continue; }
-        const bool have = src.kind == 0 ? x.pixels != nullptr : (src.kind == 1 || src.kind == 3) ? src.jpeg && src.jpeg->jc.w == x.width && src.jpeg->jc.h == x.height :
-                          (src.kind == 2 || src.kind == 4) && src.png && src.png->sl.w == x.width && src.png->sl.h == x.height && !(x.channels == 3 && src.png->sl.has_alpha());
-        if (!have || !x.width || !x.height || (x.channels != 3 && x.channels != 4)) { st[i] = MI_INVALID_ARGUMENT; if (release) release(user, i); continue; }
-        // a kind-3 source that its upload call would refuse fails alone, not with its run
-        if (src.kind == 3 && (src.jpeg->jc.color == JPEG_RGB || e->color_model == 1 || (x.channels == 4 && e->alpha_mode == 2))) {
-          st[i] = src.jpeg->jc.color == JPEG_RGB && e->color_model != 1 && !(x.channels == 4 && e->alpha_mode == 2) ? MI_UNSUPPORTED : MI_INVALID_ARGUMENT;
-          if (release) release(user, i);
-          continue;
-        }
-        // so does a kind-4 source of bit depth 16 under an alpha mode that takes no deep image of its channels (batch_takes_deep)
-        if (src.kind == 4 && png_goes_deep(src.png) && x.channels == 4 && (src.png->sl.has_alpha() ? e->alpha_mode != 0 : e->alpha_mode == 2)) {
-          st[i] = MI_INVALID_ARGUMENT;
-          if (release) release(user, i);
-          continue;
-        }
+        if (const int why = source_refusal(*e, src)) { st[i] = why; if (release) release(user, i); continue; }
         Shape *sh = shape_for(x);
         if (sh != run_shape || run.size() >= sh->cap) flush(true);
         run_shape = sh; run.push_back(i - i0);
-        if (run.size() == 1) ensure_slot(sh, sh->next, src.kind == 0, src.kind == 2 || src.kind == 4 ? sh->cap * png_call_bytes(1, &src.png) : 0);   // made in the background while the rest of the run arrives
+        if (run.size() == 1) ensure_slot(sh, sh->next, src.kind == MI_SOURCE_HOST, is_png(src.kind) ? sh->cap * png_call_bytes(1, &src.png) : 0);   // made in the background while the rest of the run arrives
       }
       if (timing) fprintf(stderr, "[mi_avif %8.1f ms] dev %d: images %zu..%zu fetched\n", since(), dev, i0, i1);
       flush(cursor.load() < n);
@@ -1537,9 +746,9 @@ int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source
   for (size_t i = 0; i < n; i++) { if (status) status[i] = st[i]; if (first == MI_OK && st[i] != MI_OK) first = st[i]; }
   return first;
 }
-// the host-pixel form: every source is kind 0
+// the host-pixel form: every source is MI_SOURCE_HOST
 struct StreamAdapter { mi_fetch_fn fetch; mi_release_fn release; void *user; };
-static int fetch_host_source(void *user, size_t i, mi_image_source *src) { const StreamAdapter *a = (const StreamAdapter *)user; src->kind = 0; src->jpeg = nullptr; src->png = nullptr; return a->fetch(a->user, i, &src->desc); }
+static int fetch_host_source(void *user, size_t i, mi_image_source *src) { const StreamAdapter *a = (const StreamAdapter *)user; src->kind = MI_SOURCE_HOST; src->jpeg = nullptr; src->png = nullptr; return a->fetch(a->user, i, &src->desc); }
 static void release_host_source(void *user, size_t i) { const StreamAdapter *a = (const StreamAdapter *)user; a->release(a->user, i); }
 int mi_ravif_encode_stream(const mi_ravif_encoder *e, size_t n, mi_fetch_fn fetch, mi_release_fn release, void *user, mi_encoded_image *out, int *status, const int *devices, int ndev) {
   if (!e || !fetch || (n && !out)) return MI_INVALID_ARGUMENT;
@@ -1552,7 +761,6 @@ int mi_ravif_encode_batch(const mi_ravif_encoder *e, size_t n, const mi_image_de
   if (!e || (n && (!in || !out))) return MI_INVALID_ARGUMENT;
   return mi_ravif_encode_stream(e, n, fetch_from_array, nullptr, (void *)in, out, status, devices, ndev);
 }
-int mi_ravif_encode_rgb(const mi_ravif_encoder *e, const uint8_t *rgb, uint32_t w, uint32_t h, size_t stride_px, mi_encoded_image *out) { return encode_one(e, rgb, 3, w, h, stride_px, out); }
 
 // level 1: caller-supplied planes (encode_to_av1). Planes go straight into the frame's src[] (edge-replicated on the host).
 int mi_av1_encode_planes(const mi_av1_config *cfg, const void *const planes[3], const size_t stride_bytes[3], uint8_t **out_obu, size_t *out_len, uint16_t *recon[3]) {

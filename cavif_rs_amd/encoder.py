@@ -316,6 +316,7 @@ def _is_device_array(x):
 
 
 DECODED_WHICH = {'recon': 0, 'source': 1}                   # MI_DECODED_*
+SOURCE_HOST, SOURCE_JPEG, SOURCE_PNG, SOURCE_JPEG_YCBCR, SOURCE_PNG_DEEP = range(5)       # MI_SOURCE_*: what mi_ravif_encode_sources takes
 
 
 def _decoded_which(name):
@@ -812,11 +813,11 @@ class Encoder:
     def encode_jpeg(self, coeffs_or_bytes, ycbcr=True):
         """a JPEG file (bytes or a JpegCoeffs) as an opaque picture, decoded on the device.  ycbcr=True: the frame is coded from the file's own Y, Cb, Cr
         (mi_batch_upload_jpeg_ycbcr: no conversion to RGB and back; a file whose colour is RGB raises Unsupported); ycbcr=False: from the RGB pixels
-        decode_jpeg gives, the file of encode_rgb over them.  One source of kind 3 or 1 through mi_ravif_encode_sources (a 3-channel slot)."""
+        decode_jpeg gives, the file of encode_rgb over them.  One source of kind SOURCE_JPEG_YCBCR or SOURCE_JPEG through mi_ravif_encode_sources (a 3-channel slot)."""
         c = coeffs_or_bytes if isinstance(coeffs_or_bytes, JpegCoeffs) else JpegCoeffs(coeffs_or_bytes)
         if not c._h:
             raise AvifError(4)
-        return _encode_sources(self, [(3 if ycbcr else 1, c, 3)], None)[0]
+        return _encode_sources(self, [(SOURCE_JPEG_YCBCR if ycbcr else SOURCE_JPEG, c, 3)], None)[0]
 
     def encode_ycbcr_device(self, y, cb, cr=None, subsampling=(2, 2)):
         """8-bit BT.601 full-range planes in device memory (objects with __cuda_array_interface__; see BatchEncoder.upload_device_ycbcr for the shapes) as
@@ -868,36 +869,38 @@ def encode_many(encoder, images, devices=None, jpeg_ycbcr=False, png_deep=False)
     """mi_ravif_encode_sources: the reference's files.into_par_iter() (src/main.rs:223) over the node's GPUs.
     images: list of HxWx3 / HxWx4 uint8 arrays (shapes may differ), JpegCoeffs objects (parse_jpeg; encoded as the RGBA pictures decode_jpeg
     gives, decoded on the device) and PngScanlines objects (parse_png; encoded as the RGBA pictures load_rgba gives, unfiltered and expanded on the
-    device).  jpeg_ycbcr=True: a JpegCoeffs whose colour is not RGB is coded from the file's own Y, Cb, Cr (source kind 3) instead.
-    png_deep=True: a PngScanlines goes as source kind 4: a file of bit depth 16 is coded from all 16 bits of its samples.
+    device).  jpeg_ycbcr=True: a JpegCoeffs whose colour is not RGB is coded from the file's own Y, Cb, Cr (source kind SOURCE_JPEG_YCBCR) instead.
+    png_deep=True: a PngScanlines goes as source kind SOURCE_PNG_DEEP: a file of bit depth 16 is coded from all 16 bits of its samples.
     Returns a list of EncodedImage."""
     items = []
     for im in images:
         if isinstance(im, (JpegCoeffs, PngScanlines)):
             if not im._h:
                 raise AvifError(4)
-            items.append((4 if png_deep else 2, im, 4) if isinstance(im, PngScanlines) else (3 if jpeg_ycbcr and im.color != 'rgb' else 1, im, 4))
+            items.append((SOURCE_PNG_DEEP if png_deep else SOURCE_PNG, im, 4) if isinstance(im, PngScanlines) else
+                         (SOURCE_JPEG_YCBCR if jpeg_ycbcr and im.color != 'rgb' else SOURCE_JPEG, im, 4))
             continue
         if _is_device_array(im):
             raise TypeError('encode_many takes host arrays, JpegCoeffs and PngScanlines; pixels in device memory go through BatchEncoder.upload_device')
         a = np.ascontiguousarray(im, dtype=np.uint8)
         if a.ndim != 3 or a.shape[2] not in (3, 4):
             raise AvifError(4)
-        items.append((0, a, a.shape[2]))
+        items.append((SOURCE_HOST, a, a.shape[2]))
     return _encode_sources(encoder, items, devices)
 
 
 def _encode_sources(encoder, items, devices):
-    """mi_ravif_encode_sources over (kind, object, channels of the slot) triples: kind 0 a contiguous uint8 array, 1 / 3 a JpegCoeffs, 2 / 4 a PngScanlines"""
+    """mi_ravif_encode_sources over (kind, object, channels of the slot) triples: SOURCE_HOST a contiguous uint8 array, SOURCE_JPEG / _JPEG_YCBCR a JpegCoeffs,
+    SOURCE_PNG / _PNG_DEEP a PngScanlines"""
     L = load_library()
 
     def fetch(_user, i, src):
         (kind, it, channels), s = items[i], src.contents
         s.kind = kind
-        if kind in (2, 4):
+        if kind in (SOURCE_PNG, SOURCE_PNG_DEEP):
             s.jpeg, s.png = None, it._h
             s.desc.pixels, s.desc.width, s.desc.height, s.desc.stride_px, s.desc.channels = None, it.width, it.height, it.width, channels
-        elif kind in (1, 3):
+        elif kind in (SOURCE_JPEG, SOURCE_JPEG_YCBCR):
             s.jpeg, s.png = it._h, None
             s.desc.pixels, s.desc.width, s.desc.height, s.desc.stride_px, s.desc.channels = None, it.width, it.height, it.width, channels
         else:

@@ -104,26 +104,29 @@ typedef int (*mi_fetch_fn)(void *user, size_t index, mi_image_desc *desc);
 typedef void (*mi_release_fn)(void *user, size_t index);
 int  mi_ravif_encode_stream(const mi_ravif_encoder *e, size_t n, mi_fetch_fn fetch, mi_release_fn release, void *user, mi_encoded_image *out, int *status, const int *devices, int ndev);
 
-/* The same fan-out over sources that need not be host pixels.  kind 1: the coefficients of a parsed JPEG file (mi_jpeg_parse below); desc.width / height /
+/* The same fan-out over sources that need not be host pixels; the kinds are named MI_SOURCE_* below.  MI_SOURCE_JPEG (kind 1): the coefficients of a parsed
+ * JPEG file (mi_jpeg_parse below); desc.width / height /
  * channels name the batch slot the picture is decoded into on the device (width and height must be the file's; channels 4 gives the pixels
  * mi_jpeg_decode_rgba gives, 3 the same without alpha), desc.pixels is unused.  Images are grouped into runs by (width, height, channels), so a JPEG and a
- * PNG picture of one size share a run.  `release` is called once the pixels (kind 0) or the coefficients (kind 1) are in pinned staging: the handle may
- * be freed then.  kind 2: the scanlines of a parsed PNG file (mi_png_parse below), unfiltered and expanded on the device; desc as for kind 1 (channels 3 only
+ * PNG picture of one size share a run.  `release` is called once the pixels (MI_SOURCE_HOST, kind 0) or the coefficients (kind 1) are in pinned staging: the handle may
+ * be freed then.  MI_SOURCE_PNG (kind 2): the scanlines of a parsed PNG file (mi_png_parse below), unfiltered and expanded on the device; desc as for kind 1 (channels 3 only
  * for files without an alpha channel and without tRNS, else the image is MI_INVALID_ARGUMENT), release once the scanlines are in pinned staging.
- * kind 3: a parsed JPEG file as for kind 1, uploaded through mi_batch_upload_jpeg_ycbcr: the frame is coded from the file's own (Y, Cb, Cr) without the detour over
+ * MI_SOURCE_JPEG_YCBCR (kind 3): a parsed JPEG file as for kind 1, uploaded through mi_batch_upload_jpeg_ycbcr: the frame is coded from the file's own (Y, Cb, Cr) without the detour over
  * RGB.  A file whose colour is RGB gets MI_UNSUPPORTED, and an encoder with the RGB colour model or (channels 4) the premultiplied alpha mode
  * MI_INVALID_ARGUMENT, for that image alone.  Runs are grouped by (width, height, channels) as before, so kinds 0 to 3 mix in one run.
- * kind 4: a parsed PNG file as for kind 2, uploaded through mi_batch_upload_png_deep (below): a file of bit depth 16 is coded from all 16 bits of its samples, any
+ * MI_SOURCE_PNG_DEEP (kind 4): a parsed PNG file as for kind 2, uploaded through mi_batch_upload_png_deep (below): a file of bit depth 16 is coded from all 16 bits of its samples, any
  * other file exactly as kind 2.  A 16-bit file that the alpha rules of deep input refuse (4 channels: alpha or tRNS unless alpha_mode is 0; any under
  * alpha_mode 2) gets MI_INVALID_ARGUMENT, for that image alone.
- * mi_ravif_encode_stream is this call with kind 0 throughout.  Pictures in device memory are not a kind here (a pointer belongs to one
+ * mi_ravif_encode_stream is this call with MI_SOURCE_HOST throughout.  Pictures in device memory are not a kind here (a pointer belongs to one
  * device, the shared cursor hands images to any): they enter through mi_ravif_encode_device and mi_batch_upload_device. */
+enum { MI_SOURCE_HOST = 0, MI_SOURCE_JPEG = 1, MI_SOURCE_PNG = 2, MI_SOURCE_JPEG_YCBCR = 3, MI_SOURCE_PNG_DEEP = 4 };
 typedef struct mi_jpeg_coeffs mi_jpeg_coeffs;   /* opaque: one parsed file, host memory only */
 typedef struct mi_png_scanlines mi_png_scanlines;      /* opaque: one inflated file, host memory only */
 typedef struct mi_image_source {
-  int kind;                   /* 0 host pixels (desc), 1 JPEG coefficients (jpeg; desc.width/height/channels say the slot), 2 PNG scanlines (png; desc likewise),
-                                 3 JPEG coefficients kept as the file's own YCbCr (jpeg; desc as for kind 1; mi_batch_upload_jpeg_ycbcr below),
-                                 4 PNG scanlines, 16-bit files through their deep slot (png; desc as for kind 2; mi_batch_upload_png_deep below) */
+  int kind;                   /* MI_SOURCE_HOST host pixels (desc), MI_SOURCE_JPEG JPEG coefficients (jpeg; desc.width/height/channels say the slot), MI_SOURCE_PNG PNG
+                                 scanlines (png; desc likewise), MI_SOURCE_JPEG_YCBCR JPEG coefficients kept as the file's own YCbCr (jpeg; desc as for kind 1;
+                                 mi_batch_upload_jpeg_ycbcr below), MI_SOURCE_PNG_DEEP PNG scanlines, 16-bit files through their deep slot (png; desc as for
+                                 kind 2; mi_batch_upload_png_deep below) */
   mi_image_desc desc;
   const mi_jpeg_coeffs *jpeg;
   const mi_png_scanlines *png; /* kinds 2 and 4 only (the struct grew by this field at its tail: never read for kinds 0 and 1) */

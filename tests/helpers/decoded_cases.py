@@ -1,7 +1,7 @@
 """Child-process side of the decoded-pixel tests (TEST INFRASTRUCTURE): the case table, a numpy restatement of the pixel specification and the
 runs over the library under test (tests/test_decoded_emu.py: the SIMT-emulated build; tests/test_gpu_decoded.py: the product library), one JSON line per case.
 
-    python tests/helpers/decoded_cases.py ROOT sizes|settings|destinations|alpha|effects|refusals|encode_decoded|all|large|torch
+    python tests/helpers/decoded_cases.py ROOT sizes|settings|destinations|alpha|effects|refusals|defaults|encode_decoded|all|large|torch
 
 The expected bytes come from the restatement below, applied to the planes the library hands out (BatchEncoder.recon / .source); every comparison is for
 equality and no case is excused.  tests/test_decoded_reference.py holds the restatement itself against known answers, the oracle's forward transform and
@@ -342,6 +342,33 @@ def run_refusals(lib):
     b.close()
 
 
+def run_defaults(lib):
+    """strides of 0 mean packed: the two 9 x 5 images of a batch, decoded into a target described by zeros and into one described by its packed strides written out,
+    leave the same bytes in the carrier (the restated ones, the sentinel everywhere else); a row stride one byte below the packed row is refused under both"""
+    m, L = lib.m, lib.L
+    w, h, n, bd = 9, 5, 2, 10
+    e = m.Encoder().with_speed(10).with_quality(60).with_bit_depth(bd)
+    b = encoded_batch(m, e, [content(950 + i, h, w) for i in range(n)])
+    car = Carrier(lib)
+    for layout, c in ((0, 3), (0, 4), (1, 3), (1, 4)):
+        written = dict(row=w * c, inner=c, image=h * w * c) if layout == 0 else dict(row=w, inner=h * w, image=c * h * w)
+        strides = (written['image'], written['row'], written['inner'], 1) if layout == 0 else (written['image'], written['row'], 1, written['inner'])
+        expect = np.full(CARRIER_W * 3, SENTINEL, np.uint8)
+        view = np.lib.stride_tricks.as_strided(expect[MARGIN:], shape=(n, h, w, c), strides=strides)
+        for i in range(n):
+            view[i] = restate(b.recon(i), bd, 'ycbcr', channels=c)
+        sts, got, short = [], [], []
+        for kw in (dict(row=0, inner=0, image=0), written):
+            car.fill()
+            sts.append(L.mi_batch_decode_device(b._h, 0, n, 0, C.byref(lib.target(car.dev + MARGIN, layout, c, **kw))))
+            got.append(car.read())
+            short.append(L.mi_batch_decode_device(b._h, 0, n, 0, C.byref(lib.target(car.dev + MARGIN, layout, c, **dict(kw, row=written['row'] - 1)))))
+        emit('defaults: decode %s %d channels' % ('CHW' if layout else 'HWC', c), sts == [0, 0] and np.array_equal(got[0], got[1]) and np.array_equal(got[0], expect) and short == [INVALID] * 2,
+             statuses=sts, short=short)
+    car.close()
+    b.close()
+
+
 def run_encode_decoded(lib):
     m = lib.m
     e = m.Encoder().with_speed(10).with_quality(70)
@@ -398,7 +425,7 @@ def run_torch(lib):
              np.array_equal(dec_t.cpu().numpy(), dec_h) and img_t.avif_file == img_h.avif_file and prem_t == prem_h)
 
 
-RUNS = {'sizes': run_sizes, 'settings': run_settings, 'destinations': run_destinations, 'alpha': run_alpha, 'effects': run_effects, 'refusals': run_refusals, 'encode_decoded': run_encode_decoded}
+RUNS = {'sizes': run_sizes, 'settings': run_settings, 'destinations': run_destinations, 'alpha': run_alpha, 'effects': run_effects, 'refusals': run_refusals, 'defaults': run_defaults, 'encode_decoded': run_encode_decoded}
 
 
 def main():

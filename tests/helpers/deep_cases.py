@@ -1,7 +1,7 @@
 """Child-process side of the deep (16-bit) input tests (TEST INFRASTRUCTURE): run with MI_AVIF_LIB pointing at the library under test
 (tests/test_deep_input_emu.py: the SIMT-emulated build; tests/test_gpu_deep_input.py: the product library), prints one JSON line per case.
 
-    python tests/helpers/deep_cases.py ROOT ingest16|front|png16|files|mixed|refused|sources|all|torch
+    python tests/helpers/deep_cases.py ROOT ingest16|defaults|front|png16|files|mixed|refused|sources|all|torch
 
 The expected samples and planes are the numpy restatement of include/mi_avif.h in tests/helpers/deep_ref.py (itself checked by tests/test_deep_reference.py), the
 expected files come from the CPU oracle over those planes.  Device sources live in the 8-bit input slot of a carrier batch that merely carries bytes, as in
@@ -128,6 +128,39 @@ def run_ingest16(lib):
     st = L.mi_batch_upload_device16(b, 0, 1, C.byref(pixels16(lib, ptr, 0, 4, 8, 1, **kw)))
     emit('ingest16 view: packed, strides 0, 8 bits msb-aligned', st == 0 and kw == dict(row=0, inner=0, image=0) and np.array_equal(read16(lib, b, 0, w, h, 4), (one[0] >> 8) * 257), status=st)
     L.mi_batch_destroy(b)
+    car.close()
+
+
+def run_defaults(lib):
+    """strides of 0 mean packed: two 9 x 5 uint16 pictures back to back, described by zeros and by their packed strides written out, fill the deep slots alike (and
+    with the source's samples).  Before that, on the batch that has no deep slots yet: a row stride one byte below the packed row, an odd one above it and an even one two bytes below it are refused
+    under both descriptions, as are an odd and a short even pixel or plane stride, and the footprint stays what it was (the first accepted call then adds the slots to it)"""
+    L = lib.L
+    car = Carrier16(lib)
+    rng = np.random.default_rng(162)
+    w, h, n = 9, 5, 2
+    for layout, c in itertools.product((0, 1), (3, 4)):
+        b = batch(lib, encoder(lib, alpha_mode=0), n, w, h, c)
+        px = rng.integers(0, 65536, (n, h, w, c), dtype=np.uint16)
+        ptr, written = car.place(px, layout, 0, 0)
+        assert written == (dict(row=2 * w * c, inner=2 * c, image=2 * h * w * c) if layout == 0 else dict(row=2 * w, inner=2 * h * w, image=2 * c * h * w))
+        both = (dict(row=0, inner=0, image=0), written)
+        up = lambda kw: L.mi_batch_upload_device16(b, 0, n, C.byref(pixels16(lib, ptr, layout, c, **kw)))
+        before = footprint(lib, b)
+        # odd strides (one byte below the packed row among them), then even ones below the packed extent: a row two bytes short, pixels two bytes closer than their channels (HWC), planes two bytes closer than a row (CHW)
+        refused = [up(dict(kw, row=written['row'] + d)) for kw in both for d in (-1, 1)] + [up(dict(written, inner=written['inner'] + 1)), up(dict(written, image=written['image'] + 1))]
+        refused += [up(dict(kw, row=written['row'] - 2)) for kw in both] + [up(dict(written, inner=(2 * c if layout == 0 else 2 * w) - 2))]
+        kept = footprint(lib, b) == before
+        blank = np.full((h, w, c), SENTINEL, np.uint16)
+        sts, got = [], []
+        for kw in both:
+            sts.append(up(kw))
+            got.append(np.stack([read16(lib, b, i, w, h, c) for i in range(n)]))
+            for i in range(n):
+                assert L.mi_batch_upload16(b, i, blank.ctypes.data, w, c) == 0     # the next call finds nothing of this one
+        emit('defaults: upload16 %s %d channels' % ('CHW' if layout else 'HWC', c), sts == [OK, OK] and np.array_equal(got[0], got[1]) and np.array_equal(got[0], px) and
+             refused == [INVALID] * 9 and kept and footprint(lib, b) == before + 2 * n * h * w * c, statuses=sts, refused=refused, footprint_kept=kept)
+        L.mi_batch_destroy(b)
     car.close()
 
 
@@ -556,13 +589,13 @@ def run_torch(lib):
     emit('torch: float pixels, a channel mismatch, 7 bits', errs == ['type', 4, 4], errors=errs)
 
 
-RUNS = {'ingest16': run_ingest16, 'front': run_front, 'png16': run_png16, 'files': run_files, 'mixed': run_mixed, 'refused': run_refused, 'sources': run_sources}
+RUNS = {'ingest16': run_ingest16, 'defaults': run_defaults, 'front': run_front, 'png16': run_png16, 'files': run_files, 'mixed': run_mixed, 'refused': run_refused, 'sources': run_sources}
 
 
 def expected_rows():
     """case-name prefix -> number of rows a complete run prints"""
     return {'ingest16': len(SYNTH_SIZES) * 2 * len(INGEST_CHANNELS) * len(INGEST_BITS) * len(INGEST_LAYOUTS) + 2, 'front': 4 * (1 + len(SYNTH_SIZES) + 1 + 1) + 1,
-            'png16': len(PNG_SIZES) * 4 + 2 + 1 + 1, 'files oracle': len(FILE_SETTINGS) * 2 * len(FILE_SIZES), 'mixed': 5, 'refused': 6 + 7, 'accepted': 2, 'sources': 3, 'torch': 5}
+            'png16': len(PNG_SIZES) * 4 + 2 + 1 + 1, 'files oracle': len(FILE_SETTINGS) * 2 * len(FILE_SIZES), 'mixed': 5, 'refused': 6 + 7, 'accepted': 2, 'sources': 3, 'torch': 5, 'defaults': 4}
 
 
 def main():

@@ -1,7 +1,7 @@
 """Child-process side of the device-resident input tests (TEST INFRASTRUCTURE): run with MI_AVIF_LIB pointing at the library under test
 (tests/test_device_input_emu.py: the SIMT-emulated build; tests/test_gpu_device_input.py: the product library), prints one JSON line per case.
 
-    python tests/helpers/device_input_cases.py ROOT ingest|jpeg|refusals|batch|stream|all|torch
+    python tests/helpers/device_input_cases.py ROOT ingest|jpeg|refusals|defaults|batch|stream|all|torch
 
 A "device source" is the HBM input slot of a second, 3-channel batch that merely carries bytes: they get there through the existing mi_batch_upload,
 and mi_batch_device_input of that batch plus a byte offset is the source pointer.  Everything is compared for equality; no case is excused.
@@ -246,6 +246,30 @@ def run_refusals(lib):
     car.close()
 
 
+def run_defaults(lib):
+    """strides of 0 mean packed: two 9 x 5 pictures back to back, described by zeros and by their packed strides written out, fill the slots alike (and with the
+    source's pixels); a row stride one byte below the packed row is refused under both descriptions"""
+    L = lib.L
+    car = Carrier(lib, 41)
+    w, h, n, off = 9, 5, 2, 64
+    for layout, c in itertools.product((0, 1), (3, 4)):
+        b = lib.batch(n, w, h, c)
+        written, want = source(car, layout, c, w, h, 0, off, n=n)
+        assert written == (dict(row=w * c, inner=c, image=h * w * c) if layout == 0 else dict(row=w, inner=h * w, image=c * h * w))
+        blank = np.full((h, w, c), 0x5A, np.uint8)
+        sts, got, short = [], [], []
+        for kw in (dict(row=0, inner=0, image=0), written):
+            for i in range(n):
+                assert L.mi_batch_upload(b, i, blank.ctypes.data, w) == 0          # whatever the call before left in the slots is gone
+            sts.append(L.mi_batch_upload_device(b, 0, n, C.byref(lib.pixels(car.dev + off, layout, c, **kw))))
+            got.append(np.stack([lib.read_input(b, i, w, h, c) for i in range(n)]))
+            short.append(L.mi_batch_upload_device(b, 0, n, C.byref(lib.pixels(car.dev + off, layout, c, **dict(kw, row=written['row'] - 1)))))
+        emit('defaults: upload %s %d channels' % ('CHW' if layout else 'HWC', c), sts == [0, 0] and np.array_equal(got[0], got[1]) and np.array_equal(got[0], want) and short == [4, 4],
+             statuses=sts, short=short)
+        L.mi_batch_destroy(b)
+    car.close()
+
+
 def run_batch(lib):
     """image 0 from the host, image 1 ingested from a planar device source, image 2 a JPEG: the files of a batch fed the same pixels through mi_batch_upload alone"""
     from tests.helpers.jpeg_cases import fixture
@@ -395,7 +419,7 @@ def run_torch(lib):
     emit('torch: float tensors, device tensors in encode_many, a channel mismatch', errs[0] is not None and errs[1] is not None and 'BatchEncoder.upload_device' in errs[1] and errs[2] == 4, errors=errs)
 
 
-RUNS = {'ingest': run_ingest, 'jpeg': run_jpeg, 'refusals': run_refusals, 'batch': run_batch, 'stream': run_stream}
+RUNS = {'ingest': run_ingest, 'jpeg': run_jpeg, 'refusals': run_refusals, 'defaults': run_defaults, 'batch': run_batch, 'stream': run_stream}
 
 
 def main():

@@ -1,7 +1,7 @@
 """Child-process side of the resize-on-input tests (TEST INFRASTRUCTURE): the case table, a numpy restatement of the pixel specification and the
 runs over the library under test (tests/test_resize_emu.py: the SIMT-emulated build; tests/test_gpu_resize.py: the product library), one JSON line per case.
 
-    python tests/helpers/resize_cases.py ROOT table|table-large|handles|same|refusals|e2e|batch|all|torch
+    python tests/helpers/resize_cases.py ROOT table|table-large|handles|same|refusals|defaults|e2e|batch|all|torch
 
 The expected pixels come from the restatement below and never from Pillow: tests/test_resize_reference.py ties the restatement to Pillow for every case of the
 table.  A "device source" is a window into the HBM input slot of a second batch that merely carries bytes (as in device_input_cases.py).  Everything is
@@ -337,6 +337,34 @@ def run_refusals(lib):
     car.close()
 
 
+def run_defaults(lib):
+    """strides of 0 mean packed: two 9 x 5 pictures back to back, described by zeros and by their packed strides written out, are resampled into the same slot bytes
+    (the restated ones); a row stride one byte below the packed row is refused under both descriptions"""
+    L = lib.L
+    (sw, sh), (w, h), n, off, f = (9, 5), (6, 4), 2, 64, 'bicubic'
+    car = Carrier(lib, off + n * sw * sh * 4 + 256)
+    for layout, c in itertools.product((0, 1), (3, 4)):
+        b = lib.batch(n, w, h, c)
+        px = content(95 + 2 * c + layout, n, sh, sw, c, 0)
+        written, view = source(car, layout, c, sw, sh, 0, off, n=n)
+        assert written == (dict(row=sw * c, inner=c, image=sh * sw * c) if layout == 0 else dict(row=sw, inner=sh * sw, image=c * sh * sw))
+        view[...] = px
+        car.put()
+        want = np.stack([expected_slot(restate(px[i], w, h, f), c) for i in range(n)])
+        blank = np.full((h, w, c), 0x5A, np.uint8)
+        sts, got, short = [], [], []
+        for kw in (dict(row=0, inner=0, image=0), written):
+            for i in range(n):
+                assert L.mi_batch_upload(b, i, blank.ctypes.data, w) == 0          # whatever the call before left in the slots is gone
+            sts.append(resize_device(lib, b, 0, n, lib.pixels(car.dev + off, layout, c, **kw), sw, sh, f))
+            got.append(np.stack([lib.read_input(b, i, w, h, c) for i in range(n)]))
+            short.append(resize_device(lib, b, 0, n, lib.pixels(car.dev + off, layout, c, **dict(kw, row=written['row'] - 1)), sw, sh, f))
+        emit('defaults: resize %s %d channels' % ('CHW' if layout else 'HWC', c), sts == [0, 0] and np.array_equal(got[0], got[1]) and np.array_equal(got[0], want) and short == [INVALID] * 2,
+             statuses=sts, short=short)
+        L.mi_batch_destroy(b)
+    car.close()
+
+
 def run_e2e(lib):
     """Encoder.encode_resized over the handle forms against encode_rgb / encode_rgba of the restated pixels"""
     m = lib.m
@@ -425,7 +453,7 @@ def run_torch(lib):
     b.close()
 
 
-RUNS = {'table': run_table, 'handles': run_handles, 'same': run_same, 'refusals': run_refusals, 'e2e': run_e2e, 'batch': run_batch}
+RUNS = {'table': run_table, 'handles': run_handles, 'same': run_same, 'refusals': run_refusals, 'defaults': run_defaults, 'e2e': run_e2e, 'batch': run_batch}
 
 
 def main():

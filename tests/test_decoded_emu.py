@@ -76,5 +76,10 @@ def test_calls_are_refused_with_invalid_argument(emu_env):
     _all_ok(_run(emu_env, 'refusals', 600), 'refused', 10)
 
 
+def test_strides_of_zero_mean_packed(emu_env):
+    """two 9 x 5 images, HWC and CHW targets of 3 and 4 channels: zeros and the packed strides written out give the same target bytes; a row one byte short is refused"""
+    _all_ok(_run(emu_env, 'defaults', 600), 'defaults', 4)
+
+
 def test_encode_decoded_equals_encode_and_the_batch_path(emu_env):
     _all_ok(_run(emu_env, 'encode_decoded', 600), 'encode_decoded', 1)

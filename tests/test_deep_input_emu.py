@@ -40,6 +40,12 @@ def test_device_arrays_fill_the_deep_slots(emu_env):
     check(_run(emu_env, 'ingest16', 900), 'ingest16')
 
 
+def test_strides_of_zero_mean_packed(emu_env):
+    """two 9 x 5 pictures, HWC and CHW, 3 and 4 channels: zeros and the packed strides written out give the same deep slots; a row one byte short and odd strides
+    are refused, and the refused calls leave the batch's footprint alone"""
+    check(_run(emu_env, 'defaults', 600), 'defaults')
+
+
 def test_deep_front_end_writes_the_specified_planes(emu_env):
     """frontend_deep_kernel: every grey level, every level of pure red and of pure blue (cut into 64 x 64 tiles here), random images at eight sizes, the 216
     corner colours, at depths 8 and 10 under both colour models; the alpha flag from a single 65534"""

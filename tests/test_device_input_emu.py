@@ -65,6 +65,11 @@ def test_uploads_are_refused_with_invalid_argument(emu_env):
     _all_ok(_run(emu_env, 'refusals', 600), 'refused', 6)
 
 
+def test_strides_of_zero_mean_packed(emu_env):
+    """two 9 x 5 pictures, HWC and CHW, 3 and 4 channels: zeros and the packed strides written out give the same slots; a row one byte short is refused"""
+    _all_ok(_run(emu_env, 'defaults', 600), 'defaults', 4)
+
+
 def test_batch_of_host_ingested_and_jpeg_images(emu_env):
     _all_ok(_run(emu_env, 'batch', 900), 'batch', 1)
 

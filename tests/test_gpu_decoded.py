@@ -63,6 +63,10 @@ def test_calls_are_refused_with_invalid_argument(table):
     _of(table, 'refused', 10)
 
 
+def test_strides_of_zero_mean_packed(table):
+    _of(table, 'defaults', 4)
+
+
 def test_encode_decoded_equals_encode_and_the_batch_path(table):
     _of(table, 'encode_decoded', 1)
 

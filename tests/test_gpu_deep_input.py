@@ -41,6 +41,10 @@ def test_device_arrays_fill_the_deep_slots(table):
     _of(table, 'ingest16')
 
 
+def test_strides_of_zero_mean_packed(table):
+    _of(table, 'defaults')
+
+
 def test_deep_front_end_writes_the_specified_planes(table):
     _of(table, 'front')
 

@@ -52,6 +52,10 @@ def test_uploads_are_refused_with_invalid_argument(table):
     _of(table, 'refused', 6)
 
 
+def test_strides_of_zero_mean_packed(table):
+    _of(table, 'defaults', 4)
+
+
 def test_batch_of_host_ingested_and_jpeg_images(table):
     _of(table, 'batch', 1)
 

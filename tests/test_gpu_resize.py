@@ -58,6 +58,10 @@ def test_calls_are_refused_with_invalid_argument(table):
     _of(table, 'accepted', 1)
 
 
+def test_strides_of_zero_mean_packed(table):
+    _of(table, 'defaults', 4)
+
+
 def test_encode_resized_equals_encoding_the_restated_pixels(table):
     _of(table, 'e2e', 3)
 

@@ -64,6 +64,11 @@ def test_calls_are_refused_with_invalid_argument(emu_env):
     _all_ok(rows, 'accepted', 1)
 
 
+def test_strides_of_zero_mean_packed(emu_env):
+    """two 9 x 5 sources, HWC and CHW, 3 and 4 channels: zeros and the packed strides written out give the same slots; a row one byte short is refused"""
+    _all_ok(_run(emu_env, 'defaults', 600), 'defaults', 4)
+
+
 def test_encode_resized_equals_encoding_the_restated_pixels(emu_env):
     _all_ok(_run(emu_env, 'e2e', 900), 'e2e', 3)
 
