@@ -89,7 +89,10 @@ int host_threads() {
 }
 int usage(const char *msg) {
   fprintf(stderr, "error: %s\nusage: cavif_mi [-Q quality 1-100] [-s speed 1-10] [-j threads] [-f|--overwrite] [-o path] [-q] [--dirty-alpha]\n"
-                  "                [--color ycbcr|rgb] [--depth 8|10|auto] [--devices 0,1,..] [--rdo-passes 1|2] [--jpeg-ycbcr] [--deep-png] IMAGES...   (\"-\" = stdin/stdout)\n", msg);
+                  "                [--color ycbcr|rgb] [--depth 8|10|auto] [--devices 0,1,..] [--rdo-passes 1|2] [--jpeg-ycbcr] [--deep-png] [--color-managed] IMAGES...   (\"-\" = stdin/stdout)\n"
+                  "  --color-managed  convert every file to sRGB by its own colour description (an ICC profile, or PNG gAMA / cHRM) on the GPU; a file whose profile\n"
+                  "                   is unsupported or malformed is encoded unmanaged (one warning line unless -q).  With --jpeg-ycbcr a JPEG whose description\n"
+                  "                   asks for a conversion goes the RGB way: the conversion needs RGB.  Combines with --deep-png.\n", msg);
   return 1;
 }
 
@@ -134,7 +137,7 @@ int main(int argc, char **argv) {
     }
   }
   float quality = 80.f; int speed = 4, threads = 0, depth = 0, color_model = 0, rdo_passes = 1;
-  bool overwrite = false, quiet = false, dirty_alpha = false, have_output = false, output_stdio = false, jpeg_ycbcr = false, deep_png = false;
+  bool overwrite = false, quiet = false, dirty_alpha = false, have_output = false, output_stdio = false, jpeg_ycbcr = false, deep_png = false, color_managed = false;
   std::string output; std::vector<std::string> images; std::vector<int> devices;
   // clap syntax (src/main.rs:45-110): --name value, --name=value, -n value, -nvalue, -n=value, combined short flags (-fq)
   std::vector<std::string> args;
@@ -171,6 +174,7 @@ int main(int argc, char **argv) {
     else if (a == "--dirty-alpha") dirty_alpha = true;
     else if (a == "--jpeg-ycbcr") jpeg_ycbcr = true;                                                                                                   // extension: not a cavif flag
     else if (a == "--deep-png") deep_png = true;                                                                                                       // extension: not a cavif flag
+    else if (a == "--color-managed") color_managed = true;                                                                                             // extension: not a cavif flag
     else if (a == "--color") { const std::string v = value("--color"); if (v == "ycbcr") color_model = 0; else if (v == "rgb") color_model = 1; else return usage("bad color type"); }
     else if (a == "--rdo-passes") { rdo_passes = atoi(value("--rdo-passes")); if (rdo_passes < 1 || rdo_passes > 2) return usage("bad --rdo-passes (1 or 2)"); }   // extension: not a cavif flag
     else if (a == "--depth") { const std::string v = value("--depth"); depth = v == "8" ? 8 : v == "10" ? 10 : 0; if (v != "8" && v != "10" && v != "auto") return usage("bad depth"); }
@@ -208,7 +212,7 @@ int main(int argc, char **argv) {
   enc.threads = threads > 0 ? threads : host_threads();
 
   // load + decide output paths (process(), :169-200); failures are collected per file and reported at the end
-  struct Job { std::string in_name, out_path; bool out_stdio = false; mi_jpeg_coeffs *jpeg = nullptr; mi_png_scanlines *png = nullptr; uint32_t w = 0, h = 0; bool ycbcr = false, deep = false; std::string error; };
+  struct Job { std::string in_name, out_path; bool out_stdio = false; mi_jpeg_coeffs *jpeg = nullptr; mi_png_scanlines *png = nullptr; uint32_t w = 0, h = 0; bool ycbcr = false, deep = false, managed = false; std::string error; };
   std::vector<Job> jobs(files.size());
   // the reference loads inside files.into_par_iter() (src/main.rs:223): file reads + PNG inflate / JPEG entropy decodes fan out over the host cores; a JPEG leaves
   // its loader as coefficients (dequantisation, IDCT, upsampling and colour run on the device that encodes it), a PNG as filtered scanlines (unfiltered and
@@ -227,6 +231,19 @@ int main(int argc, char **argv) {
       int color = 2, png_depth = 0;
       if (!st && is_png && deep_png && mi_png_scanlines_info(j.png, nullptr, &png_depth) == MI_OK) j.deep = png_depth == 16 && (!png_alpha || dirty_alpha);
       if (!st && is_jpeg && jpeg_ycbcr && color_model == 0 && mi_jpeg_coeffs_info(j.jpeg, &color, nullptr, nullptr) == MI_OK) j.ycbcr = color != 2;
+      if (!st && color_managed) {
+        // what the file says about its colour, probed here (parsed, no tables) to learn whether it can be converted; the encoder bakes one transform per distinct description
+        const uint8_t *icc = nullptr; size_t icc_len = 0; int what = 0, cst = MI_OK; double gamma = 0.0, chrm[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+        if (is_jpeg) { if (mi_jpeg_coeffs_icc(j.jpeg, &icc, &icc_len) == MI_OK && icc) what = 1; }
+        else cst = mi_png_scanlines_colour(j.png, &what, &icc, &icc_len, &gamma, chrm);
+        int identity = 1; bool has_chrm = false;
+        for (int k = 0; k < 8; k++) has_chrm = has_chrm || chrm[k] != 0.0;                       // eight zeros: the file has no cHRM
+        if (cst == MI_OK && what == 1) cst = mi_colour_probe_icc(icc, icc_len, &identity);
+        else if (cst == MI_OK && what == 3) { cst = mi_colour_probe_png(gamma, has_chrm ? chrm : nullptr, &identity); if (cst == MI_INVALID_ARGUMENT) cst = MI_ENCODING_ERROR; }
+        j.managed = cst == MI_OK && !identity;
+        if (cst != MI_OK && !quiet) fprintf(stderr, "warning: %s: %s colour profile; encoding it unmanaged\n", j.in_name.c_str(), cst == MI_UNSUPPORTED ? "unsupported" : "malformed");
+        if (j.managed) j.ycbcr = false;                             // the conversion needs RGB
+      }
       if (st) j.error = st == MI_UNSUPPORTED ? "unsupported image format (this build reads PNG and baseline/progressive 8-bit JPEG)" :
                         st == MI_NO_DEVICE ? "no HIP device (this encoder has no CPU fallback)" : "corrupt image data";
     }
@@ -266,7 +283,8 @@ int main(int argc, char **argv) {
     { std::unique_lock<std::mutex> lk(*c->mu); c->cv->wait(lk, [&] { return (*c->loaded)[i] != 0; }); }
     const Job &j = (*c->jobs)[i];
     if (!j.error.empty()) return MI_INVALID_ARGUMENT;           // reported from the job's own message below
-    src->kind = j.jpeg ? (j.ycbcr ? MI_SOURCE_JPEG_YCBCR : MI_SOURCE_JPEG) : j.png ? (j.deep ? MI_SOURCE_PNG_DEEP : MI_SOURCE_PNG) : MI_SOURCE_HOST; src->jpeg = j.jpeg; src->png = j.png;
+    src->kind = j.jpeg ? (j.managed ? MI_SOURCE_JPEG_MANAGED : j.ycbcr ? MI_SOURCE_JPEG_YCBCR : MI_SOURCE_JPEG) :
+                j.png ? (j.managed ? (j.deep ? MI_SOURCE_PNG_DEEP_MANAGED : MI_SOURCE_PNG_MANAGED) : j.deep ? MI_SOURCE_PNG_DEEP : MI_SOURCE_PNG) : MI_SOURCE_HOST; src->jpeg = j.jpeg; src->png = j.png;
     mi_image_desc *d = &src->desc;
     d->pixels = nullptr; d->width = j.w; d->height = j.h; d->stride_px = j.w; d->channels = 4;     // a JPEG or PNG into an RGBA slot: the pixels load_rgba gives it
     return MI_OK;

@@ -510,7 +510,14 @@ int mi_jpeg_coeffs_info(const mi_jpeg_coeffs *c, int *color, int *hsub, int *vsu
 }
 
 // ---- PNG input: the host half behind a handle, the device half on the batch's stream ----
-struct mi_png_scanlines { PngScanlines sl; };
+struct mi_png_scanlines { PngScanlines sl; std::mutex colour_mu; };
+// the file's colour description, resolved on first use (png_resolve_colour inflates the iCCP chunk then): a handle may be asked from several threads
+static const PngScanlines &png_handle_colour(const mi_png_scanlines *p) {
+  mi_png_scanlines *const q = const_cast<mi_png_scanlines *>(p);
+  std::lock_guard<std::mutex> lk(q->colour_mu);
+  png_resolve_colour(q->sl);
+  return q->sl;
+}
 
 // png_read_scanlines behind a handle: host work only (chunk walk, inflate, filter-byte and palette-index checks), the statuses of mi_png_decode_rgba
 int mi_png_parse(const uint8_t *data, size_t len, mi_png_scanlines **out, uint32_t *w, uint32_t *h, int *has_alpha) {
@@ -773,6 +780,148 @@ int mi_batch_resize_png(mi_batch *b, int index, const mi_png_scanlines *p, int f
   if (int st = batch_reserve_scratch(b, inter_at + resample_inter_bytes(1, p->sl.h, b->w))) return st;
   if (int st = batch_png_expand(b, 1, &p, p->sl.w, p->sl.h, channels, b->d_rs_scratch.get())) return st;
   return batch_resample(b, index, 1, resample_scratch_source(b, p->sl.w, p->sl.h, channels), filter, inter_at);
+}
+
+// ---- colour-managed input: a file's colour description baked into a transform to sRGB, applied to slots in place (icc_reader.h, dev_colour.h) ----
+// A transform is host state, baked once; the first conversion on a device leaves a copy of its tables there (70 KB), which goes with the transform.
+struct mi_colour_transform {
+  ColourTables t;
+  std::mutex mu;
+  struct DevCopy { int device; uint8_t *base; };
+  std::vector<DevCopy> copies;
+};
+static constexpr size_t MI_COLOUR_TAB8_BYTES = 1024 * sizeof(uint32_t), MI_COLOUR_LIN16_BYTES = 3 * MI_COLOUR_LIN16 * sizeof(uint32_t), MI_COLOUR_OUT16_BYTES = MI_COLOUR_OUT16 * sizeof(uint16_t);
+static_assert(MI_COLOUR_LIN16 == CT_LIN16_SEG + 2 && MI_COLOUR_OUT16 == CT_OUT16_SEG + 2, "dev_colour.h and icc_reader.h speak about the same tables");
+// the tables on `device` (copied there by the first call that asks, blocking); false = could not be allocated
+static bool colour_on_device(mi_colour_transform *t, int device, ColourDev &d) {
+  std::lock_guard<std::mutex> lk(t->mu);
+  uint8_t *base = nullptr;
+  for (const auto &c : t->copies) if (c.device == device) base = c.base;
+  if (!base) {
+    std::vector<uint8_t> host(MI_COLOUR_TAB8_BYTES + MI_COLOUR_LIN16_BYTES + MI_COLOUR_OUT16_BYTES);
+    memcpy(host.data(), t->t.lin8.data(), 768 * sizeof(uint32_t));
+    memcpy(host.data() + 768 * sizeof(uint32_t), t->t.thresholds.data(), 256 * sizeof(uint32_t));
+    memcpy(host.data() + MI_COLOUR_TAB8_BYTES, t->t.lin16.data(), MI_COLOUR_LIN16_BYTES);
+    memcpy(host.data() + MI_COLOUR_TAB8_BYTES + MI_COLOUR_LIN16_BYTES, t->t.out16.data(), MI_COLOUR_OUT16_BYTES);
+    if (hipMalloc((void **)&base, host.size()) != hipSuccess) return false;
+    if (hipMemcpy(base, host.data(), host.size(), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(base); return false; }
+    t->copies.push_back({ device, base });
+  }
+  d.tab8 = (const uint32_t *)base; d.lin16 = (const uint32_t *)(base + MI_COLOUR_TAB8_BYTES); d.out16 = (const uint16_t *)(base + MI_COLOUR_TAB8_BYTES + MI_COLOUR_LIN16_BYTES);
+  for (int i = 0; i < 9; i++) d.m[i] = (long long)t->t.matrix[i];
+  return true;
+}
+static int colour_transform_make(int st, std::unique_ptr<mi_colour_transform> &t, mi_colour_transform **out) {
+  if (st) return st;
+  *out = t.release();
+  return MI_OK;
+}
+// (for the stream workers: the transform of a description, or nullptr when it cannot be converted -- an unsupported or malformed profile, degenerate chromaticities)
+static mi_colour_transform *colour_transform_from_description(const ColourDescription &d) {
+  try {
+    std::unique_ptr<mi_colour_transform> t(new mi_colour_transform);
+    return colour_tables_from_description(d, t->t) == 0 ? t.release() : nullptr;
+  } catch (const std::exception &) { return nullptr; }
+}
+int mi_colour_transform_from_icc(const uint8_t *icc, size_t len, mi_colour_transform **out) {
+  if (!out) return MI_INVALID_ARGUMENT;
+  *out = nullptr;
+  if (!icc) return MI_INVALID_ARGUMENT;
+  try {                                                       // nothing may unwind through the C ABI
+    std::unique_ptr<mi_colour_transform> t(new mi_colour_transform);
+    return colour_transform_make(colour_tables_from_icc(icc, len, t->t), t, out);
+  } catch (const std::exception &) { return MI_ENCODING_ERROR; }
+}
+int mi_colour_transform_from_png(double file_gamma, const double *chrm8_or_null, mi_colour_transform **out) {
+  if (!out) return MI_INVALID_ARGUMENT;
+  *out = nullptr;
+  try {
+    std::unique_ptr<mi_colour_transform> t(new mi_colour_transform);
+    return colour_transform_make(file_gamma == 0.0 && !chrm8_or_null ? MI_OK : colour_tables_from_png(file_gamma, chrm8_or_null, t->t), t, out);   // 0 and no cHRM: no description at all
+  } catch (const std::exception &) { return MI_ENCODING_ERROR; }
+}
+// (the device copies go first: hipFree waits for whatever the device still runs with them)
+void mi_colour_transform_free(mi_colour_transform *t) {
+  if (!t) return;
+  for (const auto &c : t->copies) { (void)hipSetDevice(c.device); (void)hipFree(c.base); }
+  delete t;
+}
+// what the two calls above would answer, without the tables: the profile is parsed and the matrix made, no curve is evaluated
+int mi_colour_probe_icc(const uint8_t *icc, size_t len, int *is_identity) {
+  if (!icc) return MI_INVALID_ARGUMENT;
+  try {
+    ColourTables t;
+    const int st = colour_tables_from_icc(icc, len, t, false);
+    if (!st && is_identity) *is_identity = t.identity ? 1 : 0;
+    return st;
+  } catch (const std::exception &) { return MI_ENCODING_ERROR; }
+}
+int mi_colour_probe_png(double file_gamma, const double *chrm8_or_null, int *is_identity) {
+  try {
+    ColourTables t;
+    const int st = file_gamma == 0.0 && !chrm8_or_null ? MI_OK : colour_tables_from_png(file_gamma, chrm8_or_null, t, false);
+    if (!st && is_identity) *is_identity = t.identity ? 1 : 0;
+    return st;
+  } catch (const std::exception &) { return MI_ENCODING_ERROR; }
+}
+int mi_colour_transform_is_identity(const mi_colour_transform *t) { return t && t->t.identity ? 1 : 0; }
+size_t mi_colour_transform_table(const mi_colour_transform *t, int which, const void **data) {
+  if (!t || !data || t->t.identity) return 0;
+  switch (which) {
+    case 0: *data = t->t.matrix; return 9;
+    case 1: *data = t->t.lin8.data(); return t->t.lin8.size();
+    case 2: *data = t->t.thresholds.data(); return t->t.thresholds.size();
+    case 3: *data = t->t.lin16.data(); return t->t.lin16.size();
+    case 4: *data = t->t.out16.data(); return t->t.out16.size();
+    default: return 0;
+  }
+}
+int mi_png_scanlines_colour(const mi_png_scanlines *p, int *what, const uint8_t **icc, size_t *icc_len, double *file_gamma, double chrm8[8]) {
+  if (!p || !what) return MI_INVALID_ARGUMENT;
+  try { (void)png_handle_colour(p); } catch (const std::exception &) { return MI_ENCODING_ERROR; }      // nothing may unwind through the C ABI
+  const PngScanlines &sl = p->sl;
+  *what = sl.colour;
+  if (icc) *icc = sl.colour == 1 && !sl.icc_oversize ? sl.icc.data() : nullptr;
+  if (icc_len) *icc_len = sl.colour == 1 && !sl.icc_oversize ? sl.icc.size() : 0;
+  if (file_gamma) *file_gamma = sl.colour == 3 ? sl.file_gamma : 0.0;
+  if (chrm8) for (int i = 0; i < 8; i++) chrm8[i] = sl.colour == 3 && sl.has_chrm ? sl.chrm[i] : 0.0;
+  return sl.colour == 1 && sl.icc_oversize ? MI_UNSUPPORTED : MI_OK;
+}
+int mi_jpeg_coeffs_icc(const mi_jpeg_coeffs *c, const uint8_t **icc, size_t *len) {
+  if (!c || !icc || !len) return MI_INVALID_ARGUMENT;
+  *icc = c->jc.icc.empty() ? nullptr : c->jc.icc.data(); *len = c->jc.icc.size();
+  return MI_OK;
+}
+
+// The colour channels of slots [first, first + count) through `t`, in place, on the batch's stream (after the uploads that filled them): one launch per run of
+// slots of one kind, all images of a run in grid z.  Every check comes first; a refused call and the identity transform launch and allocate nothing.
+int mi_batch_convert_colour(mi_batch *b, int first, int count, mi_colour_transform *t) {
+  if (!batch_range_ok(b, first, count) || !t) return MI_INVALID_ARGUMENT;
+  for (int i = first; i < first + count; i++) if (b->kinds[i] != MI_INPUT_RGB && b->kinds[i] != MI_INPUT_RGB16) return MI_INVALID_ARGUMENT;
+  if (t->t.identity) return MI_OK;
+  (void)hipSetDevice(b->device);
+  ColourDev d;
+  if (!colour_on_device(t, b->device, d)) return MI_ENCODING_ERROR;
+  const uint32_t w = b->w, h = b->h;
+  for (int i = first; i < first + count;) {
+    const int kind = b->kinds[i];
+    int j = i + 1;
+    while (j < first + count && b->kinds[j] == kind) j++;
+    const dim3 grid(((w + 3) / 4 + 63) / 64, (h + MI_COLOUR_ROWS - 1) / MI_COLOUR_ROWS, (unsigned)(j - i));
+    if (kind == MI_INPUT_RGB) {
+      uint8_t *const slots = mi_batch_device_input(b, i);
+      if (b->channels == 4) hipLaunchKernelGGL((colour_convert_kernel<4>), grid, dim3(64), 0, b->stream, d, slots, w, h);
+      else hipLaunchKernelGGL((colour_convert_kernel<3>), grid, dim3(64), 0, b->stream, d, slots, w, h);
+    } else {
+      uint16_t *const slots = mi_batch_device_input16(b, i);
+      if (!slots) return MI_ENCODING_ERROR;
+      if (b->channels == 4) hipLaunchKernelGGL((colour_convert16_kernel<4>), grid, dim3(64), 0, b->stream, d, slots, w, h);
+      else hipLaunchKernelGGL((colour_convert16_kernel<3>), grid, dim3(64), 0, b->stream, d, slots, w, h);
+    }
+    i = j;
+  }
+  HIP_OK(hipGetLastError());
+  return MI_OK;
 }
 
 }  // extern "C"

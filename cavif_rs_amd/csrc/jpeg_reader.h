@@ -2,7 +2,8 @@
 // src/main.rs:258, which accepts JPEG next to PNG).  Only the strictly serial part lives here: marker parsing and Huffman decoding (baseline / extended
 // sequential, and progressive with spectral selection + successive approximation).  No pixel arithmetic: dequantisation, the inverse DCT, chroma
 // upsampling and the colour transform are the kernels of dev_jpeg.h.  Written from ITU-T T.81 (markers: annex B; Huffman tables: annex C; sequential
-// decoding: annex F.2; progressive: annex G.2) and the JFIF / Adobe APP14 conventions.
+// decoding: annex F.2; progressive: annex G.2) and the JFIF / Adobe APP14 conventions; the APP2 segments of an embedded ICC profile (ICC.1 annex B.4) are
+// joined and kept for colour-managed input, and change neither the coefficients nor the status of any file.
 // Stricter than libjpeg where that is simpler: a stream that ends before every block of every scan is decoded, a file without EOI, a component no scan
 // covered and a progressive file whose scans leave a coefficient short of full precision are MI_ENCODING_ERROR -- nothing partial is ever decoded.
 #pragma once
@@ -29,6 +30,27 @@ struct JpegCoeffs {
   JpegComp comp[3];
   size_t nblocks = 0;
   std::vector<int16_t> coef;        // nblocks x 64, natural (de-zigzagged) order, component after component, row-major over each block grid
+  std::vector<uint8_t> icc;         // the embedded ICC profile (APP2 "ICC_PROFILE\0" segments joined by sequence number), empty = none
+};
+
+// APP2 "ICC_PROFILE\0" + sequence number (1..count) + count + bytes: the segments of one file in any order.  finish() joins them; a missing or duplicate
+// number, a zero or disagreeing count mean that the file has no profile.  Never an error of the picture.
+struct JpegIccParts {
+  struct Part { int seq; const uint8_t *data; size_t len; };
+  std::vector<Part> parts; int count = 0; bool broken = false;
+  void add(const uint8_t *seg, size_t n) {
+    if (n < 14 || memcmp(seg, "ICC_PROFILE\0", 12) != 0) return;
+    const int seq = seg[12], cnt = seg[13];
+    if (seq == 0 || cnt == 0 || seq > cnt || (count && cnt != count)) { broken = true; return; }
+    count = cnt;
+    for (const Part &p : parts) if (p.seq == seq) { broken = true; return; }
+    parts.push_back(Part{ seq, seg + 14, n - 14 });
+  }
+  void finish(std::vector<uint8_t> &icc) const {
+    icc.clear();
+    if (broken || !count || (int)parts.size() != count) return;
+    for (int s = 1; s <= count; s++) for (const Part &p : parts) if (p.seq == s) icc.insert(icc.end(), p.data, p.data + p.len);
+  }
 };
 
 static const uint8_t jpeg_zigzag[64] = { 0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
@@ -122,6 +144,7 @@ inline int jpeg_read_coeffs(const uint8_t *d, size_t len, JpegCoeffs &out) {
   std::vector<JpegHuff> huff(8);                                 // 0-3 DC, 4-7 AC
   bool jfif = false, adobe = false, have_frame = false, progressive = false, saw_eoi = false;
   int adobe_transform = 0;
+  JpegIccParts icc_parts;
   uint32_t restart_interval = 0;
   int8_t coef_bits[3][64];                                       // progressive: the point transform each coefficient has reached, -1 = not sent yet
   memset(coef_bits, -1, sizeof(coef_bits));
@@ -146,6 +169,7 @@ inline int jpeg_read_coeffs(const uint8_t *d, size_t len, JpegCoeffs &out) {
     pos += L;
     if (m == 0xE0) { if (n >= 12 && !memcmp(seg, "JFIF\0", 5)) jfif = true; }
     else if (m == 0xEE) { if (n >= 12 && !memcmp(seg, "Adobe", 5)) { adobe = true; adobe_transform = seg[11]; } }
+    else if (m == 0xE2) icc_parts.add(seg, n);                   // ICC profile segments: kept for mi_jpeg_coeffs_icc, nothing else reads them
     else if ((m >= 0xE1 && m <= 0xEF) || m == 0xFE) {}           // other APPn, COM: skipped
     else if (m == 0xDB) {                                        // DQT
       for (size_t i = 0; i < n;) {
@@ -336,6 +360,7 @@ inline int jpeg_read_coeffs(const uint8_t *d, size_t len, JpegCoeffs &out) {
   else if (jfif) out.color = JPEG_YCBCR;
   else if (adobe) out.color = adobe_transform == 0 ? JPEG_RGB : JPEG_YCBCR;
   else out.color = (out.comp[0].id == 'R' && out.comp[1].id == 'G' && out.comp[2].id == 'B') ? JPEG_RGB : JPEG_YCBCR;
+  icc_parts.finish(out.icc);
   return 0;
 }
 

@@ -25,6 +25,8 @@
 #include "dev_quality.h"
 #include "dev_decoded.h"
 #include "dev_deep.h"
+#include "icc_reader.h"
+#include "dev_colour.h"
 #include "host_frames.h"
 
 // The product library reads no environment variables; probe builds (tools/) get MI_AVIF_TIMING=1 (-DMI_TUNING_KNOBS: host-side timeline on stderr)
@@ -530,8 +532,17 @@ int mi_ravif_encode_device_resized(const mi_ravif_encoder *e, const mi_device_pi
 }
 
 // ---- the stream worker: the kinds of source it takes (MI_SOURCE_*) ----
-static bool is_jpeg(int kind) { return kind == MI_SOURCE_JPEG || kind == MI_SOURCE_JPEG_YCBCR; }
-static bool is_png(int kind) { return kind == MI_SOURCE_PNG || kind == MI_SOURCE_PNG_DEEP; }
+// (the managed kinds: as MI_SOURCE_JPEG / _PNG / _PNG_DEEP, with the file's own colour description applied after the upload)
+static bool is_managed(int kind) { return kind == MI_SOURCE_JPEG_MANAGED || kind == MI_SOURCE_PNG_MANAGED || kind == MI_SOURCE_PNG_DEEP_MANAGED; }
+static int upload_kind(int kind) { return kind == MI_SOURCE_JPEG_MANAGED ? MI_SOURCE_JPEG : kind == MI_SOURCE_PNG_MANAGED ? MI_SOURCE_PNG : kind == MI_SOURCE_PNG_DEEP_MANAGED ? MI_SOURCE_PNG_DEEP : kind; }
+static bool is_jpeg(int kind) { kind = upload_kind(kind); return kind == MI_SOURCE_JPEG || kind == MI_SOURCE_JPEG_YCBCR; }
+static bool is_png(int kind) { kind = upload_kind(kind); return kind == MI_SOURCE_PNG || kind == MI_SOURCE_PNG_DEEP; }
+// the colour description of a managed source (icc_reader.h: the kind travels beside the bytes; a view into the source's handle)
+static ColourDescription source_colour_description(const mi_image_source &src) {
+  if (is_jpeg(src.kind)) return colour_description_of_icc(src.jpeg->jc.icc.data(), src.jpeg->jc.icc.size());
+  const PngScanlines &sl = png_handle_colour(src.png);
+  return colour_description_of_png(sl.colour, sl.icc_oversize, sl.icc.data(), sl.icc.size(), sl.file_gamma, sl.has_chrm, sl.chrm);
+}
 // MI_OK, or the status of a fetched source that names nothing usable or that its upload call would refuse: it fails alone, not with its run
 static int source_refusal(const mi_ravif_encoder &e, const mi_image_source &src) {
   const mi_image_desc &x = src.desc;
@@ -540,7 +551,7 @@ static int source_refusal(const mi_ravif_encoder &e, const mi_image_source &src)
   if (!have || !x.width || !x.height || (x.channels != 3 && x.channels != 4)) return MI_INVALID_ARGUMENT;
   if (src.kind == MI_SOURCE_JPEG_YCBCR && !batch_takes_ycbcr(e, x.channels)) return MI_INVALID_ARGUMENT;      // the batch's rule first, then the file's colour, as in mi_batch_upload_jpeg_ycbcr
   if (src.kind == MI_SOURCE_JPEG_YCBCR && src.jpeg->jc.color == JPEG_RGB) return MI_UNSUPPORTED;
-  if (src.kind == MI_SOURCE_PNG_DEEP && png_goes_deep(src.png) && !batch_takes_deep(e, x.channels, src.png->sl.has_alpha() ? 4 : 3)) return MI_INVALID_ARGUMENT;
+  if (upload_kind(src.kind) == MI_SOURCE_PNG_DEEP && png_goes_deep(src.png) && !batch_takes_deep(e, x.channels, src.png->sl.has_alpha() ? 4 : 3)) return MI_INVALID_ARGUMENT;
   return MI_OK;
 }
 
@@ -588,6 +599,21 @@ int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source
     struct Slot { mi_batch *b = nullptr; std::future<mi_batch *> making; std::vector<size_t> idx; bool busy = false, jpeg = false, deep = false; size_t bytes = 0, png_bytes = 0; };
     struct Shape { uint32_t w, h; int ch; size_t cap; Slot slot[NSLOT_MAX]; int next = 0; size_t runs = 0, last_use = 0; };
     std::vector<std::unique_ptr<Shape>> shapes;
+    // the transforms of the managed sources, by the bytes of their colour description (hash, then compare): a thousand photos of one phone bake one transform.
+    // nullptr = unsupported or malformed.  They live until the worker's last run has been collected.
+    struct Baked { ColourKey key; mi_colour_transform *t; };
+    std::vector<Baked> baked;
+    auto transform_for = [&](const mi_image_source &src) -> mi_colour_transform * {
+      const ColourDescription desc = source_colour_description(src);
+      if (desc.kind == 0) return nullptr;
+      uint8_t scratch[80]; const uint8_t *p = nullptr; size_t n = 0;
+      colour_description_bytes(desc, scratch, p, n);
+      const uint64_t hash = colour_hash(p, n);
+      for (const Baked &c : baked) if (colour_key_matches(c.key, desc.kind, hash, p, n)) return c.t;
+      baked.push_back(Baked{ colour_key_make(desc.kind, hash, p, n), nullptr });
+      baked.back().t = colour_transform_from_description(colour_description_of_key(baked.back().key));
+      return baked.back().t;
+    };
     size_t live_bytes = 0, tick = 0;
     auto charge = [&](Slot &sl, size_t extra) { sl.bytes += extra; live_bytes += extra; };      // what a slot's object holds on the device and pinned counts against the worker's budget
     auto reset_accounting = [&](Slot &sl) { live_bytes -= std::min(live_bytes, sl.bytes); sl.bytes = 0; sl.jpeg = false; sl.deep = false; sl.png_bytes = 0; };
@@ -671,8 +697,8 @@ int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source
           const mi_image_source &src = d[run[k]];
           if (is_png(src.kind)) {
             upload_host(k); host_from = k + 1;
-            if (!pngs.empty() && png_kind != src.kind) upload_png();
-            if (pngs.empty()) { png_from = k; png_kind = src.kind; }
+            if (!pngs.empty() && png_kind != upload_kind(src.kind)) upload_png();
+            if (pngs.empty()) { png_from = k; png_kind = upload_kind(src.kind); }
             pngs.push_back(src.png);
             continue;
           }
@@ -692,6 +718,17 @@ int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source
         }
         upload_png();
         upload_host(run.size());
+        // the managed sources, after their uploads on the same stream: neighbours that share a transform share a call
+        std::vector<mi_colour_transform *> ts(run.size(), nullptr);                // one look-up (one hash of the description) per managed source
+        try { for (size_t k = 0; k < run.size(); k++) if (is_managed(d[run[k]].kind)) ts[k] = transform_for(d[run[k]]); } catch (const std::exception &) { rc = MI_ENCODING_ERROR; }
+        for (size_t k = 0; k < run.size() && rc == MI_OK;) {
+          mi_colour_transform *const t = ts[k];
+          size_t k1 = k + 1;
+          if (!t) { k = k1; continue; }
+          while (k1 < run.size() && ts[k1] == t) k1++;
+          rc = mi_batch_convert_colour(sl.b, (int)k, (int)(k1 - k), t);
+          k = k1;
+        }
         if (timing) fprintf(stderr, "[mi_avif %8.1f ms] dev %d: slot %d staged, uploads enqueued\n", since(), dev, j);
       }
       if (release) for (size_t k : run) release(user, i0 + k);   // staged (or failed): the caller's pixels are no longer read
@@ -736,6 +773,7 @@ int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source
       pool_release(sl.b);                                      // back to the pool: the next call (or nobody, at process exit) gets them
       sl.b = nullptr;
     }
+    for (const Baked &c : baked) mi_colour_transform_free(c.t);
     warm.get();
     if (timing) fprintf(stderr, "[mi_avif %8.1f ms] dev %d: worker done\n", since(), dev);
   };

@@ -1,7 +1,8 @@
 // png_reader.h -- PNG -> RGBA8, the input side of the cavif CLI (reference: load_rgba, src/main.rs:265-283, which maps
 // every load_image pixel kind to RGBA8: RGB -> alpha 255, 16-bit -> high byte, gray -> r=g=b).
 // Host C++ over zlib's inflate; written from the PNG specification (chunks IHDR / PLTE / tRNS / IDAT / IEND, the five
-// scanline filters, Adam7).  JPEG bytes get MI_UNSUPPORTED here: the reference's other input format has its own reader
+// scanline filters, Adam7).  The colour chunks before IDAT (iCCP, sRGB, gAMA, cHRM) are kept beside the scanlines for colour-managed input and
+// change neither the pixels nor the status of any file.  JPEG bytes get MI_UNSUPPORTED here: the reference's other input format has its own reader
 // (jpeg_reader.h + dev_jpeg.h), and mi_image_decode_rgba picks between the two.
 #pragma once
 #include <algorithm>
@@ -51,8 +52,51 @@ struct PngScanlines {
   bool has_key = false, has_trns = false; uint16_t key[3] = { 0, 0, 0 };          // tRNS colour key of gray (key[0]) and truecolour files, compared on all 16 bits
   int npass = 0; PngPass pass[7];                                                 // the passes that have pixels, in stream order
   std::vector<uint8_t> raw;
+  // what the file says about its colour (the chunks before IDAT), by the PNG specification's priority: 1 iCCP (icc, or icc_oversize when it inflates beyond
+  // PNG_ICC_MAX), 2 sRGB, 3 gAMA (file_gamma, with cHRM's white x y, red x y, green x y, blue x y when has_chrm; a cHRM chunk of eight zeros counts as absent),
+  // 0 none.  Nothing in the pixel path reads it.  The reader keeps the first iCCP chunk's body as it is in the file (iccp_body); `colour` and `icc` are valid
+  // after png_resolve_colour, which inflates it: a file that is never asked about its colour never pays for that.
+  int colour = 0; std::vector<uint8_t> icc; bool icc_oversize = false; double file_gamma = 0.0; bool has_chrm = false; double chrm[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+  std::vector<uint8_t> iccp_body; bool has_srgb = false, colour_resolved = false;
   bool has_alpha() const { return ctype == 4 || ctype == 6 || has_trns; }
 };
+
+constexpr size_t PNG_ICC_MAX = (size_t)4 << 20;
+// the body of an iCCP chunk (name, 0, compression method 0, zlib stream) -> the profile; false = broken (the chunk then counts as absent); *oversize = inflates beyond PNG_ICC_MAX
+inline bool png_inflate_iccp(const uint8_t *body, size_t n, std::vector<uint8_t> &icc, bool *oversize) {
+  *oversize = false;
+  size_t k = 0;
+  while (k < n && k < 80 && body[k]) k++;
+  if (k == 0 || k >= 80 || k + 2 > n || body[k] != 0 || body[k + 1] != 0) return false;
+  const uint8_t *z = body + k + 2; const size_t zn = n - k - 2;
+  if (zn == 0 || zn > 0xFFFFFFFFu) return false;
+  z_stream zs; memset(&zs, 0, sizeof(zs));
+  if (inflateInit(&zs) != Z_OK) return false;
+  zs.next_in = const_cast<uint8_t *>(z); zs.avail_in = (uInt)zn;
+  icc.clear();
+  uint8_t buf[16384]; int zr = Z_OK;
+  while (zr == Z_OK) {
+    zs.next_out = buf; zs.avail_out = sizeof(buf);
+    zr = inflate(&zs, Z_NO_FLUSH);
+    if (zr != Z_OK && zr != Z_STREAM_END) break;
+    icc.insert(icc.end(), buf, buf + (sizeof(buf) - zs.avail_out));
+    if (icc.size() > PNG_ICC_MAX) { inflateEnd(&zs); icc.clear(); *oversize = true; return true; }
+    if (zr == Z_OK && zs.avail_in == 0 && zs.avail_out != 0) break;      // the stream ends before its end marker
+  }
+  inflateEnd(&zs);
+  if (zr != Z_STREAM_END || icc.empty()) { icc.clear(); return false; }
+  return true;
+}
+
+// the file's colour description by priority (PngScanlines::colour): inflates the kept iCCP body once; a broken profile chunk counts as absent.  Not thread-safe:
+// whoever shares a PngScanlines between threads calls it under a lock (mi_png_scanlines does)
+inline void png_resolve_colour(PngScanlines &sl) {
+  if (sl.colour_resolved) return;
+  const bool have_icc = !sl.iccp_body.empty() && png_inflate_iccp(sl.iccp_body.data(), sl.iccp_body.size(), sl.icc, &sl.icc_oversize);
+  std::vector<uint8_t>().swap(sl.iccp_body);
+  sl.colour = have_icc ? 1 : sl.has_srgb ? 2 : sl.file_gamma > 0.0 ? 3 : 0;
+  sl.colour_resolved = true;
+}
 
 // Chunk walk, IHDR / PLTE / tRNS checks, size guard and inflate; every filter byte is checked (> 4 is an error), and so is every palette index when
 // PLTE is shorter than the index range -- for that the scanlines are unfiltered here and handed on as a filter-0 stream.
@@ -77,6 +121,12 @@ inline int png_read_scanlines(const uint8_t *d, size_t len, PngScanlines &sl) {
     else if (!memcmp(type, "tRNS", 4)) trns.assign(body, body + n);
     else if (!memcmp(type, "IDAT", 4)) idat.insert(idat.end(), body, body + n);
     else if (!memcmp(type, "IEND", 4)) break;
+    else if (idat.empty()) {                                   // the colour chunks come before IDAT; a broken one counts as absent and never as an error of the picture
+      if (!memcmp(type, "iCCP", 4)) { if (sl.iccp_body.empty()) sl.iccp_body.assign(body, body + n); }
+      else if (!memcmp(type, "sRGB", 4)) sl.has_srgb = sl.has_srgb || n == 1;
+      else if (!memcmp(type, "gAMA", 4)) { if (n == 4 && png_be32(body) != 0) sl.file_gamma = (double)png_be32(body) / 100000.0; }
+      else if (!memcmp(type, "cHRM", 4)) { if (n == 32) { for (int i = 0; i < 8; i++) { sl.chrm[i] = (double)png_be32(body + 4 * i) / 100000.0; sl.has_chrm = sl.has_chrm || sl.chrm[i] != 0.0; } } }
+    }
     pos += 12 + (size_t)n;
   }
   if (!have_ihdr || idat.empty()) return 3;

@@ -178,6 +178,18 @@ def load_library():
     L.mi_png_scanlines_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.mi_ravif_encode_device16.argtypes = [C.POINTER(_RavifEncoder), C.POINTER(_DevicePixels16), C.c_uint32, C.c_uint32, C.POINTER(_EncodedImage)]
     L.mi_ravif_encode_device_ycbcr.argtypes = [C.POINTER(_RavifEncoder), C.POINTER(_DevicePlanes), C.c_uint32, C.c_uint32, C.POINTER(_EncodedImage)]
+    L.mi_colour_transform_from_icc.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p)]
+    L.mi_colour_transform_from_png.argtypes = [C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_void_p)]
+    L.mi_colour_transform_free.argtypes = [C.c_void_p]
+    L.mi_colour_transform_free.restype = None
+    L.mi_colour_transform_is_identity.argtypes = [C.c_void_p]
+    L.mi_colour_probe_icc.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_int)]
+    L.mi_colour_probe_png.argtypes = [C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int)]
+    L.mi_colour_transform_table.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+    L.mi_colour_transform_table.restype = C.c_size_t
+    L.mi_png_scanlines_colour.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.mi_jpeg_coeffs_icc.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+    L.mi_batch_convert_colour.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     _LIB = L
     return L
 
@@ -249,6 +261,9 @@ class JpegCoeffs:
         if st:
             raise AvifError(st)
         self.color, self.subsampling = self.COLORS[color.value], (hs.value, vs.value)
+        p, n = C.c_void_p(), C.c_size_t()
+        L.mi_jpeg_coeffs_icc(self._h, C.byref(p), C.byref(n))
+        self.icc_profile = C.string_at(p.value, n.value) if p.value and n.value else None   # the file's APP2 ICC profile, or None
 
     def close(self):
         if getattr(self, '_h', None):
@@ -284,6 +299,11 @@ class PngScanlines:
         ct, bd = C.c_int(), C.c_int()
         L.mi_png_scanlines_info(self._h, C.byref(ct), C.byref(bd))
         self.color_type, self.bit_depth = ct.value, bd.value
+        # what the file says about its colour: None, ('icc', bytes), ('srgb',) or ('gamma', file_gamma, the eight cHRM values or None); a profile that inflates
+        # beyond 4 MiB shows as ('icc', None)
+        what, p, n, g, chrm = C.c_int(), C.c_void_p(), C.c_size_t(), C.c_double(), (C.c_double * 8)()
+        L.mi_png_scanlines_colour(self._h, C.byref(what), C.byref(p), C.byref(n), C.byref(g), chrm)
+        self.colour = (None, ('icc', C.string_at(p.value, n.value) if p.value else None), ('srgb',), ('gamma', g.value, tuple(chrm) if any(chrm) else None))[what.value]
 
     def close(self):
         if getattr(self, '_h', None):
@@ -302,6 +322,73 @@ def parse_png(data):
     return PngScanlines(data)
 
 
+class ColourTransform:
+    """A colour description baked into a transform to sRGB (mi_colour_transform): host state, applied to batch slots on the device by
+    BatchEncoder.convert_colour.  from_icc(bytes): an ICC v2 / v4 RGB matrix/TRC profile (any other well-formed profile raises Unsupported, a malformed one
+    EncodingError); from_png(gamma, chrm=None): a gAMA value with the eight cHRM values or None; for_source(handle): what a PngScanlines or JpegCoeffs says
+    about itself (the identity when it says nothing).  `is_identity`: converting is a no-op.  close() (or the garbage collector) frees it."""
+
+    def __init__(self, handle):
+        self._L, self._h = load_library(), handle
+        self.is_identity = bool(self._L.mi_colour_transform_is_identity(handle))
+
+    @classmethod
+    def from_icc(cls, profile):
+        L = load_library()
+        profile = bytes(profile)
+        h = C.c_void_p()
+        st = L.mi_colour_transform_from_icc(profile, len(profile), C.byref(h))
+        if st:
+            raise AvifError(st)
+        return cls(h.value)
+
+    @classmethod
+    def from_png(cls, gamma, chrm=None):
+        L = load_library()
+        h = C.c_void_p()
+        c = None
+        if chrm is not None:
+            if len(chrm) != 8:
+                raise AvifError(4)
+            c = (C.c_double * 8)(*[float(v) for v in chrm])
+        st = L.mi_colour_transform_from_png(float(gamma), c, C.byref(h))
+        if st:
+            raise AvifError(st)
+        return cls(h.value)
+
+    @classmethod
+    def for_source(cls, handle):
+        what = handle.colour if isinstance(handle, PngScanlines) else ('icc', handle.icc_profile) if handle.icc_profile else None
+        if what and what[0] == 'icc':
+            if what[1] is None:
+                raise AvifError(2)                      # a PNG profile beyond the 4 MiB cap
+            return cls.from_icc(what[1])
+        if what and what[0] == 'gamma':
+            return cls.from_png(what[1], what[2])
+        return cls.from_png(0.0)
+
+    def table(self, which):
+        """the baked integers (tests): 0 matrix (int64, 3 x 3), 1 lin8 (3 x 256), 2 U (256), 3 lin16 (3 x 4098), 4 out16 (8194); None for the identity"""
+        p = C.c_void_p()
+        n = self._L.mi_colour_transform_table(self._h, which, C.byref(p))
+        if not n:
+            return None
+        dt = (np.int64, np.uint32, np.uint32, np.uint32, np.uint16)[which]
+        a = np.frombuffer(C.string_at(p.value, n * np.dtype(dt).itemsize), dtype=dt).copy()
+        return a.reshape(3, -1) if which in (0, 1, 3) else a
+
+    def close(self):
+        if getattr(self, '_h', None):
+            self._L.mi_colour_transform_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 RESAMPLE_FILTERS = {'box': 0, 'bilinear': 1, 'bicubic': 2, 'lanczos': 3}       # MI_RESAMPLE_*: Pillow's filters of the same names
 
 
@@ -316,7 +403,7 @@ def _is_device_array(x):
 
 
 DECODED_WHICH = {'recon': 0, 'source': 1}                   # MI_DECODED_*
-SOURCE_HOST, SOURCE_JPEG, SOURCE_PNG, SOURCE_JPEG_YCBCR, SOURCE_PNG_DEEP = range(5)       # MI_SOURCE_*: what mi_ravif_encode_sources takes
+SOURCE_HOST, SOURCE_JPEG, SOURCE_PNG, SOURCE_JPEG_YCBCR, SOURCE_PNG_DEEP, SOURCE_JPEG_MANAGED, SOURCE_PNG_MANAGED, SOURCE_PNG_DEEP_MANAGED = range(8)   # MI_SOURCE_*: what mi_ravif_encode_sources takes
 
 
 def _decoded_which(name):
@@ -819,6 +906,38 @@ class Encoder:
             raise AvifError(4)
         return _encode_sources(self, [(SOURCE_JPEG_YCBCR if ycbcr else SOURCE_JPEG, c, 3)], None)[0]
 
+    def encode_managed(self, data_or_handle, deep=False):
+        """a PNG or JPEG file (bytes, a PngScanlines or a JpegCoeffs) converted to sRGB by its own colour description -- an ICC profile, or gAMA with an
+        optional cHRM -- on the device, then encoded: a one-image batch, uploaded as upload_png / upload_jpeg do, then convert_colour.  Opaque or with alpha
+        by the file.  deep=True sends a 16-bit PNG through its deep slot (the alpha rules of deep input apply).  A file whose profile is unsupported or
+        malformed is encoded unmanaged (as the stream fan-out and cavif_mi --color-managed do); a file that says nothing, or sRGB, is encoded as it is."""
+        src = data_or_handle
+        if not isinstance(src, (PngScanlines, JpegCoeffs)):
+            src = bytes(src)
+            src = PngScanlines(src) if src[:8] == b'\x89PNG\r\n\x1a\n' else JpegCoeffs(src)
+        if not src._h:
+            raise AvifError(4)
+        try:
+            t = ColourTransform.for_source(src)
+        except AvifError as ex:
+            if ex.code not in (2, 3):
+                raise
+            t = None
+        b = BatchEncoder(self, 1, src.width, src.height, 4 if isinstance(src, PngScanlines) and src.has_alpha else 3)
+        try:
+            if isinstance(src, PngScanlines):
+                b.upload_png(0, src, deep=deep)
+            else:
+                b.upload_jpeg(0, src)
+            if t is not None:
+                b.convert_colour(0, t)
+            b.encode()
+            return b.get(0)
+        finally:
+            b.close()
+            if t is not None:
+                t.close()
+
     def encode_ycbcr_device(self, y, cb, cr=None, subsampling=(2, 2)):
         """8-bit BT.601 full-range planes in device memory (objects with __cuda_array_interface__; see BatchEncoder.upload_device_ycbcr for the shapes) as
         one opaque picture: mi_ravif_encode_device_ycbcr"""
@@ -865,20 +984,43 @@ class Encoder:
         return self._raw(load_library().mi_ravif_encode_raw_planes_10, np.uint16, planes, alpha, width, height, color_pixel_range, matrix_coefficients)
 
 
-def encode_many(encoder, images, devices=None, jpeg_ycbcr=False, png_deep=False):
+def _source_converts(handle):
+    """a parsed file's own colour description gives a usable transform that is not the identity (mi_colour_probe_*: parsed, nothing baked): the rule by which
+    cavif_mi --color-managed sends a JPEG the RGB way under --jpeg-ycbcr"""
+    L = load_library()
+    what = handle.colour if isinstance(handle, PngScanlines) else ('icc', handle.icc_profile) if handle.icc_profile else None
+    ident = C.c_int(1)
+    if what and what[0] == 'icc':
+        st = L.mi_colour_probe_icc(what[1], len(what[1]), C.byref(ident)) if what[1] is not None else 2
+    elif what and what[0] == 'gamma':
+        st = L.mi_colour_probe_png(what[1], (C.c_double * 8)(*what[2]) if what[2] else None, C.byref(ident))
+    else:
+        return False
+    return st == 0 and not ident.value
+
+
+def encode_many(encoder, images, devices=None, jpeg_ycbcr=False, png_deep=False, managed=False):
     """mi_ravif_encode_sources: the reference's files.into_par_iter() (src/main.rs:223) over the node's GPUs.
     images: list of HxWx3 / HxWx4 uint8 arrays (shapes may differ), JpegCoeffs objects (parse_jpeg; encoded as the RGBA pictures decode_jpeg
     gives, decoded on the device) and PngScanlines objects (parse_png; encoded as the RGBA pictures load_rgba gives, unfiltered and expanded on the
     device).  jpeg_ycbcr=True: a JpegCoeffs whose colour is not RGB is coded from the file's own Y, Cb, Cr (source kind SOURCE_JPEG_YCBCR) instead.
     png_deep=True: a PngScanlines goes as source kind SOURCE_PNG_DEEP: a file of bit depth 16 is coded from all 16 bits of its samples.
+    managed=True: a parsed file is converted to sRGB by its own colour description after its upload (the source kinds SOURCE_*_MANAGED); a file whose
+    profile is unsupported or malformed is coded unmanaged and raises nothing.  With jpeg_ycbcr, a JPEG whose profile gives a usable transform that is not
+    the identity goes the RGB way (the conversion needs RGB), every other one keeps its YCbCr: cavif_mi's rule.  Host arrays are never converted.
     Returns a list of EncodedImage."""
     items = []
     for im in images:
         if isinstance(im, (JpegCoeffs, PngScanlines)):
             if not im._h:
                 raise AvifError(4)
-            items.append((SOURCE_PNG_DEEP if png_deep else SOURCE_PNG, im, 4) if isinstance(im, PngScanlines) else
-                         (SOURCE_JPEG_YCBCR if jpeg_ycbcr and im.color != 'rgb' else SOURCE_JPEG, im, 4))
+            if managed and isinstance(im, PngScanlines):
+                items.append((SOURCE_PNG_DEEP_MANAGED if png_deep else SOURCE_PNG_MANAGED, im, 4))
+            elif managed and (not jpeg_ycbcr or im.color == 'rgb' or _source_converts(im)):
+                items.append((SOURCE_JPEG_MANAGED, im, 4))
+            else:
+                items.append((SOURCE_PNG_DEEP if png_deep else SOURCE_PNG, im, 4) if isinstance(im, PngScanlines) else
+                             (SOURCE_JPEG_YCBCR if jpeg_ycbcr and im.color != 'rgb' else SOURCE_JPEG, im, 4))
             continue
         if _is_device_array(im):
             raise TypeError('encode_many takes host arrays, JpegCoeffs and PngScanlines; pixels in device memory go through BatchEncoder.upload_device')
@@ -897,10 +1039,10 @@ def _encode_sources(encoder, items, devices):
     def fetch(_user, i, src):
         (kind, it, channels), s = items[i], src.contents
         s.kind = kind
-        if kind in (SOURCE_PNG, SOURCE_PNG_DEEP):
+        if kind in (SOURCE_PNG, SOURCE_PNG_DEEP, SOURCE_PNG_MANAGED, SOURCE_PNG_DEEP_MANAGED):
             s.jpeg, s.png = None, it._h
             s.desc.pixels, s.desc.width, s.desc.height, s.desc.stride_px, s.desc.channels = None, it.width, it.height, it.width, channels
-        elif kind in (SOURCE_JPEG, SOURCE_JPEG_YCBCR):
+        elif kind in (SOURCE_JPEG, SOURCE_JPEG_YCBCR, SOURCE_JPEG_MANAGED):
             s.jpeg, s.png = it._h, None
             s.desc.pixels, s.desc.width, s.desc.height, s.desc.stride_px, s.desc.channels = None, it.width, it.height, it.width, channels
         else:
@@ -1012,6 +1154,17 @@ class BatchEncoder:
         st = (self._L.mi_batch_upload_png_deep if deep else self._L.mi_batch_upload_png)(self._h, first, len(handles), arr)
         if st:
             raise AvifError(st)
+
+    def convert_colour(self, first, transform, count=1):
+        """mi_batch_convert_colour: the colour channels of slots first.. through a ColourTransform, in place, on the batch's stream after the uploads that filled
+        them; 8-bit and deep slots alike, alpha untouched, the input kind unchanged.  The identity transform launches nothing.  A YCbCr slot, a range past the
+        capacity or a call in flight raises InvalidArgument.  The transform is kept referenced until wait()."""
+        if not isinstance(transform, ColourTransform) or not transform._h:
+            raise AvifError(4)
+        st = self._L.mi_batch_convert_colour(self._h, first, count, transform._h)
+        if st:
+            raise AvifError(st)
+        self._sources.append(transform)
 
     def resize_device(self, first, pixels, filter='lanczos'):
         """upload_device for pictures of any size (taken from the array): resampled into the slots on the batch's stream, the pixels of Pillow's

@@ -117,9 +117,14 @@ int  mi_ravif_encode_stream(const mi_ravif_encoder *e, size_t n, mi_fetch_fn fet
  * MI_SOURCE_PNG_DEEP (kind 4): a parsed PNG file as for kind 2, uploaded through mi_batch_upload_png_deep (below): a file of bit depth 16 is coded from all 16 bits of its samples, any
  * other file exactly as kind 2.  A 16-bit file that the alpha rules of deep input refuse (4 channels: alpha or tRNS unless alpha_mode is 0; any under
  * alpha_mode 2) gets MI_INVALID_ARGUMENT, for that image alone.
+ * MI_SOURCE_JPEG_MANAGED (kind 5), MI_SOURCE_PNG_MANAGED (6), MI_SOURCE_PNG_DEEP_MANAGED (7): as kinds 1, 2 and 4 (fields, refusals, release), with the file's own
+ * colour description -- a JPEG's APP2 profile; a PNG's iCCP profile, else gAMA with an optional cHRM -- applied to the slot after the upload
+ * (mi_batch_convert_colour below).  A file that says nothing or sRGB, and a file whose profile is unsupported or malformed, is encoded unmanaged with status MI_OK.
+ * A worker bakes one transform per distinct description (cached by the description's bytes: hash, then compare); neighbours of a run that share it share a launch.
  * mi_ravif_encode_stream is this call with MI_SOURCE_HOST throughout.  Pictures in device memory are not a kind here (a pointer belongs to one
  * device, the shared cursor hands images to any): they enter through mi_ravif_encode_device and mi_batch_upload_device. */
-enum { MI_SOURCE_HOST = 0, MI_SOURCE_JPEG = 1, MI_SOURCE_PNG = 2, MI_SOURCE_JPEG_YCBCR = 3, MI_SOURCE_PNG_DEEP = 4 };
+enum { MI_SOURCE_HOST = 0, MI_SOURCE_JPEG = 1, MI_SOURCE_PNG = 2, MI_SOURCE_JPEG_YCBCR = 3, MI_SOURCE_PNG_DEEP = 4,
+       MI_SOURCE_JPEG_MANAGED = 5, MI_SOURCE_PNG_MANAGED = 6, MI_SOURCE_PNG_DEEP_MANAGED = 7 };
 typedef struct mi_jpeg_coeffs mi_jpeg_coeffs;   /* opaque: one parsed file, host memory only */
 typedef struct mi_png_scanlines mi_png_scanlines;      /* opaque: one inflated file, host memory only */
 typedef struct mi_image_source {
@@ -129,7 +134,7 @@ typedef struct mi_image_source {
                                  kind 2; mi_batch_upload_png_deep below) */
   mi_image_desc desc;
   const mi_jpeg_coeffs *jpeg;
-  const mi_png_scanlines *png; /* kinds 2 and 4 only (the struct grew by this field at its tail: never read for kinds 0 and 1) */
+  const mi_png_scanlines *png; /* kinds 2, 4, 6 and 7 only (the struct grew by this field at its tail: never read for kinds 0 and 1) */
 } mi_image_source;
 typedef int (*mi_fetch_source_fn)(void *user, size_t index, mi_image_source *src);
 int  mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source_fn fetch, mi_release_fn release, void *user, mi_encoded_image *out,
@@ -311,6 +316,49 @@ int  mi_batch_upload16(mi_batch *b, int index, const uint16_t *pixels, size_t st
 int  mi_batch_upload_png_deep(mi_batch *b, int first, int count, const mi_png_scanlines *const *png);
 int  mi_png_scanlines_info(const mi_png_scanlines *p, int *color_type, int *bit_depth);
 int  mi_ravif_encode_device16(const mi_ravif_encoder *e, const mi_device_pixels16 *src, uint32_t w, uint32_t h, mi_encoded_image *out);
+/* ---- colour-managed input (opt-in: without these calls every slot holds the bytes it held before).  Every file this library writes is tagged
+ * sRGB; a source that says something else about its colour is converted to sRGB in its slot, on the device, before it is encoded.
+ * A transform (mi_colour_transform) is host state, baked once: three input curves, the 3 x 3 matrix inverse(sRGB colorants, D50) * (source colorants, D50) and the
+ * sRGB output curve; relative colorimetric, no black-point compensation, each channel clipped to [0, 1] in linear light.  It may be used by any number of
+ * batches, on any device, from any thread, and is released with mi_colour_transform_free (NULL is fine) once no conversion that uses it is still queued (the free
+ * waits for the device).
+ * mi_colour_transform_from_icc: an ICC v2 / v4 RGB matrix/TRC profile (colour space 'RGB ', PCS 'XYZ ', tags rXYZ gXYZ bXYZ rTRC gTRC bTRC; 'curv' with 0, 1 or n
+ * entries, 'para' of types 0..4).  MI_UNSUPPORTED: a well-formed profile of another kind (A2B0 tables, CMYK, grey, Lab PCS, device link, abstract, named colours).
+ * MI_ENCODING_ERROR: a malformed one (a size field beyond the data, a tag outside the profile, a table larger than its tag, a truncated header, a missing tag,
+ * singular colorants).  The parser never reads outside [icc, icc + len).  An ICC transform is never the identity.
+ * mi_colour_transform_from_png: a gAMA value (file_gamma, e.g. 0.45455: the input curve is the pure power 1 / file_gamma) with the eight cHRM values (white x y,
+ * red x y, green x y, blue x y; the white point Bradford-adapted to D50) or NULL (sRGB's primaries).  The identity: |file_gamma * 2.2 - 1| < 0.05 without cHRM
+ * (libpng's significance threshold), and file_gamma 0 without cHRM (a file with an sRGB chunk or no description).  MI_INVALID_ARGUMENT: a gamma that is
+ * negative or not finite; MI_ENCODING_ERROR: degenerate chromaticities.
+ * mi_colour_probe_icc / mi_colour_probe_png: the status the two calls above would give for the same arguments and, with MI_OK, whether the transform would be the
+ * identity (*is_identity, may be NULL), without baking anything: the profile is parsed and the matrix made, no curve is evaluated.  What a loader asks to learn
+ * whether a file can be managed.
+ * mi_colour_transform_is_identity: 1 for such a transform, else 0.  mi_colour_transform_table: the baked integers (tests and debugging): which 0 the matrix
+ * (9 int64, 30 fractional bits, row-major), 1 lin8 (3 x 256 uint32), 2 U (256 uint32), 3 lin16 (3 x 4098 uint32), 4 out16 (8194 uint16); returns the number of
+ * entries and points *data at them (valid while the transform lives), 0 for the identity.  The tables are specified in cavif_rs_amd/csrc/icc_reader.h.
+ * mi_png_scanlines_colour: what a parsed PNG says, by the PNG specification's priority: *what 1 an iCCP profile (*icc, *icc_len: inflated, valid while the handle
+ * lives), 2 an sRGB chunk, 3 gAMA (*file_gamma; chrm8 gets the cHRM values, or eight zeros when the file has none; a cHRM chunk of eight zeros counts as absent), 0 nothing.
+ * A broken colour chunk counts as absent.  mi_png_parse keeps the iCCP chunk as it is in the file; the first call here (or the first managed use of the handle)
+ * inflates it, so a file that is never asked about its colour does not pay for its profile.  MI_UNSUPPORTED (with *what 1, *icc NULL): a profile that inflates beyond 4 MiB.  Any pointer but p and what may be NULL.
+ * mi_jpeg_coeffs_icc: the profile of a parsed JPEG (APP2 "ICC_PROFILE" segments in any order, joined by sequence number), or *icc NULL, *len 0 when the file has
+ * none or its segments do not add up (a missing or duplicate number, disagreeing counts).
+ * mi_batch_convert_colour: the colour channels of slots [first, first + count) through the transform, IN PLACE, on the batch's stream (ordered after the uploads
+ * that filled them, before the next encode).  The launches are asynchronous; the FIRST conversion of a transform on a device first copies the transform's tables
+ * there (one hipMalloc and one blocking 70 KB hipMemcpy, which wait for the device), every later one enqueues and returns.  MI_INPUT_RGB slots are converted in the 8-bit slot array, MI_INPUT_RGB16 slots in the deep one; alpha is
+ * never touched and the input kind stays.  The arithmetic is integers only and specified in cavif_rs_amd/csrc/dev_colour.h.  The identity transform is a no-op
+ * that launches nothing.  MI_INVALID_ARGUMENT: an MI_INPUT_YCBCR slot in the range, a range past the capacity, a null transform, a call between
+ * mi_batch_encode_async and mi_batch_wait; a refused call allocates nothing (mi_batch_footprint). */
+typedef struct mi_colour_transform mi_colour_transform;
+int  mi_colour_transform_from_icc(const uint8_t *icc, size_t len, mi_colour_transform **out);
+int  mi_colour_transform_from_png(double file_gamma, const double *chrm8_or_null, mi_colour_transform **out);
+void mi_colour_transform_free(mi_colour_transform *t);
+int  mi_colour_probe_icc(const uint8_t *icc, size_t len, int *is_identity);
+int  mi_colour_probe_png(double file_gamma, const double *chrm8_or_null, int *is_identity);
+int  mi_colour_transform_is_identity(const mi_colour_transform *t);
+size_t mi_colour_transform_table(const mi_colour_transform *t, int which, const void **data);
+int  mi_png_scanlines_colour(const mi_png_scanlines *p, int *what, const uint8_t **icc, size_t *icc_len, double *file_gamma, double chrm8[8]);
+int  mi_jpeg_coeffs_icc(const mi_jpeg_coeffs *c, const uint8_t **icc, size_t *len);
+int  mi_batch_convert_colour(mi_batch *b, int first, int count, mi_colour_transform *t);
 /* resize on input: the source has any size and is resampled into the slot on the batch's stream, no sync.  The pixels are exactly those of Pillow's
  * Image.resize((w, h), resample=filter, reducing_gap=None) on 8-bit pictures: coefficients in double on the host, 22-bit fixed-point taps, horizontal pass
  * first into an 8-bit intermediate, then the vertical one, a pass whose axis keeps its length skipped; 4-channel sources are premultiplied before the passes and
