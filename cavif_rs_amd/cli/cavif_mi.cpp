@@ -105,6 +105,27 @@ int usage(const char *msg) {
 #include <sys/prctl.h>
 #include <sys/wait.h>
 static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+// one input file: where it goes, what its loader made of it (a JPEG leaves it as coefficients, a PNG as filtered scanlines) and how it is to be sent
+struct Job { std::string in_name, out_path; bool out_stdio = false; mi_jpeg_coeffs *jpeg = nullptr; mi_png_scanlines *png = nullptr; uint32_t w = 0, h = 0; bool ycbcr = false, deep = false, managed = false; std::string error; };
+// the source kind (MI_SOURCE_*) of a loaded job: its file type, then managed (which has switched ycbcr off), ycbcr / deep
+static int source_kind(const Job &j) {
+  if (j.jpeg) return j.managed ? MI_SOURCE_JPEG_MANAGED : j.ycbcr ? MI_SOURCE_JPEG_YCBCR : MI_SOURCE_JPEG;
+  if (j.png) return j.managed ? (j.deep ? MI_SOURCE_PNG_DEEP_MANAGED : MI_SOURCE_PNG_MANAGED) : j.deep ? MI_SOURCE_PNG_DEEP : MI_SOURCE_PNG;
+  return MI_SOURCE_HOST;
+}
+// --color-managed: what the parsed file says about its colour, probed (parsed, no tables) to learn whether it can be converted; the encoder bakes one transform per
+// distinct description.  True: a usable transform that is not the identity.  An unsupported or malformed profile: one warning line (unless quiet), false.
+static bool probe_managed(const Job &j, bool quiet) {
+  const uint8_t *icc = nullptr; size_t icc_len = 0; int what = 0, cst = MI_OK; double gamma = 0.0, chrm[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+  if (j.jpeg) { if (mi_jpeg_coeffs_icc(j.jpeg, &icc, &icc_len) == MI_OK && icc) what = 1; }
+  else cst = mi_png_scanlines_colour(j.png, &what, &icc, &icc_len, &gamma, chrm);
+  int identity = 1; bool has_chrm = false;
+  for (int k = 0; k < 8; k++) has_chrm = has_chrm || chrm[k] != 0.0;                       // eight zeros: the file has no cHRM
+  if (cst == MI_OK && what == 1) cst = mi_colour_probe_icc(icc, icc_len, &identity);
+  else if (cst == MI_OK && what == 3) { cst = mi_colour_probe_png(gamma, has_chrm ? chrm : nullptr, &identity); if (cst == MI_INVALID_ARGUMENT) cst = MI_ENCODING_ERROR; }
+  if (cst != MI_OK && !quiet) fprintf(stderr, "warning: %s: %s colour profile; encoding it unmanaged\n", j.in_name.c_str(), cst == MI_UNSUPPORTED ? "unsupported" : "malformed");
+  return cst == MI_OK && !identity;
+}
 int main(int argc, char **argv) {
   const double t_start = now_s(); const bool timing = getenv("CAVIF_MI_TIMING") != nullptr;
   // The loaders' buffers (file, inflate output: ~6 MB each) come from the heap arenas and stay there: as anonymous mappings every one of them is an
@@ -212,7 +233,6 @@ int main(int argc, char **argv) {
   enc.threads = threads > 0 ? threads : host_threads();
 
   // load + decide output paths (process(), :169-200); failures are collected per file and reported at the end
-  struct Job { std::string in_name, out_path; bool out_stdio = false; mi_jpeg_coeffs *jpeg = nullptr; mi_png_scanlines *png = nullptr; uint32_t w = 0, h = 0; bool ycbcr = false, deep = false, managed = false; std::string error; };
   std::vector<Job> jobs(files.size());
   // the reference loads inside files.into_par_iter() (src/main.rs:223): file reads + PNG inflate / JPEG entropy decodes fan out over the host cores; a JPEG leaves
   // its loader as coefficients (dequantisation, IDCT, upsampling and colour run on the device that encodes it), a PNG as filtered scanlines (unfiltered and
@@ -231,19 +251,8 @@ int main(int argc, char **argv) {
       int color = 2, png_depth = 0;
       if (!st && is_png && deep_png && mi_png_scanlines_info(j.png, nullptr, &png_depth) == MI_OK) j.deep = png_depth == 16 && (!png_alpha || dirty_alpha);
       if (!st && is_jpeg && jpeg_ycbcr && color_model == 0 && mi_jpeg_coeffs_info(j.jpeg, &color, nullptr, nullptr) == MI_OK) j.ycbcr = color != 2;
-      if (!st && color_managed) {
-        // what the file says about its colour, probed here (parsed, no tables) to learn whether it can be converted; the encoder bakes one transform per distinct description
-        const uint8_t *icc = nullptr; size_t icc_len = 0; int what = 0, cst = MI_OK; double gamma = 0.0, chrm[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-        if (is_jpeg) { if (mi_jpeg_coeffs_icc(j.jpeg, &icc, &icc_len) == MI_OK && icc) what = 1; }
-        else cst = mi_png_scanlines_colour(j.png, &what, &icc, &icc_len, &gamma, chrm);
-        int identity = 1; bool has_chrm = false;
-        for (int k = 0; k < 8; k++) has_chrm = has_chrm || chrm[k] != 0.0;                       // eight zeros: the file has no cHRM
-        if (cst == MI_OK && what == 1) cst = mi_colour_probe_icc(icc, icc_len, &identity);
-        else if (cst == MI_OK && what == 3) { cst = mi_colour_probe_png(gamma, has_chrm ? chrm : nullptr, &identity); if (cst == MI_INVALID_ARGUMENT) cst = MI_ENCODING_ERROR; }
-        j.managed = cst == MI_OK && !identity;
-        if (cst != MI_OK && !quiet) fprintf(stderr, "warning: %s: %s colour profile; encoding it unmanaged\n", j.in_name.c_str(), cst == MI_UNSUPPORTED ? "unsupported" : "malformed");
-        if (j.managed) j.ycbcr = false;                             // the conversion needs RGB
-      }
+      if (!st && color_managed) j.managed = probe_managed(j, quiet);
+      if (j.managed) j.ycbcr = false;                               // the conversion needs RGB
       if (st) j.error = st == MI_UNSUPPORTED ? "unsupported image format (this build reads PNG and baseline/progressive 8-bit JPEG)" :
                         st == MI_NO_DEVICE ? "no HIP device (this encoder has no CPU fallback)" : "corrupt image data";
     }
@@ -283,8 +292,7 @@ int main(int argc, char **argv) {
     { std::unique_lock<std::mutex> lk(*c->mu); c->cv->wait(lk, [&] { return (*c->loaded)[i] != 0; }); }
     const Job &j = (*c->jobs)[i];
     if (!j.error.empty()) return MI_INVALID_ARGUMENT;           // reported from the job's own message below
-    src->kind = j.jpeg ? (j.managed ? MI_SOURCE_JPEG_MANAGED : j.ycbcr ? MI_SOURCE_JPEG_YCBCR : MI_SOURCE_JPEG) :
-                j.png ? (j.managed ? (j.deep ? MI_SOURCE_PNG_DEEP_MANAGED : MI_SOURCE_PNG_MANAGED) : j.deep ? MI_SOURCE_PNG_DEEP : MI_SOURCE_PNG) : MI_SOURCE_HOST; src->jpeg = j.jpeg; src->png = j.png;
+    src->kind = source_kind(j); src->jpeg = j.jpeg; src->png = j.png;
     mi_image_desc *d = &src->desc;
     d->pixels = nullptr; d->width = j.w; d->height = j.h; d->stride_px = j.w; d->channels = 4;     // a JPEG or PNG into an RGBA slot: the pixels load_rgba gives it
     return MI_OK;

@@ -1,6 +1,7 @@
 // mi_avif.hip -- the entry points of include/mi_avif.h: the batch's lifecycle and its encode (K0 front end, pack + D2H, AVIF containers, timing), its
-// pool, the stream worker and the level-1 plane encoder.  Every call through which pixels reach a slot or leave it (host, device,
-// JPEG, PNG, 16-bit, resize, decoded output) is host_input.h, included below the pool.  The frame chain they all run (plans, arena, K1 tile search, K2 deblock,
+// pool, the one-call entry points and the level-1 plane encoder.  Every call through which pixels reach a slot or leave it (host, device,
+// JPEG, PNG, 16-bit, resize, decoded output) is host_input.h, included below the pool; the stream fan-out (source kinds, per-device worker, mi_ravif_encode_sources /
+// _stream / _batch) is host_stream.h, included below the one-call entry points.  The frame chain they all run (plans, arena, K1 tile search, K2 deblock,
 // K3 CDEF, K5 restoration, K4 tile entropy coding, readback) is host_frames.h.  One HIP stream per batch, no hidden device syncs
 // other than the two points where the host needs device results (alpha flags, tile lengths).
 #include <hip/hip_runtime.h>
@@ -31,12 +32,6 @@
 
 // The product library reads no environment variables; probe builds (tools/) get MI_AVIF_TIMING=1 (-DMI_TUNING_KNOBS: host-side timeline on stderr)
 // and MI_DEBUG_LEVEL (-DMI_DEBUG_HOOKS=1: bisect levels of the tile search).
-// the streaming form's rotation: resident batch objects per image shape, and the first run's share of a full run
-#ifndef MI_STREAM_SLOTS_DEFAULT
-#define MI_STREAM_SLOTS_DEFAULT 2          /* 256 x 1080p files end to end: 1.32 s with two, 1.48 with three, 1.51 with four (profiles/r05zk_e2e_knobs.txt, matrix 5) */
-#endif
-#define MI_STREAM_FIRST_RUN_NUM 1         /* a worker's first run as a share of a full one: a whole run (a half run started the GPU ~0.03 s earlier and cost two runs of 16 images, */
-#define MI_STREAM_FIRST_RUN_DEN 1         /* 0.09 s of tile search each against 0.10 for 32: worker phase 1.24 -> 1.20 s on 256 files, profiles/r05zk_e2e_knobs.txt matrix 6) */
 static inline bool mi_timing_enabled() {
 #ifdef MI_TUNING_KNOBS
   static const bool on = getenv("MI_AVIF_TIMING") != nullptr; return on;
@@ -531,274 +526,11 @@ int mi_ravif_encode_device_resized(const mi_ravif_encoder *e, const mi_device_pi
   return encode_pooled(e, w, h, src->channels, out, [&](mi_batch *b) { return mi_batch_resize_device(b, 0, 1, src, src_w, src_h, filter); });
 }
 
-// ---- the stream worker: the kinds of source it takes (MI_SOURCE_*) ----
-// (the managed kinds: as MI_SOURCE_JPEG / _PNG / _PNG_DEEP, with the file's own colour description applied after the upload)
-static bool is_managed(int kind) { return kind == MI_SOURCE_JPEG_MANAGED || kind == MI_SOURCE_PNG_MANAGED || kind == MI_SOURCE_PNG_DEEP_MANAGED; }
-static int upload_kind(int kind) { return kind == MI_SOURCE_JPEG_MANAGED ? MI_SOURCE_JPEG : kind == MI_SOURCE_PNG_MANAGED ? MI_SOURCE_PNG : kind == MI_SOURCE_PNG_DEEP_MANAGED ? MI_SOURCE_PNG_DEEP : kind; }
-static bool is_jpeg(int kind) { kind = upload_kind(kind); return kind == MI_SOURCE_JPEG || kind == MI_SOURCE_JPEG_YCBCR; }
-static bool is_png(int kind) { kind = upload_kind(kind); return kind == MI_SOURCE_PNG || kind == MI_SOURCE_PNG_DEEP; }
-// the colour description of a managed source (icc_reader.h: the kind travels beside the bytes; a view into the source's handle)
-static ColourDescription source_colour_description(const mi_image_source &src) {
-  if (is_jpeg(src.kind)) return colour_description_of_icc(src.jpeg->jc.icc.data(), src.jpeg->jc.icc.size());
-  const PngScanlines &sl = png_handle_colour(src.png);
-  return colour_description_of_png(sl.colour, sl.icc_oversize, sl.icc.data(), sl.icc.size(), sl.file_gamma, sl.has_chrm, sl.chrm);
-}
-// MI_OK, or the status of a fetched source that names nothing usable or that its upload call would refuse: it fails alone, not with its run
-static int source_refusal(const mi_ravif_encoder &e, const mi_image_source &src) {
-  const mi_image_desc &x = src.desc;
-  const bool have = src.kind == MI_SOURCE_HOST ? x.pixels != nullptr : is_jpeg(src.kind) ? src.jpeg && src.jpeg->jc.w == x.width && src.jpeg->jc.h == x.height :
-                    is_png(src.kind) && src.png && src.png->sl.w == x.width && src.png->sl.h == x.height && !(x.channels == 3 && src.png->sl.has_alpha());
-  if (!have || !x.width || !x.height || (x.channels != 3 && x.channels != 4)) return MI_INVALID_ARGUMENT;
-  if (src.kind == MI_SOURCE_JPEG_YCBCR && !batch_takes_ycbcr(e, x.channels)) return MI_INVALID_ARGUMENT;      // the batch's rule first, then the file's colour, as in mi_batch_upload_jpeg_ycbcr
-  if (src.kind == MI_SOURCE_JPEG_YCBCR && src.jpeg->jc.color == JPEG_RGB) return MI_UNSUPPORTED;
-  if (upload_kind(src.kind) == MI_SOURCE_PNG_DEEP && png_goes_deep(src.png) && !batch_takes_deep(e, x.channels, src.png->sl.has_alpha() ? 4 : 3)) return MI_INVALID_ARGUMENT;
-  return MI_OK;
-}
+}  // extern "C"
 
-// The reference's files.into_par_iter() (src/main.rs:223) over the GPUs of one node: images are independent, so a host
-// thread per device pulls runs of equally-shaped images from a shared cursor and pushes each run through one resident
-// batch (no collective, no cross-device traffic).  status[i] receives the per-image result; returns the first failure.
-// Streaming form of the fan-out: image i is obtained through `fetch(user, i, &desc)` when a worker is about to stage it (the
-// call may block until the pixels exist -- e.g. until a loader thread has decoded the file), so loading, upload, encoding and
-// assembly of consecutive runs overlap.  fetch returns MI_OK or a status that becomes the image's status.  An image is host pixels (MI_SOURCE_HOST) or the
-// coefficients of a parsed JPEG (MI_SOURCE_JPEG; _JPEG_YCBCR: the same, kept as the file's own YCbCr) or the scanlines of a parsed PNG (MI_SOURCE_PNG; _PNG_DEEP: the
-// same, a file of bit depth 16 through its deep slot), whose pixels come into being in the batch's HBM input slot; mi_ravif_encode_stream is this
-// with MI_SOURCE_HOST throughout.
-int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source_fn fetch, mi_release_fn release, void *user, mi_encoded_image *out, int *status, const int *devices, int ndev) {
-  if (!e || !fetch || (n && !out)) return MI_INVALID_ARGUMENT;
-  const int have = mi_device_count();
-  std::vector<int> devs;
-  if (devices && ndev > 0) devs.assign(devices, devices + ndev); else for (int d = 0; d < have; d++) devs.push_back(d);
-  for (int d : devs) if (d < 0 || d >= have) { fprintf(stderr, "mi_avif: no HIP device %d (no CPU fallback)\n", d); return MI_NO_DEVICE; }
-  if (devs.empty()) { fprintf(stderr, "mi_avif: no HIP device (no CPU fallback)\n"); return MI_NO_DEVICE; }
-  std::vector<int> st(n, MI_OK);
-  for (size_t i = 0; i < n; i++) { out[i].avif_file = nullptr; out[i].avif_len = out[i].color_byte_size = out[i].alpha_byte_size = 0; }
-  std::atomic<size_t> cursor{ 0 };
-  // A run holds at most 32 images, and no more than an even share of the job when it is small (64 files on 8 GPUs: 8 each, not 32 + 32 + nothing).
-  const size_t max_run = std::min<size_t>(32, std::max<size_t>(1, (n + devs.size() - 1) / devs.size()));
-  const bool timing = mi_timing_enabled();
-  const auto t0 = std::chrono::steady_clock::now();
-  auto since = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3; };
-  // Per device: two resident batch objects (from the pool) per image shape (MI_STREAM_SLOTS_DEFAULT).  While one batch encodes, the host fills the next one's
-  // pinned staging and enqueues its H2D + encode, so uploads, tile search, entropy coding and the host-side assembly of consecutive runs overlap
-  // (the same rotation bench.py drives).  Memory is bounded: a batch object holds as many images of its shape as fit MI_SLOT_BYTES (one 12 MP RGBA
-  // image needs ~1.5 GB: such a shape gets runs of a few images, not 32), and before a new object is made the worker gives back the objects of the
-  // shapes it has not used for the longest time until the total stays under its budget (a share of the device's free memory at the start).
-  constexpr size_t MI_SLOT_BYTES = (size_t)8 << 30;
-  auto est_bytes = [](uint32_t w, uint32_t h, int ch, size_t images) { return images * (size_t)w * h * (ch == 4 ? 110 : 82) + ((size_t)32 << 20); };   // arena + records + staging per pixel (measured on the planner)
-  // what a batch object adds at its first JPEG image: MI_BATCH_JPEG_STAGED images' coefficients (at most three full planes of int16) pinned and on the device, one image's planes
-  auto est_jpeg_bytes = [](uint32_t w, uint32_t h) { return ((size_t)w + 15) * ((size_t)h + 15) * (2 * MI_BATCH_JPEG_STAGED * 6 + 3) + ((size_t)3 << 20); };
-  auto worker = [&](int dev) {
-    mi_ravif_encoder enc = *e; enc.device = dev;
-    std::future<int> warm = std::async(std::launch::async, [dev]() { return hipSetDevice(dev) == hipSuccess ? ensure_tables(dev) : (int)MI_ENCODING_ERROR; });
-    size_t budget = (size_t)48 << 30;
-    { size_t fr = 0, tot = 0; if (hipSetDevice(dev) == hipSuccess && hipMemGetInfo(&fr, &tot) == hipSuccess && fr) budget = fr / 10 * 6; }
-    { int sharing = 0; for (int d2 : devs) sharing += d2 == dev; budget /= (size_t)std::max(1, sharing); }      // workers on the same ordinal (devices = [0, 0]) split what is free
-    static constexpr int NSLOT_MAX = 4;
-    const int NSLOT = MI_STREAM_SLOTS_DEFAULT;
-    struct Slot { mi_batch *b = nullptr; std::future<mi_batch *> making; std::vector<size_t> idx; bool busy = false, jpeg = false, deep = false; size_t bytes = 0, png_bytes = 0; };
-    struct Shape { uint32_t w, h; int ch; size_t cap; Slot slot[NSLOT_MAX]; int next = 0; size_t runs = 0, last_use = 0; };
-    std::vector<std::unique_ptr<Shape>> shapes;
-    // the transforms of the managed sources, by the bytes of their colour description (hash, then compare): a thousand photos of one phone bake one transform.
-    // nullptr = unsupported or malformed.  They live until the worker's last run has been collected.
-    struct Baked { ColourKey key; mi_colour_transform *t; };
-    std::vector<Baked> baked;
-    auto transform_for = [&](const mi_image_source &src) -> mi_colour_transform * {
-      const ColourDescription desc = source_colour_description(src);
-      if (desc.kind == 0) return nullptr;
-      uint8_t scratch[80]; const uint8_t *p = nullptr; size_t n = 0;
-      colour_description_bytes(desc, scratch, p, n);
-      const uint64_t hash = colour_hash(p, n);
-      for (const Baked &c : baked) if (colour_key_matches(c.key, desc.kind, hash, p, n)) return c.t;
-      baked.push_back(Baked{ colour_key_make(desc.kind, hash, p, n), nullptr });
-      baked.back().t = colour_transform_from_description(colour_description_of_key(baked.back().key));
-      return baked.back().t;
-    };
-    size_t live_bytes = 0, tick = 0;
-    auto charge = [&](Slot &sl, size_t extra) { sl.bytes += extra; live_bytes += extra; };      // what a slot's object holds on the device and pinned counts against the worker's budget
-    auto reset_accounting = [&](Slot &sl) { live_bytes -= std::min(live_bytes, sl.bytes); sl.bytes = 0; sl.jpeg = false; sl.deep = false; sl.png_bytes = 0; };
-    auto collect = [&](Slot &sl) {
-      if (!sl.busy) return;
-      const int rc = mi_batch_wait(sl.b);
-      if (timing) fprintf(stderr, "[mi_avif %8.1f ms] dev %d: run of %zu done (on the device: front end %.1f, tile search %.1f, deblock %.1f, cdef + restoration %.1f, entropy %.1f, pack + D2H %.1f ms)\n", since(), dev, sl.idx.size(),
-                          mi_batch_stage_ms(sl.b, 0), mi_batch_stage_ms(sl.b, 1), mi_batch_stage_ms(sl.b, 2), mi_batch_stage_ms(sl.b, 3), mi_batch_stage_ms(sl.b, 4), mi_batch_stage_ms(sl.b, 5));
-      for (size_t k = 0; k < sl.idx.size(); k++) st[sl.idx[k]] = rc == MI_OK ? mi_batch_get(sl.b, (int)k, &out[sl.idx[k]]) : rc;
-      sl.busy = false;
-    };
-    auto drop = [&](Slot &sl) {                                 // finish the slot's run and give its object back to the device
-      collect(sl);
-      if (sl.making.valid()) sl.b = sl.making.get();
-      if (sl.b) mi_batch_destroy(sl.b);
-      sl.b = nullptr; reset_accounting(sl);
-    };
-    auto make_room = [&](Shape *keep, size_t need) {
-      while (live_bytes + need > budget) {
-        Shape *victim = nullptr;
-        for (auto &c : shapes) if (c.get() != keep && (!victim || c->last_use < victim->last_use)) { bool any = false; for (Slot &sl : c->slot) any |= sl.b || sl.making.valid(); if (any) victim = c.get(); }
-        if (!victim) break;
-        for (Slot &sl : victim->slot) drop(sl);
-      }
-    };
-    auto ensure_slot = [&](Shape *sh, int j, bool host_staging, size_t png_staging) {
-      Slot &sl = sh->slot[j];
-      if (sl.b || sl.making.valid()) return;
-      const size_t need = est_bytes(sh->w, sh->h, sh->ch, sh->cap);
-      make_room(sh, need);
-      sl.bytes = need; live_bytes += need;
-      const mi_ravif_encoder ec = enc; const uint32_t w = sh->w, h = sh->h; const int ch = sh->ch; const int c = (int)sh->cap;
-      // the pinned pixel staging with it when host pixels are coming (a run of JPEG / PNG sources never pins it)
-      // and the PNG staging when scanlines are coming (png_staging: the bytes a full run is expected to need; a call that needs more grows it)
-      sl.making = std::async(std::launch::async, [ec, c, w, h, ch, host_staging, png_staging]() {
-        mi_batch *nb = pool_acquire(&ec, c, w, h, ch);
-        if (nb && host_staging) (void)mi_batch_input(nb, 0);
-        if (nb && png_staging) (void)batch_reserve_png(nb, png_staging);
-        return nb;
-      });
-    };
-    auto shape_for = [&](const mi_image_desc &x) {
-      for (auto &c : shapes) if (c->w == x.width && c->h == x.height && c->ch == x.channels) return c.get();
-      const size_t per = est_bytes(x.width, x.height, x.channels, 1);
-      const size_t cap = std::max<size_t>(1, std::min(max_run, MI_SLOT_BYTES / per));
-      shapes.emplace_back(new Shape{ x.width, x.height, x.channels, cap, {}, 0, 0, 0 });
-      return shapes.back().get();
-    };
-    // one run (<= the shape's capacity) through the shape's next slot
-    auto submit = [&](Shape *sh, const std::vector<mi_image_source> &d, const std::vector<size_t> &run, size_t i0, bool more) {
-      const mi_image_desc &d0 = d[run[0]].desc;
-      sh->last_use = ++tick; sh->runs++;
-      const int j = sh->next; sh->next = (j + 1) % NSLOT;
-      Slot &sl = sh->slot[j];
-      collect(sl);                                           // the slot's previous run, if any
-      bool any_host = false; for (size_t k : run) any_host |= d[k].kind == MI_SOURCE_HOST;
-      size_t png_run = 0; { std::vector<const mi_png_scanlines *> all; for (size_t k : run) if (is_png(d[k].kind)) all.push_back(d[k].png); if (!all.empty()) png_run = png_call_bytes((int)all.size(), all.data()); }
-      ensure_slot(sh, j, any_host, png_run);
-      if (sl.making.valid()) sl.b = sl.making.get();
-      if (!sl.b) reset_accounting(sl);                       // the object could not be made: nothing of it is resident
-      int rc = sl.b ? mi_batch_set_count(sl.b, (int)run.size()) : MI_ENCODING_ERROR;
-      if (timing) fprintf(stderr, "[mi_avif %8.1f ms] dev %d: slot %d ready\n", since(), dev, j);
-      if (rc == MI_OK) {
-        // host images: pinned staging, then one H2D per stretch of neighbours (never across a JPEG or PNG image's slot: the staging there is stale).  JPEG images:
-        // coefficients to the batch's own staging, decoded into the slot on the batch's stream.  PNG images: a stretch of neighbours goes up in one
-        // mi_batch_upload_png call (one H2D, one launch per kernel); what the batch's PNG staging holds, pinned and on the device, joins the worker's budget.
-        const size_t row = (size_t)d0.width * d0.channels;
-        size_t host_from = 0;
-        auto upload_host = [&](size_t end) { if (rc == MI_OK && end > host_from) rc = mi_batch_upload_async(sl.b, (int)host_from, (int)(end - host_from)); };
-        std::vector<const mi_png_scanlines *> pngs; size_t png_from = 0; int png_kind = MI_SOURCE_PNG;       // a stretch holds one kind: _PNG goes through mi_batch_upload_png, _PNG_DEEP through _png_deep
-        auto upload_png = [&]() {
-          if (rc == MI_OK && !pngs.empty()) {
-            const size_t extra = 2 * (png_call_bytes((int)pngs.size(), pngs.data()) + ((size_t)1 << 20));
-            if (extra > sl.png_bytes) { charge(sl, extra - sl.png_bytes); sl.png_bytes = extra; }
-            if (png_kind == MI_SOURCE_PNG_DEEP && !sl.deep) { sl.deep = true; charge(sl, sh->cap * (size_t)sh->w * sh->h * sh->ch * 2); }   // the deep slots join the worker's budget
-            rc = png_kind == MI_SOURCE_PNG_DEEP ? mi_batch_upload_png_deep(sl.b, (int)png_from, (int)pngs.size(), pngs.data()) : mi_batch_upload_png(sl.b, (int)png_from, (int)pngs.size(), pngs.data());
-          }
-          pngs.clear();
-        };
-        for (size_t k = 0; k < run.size() && rc == MI_OK; k++) {
-          const mi_image_source &src = d[run[k]];
-          if (is_png(src.kind)) {
-            upload_host(k); host_from = k + 1;
-            if (!pngs.empty() && png_kind != upload_kind(src.kind)) upload_png();
-            if (pngs.empty()) { png_from = k; png_kind = upload_kind(src.kind); }
-            pngs.push_back(src.png);
-            continue;
-          }
-          upload_png();
-          if (is_jpeg(src.kind)) {
-            upload_host(k); host_from = k + 1;
-            if (!sl.jpeg) { sl.jpeg = true; charge(sl, est_jpeg_bytes(sh->w, sh->h)); }
-            if (rc == MI_OK) rc = src.kind == MI_SOURCE_JPEG_YCBCR ? mi_batch_upload_jpeg_ycbcr(sl.b, (int)k, src.jpeg) : mi_batch_upload_jpeg(sl.b, (int)k, src.jpeg);
-            continue;
-          }
-          const mi_image_desc &x = src.desc;
-          uint8_t *dst = mi_batch_input(sl.b, (int)k);
-          if (!dst) { rc = MI_ENCODING_ERROR; break; }
-          const size_t sp = x.stride_px ? x.stride_px : x.width;
-          if (sp == x.width) memcpy(dst, x.pixels, row * d0.height);
-          else for (uint32_t y = 0; y < d0.height; y++) memcpy(dst + y * row, x.pixels + (size_t)y * sp * d0.channels, row);
-        }
-        upload_png();
-        upload_host(run.size());
-        // the managed sources, after their uploads on the same stream: neighbours that share a transform share a call
-        std::vector<mi_colour_transform *> ts(run.size(), nullptr);                // one look-up (one hash of the description) per managed source
-        try { for (size_t k = 0; k < run.size(); k++) if (is_managed(d[run[k]].kind)) ts[k] = transform_for(d[run[k]]); } catch (const std::exception &) { rc = MI_ENCODING_ERROR; }
-        for (size_t k = 0; k < run.size() && rc == MI_OK;) {
-          mi_colour_transform *const t = ts[k];
-          size_t k1 = k + 1;
-          if (!t) { k = k1; continue; }
-          while (k1 < run.size() && ts[k1] == t) k1++;
-          rc = mi_batch_convert_colour(sl.b, (int)k, (int)(k1 - k), t);
-          k = k1;
-        }
-        if (timing) fprintf(stderr, "[mi_avif %8.1f ms] dev %d: slot %d staged, uploads enqueued\n", since(), dev, j);
-      }
-      if (release) for (size_t k : run) release(user, i0 + k);   // staged (or failed): the caller's pixels are no longer read
-      if (rc == MI_OK) rc = mi_batch_encode_async(sl.b);
-      if (timing) fprintf(stderr, "[mi_avif %8.1f ms] dev %d: run of %zu enqueued on slot %d\n", since(), dev, run.size(), j);
-      if (rc != MI_OK) { for (size_t k : run) st[i0 + k] = rc; return; }
-      sl.idx.clear(); for (size_t k : run) sl.idx.push_back(i0 + k);
-      sl.busy = true;
-      // a shape that keeps coming gets its next slot made while the GPU works on this run (not earlier: hipMalloc / hipHostMalloc on another
-      // thread hold runtime locks that stall this thread's copies and launches; not for a shape seen once: a directory of differently sized files)
-      if (more && sh->runs >= 2) ensure_slot(sh, sh->next, any_host, png_run);
-    };
-    size_t claims = 0;
-    for (;;) {
-      // every claim is a full run, the first one included (MI_STREAM_FIRST_RUN_NUM / _DEN)
-      const size_t first_run = std::max<size_t>(1, max_run * MI_STREAM_FIRST_RUN_NUM / MI_STREAM_FIRST_RUN_DEN);
-      const size_t want = claims++ == 0 ? first_run : max_run;
-      const size_t i0 = cursor.fetch_add(want);                // claim the index range [i0, i1)
-      if (i0 >= n) break;
-      const size_t i1 = std::min(n, i0 + want);
-      std::vector<mi_image_source> d(i1 - i0);
-      // images are staged in arrival order: a run is handed over as soon as the next image has another shape or the run is full
-      std::vector<size_t> run; Shape *run_shape = nullptr;
-      auto flush = [&](bool more) { if (!run.empty()) { submit(run_shape, d, run, i0, more); run.clear(); } };
-      for (size_t i = i0; i < i1; i++) {
-        const int rc = fetch(user, i, &d[i - i0]);
-        const mi_image_source &src = d[i - i0];
-        const mi_image_desc &x = src.desc;
-        if (rc != MI_OK) { st[i] = rc; continue; }
-        if (const int why = source_refusal(*e, src)) { st[i] = why; if (release) release(user, i); continue; }
-        Shape *sh = shape_for(x);
-        if (sh != run_shape || run.size() >= sh->cap) flush(true);
-        run_shape = sh; run.push_back(i - i0);
-        if (run.size() == 1) ensure_slot(sh, sh->next, src.kind == MI_SOURCE_HOST, is_png(src.kind) ? sh->cap * png_call_bytes(1, &src.png) : 0);   // made in the background while the rest of the run arrives
-      }
-      if (timing) fprintf(stderr, "[mi_avif %8.1f ms] dev %d: images %zu..%zu fetched\n", since(), dev, i0, i1);
-      flush(cursor.load() < n);
-    }
-    for (auto &c : shapes) for (Slot &sl : c->slot) {
-      collect(sl);
-      if (sl.making.valid()) sl.b = sl.making.get();
-      pool_release(sl.b);                                      // back to the pool: the next call (or nobody, at process exit) gets them
-      sl.b = nullptr;
-    }
-    for (const Baked &c : baked) mi_colour_transform_free(c.t);
-    warm.get();
-    if (timing) fprintf(stderr, "[mi_avif %8.1f ms] dev %d: worker done\n", since(), dev);
-  };
-  std::vector<std::thread> th;
-  for (int d : devs) th.emplace_back(worker, d);
-  for (auto &t : th) t.join();
-  int first = MI_OK;
-  for (size_t i = 0; i < n; i++) { if (status) status[i] = st[i]; if (first == MI_OK && st[i] != MI_OK) first = st[i]; }
-  return first;
-}
-// the host-pixel form: every source is MI_SOURCE_HOST
-struct StreamAdapter { mi_fetch_fn fetch; mi_release_fn release; void *user; };
-static int fetch_host_source(void *user, size_t i, mi_image_source *src) { const StreamAdapter *a = (const StreamAdapter *)user; src->kind = MI_SOURCE_HOST; src->jpeg = nullptr; src->png = nullptr; return a->fetch(a->user, i, &src->desc); }
-static void release_host_source(void *user, size_t i) { const StreamAdapter *a = (const StreamAdapter *)user; a->release(a->user, i); }
-int mi_ravif_encode_stream(const mi_ravif_encoder *e, size_t n, mi_fetch_fn fetch, mi_release_fn release, void *user, mi_encoded_image *out, int *status, const int *devices, int ndev) {
-  if (!e || !fetch || (n && !out)) return MI_INVALID_ARGUMENT;
-  StreamAdapter a{ fetch, release, user };
-  return mi_ravif_encode_sources(e, n, fetch_host_source, release ? release_host_source : nullptr, &a, out, status, devices, ndev);
-}
-// The reference's files.into_par_iter() (src/main.rs:223) over the GPUs of one node with every image already in host memory.
-static int fetch_from_array(void *user, size_t i, mi_image_desc *d) { *d = ((const mi_image_desc *)user)[i]; return MI_OK; }
-int mi_ravif_encode_batch(const mi_ravif_encoder *e, size_t n, const mi_image_desc *in, mi_encoded_image *out, int *status, const int *devices, int ndev) {
-  if (!e || (n && (!in || !out))) return MI_INVALID_ARGUMENT;
-  return mi_ravif_encode_stream(e, n, fetch_from_array, nullptr, (void *)in, out, status, devices, ndev);
-}
+#include "host_stream.h"
+
+extern "C" {
 
 // level 1: caller-supplied planes (encode_to_av1). Planes go straight into the frame's src[] (edge-replicated on the host).
 int mi_av1_encode_planes(const mi_av1_config *cfg, const void *const planes[3], const size_t stride_bytes[3], uint8_t **out_obu, size_t *out_len, uint16_t *recon[3]) {

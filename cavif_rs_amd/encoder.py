@@ -322,6 +322,11 @@ def parse_png(data):
     return PngScanlines(data)
 
 
+def _colour_of(handle):
+    """what a parsed file says about its colour: ('icc', profile bytes, or None for a PNG profile beyond the cap), ('gamma', gAMA, cHRM or None), or None"""
+    return handle.colour if isinstance(handle, PngScanlines) else ('icc', handle.icc_profile) if handle.icc_profile else None
+
+
 class ColourTransform:
     """A colour description baked into a transform to sRGB (mi_colour_transform): host state, applied to batch slots on the device by
     BatchEncoder.convert_colour.  from_icc(bytes): an ICC v2 / v4 RGB matrix/TRC profile (any other well-formed profile raises Unsupported, a malformed one
@@ -358,7 +363,7 @@ class ColourTransform:
 
     @classmethod
     def for_source(cls, handle):
-        what = handle.colour if isinstance(handle, PngScanlines) else ('icc', handle.icc_profile) if handle.icc_profile else None
+        what = _colour_of(handle)
         if what and what[0] == 'icc':
             if what[1] is None:
                 raise AvifError(2)                      # a PNG profile beyond the 4 MiB cap
@@ -404,6 +409,8 @@ def _is_device_array(x):
 
 DECODED_WHICH = {'recon': 0, 'source': 1}                   # MI_DECODED_*
 SOURCE_HOST, SOURCE_JPEG, SOURCE_PNG, SOURCE_JPEG_YCBCR, SOURCE_PNG_DEEP, SOURCE_JPEG_MANAGED, SOURCE_PNG_MANAGED, SOURCE_PNG_DEEP_MANAGED = range(8)   # MI_SOURCE_*: what mi_ravif_encode_sources takes
+_SOURCE_HANDLE_FIELD = {SOURCE_HOST: None, SOURCE_JPEG: 'jpeg', SOURCE_PNG: 'png', SOURCE_JPEG_YCBCR: 'jpeg', SOURCE_PNG_DEEP: 'png',      # the field of mi_image_source that carries
+                        SOURCE_JPEG_MANAGED: 'jpeg', SOURCE_PNG_MANAGED: 'png', SOURCE_PNG_DEEP_MANAGED: 'png'}                      # the kind's handle (None: host pixels in desc)
 
 
 def _decoded_which(name):
@@ -988,7 +995,7 @@ def _source_converts(handle):
     """a parsed file's own colour description gives a usable transform that is not the identity (mi_colour_probe_*: parsed, nothing baked): the rule by which
     cavif_mi --color-managed sends a JPEG the RGB way under --jpeg-ycbcr"""
     L = load_library()
-    what = handle.colour if isinstance(handle, PngScanlines) else ('icc', handle.icc_profile) if handle.icc_profile else None
+    what = _colour_of(handle)
     ident = C.c_int(1)
     if what and what[0] == 'icc':
         st = L.mi_colour_probe_icc(what[1], len(what[1]), C.byref(ident)) if what[1] is not None else 2
@@ -997,6 +1004,17 @@ def _source_converts(handle):
     else:
         return False
     return st == 0 and not ident.value
+
+
+def _source_kind(handle, jpeg_ycbcr, png_deep, managed):
+    """the source kind of a parsed file under encode_many's flags (its docstring states the rule)"""
+    if isinstance(handle, PngScanlines):
+        if managed:
+            return SOURCE_PNG_DEEP_MANAGED if png_deep else SOURCE_PNG_MANAGED
+        return SOURCE_PNG_DEEP if png_deep else SOURCE_PNG
+    if managed and (not jpeg_ycbcr or handle.color == 'rgb' or _source_converts(handle)):
+        return SOURCE_JPEG_MANAGED
+    return SOURCE_JPEG_YCBCR if jpeg_ycbcr and handle.color != 'rgb' else SOURCE_JPEG
 
 
 def encode_many(encoder, images, devices=None, jpeg_ycbcr=False, png_deep=False, managed=False):
@@ -1014,13 +1032,7 @@ def encode_many(encoder, images, devices=None, jpeg_ycbcr=False, png_deep=False,
         if isinstance(im, (JpegCoeffs, PngScanlines)):
             if not im._h:
                 raise AvifError(4)
-            if managed and isinstance(im, PngScanlines):
-                items.append((SOURCE_PNG_DEEP_MANAGED if png_deep else SOURCE_PNG_MANAGED, im, 4))
-            elif managed and (not jpeg_ycbcr or im.color == 'rgb' or _source_converts(im)):
-                items.append((SOURCE_JPEG_MANAGED, im, 4))
-            else:
-                items.append((SOURCE_PNG_DEEP if png_deep else SOURCE_PNG, im, 4) if isinstance(im, PngScanlines) else
-                             (SOURCE_JPEG_YCBCR if jpeg_ycbcr and im.color != 'rgb' else SOURCE_JPEG, im, 4))
+            items.append((_source_kind(im, jpeg_ycbcr, png_deep, managed), im, 4))
             continue
         if _is_device_array(im):
             raise TypeError('encode_many takes host arrays, JpegCoeffs and PngScanlines; pixels in device memory go through BatchEncoder.upload_device')
@@ -1038,15 +1050,12 @@ def _encode_sources(encoder, items, devices):
 
     def fetch(_user, i, src):
         (kind, it, channels), s = items[i], src.contents
-        s.kind = kind
-        if kind in (SOURCE_PNG, SOURCE_PNG_DEEP, SOURCE_PNG_MANAGED, SOURCE_PNG_DEEP_MANAGED):
-            s.jpeg, s.png = None, it._h
-            s.desc.pixels, s.desc.width, s.desc.height, s.desc.stride_px, s.desc.channels = None, it.width, it.height, it.width, channels
-        elif kind in (SOURCE_JPEG, SOURCE_JPEG_YCBCR, SOURCE_JPEG_MANAGED):
-            s.jpeg, s.png = it._h, None
+        s.kind, s.jpeg, s.png = kind, None, None
+        field = _SOURCE_HANDLE_FIELD[kind]
+        if field:
+            setattr(s, field, it._h)
             s.desc.pixels, s.desc.width, s.desc.height, s.desc.stride_px, s.desc.channels = None, it.width, it.height, it.width, channels
         else:
-            s.jpeg, s.png = None, None
             s.desc.pixels, s.desc.width, s.desc.height, s.desc.stride_px, s.desc.channels = it.ctypes.data, it.shape[1], it.shape[0], it.shape[1], channels
         return 0
     out = (_EncodedImage * len(items))()

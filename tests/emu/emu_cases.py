@@ -92,6 +92,20 @@ if which == 'twodev':                              # MI_EMU_DEVICES=2: two DISTI
         ok_all &= ok
         print(json.dumps({'case': 'batch object + encode_rgb on device %d' % dev, 'ok': bool(ok), 's': round(time.time() - t, 2)}), flush=True)
     sys.exit(0 if ok_all else 1)
+if which == 'evict':                               # the stream worker's eviction path, seen through the emulator's allocation counters: one worker on device 0 (192 MiB free, a budget of
+    import ctypes                                  # 115 MiB against its estimate of 32 MiB and more per batch object) over seven shapes; a fresh process, so the peak is this call's
+    from cavif_rs_amd.synth import synth_image
+    L = ctypes.CDLL(_enc.library_path()); L.emu_mem_count.restype = ctypes.c_longlong
+    shapes = [(40 + 8 * k2, 24 + 8 * (k2 % 3)) for k2 in range(7)]
+    imgs = [synth_image(w, h, index=k2, alpha=(k2 % 4 == 3)) for k2, (w, h) in enumerate(shapes)] + [synth_image(*shapes[1], index=20)]
+    e = m.Encoder().with_quality(70).with_speed(8)
+    ref = [oracle.ravif_encode(im, quality=70, alpha_quality=80, speed=8)[0] for im in imgs]
+    t = time.time()
+    before = [L.emu_mem_count(0, k2) for k2 in range(2)]
+    ok = [g.avif_file for g in m.encode_many(e, imgs, devices=[0])] == ref
+    print(json.dumps({'case': 'stream, 7 shapes, 1 worker: device allocations', 'ok': bool(ok), 'allocs': L.emu_mem_count(0, 0) - before[0], 'frees': L.emu_mem_count(0, 1) - before[1],
+                      'peak': L.emu_mem_count(0, 2), 's': round(time.time() - t, 2)}), flush=True)
+    sys.exit(0 if ok else 1)
 if which == 'blk64':                               # the 64x64 level (dev_blk64.h): smooth pictures on which 64x64 blocks win, bottom-up (speed 1) and top-down, 4:4:4 and 4:0:0
     from tests.test_oracle_dav1d import smooth_planes
     ok_all = True

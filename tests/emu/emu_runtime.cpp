@@ -37,6 +37,7 @@ void *emu_alloc(size_t n) {
 static std::mutex g_reg_mu;
 static std::map<uintptr_t, std::pair<size_t, int>> g_reg;          // base -> (bytes, device)
 static std::atomic<long> g_launches[64];
+static struct DevMem { long long allocs, frees, live, peak; } g_mem[64];      // hipMalloc / hipFree per emulated device and its live device bytes (guarded by g_reg_mu)
 namespace emu {
 int device_count() { static const int n = [] { const char *e = getenv("MI_EMU_DEVICES"); const int v = e ? atoi(e) : 1; return v < 1 ? 1 : (v > 64 ? 64 : v); }(); return n; }
 int &cur_dev() { static thread_local int d = 0; return d; }
@@ -55,14 +56,29 @@ void check_dev_ptr(const void *p, const char *what) {
 }
 }
 extern "C" long emu_launch_count(int dev) { return dev >= 0 && dev < 64 ? g_launches[dev].load() : -1; }
+// which: 0 device allocations so far, 1 frees of device allocations, 2 the peak of the live device bytes
+extern "C" long long emu_mem_count(int dev, int which) {
+  if (dev < 0 || dev >= 64 || which < 0 || which > 2) return -1;
+  std::lock_guard<std::mutex> lk(g_reg_mu);
+  return which == 0 ? g_mem[dev].allocs : which == 1 ? g_mem[dev].frees : g_mem[dev].peak;
+}
 void *emu_alloc_dev(size_t n) {
   void *p = emu_alloc(n);
-  if (p) { std::lock_guard<std::mutex> lk(g_reg_mu); g_reg[(uintptr_t)p] = { n ? n : 1, emu::cur_dev() }; }
+  if (p) {
+    std::lock_guard<std::mutex> lk(g_reg_mu);
+    g_reg[(uintptr_t)p] = { n ? n : 1, emu::cur_dev() };
+    DevMem &m = g_mem[emu::cur_dev()];
+    m.allocs++; m.live += (long long)(n ? n : 1); m.peak = std::max(m.peak, m.live);
+  }
   return p;
 }
 void emu_free(void *p) {
   if (!p) return;
-  { std::lock_guard<std::mutex> lk(g_reg_mu); g_reg.erase((uintptr_t)p); }
+  {
+    std::lock_guard<std::mutex> lk(g_reg_mu);
+    auto it = g_reg.find((uintptr_t)p);
+    if (it != g_reg.end()) { DevMem &m = g_mem[it->second.second]; m.frees++; m.live -= (long long)it->second.first; g_reg.erase(it); }      // (host allocations are not registered)
+  }
   void *b = (uint8_t *)p - 64; munmap(b, *(size_t *)b);
 }
 double emu_now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }

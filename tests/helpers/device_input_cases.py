@@ -342,6 +342,15 @@ def run_stream(lib):
     got = [enc._take(o).avif_file if s == 0 else None for o, s in zip(out, status)]
     emit('stream: a JPEG source whose slot has another size fails alone', rc == 4 and list(status) == [0, 0, 4, 0, 0, 0] and [g == w for g, w in zip(got, want)] == [True, True, False, True, True, True] and
          sorted(released) == list(range(n)), rc=rc, statuses=list(status))
+    # a fetch that fails: its status is the image's, and release is not called for it
+    def fetch_but_one(user, i, src):
+        return 3 if i == 2 else fetch(user, i, src)
+    fetched.clear(); released.clear()
+    out = (enc._EncodedImage * n)()
+    rc = L.mi_ravif_encode_sources(C.byref(ec), n, enc._FETCH_SOURCE(fetch_but_one), enc._RELEASE(release), None, out, status, None, 0)
+    got = [enc._take(o).avif_file if s == 0 else None for o, s in zip(out, status)]
+    emit('stream: a fetch that returns 3 fails alone and is not released', rc == 3 and list(status) == [0, 0, 3, 0, 0, 0] and [g == w for g, w in zip(got, want)] == [True, True, False, True, True, True] and
+         sorted(released) == [0, 1, 3, 4, 5], rc=rc, statuses=list(status), released=sorted(released))
     for kind, what, _, _ in items:
         if kind == 1:
             L.mi_jpeg_coeffs_free(what)

@@ -76,10 +76,10 @@ def test_batch_of_host_ingested_and_jpeg_images(emu_env):
 
 def test_stream_of_mixed_sources(emu_env):
     """mi_ravif_encode_sources: JPEG coefficients and host pixels of one size share a run; release once per image"""
-    _all_ok(_run(emu_env, 'stream', 900), 'stream', 3)
+    _all_ok(_run(emu_env, 'stream', 900), 'stream', 4)
 
 
 def test_stream_of_mixed_sources_on_two_devices(emu_env):
     rows = _run(emu_env, 'stream', 900, MI_EMU_DEVICES='2')
-    _all_ok(rows, 'stream', 3)
+    _all_ok(rows, 'stream', 4)
     assert rows[0]['devices'] == 2

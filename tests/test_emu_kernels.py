@@ -27,11 +27,11 @@ def _run(emu_env, which, timeout, **extra):
 # first of them is asked for, and each test waits for its own.  job -> (case set of tests/emu/emu_cases.py, timeout, extra environment); test -> its jobs.
 _JOBS = {'quick': ('quick', 900, {}), 'quick_reverse': ('quick', 900, {'MI_EMU_REVERSE': '1'}), 'rect': ('rect', 900, {}),
          'blk64': ('blk64', 900, {}), 'blk64_reverse': ('blk64', 900, {'MI_EMU_REVERSE': '1'}), 'batch': ('batch', 1200, {}),
-         'giveup': ('giveup', 900, {'MI_EMU_DROP_PUBLISH': '1'}), 'twodev': ('twodev', 1200, {'MI_EMU_DEVICES': '2'})}
+         'giveup': ('giveup', 900, {'MI_EMU_DROP_PUBLISH': '1'}), 'twodev': ('twodev', 1200, {'MI_EMU_DEVICES': '2'}), 'evict': ('evict', 900, {})}
 _TEST_JOBS = {'test_emulated_kernels_equal_oracle': ['quick'], 'test_emulated_kernels_do_not_depend_on_lane_order': ['quick_reverse'],
               'test_emulated_kernels_rect_partition_cases': ['rect'], 'test_emulated_kernels_64x64_level': ['blk64', 'blk64_reverse'],
               'test_emulated_batch_api_equals_oracle': ['batch'], 'test_a_dependency_wait_that_never_ends_fails_the_encode_in_bounded_time': ['giveup'],
-              'test_two_distinct_emulated_devices': ['twodev']}
+              'test_two_distinct_emulated_devices': ['twodev'], 'test_stream_worker_gives_back_the_least_recently_used_shapes': ['evict']}
 
 
 @pytest.fixture(scope='module')
@@ -102,6 +102,23 @@ def test_two_distinct_emulated_devices(emu_jobs):
     (a copy or a kernel argument naming the other device's allocation aborts).  Both devices must do work; every file == oracle.  Unmeasured on real multi-GPU hardware."""
     p, rows = emu_jobs['twodev'].result()
     assert len(rows) == 4 and all(r['ok'] for r in rows) and p.returncode == 0, (rows, p.stderr[-2000:])
+
+
+# What the emulator counted on device 0 around encode_many(7 shapes + 1, devices=[0]) at commit fb0ffc2 (the stream worker as one function in mi_avif.hip) with only the
+# counters added: the same in five fresh processes.  With the worker's eviction loop disabled the same job frees nothing and peaks at 135 353 104 bytes
+# (profiles/stream_worker.md).
+EVICT_ALLOCS, EVICT_FREES, EVICT_PEAK_BYTES = 115, 68, 59793600
+
+
+def test_stream_worker_gives_back_the_least_recently_used_shapes(emu_jobs):
+    """The stream worker's budget: before it makes a batch object it gives back the objects of the shapes it has used longest ago (StreamWorker::make_room).  The files
+    cannot show that; the emulated device's allocation counters can.  One worker, seven shapes, a device that reports 192 MB free: device allocations, frees and the
+    peak of live device bytes equal what the worker did before it was restructured, and every file equals the oracle's."""
+    p, rows = emu_jobs['evict'].result()
+    assert len(rows) == 1 and rows[0]['ok'] and p.returncode == 0, (rows, p.stderr[-2000:])
+    print(rows[0])
+    assert (rows[0]['allocs'], rows[0]['frees']) == (EVICT_ALLOCS, EVICT_FREES), rows
+    assert rows[0]['peak'] == EVICT_PEAK_BYTES, rows
 
 
 def test_product_library_is_not_the_emulator():

@@ -61,7 +61,7 @@ def test_batch_of_host_ingested_and_jpeg_images(table):
 
 
 def test_stream_of_mixed_sources(table):
-    _of(table, 'stream', 3)
+    _of(table, 'stream', 4)
 
 
 def test_new_jpeg_path_equals_the_old_one_beyond_the_fixture_sizes():
