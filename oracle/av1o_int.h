@@ -179,6 +179,16 @@ int av1o_test_loop_filters(const int *par, int64_t rdmult, uint16_t *const src[3
                            const uint8_t *m_txsize, const uint8_t *m_bsize, const uint8_t *m_skip, int64_t *tally, int *lf_level, int8_t *cdef_idx,
                            uint32_t *act, uint32_t *svar8, uint8_t *lr_type, uint8_t *lr_set, int8_t *lr_xqd);
 
+/* tests only: intra prediction, chroma from luma and the search's block distortions on caller-supplied planes and blocks (av1o_test_predict.c) */
+int64_t av1o_satd_block_wh(const uint16_t *src, int ss, const uint16_t *pred, int ps, int w, int h);
+int64_t av1o_sse_block_wh(const uint16_t *a, int as, const uint16_t *b, int bs_, int w, int h);
+int av1o_test_predict(const int *par, const uint16_t *luma, const uint16_t *plane, uint16_t *dst);
+int64_t av1o_test_distortion(const uint16_t *src, const uint16_t *pred, int w, int h, int what);
+/* tests only: records the availability flags the walker reads off m_decoded during the encodes that follow (av1o_search.c); buf: cap x 9 ints, NULL = off */
+void av1o_test_avail_trace(int *buf, int cap);
+int av1o_test_avail_trace_count(void);
+int64_t av1o_test_psy_dist(const uint16_t *src, const uint16_t *rec, int n, int bd, uint32_t *sv, uint32_t *act);
+
 /* headers */
 size_t av1o_write_obus(Av1oFrame *f, uint8_t **tile_data, size_t *tile_len, uint8_t **out);
 #endif

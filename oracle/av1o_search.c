@@ -78,6 +78,16 @@ static void set_decoded(Av1oFrame *f, int r, int c, int bs, int v) {
   const int w4 = 1 << (dim_wl(bs) - 2), h4 = 1 << (dim_hl(bs) - 2);
   for (int i = 0; i < h4; i++) memset(f->m_decoded + (r + i) * f->mi_stride + c, v, (size_t)w4);
 }
+/* tests only (av1o_test_predict.c): while a trace is installed, every above-right / below-left flag the walker reads off m_decoded is recorded as
+ * { kind, r, c, size code, have_above_rt, have_below_lft, r, c and size code of the block }: kind 0 = a block (try_block), 1 = one of its luma transform sub-blocks */
+static __thread int *avail_trace; static __thread int avail_trace_cap, avail_trace_n;
+void av1o_test_avail_trace(int *buf, int cap) { avail_trace = buf; avail_trace_cap = cap; avail_trace_n = 0; }
+int av1o_test_avail_trace_count(void) { return avail_trace_n; }
+static void avail_log(int kind, int r, int c, int code, int ar, int bl, int br, int bc, int bcode) {
+  if (!avail_trace) return;
+  if (avail_trace_n < avail_trace_cap) { int *e = avail_trace + 9 * avail_trace_n; e[0] = kind; e[1] = r; e[2] = c; e[3] = code; e[4] = ar; e[5] = bl; e[6] = br; e[7] = bc; e[8] = bcode; }
+  avail_trace_n++;
+}
 static void fill_map2(uint8_t *m, int ms, int r, int c, int w4, int h4, int v) {
   for (int i = 0; i < h4; i++) memset(m + (r + i) * ms + c, v, (size_t)w4);
 }
@@ -147,6 +157,9 @@ static int64_t sse_block_wh(const uint16_t *a, int as, const uint16_t *b, int bs
   return s;
 }
 static int64_t sse_block(const uint16_t *a, int as, const uint16_t *b, int bs_, int n) { return sse_block_wh(a, as, b, bs_, n, n); }
+/* tests only (av1o_test_predict.c): the two block distortions above */
+int64_t av1o_satd_block_wh(const uint16_t *src, int ss, const uint16_t *pred, int ps, int w, int h) { return satd_block_wh(src, ss, pred, ps, w, h); }
+int64_t av1o_sse_block_wh(const uint16_t *a, int as, const uint16_t *b, int bs_, int w, int h) { return sse_block_wh(a, as, b, bs_, w, h); }
 
 /* One transform block: residual -> fwd -> quant -> rate, dequant -> inverse -> recon; returns weighted J. */
 typedef struct { int eob, cul, dcc; int64_t sse; uint32_t rate; } TxRes;
@@ -210,6 +223,7 @@ static int64_t try_block(Search *s, int r, int c, int bs) {
   const int availU = r > t->mi_row_start, availL = c > t->mi_col_start;
   const int have_ar = availU && (c + w4 < t->mi_col_end) && f->m_decoded[(r - 1) * ms + c + w4];
   const int have_bl = availL && (r + h4 < t->mi_row_end) && f->m_decoded[(r + h4) * ms + c - 1];
+  avail_log(0, r, c, bs, have_ar, have_bl, r, c, bs);
   const int amode = availU ? f->m_ymode[mi - ms] : DC_PRED, lmode = availL ? f->m_ymode[mi - 1] : DC_PRED;
   const uint32_t *ycost = f->cost + CDF_KF_Y + (intra_mode_ctx[amode] * 5 + intra_mode_ctx[lmode]) * CDF_KF_Y_STRIDE;
   #define IS_SMOOTH(m) ((m) == SMOOTH_PRED || (m) == SMOOTH_V_PRED || (m) == SMOOTH_H_PRED)
@@ -308,6 +322,7 @@ static int64_t try_block(Search *s, int r, int c, int bs) {
           const int sU = availU || bi, sL = availL || bj_;
           const int s_ar = sU && (cc + half < t->mi_col_end) && f->m_decoded[(rr - 1) * ms + cc + half];
           const int s_bl = sL && (rr + half < t->mi_row_end) && f->m_decoded[(rr + half) * ms + cc - 1];
+          avail_log(1, rr, cc, stx, s_ar, s_bl, r, c, bs);
           av1o_predict_intra(f, t, 0, cc * 4, rr * 4, 2 + stx, sL, sU, s_ar, s_bl, best_mode, best_delta, ftype_y, spred, hn);
           int64_t bj = INT64_MAX; int btx = DCT_DCT, cur = 0; TxRes btr = { 0, 0, 0, 0, 0 };
           for (int ti = 0; ti < sntx; ti++) {

@@ -49,6 +49,12 @@ def lib():
         L.av1o_avif_container.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_int] * 9 + [C.POINTER(C.POINTER(C.c_uint8))]
         L.av1o_avif_container.restype = C.c_size_t
         L.av1o_free.argtypes = [C.c_void_p]
+        # tests only (oracle/av1o_test_predict.c): prediction, block distortion and the psychovisual distortion on caller-supplied blocks
+        L.av1o_test_predict.argtypes = [C.c_void_p] * 4; L.av1o_test_predict.restype = C.c_int
+        L.av1o_test_distortion.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]; L.av1o_test_distortion.restype = C.c_int64
+        L.av1o_test_avail_trace.argtypes = [C.c_void_p, C.c_int]; L.av1o_test_avail_trace.restype = None
+        L.av1o_test_avail_trace_count.restype = C.c_int
+        L.av1o_test_psy_dist.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]; L.av1o_test_psy_dist.restype = C.c_int64
         _LIB = L
     return _LIB
 
