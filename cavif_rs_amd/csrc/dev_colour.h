@@ -2,9 +2,8 @@
 // (icc_reader.h: three input curves, a 3 x 3 matrix, the sRGB output curve).  Alpha is never read into the arithmetic and is stored back as it was.
 //   colour_convert_kernel<DC>     8-bit slots (MI_INPUT_RGB), DC = channels of the slot
 //   colour_convert16_kernel<DC>   deep slots (MI_INPUT_RGB16)
-// Both have ingest_kernel's thread shape -- one thread = four adjacent pixels of a row, the 64 lanes of a wavefront = 256 adjacent pixels, one contiguous run of
-// a slot row read and written with the widest accesses its address allows (slot_store4 / slot16_store4) -- with all images of a call in grid z and
-// MI_COLOUR_ROWS rows per workgroup, so that the table fill of the 8-bit kernel is paid once per MI_COLOUR_ROWS * 256 pixels.  No scratch in either.
+// Both work in the row groups of dev_slot.h, read with slot_load4 / slot16_load4 and written back with slot_store4 / slot16_store4, MI_COLOUR_ROWS rows per
+// workgroup (grid y counts groups of rows), so that the table fill of the 8-bit kernel is paid once per MI_COLOUR_ROWS * 256 pixels.  No scratch in either.
 //
 // The arithmetic is integers only.  With the tables of icc_reader.h (lin8, lin16, matrix, U, out16), floor division and >> on negative numbers rounding
 // towards minus infinity:
@@ -20,8 +19,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
-#include "dev_ingest.h"
-#include "dev_deep.h"
+#include "dev_slot.h"
 
 namespace mi {
 
@@ -47,40 +45,27 @@ __device__ __forceinline__ uint32_t colour_level8(const uint32_t *U, const uint3
   return lo;
 }
 
-// grid: (ceil(ceil(w / 4) / 64), ceil(h / MI_COLOUR_ROWS), images); slots = slot of the first image
+// grid: grid_by_four over w x ceil(h / MI_COLOUR_ROWS); slots = slot of the first image
 template <int DC> __global__ void __launch_bounds__(64) colour_convert_kernel(const ColourDev t, uint8_t *slots, const uint32_t w, const uint32_t h) {
   __shared__ uint32_t tab[1024];
 #pragma unroll
   for (int k = 0; k < 4; k++) ((uint4 *)tab)[threadIdx.x + 64 * k] = ((const uint4 *)t.tab8)[threadIdx.x + 64 * k];
   __syncthreads();
-  const uint32_t x0 = (blockIdx.x * 64 + threadIdx.x) * 4, img = blockIdx.z;
-  if (x0 >= w) return;
-  const uint32_t n = w - x0 < 4 ? w - x0 : 4;
   const uint32_t *const U = tab + 768;
   for (uint32_t r = 0; r < (uint32_t)MI_COLOUR_ROWS; r++) {
-    const uint32_t y = blockIdx.y * MI_COLOUR_ROWS + r;
-    if (y >= h) break;
-    uint8_t *p = slots + ((size_t)img * h * w + (size_t)y * w + x0) * DC;
-    const bool vec = n == 4 && ((uintptr_t)p & (DC == 4 ? 15 : 3)) == 0;
-    uint32_t px[4] = { 0, 0, 0, 0 };
-    if (vec && DC == 4) { const uint4 v = *(const uint4 *)p; px[0] = v.x; px[1] = v.y; px[2] = v.z; px[3] = v.w; }
-    else if (vec) {
-      const uint32_t d0 = ((const uint32_t *)p)[0], d1 = ((const uint32_t *)p)[1], d2 = ((const uint32_t *)p)[2];
-      px[0] = d0 & 0xFFFFFFu; px[1] = (d0 >> 24) | ((d1 & 0xFFFFu) << 8); px[2] = (d1 >> 16) | ((d2 & 0xFFu) << 16); px[3] = d2 >> 8;
-    } else {
-#pragma unroll
-      for (uint32_t k = 0; k < 4; k++) if (k < n) {
-        if (DC == 4) px[k] = ((const uint32_t *)p)[k];
-        else px[k] = (uint32_t)p[3 * k] | ((uint32_t)p[3 * k + 1] << 8) | ((uint32_t)p[3 * k + 2] << 16);
-      }
-    }
+    RowGroup4 g;
+    if (!row_group4(w, h, blockIdx.y * MI_COLOUR_ROWS + r, g)) break;
+    const uint32_t n = g.n;
+    uint8_t *p = slot_ptr<DC>(slots, w, h, g);
+    uint32_t px[4];
+    slot_load4<DC>(p, px, n);
 #pragma unroll
     for (uint32_t k = 0; k < 4; k++) if (k < n) {
       const uint32_t l0 = tab[px[k] & 255u], l1 = tab[256 + ((px[k] >> 8) & 255u)], l2 = tab[512 + ((px[k] >> 16) & 255u)];
       const uint32_t o0 = colour_level8(U, colour_mix(t.m, l0, l1, l2)), o1 = colour_level8(U, colour_mix(t.m + 3, l0, l1, l2)), o2 = colour_level8(U, colour_mix(t.m + 6, l0, l1, l2));
       px[k] = (px[k] & 0xFF000000u) | o0 | (o1 << 8) | (o2 << 16);
     }
-    slot_store4<DC>(p, px, n, vec);
+    slot_store4<DC>(p, px, n);
   }
 }
 
@@ -103,31 +88,13 @@ template <int DC> __global__ void __launch_bounds__(64) colour_convert16_kernel(
 #else
   const uint32_t *const lin16 = t.lin16;
 #endif
-  const uint32_t x0 = (blockIdx.x * 64 + threadIdx.x) * 4, img = blockIdx.z;
-  if (x0 >= w) return;
-  const uint32_t n = w - x0 < 4 ? w - x0 : 4;
   for (uint32_t r = 0; r < (uint32_t)MI_COLOUR_ROWS; r++) {
-    const uint32_t y = blockIdx.y * MI_COLOUR_ROWS + r;
-    if (y >= h) break;
-    uint16_t *p = slots + ((size_t)img * h * w + (size_t)y * w + x0) * DC;
+    RowGroup4 g;
+    if (!row_group4(w, h, blockIdx.y * MI_COLOUR_ROWS + r, g)) break;
+    const uint32_t n = g.n;
+    uint16_t *p = slot_ptr<DC>(slots, w, h, g);
     uint2 px[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) { px[k].x = 0; px[k].y = 0; }
-    if (n == 4) {
-      uint32_t d[2 * DC];
-      deep_load_run<2 * DC>((const uint8_t *)p, d);
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        px[k].x = deep_half(d, DC * k) | (deep_half(d, DC * k + 1) << 16);
-        px[k].y = deep_half(d, DC * k + 2) | (DC == 4 ? deep_half(d, DC * k + 3) << 16 : 0u);
-      }
-    } else {
-#pragma unroll
-      for (uint32_t k = 0; k < 4; k++) if (k < n) {
-        px[k].x = (uint32_t)p[DC * k] | ((uint32_t)p[DC * k + 1] << 16);
-        px[k].y = (uint32_t)p[DC * k + 2] | (DC == 4 ? (uint32_t)p[DC * k + 3] << 16 : 0u);
-      }
-    }
+    slot16_load4<DC>(p, px, n);
 #pragma unroll
     for (uint32_t k = 0; k < 4; k++) if (k < n) {
       const uint32_t l0 = colour_lin16(lin16, px[k].x & 0xFFFFu), l1 = colour_lin16(lin16 + MI_COLOUR_LIN16, px[k].x >> 16), l2 = colour_lin16(lin16 + 2 * MI_COLOUR_LIN16, px[k].y & 0xFFFFu);

@@ -3,8 +3,8 @@
 //   decoded_q         q(n, d) = clamp(floor((2 * 255 * n + d * peak) / (2 * d * peak)), 0, 255): 255 n / (d peak) rounded half up, in integers.  d and peak are
 //                     template arguments, so the division is by a constant (multiply-high); the word size is the smallest that holds every numerator.
 //   decoded_kernel    one launch for images [first, first + count), driven by the frame descriptors the encode left on the device (as quality_kernel is): the
-//                     colour frame of image i is frames[i], its alpha frame frames[n + i] when the batch has four channels and the frame is not idle.  One thread
-//                     = four adjacent pixels of a row, the 64 lanes of a wavefront = 256 adjacent pixels (ingest_kernel's shape): one 8-byte load per plane and
+//                     colour frame of image i is frames[i], its alpha frame frames[n + i] when the batch has four channels and the frame is not idle.  In the
+//                     row groups of dev_slot.h over the frame's own w x h: one 8-byte load per plane and
 //                     thread, then slot_store4 for packed HWC (16 bytes for RGBA, three dwords for RGB), one dword per plane for CHW, byte stores for any other
 //                     stride or alignment and for a last partial group: decided per thread from its own addresses.  No LDS, no scratch.
 // Loads stay inside the padded plane: columns come in fours from x0 < w, and the stride is a multiple of 64.  Only the visible w x h pixels are stored.
@@ -12,7 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "dev_common.h"
-#include "dev_ingest.h"
+#include "dev_slot.h"
 
 namespace mi {
 
@@ -55,11 +55,10 @@ template <int BD, int MODEL> __device__ __forceinline__ uint32_t decoded_rgb(con
 
 // grid: (ceil(ceil(w / 4) / 64), h, images of the call)
 template <int BD, int MODEL> __global__ void __launch_bounds__(64) decoded_kernel(const FrameDev *frames, const DecodedDst d) {
-  const uint32_t x0 = (blockIdx.x * 64 + threadIdx.x) * 4, y = blockIdx.y, k = blockIdx.z;
-  const FrameDev *f = frames + d.first + k;
-  const uint32_t w = (uint32_t)f->w, h = (uint32_t)f->h;
-  if (x0 >= w || y >= h) return;
-  const uint32_t n = w - x0 < 4 ? w - x0 : 4;
+  const FrameDev *f = frames + d.first + blockIdx.z;
+  RowGroup4 g;
+  if (!row_group4((uint32_t)f->w, (uint32_t)f->h, g)) return;
+  const uint32_t x0 = g.x0, y = g.y, k = g.img, n = g.n;
   constexpr long long PEAK = (1 << BD) - 1;
   uint32_t px[4];
   {
@@ -86,8 +85,8 @@ template <int BD, int MODEL> __global__ void __launch_bounds__(64) decoded_kerne
   if (d.layout == 0) {
     uint8_t *dst = row + (size_t)x0 * d.inner_stride;
     const bool packed = d.inner_stride == (unsigned long long)d.channels;
-    if (packed && d.channels == 4 && ((uintptr_t)dst & 3) == 0) slot_store4<4>(dst, px, n, ((uintptr_t)dst & 15) == 0);
-    else if (packed && d.channels == 3) slot_store4<3>(dst, px, n, ((uintptr_t)dst & 3) == 0);
+    if (packed && d.channels == 4 && ((uintptr_t)dst & 3) == 0) slot_store4<4>(dst, px, n);
+    else if (packed && d.channels == 3) slot_store4<3>(dst, px, n);
     else {
 #pragma unroll
       for (uint32_t j = 0; j < 4; j++) if (j < n) {

@@ -1,16 +1,16 @@
-// dev_jpeg.h -- the device half of the JPEG input side: quantised coefficients (jpeg_reader.h) -> RGBA8 in HBM, two kernels.
+// dev_jpeg.h -- the device half of the JPEG input side: quantised coefficients (jpeg_reader.h) -> RGBA8 in HBM, two kernels (the second in the row groups of dev_slot.h).
 // A JPEG decoder's pixels are not normative; these are libjpeg's in its default configuration (what Pillow and most tools produce), all integer:
 //   jpeg_idct_kernel  dequantise + the "islow" 8x8 inverse DCT (CONST_BITS 13, PASS1_BITS 2: column pass descaled by 11 bits, row pass by 18, round half
 //                     up, +128, clamp) -> one uint8 plane per component over the MCU-padded block grid
-//   jpeg_rgba_kernel  "fancy" (triangle) chroma upsampling 2x1 / 2x2 with edge samples replicated, then YCbCr -> RGB in 16.16 fixed point
-//                     (or a copy for grey / RGB files), alpha 255; jpeg_rgb_kernel is the same code storing packed RGB8 (3-channel batches)
-//   jpeg_ycc_kernel   the same upsampling and no colour arithmetic: (Y, Cb, Cr) as the file holds them, for slots of input kind MI_INPUT_YCBCR
+//   jpeg_colour_kernel<DC>  "fancy" (triangle) chroma upsampling 2x1 / 2x2 with edge samples replicated, then YCbCr -> RGB in 16.16 fixed point
+//                     (or a copy for grey / RGB files), alpha 255; DC 3 stores packed RGB8 (3-channel batches)
+//   jpeg_ycc_kernel<DC>     the same upsampling and no colour arithmetic: (Y, Cb, Cr) as the file holds them, for slots of input kind MI_INPUT_YCBCR
 // libjpeg computes the IDCT in 64-bit long; here products and sums are uint32_t (wrapping) and only the descale shifts see them as int32_t: identical
 // whenever libjpeg's values fit 32 bits, which they do for every encoder-made file, and some defined value for hostile coefficients.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
-#include "dev_ingest.h"
+#include "dev_slot.h"
 
 namespace mi {
 
@@ -147,14 +147,13 @@ __device__ __forceinline__ void jpeg_samples4(const uint8_t *planes, const JpegD
   }
 }
 
-// planes -> RGBA8 (DC 4) or RGB8 (DC 3) rows of stride_px pixels at a device pointer; one thread = four adjacent pixels = one 16-byte store or three
-// dword stores (vec: the destination rows are 16-byte / 4-byte aligned; otherwise, and for the pixels of a last partial group, slot_store4's narrow
-// stores).  The one implementation of the colour arithmetic; the two kernels below differ in the store alone.
-template <int DC> __device__ __forceinline__ void jpeg_colour4(const uint8_t *planes, const JpegDevGeom &g, uint8_t *out, const size_t stride_px, const int vec) {
-  const uint32_t x0 = (blockIdx.x * 64 + threadIdx.x) * 4, y = blockIdx.y;
-  if (x0 >= g.w || y >= g.h) return;
+// planes -> RGBA8 (DC 4) or RGB8 (DC 3) rows of stride_px pixels at a device pointer (a batch slot: stride_px = w), in the row groups of dev_slot.h over
+// g.w x g.h, one image per launch.  Alpha is 255.  The one implementation of the colour arithmetic.
+template <int DC> __global__ void __launch_bounds__(64) jpeg_colour_kernel(const uint8_t *planes, const JpegDevGeom g, uint8_t *out, const size_t stride_px) {
+  RowGroup4 grp;
+  if (!row_group4(g.w, g.h, grp)) return;
   int c0[4], c1[4], c2[4];
-  jpeg_samples4(planes, g, x0, y, c0, c1, c2);
+  jpeg_samples4(planes, g, grp.x0, grp.y, c0, c1, c2);
   uint32_t px[4];
   if (g.ncomp == 3) {
     for (int k = 0; k < 4; k++) {
@@ -168,25 +167,18 @@ template <int DC> __device__ __forceinline__ void jpeg_colour4(const uint8_t *pl
       px[k] = r | (gg << 8) | (b << 16) | 0xFF000000u;
     }
   } else for (int k = 0; k < 4; k++) px[k] = (uint32_t)c0[k] * 0x010101u | 0xFF000000u;
-  slot_store4<DC>(out + ((size_t)y * stride_px + x0) * DC, px, g.w - x0 < 4 ? g.w - x0 : 4, vec != 0);
-}
-__global__ void __launch_bounds__(64) jpeg_rgba_kernel(const uint8_t *planes, const JpegDevGeom g, uint8_t *rgba, const size_t stride_px, const int vec16) {
-  jpeg_colour4<4>(planes, g, rgba, stride_px, vec16);
-}
-// the same pixels without their alpha byte, for 3-channel batches: 12 bytes per thread (vec4: every destination row is 4-byte aligned)
-__global__ void __launch_bounds__(64) jpeg_rgb_kernel(const uint8_t *planes, const JpegDevGeom g, uint8_t *rgb, const size_t stride_px, const int vec4) {
-  jpeg_colour4<3>(planes, g, rgb, stride_px, vec4);
+  slot_store4<DC>(group_ptr<DC>(out, 0, stride_px, grp), px, grp.n);
 }
 // planes -> the file's own samples, no colour arithmetic: (Y, Cb, Cr, 255) of a three-component YCbCr file (chroma upsampled as above), (Y, 128, 128, 255)
-// of a grey one, into a slot of DC channels (DC 3: without the fourth byte).  Thread shape, store and `vec` as for the colour kernels.
-template <int DC> __global__ void __launch_bounds__(64) jpeg_ycc_kernel(const uint8_t *planes, const JpegDevGeom g, uint8_t *out, const size_t stride_px, const int vec) {
-  const uint32_t x0 = (blockIdx.x * 64 + threadIdx.x) * 4, y = blockIdx.y;
-  if (x0 >= g.w || y >= g.h) return;
+// of a grey one, into a slot of DC channels (DC 3: without the fourth byte).  Thread shape and store as for the colour kernel.
+template <int DC> __global__ void __launch_bounds__(64) jpeg_ycc_kernel(const uint8_t *planes, const JpegDevGeom g, uint8_t *out, const size_t stride_px) {
+  RowGroup4 grp;
+  if (!row_group4(g.w, g.h, grp)) return;
   int c0[4], c1[4] = { 128, 128, 128, 128 }, c2[4] = { 128, 128, 128, 128 };
-  jpeg_samples4(planes, g, x0, y, c0, c1, c2);
+  jpeg_samples4(planes, g, grp.x0, grp.y, c0, c1, c2);
   uint32_t px[4];
   for (int k = 0; k < 4; k++) px[k] = (uint32_t)c0[k] | ((uint32_t)c1[k] << 8) | ((uint32_t)c2[k] << 16) | 0xFF000000u;
-  slot_store4<DC>(out + ((size_t)y * stride_px + x0) * DC, px, g.w - x0 < 4 ? g.w - x0 : 4, vec != 0);
+  slot_store4<DC>(group_ptr<DC>(out, 0, stride_px, grp), px, grp.n);
 }
 
 }  // namespace mi

@@ -1,7 +1,7 @@
 // dev_planes.h -- YCbCr planes that already live in HBM (what a hardware JPEG / video decoder delivers: Y plus subsampled Cb, Cr, planar or with Cb and Cr
 // interleaved, NV12-style) -> the packed (Y, Cb, Cr[, 255]) bytes of a batch's input slot of kind MI_INPUT_YCBCR.
-//   planes_ingest_kernel  one thread = four adjacent luma pixels of a row, the 64 lanes of a wavefront = 256 adjacent pixels, all images of a call in one
-//                         launch (grid z).  Luma: one dword where the address allows it, bytes otherwise and for a last partial group.  Chroma: brought to
+//   planes_ingest_kernel  in the row groups of dev_slot.h, a group being four adjacent luma pixels.  Luma: one dword where the address allows it, bytes
+//                         otherwise and for a last partial group.  Chroma: brought to
 //                         luma resolution by jpeg_chroma4 (dev_jpeg.h: libjpeg's h2v1 / h2v2 triangle filter, edges replicated, planes of one or two
 //                         samples' width replicated; samples centred between the luma samples they cover, as in JPEG), which reads its four neighbours
 //                         per row with byte loads.  A wavefront's chroma reads cover 130 adjacent bytes of at most two rows per plane (260 interleaved),
@@ -10,7 +10,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
-#include "dev_jpeg.h"
+#include "dev_slot.h"
+#include "dev_jpeg.h"                     // jpeg_chroma4
 
 namespace mi {
 
@@ -21,18 +22,12 @@ struct PlanesSrc {
   int cpitch;                                                   // bytes from one chroma sample of a plane to the next: 1 | 2
 };
 
-// grid: (ceil(ceil(w / 4) / 64), h, images); slots = slot of the first image
+// slots = slot of the first image
 template <int DC> __global__ void __launch_bounds__(64) planes_ingest_kernel(const PlanesSrc s, uint8_t *slots) {
-  const uint32_t x0 = (blockIdx.x * 64 + threadIdx.x) * 4, y = blockIdx.y, img = blockIdx.z;
-  if (x0 >= s.w || y >= s.h) return;
-  const uint32_t n = s.w - x0 < 4 ? s.w - x0 : 4;
-  const uint8_t *q = s.y + (size_t)img * s.y_image + (size_t)y * s.y_row + x0;
-  uint32_t yv = 0;
-  if (n == 4 && ((uintptr_t)q & 3) == 0) yv = *(const uint32_t *)q;
-  else {
-#pragma unroll
-    for (uint32_t k = 0; k < 4; k++) if (k < n) yv |= (uint32_t)q[k] << (8 * k);
-  }
+  RowGroup4 g;
+  if (!row_group4(s.w, s.h, g)) return;
+  const uint32_t x0 = g.x0, y = g.y, img = g.img, n = g.n;
+  const uint32_t yv = plane_load4(s.y + (size_t)img * s.y_image + (size_t)y * s.y_row + x0, n);
   const uint8_t *cb = s.cb + (size_t)img * s.c_image, *cr = s.cr + (size_t)img * s.c_image;
   int c1[4], c2[4];
   if (s.cpitch == 2) {
@@ -45,8 +40,7 @@ template <int DC> __global__ void __launch_bounds__(64) planes_ingest_kernel(con
   uint32_t px[4];
 #pragma unroll
   for (int k = 0; k < 4; k++) px[k] = ((yv >> (8 * k)) & 255u) | ((uint32_t)c1[k] << 8) | ((uint32_t)c2[k] << 16) | 0xFF000000u;
-  uint8_t *dst = slots + ((size_t)img * s.h * s.w + (size_t)y * s.w + x0) * DC;
-  slot_store4<DC>(dst, px, n, ((uintptr_t)dst & (DC == 4 ? 15 : 3)) == 0);
+  slot_store4<DC>(slot_ptr<DC>(slots, s.w, s.h, g), px, n);
 }
 
 }  // namespace mi

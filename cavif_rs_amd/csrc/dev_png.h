@@ -14,12 +14,12 @@
 //                        with the lanes running along the rows, one sub-tile ahead of the steps that use them, and go back the same way.
 //   png_expand_kernel    unfiltered scanlines -> slot: every colour type and bit depth, MSB-first sub-byte samples, gray scaled s * 255 / max, the high
 //                        byte of 16-bit samples, the tRNS colour key compared on all 16 bits, palette + tRNS through a 256-entry table, Adam7 (the output
-//                        pixel picks its pass from (x & 7, y & 7)).  The arithmetic is png_expand_rgba's (png_reader.h).  One thread = four adjacent
-//                        output pixels, ending in slot_store4 like the JPEG colour kernels.
+//                        pixel picks its pass from (x & 7, y & 7): png_pass_row).  The arithmetic is png_expand_rgba's (png_reader.h).  In the row groups
+//                        of dev_slot.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
-#include "dev_ingest.h"
+#include "dev_slot.h"
 
 namespace mi {
 
@@ -168,16 +168,23 @@ __global__ void __launch_bounds__(64 * MI_PNG_WAVES) png_unfilter_kernel(uint8_t
   }
 }
 
-// pixel (x, y) of the picture as r | g << 8 | b << 16 | a << 24
-__device__ __forceinline__ uint32_t png_pixel(const uint8_t *buf, const PngImageDev &im, const uint32_t x, const uint32_t y) {
-  uint32_t p = 0, xx = x, yy = y;
+// the first sample byte of the row that holds pixel (x, y) in its Adam7 pass (the only pass of a non-interlaced file), and in xx the pixel's column within that pass
+__device__ __forceinline__ const uint8_t *png_pass_row(const uint8_t *buf, const PngImageDev &im, const uint32_t x, const uint32_t y, uint32_t &xx) {
+  uint32_t p = 0, yy = y;
+  xx = x;
   if (im.interlace) {
     p = (y & 1) ? 6 : (x & 1) ? 5 : (y & 2) ? 4 : (x & 2) ? 3 : (y & 4) ? 2 : (x & 4) ? 1 : 0;
     // per pass: x0 = 0 4 0 2 0 1 0, y0 = 0 0 4 0 2 0 1, dx = 8 8 4 4 2 2 1, dy = 8 8 8 4 4 2 2 (a nibble each)
     xx = (x - ((0x0102040u >> (4 * p)) & 15u)) >> ((0x0112233u >> (4 * p)) & 15u);
     yy = (y - ((0x1020400u >> (4 * p)) & 15u)) >> ((0x1122333u >> (4 * p)) & 15u);
   }
-  const uint8_t *row = buf + im.pass_off[p] + (size_t)yy * ((size_t)im.pass_rowbytes[p] + 1) + 1;
+  return buf + im.pass_off[p] + (size_t)yy * ((size_t)im.pass_rowbytes[p] + 1) + 1;
+}
+
+// pixel (x, y) of the picture as r | g << 8 | b << 16 | a << 24
+__device__ __forceinline__ uint32_t png_pixel(const uint8_t *buf, const PngImageDev &im, const uint32_t x, const uint32_t y) {
+  uint32_t xx;
+  const uint8_t *row = png_pass_row(buf, im, x, y, xx);
   const uint32_t depth = im.depth, ctype = im.ctype;
   const uint32_t channels = ctype == 0 ? 1 : ctype == 2 ? 3 : ctype == 3 ? 1 : ctype == 4 ? 2 : 4;
   const uint32_t mx = (1u << (depth > 8 ? 8 : depth)) - 1;
@@ -209,17 +216,15 @@ __device__ __forceinline__ uint32_t png_pixel(const uint8_t *buf, const PngImage
   return r | (g << 8) | (b << 16) | (a << 24);
 }
 
-// grid: (ceil(ceil(w / 4) / 64), h, images); slots = slot of the first image
+// slots = slot of the first image
 template <int DC> __global__ void __launch_bounds__(64) png_expand_kernel(const uint8_t *buf, const PngImageDev *imgs, const uint32_t w, const uint32_t h, uint8_t *slots) {
-  const uint32_t x0 = (blockIdx.x * 64 + threadIdx.x) * 4, y = blockIdx.y, img = blockIdx.z;
-  if (x0 >= w || y >= h) return;
-  const PngImageDev &im = imgs[img];
-  const uint32_t n = w - x0 < 4 ? w - x0 : 4;
+  RowGroup4 g;
+  if (!row_group4(w, h, g)) return;
+  const PngImageDev &im = imgs[g.img];
   uint32_t px[4] = { 0, 0, 0, 0 };
 #pragma unroll
-  for (uint32_t k = 0; k < 4; k++) if (k < n) px[k] = png_pixel(buf, im, x0 + k, y);
-  uint8_t *dst = slots + ((size_t)img * h * w + (size_t)y * w + x0) * DC;
-  slot_store4<DC>(dst, px, n, ((uintptr_t)dst & (DC == 4 ? 15 : 3)) == 0);
+  for (uint32_t k = 0; k < 4; k++) if (k < g.n) px[k] = png_pixel(buf, im, g.x0 + k, g.y);
+  slot_store4<DC>(slot_ptr<DC>(slots, w, h, g), px, g.n);
 }
 
 }  // namespace mi

@@ -6,16 +6,16 @@
 //                       column: a wavefront stores one contiguous 256-byte run of an intermediate row).  The source span of the tile is staged in LDS
 //                       MI_RS_CHUNK pixels at a time with the threads running along the row, and every lane adds the taps that fall into the chunk:
 //                       the tap count has no bound (257 -> 2 Lanczos: 773), the LDS tile has.  Sums are 32-bit and wrap, so their order is free.
-//   resample_v_kernel   intermediate -> slot.  One thread = four adjacent pixels of an output row (16 accumulators), the 64 lanes of a wavefront = 256
-//                       adjacent pixels: each tap is one contiguous 1 KiB run of an intermediate row; bounds and taps are uniform in a workgroup
-//                       (scalar loads).  Un-premultiplies 4-channel pictures and ends in slot_store4.  No LDS.
+//   resample_v_kernel   intermediate -> slot, in the row groups of dev_slot.h (16 accumulators per thread): each tap is one contiguous 1 KiB run of an
+//                       intermediate row; bounds and taps are uniform in a workgroup (scalar loads).  Un-premultiplies 4-channel pictures.  No LDS.
 // Tables come from the host (mi_avif.hip: resample_axis), per axis: bounds[2 i] = first sample, bounds[2 i + 1] = taps of output sample i, and the taps in
 // 22-bit fixed point, tap-major (tap j of output i at taps[j * n_out + i]: adjacent lanes read adjacent words).  An axis that keeps its length gets the
 // one-tap identity table (2^22: 2^21 + s * 2^22 >> 22 = s), so its pass moves the samples unchanged.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
-#include "dev_ingest.h"
+#include "dev_slot.h"
+#include "dev_ingest.h"                   // IngestSrc
 
 namespace mi {
 
@@ -73,12 +73,12 @@ __global__ void __launch_bounds__(64 * MI_RS_TH) resample_h_kernel(const IngestS
   if (live) inter[((size_t)img * s.h + y) * pitch + ox] = rs_clip8(acc[0]) | (rs_clip8(acc[1]) << 8) | (rs_clip8(acc[2]) << 16) | (alpha ? rs_clip8(acc[3]) << 24 : 0xFF000000u);
 }
 
-// grid: (ceil(ceil(dst_w / 4) / 64), dst_h, images); block 64.  alpha: the picture has four channels (premultiplied in the intermediate); slots = slot of the first image.
+// alpha: the picture has four channels (premultiplied in the intermediate); slots = slot of the first image.
 template <int DC> __global__ void __launch_bounds__(64) resample_v_kernel(const uint32_t *inter, const uint32_t src_h, const uint32_t pitch, const uint32_t *bounds, const int32_t *taps,
                                                                           const uint32_t dst_w, const uint32_t dst_h, const int alpha, uint8_t *slots) {
-  const uint32_t x0 = (blockIdx.x * 64 + threadIdx.x) * 4, oy = blockIdx.y, img = blockIdx.z;
-  if (x0 >= dst_w || oy >= dst_h) return;
-  const uint32_t n = dst_w - x0 < 4 ? dst_w - x0 : 4;
+  RowGroup4 g;
+  if (!row_group4(dst_w, dst_h, g)) return;
+  const uint32_t x0 = g.x0, oy = g.y, img = g.img;
   const uint32_t ymin = bounds[2 * oy], cnt = bounds[2 * oy + 1];
   const uint32_t *col = inter + ((size_t)img * src_h + ymin) * pitch + x0;         // 16-byte aligned: pitch and x0 are multiples of 4; the row's padding is read and not used
   const int32_t *k_ = taps + oy;
@@ -109,8 +109,7 @@ template <int DC> __global__ void __launch_bounds__(64) resample_v_kernel(const 
     }
     px[p] = r | (g << 8) | (b << 16) | (a << 24);
   }
-  uint8_t *dst = slots + ((size_t)img * dst_h * dst_w + (size_t)oy * dst_w + x0) * DC;
-  slot_store4<DC>(dst, px, n, ((uintptr_t)dst & (DC == 4 ? 15 : 3)) == 0);
+  slot_store4<DC>(slot_ptr<DC>(slots, dst_w, dst_h, g), px, g.n);
 }
 
 }  // namespace mi

@@ -55,14 +55,16 @@ static int batch_join(mi_batch *b, void *after_stream) {
   return MI_OK;
 }
 
-// the grid of the kernels with one thread per four pixels of a row (workgroups of 64), a grid row per picture row and a grid plane per image
+// the grid of the kernels that work in row groups (dev_slot.h: one thread per four pixels of a row, workgroups of 64), a grid row per picture row and a grid
+// plane per image
 static dim3 grid_by_four(uint32_t w, uint32_t h, int count) { return dim3(((w + 3) / 4 + 63) / 64, h, (unsigned)count); }
-// such a kernel template, `kernel`<3> or <4> by `channels`, on the batch's stream.  A macro because a template of kernels has no name to pass: `b` and
-// `channels` are evaluated twice, the kernel's arguments once per branch -- pass plain variables
-#define LAUNCH_BY_CHANNELS(b, channels, w, h, count, kernel, ...) do { \
-    if ((channels) == 4) hipLaunchKernelGGL((kernel<4>), grid_by_four(w, h, count), dim3(64), 0, (b)->stream, __VA_ARGS__); \
-    else hipLaunchKernelGGL((kernel<3>), grid_by_four(w, h, count), dim3(64), 0, (b)->stream, __VA_ARGS__); \
+// such a kernel template, `kernel`<3> or <4> by `channels`, on a stream / on the batch's stream.  A macro because a template of kernels has no name to pass:
+// `stream` and `channels` are evaluated twice, the kernel's arguments once per branch -- pass plain variables
+#define LAUNCH_BY_CHANNELS_ON(stream, channels, w, h, count, kernel, ...) do { \
+    if ((channels) == 4) hipLaunchKernelGGL((kernel<4>), grid_by_four(w, h, count), dim3(64), 0, stream, __VA_ARGS__); \
+    else hipLaunchKernelGGL((kernel<3>), grid_by_four(w, h, count), dim3(64), 0, stream, __VA_ARGS__); \
   } while (0)
+#define LAUNCH_BY_CHANNELS(b, channels, w, h, count, kernel, ...) LAUNCH_BY_CHANNELS_ON((b)->stream, channels, w, h, count, kernel, __VA_ARGS__)
 
 // Strided pictures in device memory (mi_device_pixels, mi_device_pixels16, mi_device_target -> IngestSrc, Ingest16Src, DecodedDst): pointer, layout, channels
 // and the three byte strides of `src` for pictures of w x h samples of `sample_bytes` go into `d`.  A stride of 0 means packed -- HWC: pixels back to back, rows
@@ -241,16 +243,8 @@ static int jpeg_decode_to_device(const JpegCoeffs &jc, uint8_t *h_in, uint8_t *d
   lap(0);
   hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((jc.nblocks + MI_JPEG_IDCT_BLOCKS - 1) / MI_JPEG_IDCT_BLOCKS)), dim3(256), 0, stream,
                      (const int16_t *)(d_in + quant_bytes), (const uint16_t *)d_in, g, d_planes);
-  const dim3 grid(((jc.w + 3) / 4 + 63) / 64, jc.h);
-  if (channels == 4) {
-    const int vec16 = (stride_px % 4 == 0 && ((uintptr_t)d_out & 15) == 0) ? 1 : 0;
-    if (ycc) hipLaunchKernelGGL((jpeg_ycc_kernel<4>), grid, dim3(64), 0, stream, (const uint8_t *)d_planes, g, d_out, stride_px, vec16);
-    else hipLaunchKernelGGL(jpeg_rgba_kernel, grid, dim3(64), 0, stream, (const uint8_t *)d_planes, g, d_out, stride_px, vec16);
-  } else {
-    const int vec4 = (stride_px % 4 == 0 && ((uintptr_t)d_out & 3) == 0) ? 1 : 0;        // a row is 3 * stride_px bytes
-    if (ycc) hipLaunchKernelGGL((jpeg_ycc_kernel<3>), grid, dim3(64), 0, stream, (const uint8_t *)d_planes, g, d_out, stride_px, vec4);
-    else hipLaunchKernelGGL(jpeg_rgb_kernel, grid, dim3(64), 0, stream, (const uint8_t *)d_planes, g, d_out, stride_px, vec4);
-  }
+  if (ycc) LAUNCH_BY_CHANNELS_ON(stream, channels, jc.w, jc.h, 1, jpeg_ycc_kernel, (const uint8_t *)d_planes, g, d_out, stride_px);
+  else LAUNCH_BY_CHANNELS_ON(stream, channels, jc.w, jc.h, 1, jpeg_colour_kernel, (const uint8_t *)d_planes, g, d_out, stride_px);
   HIP_OK(hipGetLastError());
   lap(1);
   return MI_OK;
@@ -902,21 +896,18 @@ int mi_batch_convert_colour(mi_batch *b, int first, int count, mi_colour_transfo
   (void)hipSetDevice(b->device);
   ColourDev d;
   if (!colour_on_device(t, b->device, d)) return MI_ENCODING_ERROR;
-  const uint32_t w = b->w, h = b->h;
+  const uint32_t w = b->w, h = b->h, row_groups = (h + MI_COLOUR_ROWS - 1) / MI_COLOUR_ROWS;    // a workgroup runs down MI_COLOUR_ROWS rows
   for (int i = first; i < first + count;) {
     const int kind = b->kinds[i];
     int j = i + 1;
     while (j < first + count && b->kinds[j] == kind) j++;
-    const dim3 grid(((w + 3) / 4 + 63) / 64, (h + MI_COLOUR_ROWS - 1) / MI_COLOUR_ROWS, (unsigned)(j - i));
     if (kind == MI_INPUT_RGB) {
       uint8_t *const slots = mi_batch_device_input(b, i);
-      if (b->channels == 4) hipLaunchKernelGGL((colour_convert_kernel<4>), grid, dim3(64), 0, b->stream, d, slots, w, h);
-      else hipLaunchKernelGGL((colour_convert_kernel<3>), grid, dim3(64), 0, b->stream, d, slots, w, h);
+      LAUNCH_BY_CHANNELS(b, b->channels, w, row_groups, j - i, colour_convert_kernel, d, slots, w, h);
     } else {
       uint16_t *const slots = mi_batch_device_input16(b, i);
       if (!slots) return MI_ENCODING_ERROR;
-      if (b->channels == 4) hipLaunchKernelGGL((colour_convert16_kernel<4>), grid, dim3(64), 0, b->stream, d, slots, w, h);
-      else hipLaunchKernelGGL((colour_convert16_kernel<3>), grid, dim3(64), 0, b->stream, d, slots, w, h);
+      LAUNCH_BY_CHANNELS(b, b->channels, w, row_groups, j - i, colour_convert16_kernel, d, slots, w, h);
     }
     i = j;
   }

@@ -37,7 +37,7 @@ def check(rows, *prefixes):
 
 def test_committed_fixtures_are_what_libjpeg_holds():
     """tools/gen_ycc_goldens.py, run in memory: the full-size YCbCr of the 27 colour fixtures and the half-scale chroma of the 13 4:2:0 ones equal the committed
-    PNG files; its own checks tie them to the committed RGB pixels (through jpeg_colour4's arithmetic) and to the numpy upsampler of ycc_cases.py"""
+    PNG files; its own checks tie them to the committed RGB pixels (through jpeg_colour_kernel's arithmetic) and to the numpy upsampler of ycc_cases.py"""
     sys.path.insert(0, os.path.join(ROOT, 'tools'))
     import gen_ycc_goldens as g
     from PIL import Image

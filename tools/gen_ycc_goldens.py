@@ -10,7 +10,7 @@
 Grey fixtures need no file (the expected triples are (L, 128, 128)); rgb_37x23_q95_keeprgb is the file the YCbCr upload refuses.
 
 Before anything is written the bytes are checked against what the repository already holds: the full-size triples pushed through the 16.16 arithmetic of
-jpeg_colour4 (dev_jpeg.h) must give the committed RGB expected pixels, and the numpy restatement of h2v2 fancy upsampling (tests/helpers/ycc_cases.py) of the
+jpeg_colour_kernel (dev_jpeg.h) must give the committed RGB expected pixels, and the numpy restatement of h2v2 fancy upsampling (tests/helpers/ycc_cases.py) of the
 half-scale chroma must give the full-size chroma.  A Pillow whose libjpeg does not do that is not the one the goldens came from, and nothing is written.
 --check compares instead of writing (exit status 1 on a difference).  Needs Pillow (made with 12.2.0) and numpy."""
 import glob
@@ -41,7 +41,7 @@ def decode_ycc(data, size=None):
 
 
 def ycc_to_rgb(ycc):
-    """jpeg_colour4's 16.16 conversion (libjpeg's jdcolor.c) in numpy"""
+    """jpeg_colour_kernel's 16.16 conversion (libjpeg's jdcolor.c) in numpy"""
     y, cb, cr = (ycc[..., i].astype(np.int64) for i in range(3))
     cb -= 128; cr -= 128
     r = y + ((91881 * cr + 32768) >> 16)
