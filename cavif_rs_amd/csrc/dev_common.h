@@ -238,9 +238,10 @@ __device__ __forceinline__ int sym_to_txtype(int set, int s) {
   return lut4(0x21309ULL, s);                             // IDTX, DCT_DCT, ADST_ADST, ADST_DCT, DCT_ADST
 }
 __device__ __forceinline__ int txtype_to_sym(int set, int t) {
-  const int n = tx_set_count(set);
-  for (int i = 0; i < n; i++) if (sym_to_txtype(set, i) == t) return i;
-  return -1;
+  // the inverse of sym_to_txtype's tables, indexed by the transform type (0..15); 15: the set has no such type
+  const unsigned long long inv12 = set == 1 ? 0xffff320fffff4651ULL : 0xffffff0fffff2431ULL, inv = set == 0 ? 0xfffffffffffffff0ULL : inv12;
+  const int s = lut4(inv, t);
+  return s == 15 ? -1 : s;
 }
 __device__ __forceinline__ int mode_to_txtype(int m) {
   // DCT_DCT, ADST_DCT, DCT_ADST, DCT_DCT, ADST_ADST, ADST_DCT, DCT_ADST, DCT_ADST, ADST_DCT, ADST_ADST, ADST_DCT, DCT_ADST, ADST_ADST, DCT_DCT

@@ -440,9 +440,16 @@ __device__ inline void predict_dir_group(const LDS FrameDev *f, int x, int y, in
   edge_upsample_group(wa, N + (pa < 90 ? N : 0), up_a, bd, gp->tmp, gl);
   const int up_l = edge_upsample_sel_dev(N, N, ftype, pa - 180);
   edge_upsample_group(wl, N + (pa > 180 ? N : 0), up_l, bd, gp->tmp, gl);
+  // pa is uniform per row: the four rows' lookups run on the scalar unit (four scalar loads in flight together) and each row keeps its own.  As vector code
+  // the lookup's constants cost the block searches registers: 32 B more scratch per lane.  A row whose lanes are inactive reads a stale angle; any integer is
+  // a valid argument.
   int dx = 0, dy = 0;
-  if (pa < 90) dx = dr_deriv_dev(pa); else if (pa > 90 && pa < 180) dx = dr_deriv_dev(180 - pa);
-  if (pa > 90 && pa < 180) dy = dr_deriv_dev(pa - 90); else if (pa > 180) dy = dr_deriv_dev(270 - pa);
+#pragma unroll
+  for (int r = 0; r < 4; r++) {
+    int sdx, sdy;
+    dr_dxdy_uni(__builtin_amdgcn_readlane(pa, 16 * r), &sdx, &sdy);
+    dx = GROUP_ID == r ? sdx : dx; dy = GROUP_ID == r ? sdy : dy;
+  }
   for (int idx = gl; idx < nn; idx += 16) {
     const int i = idx >> log2w, j = idx & (N - 1);
     int v;

@@ -9,48 +9,67 @@
 #define EDGE_LEN(N) (EDGE_OFF + 2 * (N) + 16)
 
 __device__ __forceinline__ const uint8_t *sm_weights_dev(int log2w) {
-  static __device__ const uint8_t w4[4] = { 255, 149, 85, 64 };
-  static __device__ const uint8_t w8[8] = { 255, 197, 146, 105, 73, 50, 37, 32 };
-  static __device__ const uint8_t w16[16] = { 255, 225, 196, 170, 145, 123, 102, 84, 68, 54, 43, 33, 26, 20, 17, 16 };
-  static __device__ const uint8_t w32[32] = { 255, 240, 225, 210, 196, 182, 169, 157, 145, 133, 122, 111, 101, 92, 83, 74,
-                                              66, 59, 52, 45, 39, 34, 29, 25, 21, 17, 14, 12, 10, 9, 8, 8 };
-  static __device__ const uint8_t w64[64] = { 255, 248, 240, 233, 225, 218, 210, 203, 196, 189, 182, 176, 169, 163, 156, 150,
+  // Sm_Weights_Tx_4x4 .. 64x64 in one array: the table of size n starts at n - 4
+  static __device__ const uint8_t sw[124] = { 255, 149, 85, 64,
+                                              255, 197, 146, 105, 73, 50, 37, 32,
+                                              255, 225, 196, 170, 145, 123, 102, 84, 68, 54, 43, 33, 26, 20, 17, 16,
+                                              255, 240, 225, 210, 196, 182, 169, 157, 145, 133, 122, 111, 101, 92, 83, 74,
+                                              66, 59, 52, 45, 39, 34, 29, 25, 21, 17, 14, 12, 10, 9, 8, 8,
+                                              255, 248, 240, 233, 225, 218, 210, 203, 196, 189, 182, 176, 169, 163, 156, 150,
                                               144, 138, 133, 127, 121, 116, 111, 106, 101, 96, 91, 86, 82, 77, 73, 69,
                                               65, 61, 57, 54, 50, 47, 44, 41, 38, 35, 32, 29, 27, 25, 22, 20,
                                               18, 16, 15, 13, 12, 10, 9, 8, 7, 6, 6, 5, 5, 4, 4, 4 };
-  switch (log2w) { case 2: return w4; case 3: return w8; case 4: return w16; case 5: return w32; default: return w64; }
+  const int l = ((log2w >= 2) & (log2w <= 5)) ? log2w : 6;
+  return sw + ((1 << l) - 4);
 }
+// The three lookups below are straight-line code on packed immediates.  Their arguments are uniform per 16-lane row, not per wave (the SATD stage predicts four angles
+// per wave): as a `switch` / `if` ladder each became a divergent decision tree, walked once per distinct value among the wave's rows (profiles/k1_lookups.md).
+//
+// Dr_Intra_Derivative (spec 7.11.2.4).  The 27 angles that have one are a = 3 k + r with k = a / 3 distinct for each (1..29 without 11 and 26) and r a function
+// of k: eight low bits of the value per k in four words, the two high bits (k = 1..4 only) and r (3: no such angle) in two-bit tables.  Every other a gives 0.
 __device__ __forceinline__ int dr_deriv_dev(int a) {
-  switch (a) {
-    case 3: return 1023; case 6: return 547; case 9: return 372; case 14: return 273; case 17: return 215;
-    case 20: return 178; case 23: return 151; case 26: return 132; case 29: return 116; case 32: return 102;
-    case 36: return 90; case 39: return 80; case 42: return 71; case 45: return 64; case 48: return 57;
-    case 51: return 51; case 54: return 45; case 58: return 40; case 61: return 35; case 64: return 31;
-    case 67: return 27; case 70: return 23; case 73: return 19; case 76: return 15; case 81: return 11;
-    case 84: return 7; case 87: return 3; default: return 0;
-  }
+  const int aa = (unsigned)a < 90u ? a : 0;
+  const int k = (aa * 43) >> 7;                                      // aa / 3 for 0..89
+  const unsigned long long w01 = k < 8 ? 0x97b2d7117423ff00ULL : 0x4047505a00667484ULL, w23 = k < 24 ? 0x171b1f23282d3339ULL : 0x000003070b000f13ULL;
+  const unsigned long long w = k < 16 ? w01 : w23;
+  const int v = lut8(w, k & 7) | ((int)((0x16cULL >> (2 * k)) & 3) << 8);
+  const int r = (int)((0xf035554000eaaa03ULL >> (2 * k)) & 3);
+  return aa - 3 * k == r ? v : 0;
 }
+// Edge filter strength (spec 7.11.2.9): the block classes w + h <= 8, 12, 16, 24, 32 and above; per class and filter type the smallest |delta| of strength 1, 2 and 3
+// (255: never; a strength that a class skips has the next one's threshold), eight bits per class.
 __device__ __forceinline__ int edge_strength_dev(int w, int h, int ft, int delta) {
-  const int d = iabs_(delta), blk = w + h; int s = 0;
-  if (ft == 0) {
-    if (blk <= 8) { if (d >= 56) s = 1; }
-    else if (blk <= 12) { if (d >= 40) s = 1; }
-    else if (blk <= 16) { if (d >= 40) s = 1; }
-    else if (blk <= 24) { if (d >= 8) s = 1; if (d >= 16) s = 2; if (d >= 32) s = 3; }
-    else if (blk <= 32) { if (d >= 1) s = 1; if (d >= 4) s = 2; if (d >= 32) s = 3; }
-    else { if (d >= 1) s = 3; }
-  } else {
-    if (blk <= 8) { if (d >= 40) s = 1; if (d >= 64) s = 2; }
-    else if (blk <= 16) { if (d >= 20) s = 1; if (d >= 48) s = 2; }
-    else if (blk <= 24) { if (d >= 4) s = 3; }
-    else { if (d >= 1) s = 3; }
-  }
-  return s;
+  const int d = imin_(iabs_(delta), 254), blk = w + h;
+  const int c = (blk > 8) + (blk > 12) + (blk > 16) + (blk > 24) + (blk > 32);
+  const unsigned long long t1 = ft == 0 ? 0x010108282838ULL : 0x010104141428ULL, t2 = ft == 0 ? 0x010410ffffffULL : 0x010104303040ULL;
+  const unsigned long long t3 = ft == 0 ? 0x012020ffffffULL : 0x010104ffffffULL;
+  return (d >= lut8(t1, c)) + (d >= lut8(t2, c)) + (d >= lut8(t3, c));
 }
 __device__ __forceinline__ int edge_upsample_sel_dev(int w, int h, int ft, int delta) {
   const int d = iabs_(delta), blk = w + h;
-  if (d <= 0 || d >= 40) return 0;
-  return ft == 0 ? (blk <= 16) : (blk <= 8);
+  return (int)((d > 0) & (d < 40) & (blk <= (ft == 0 ? 16 : 8)));
+}
+// dx and dy of a directional prediction of angle pa (spec 7.11.2.4 steps 5-7: dx below 180 degrees, dy above 90; 0 where the prediction does not use one).
+// dr_deriv_dev is 0 for every argument that is not a derivative's angle, a negative one included, which stands for the conditions.
+__device__ __forceinline__ void dr_dxdy_dev(int pa, int *dx, int *dy) {
+  *dx = dr_deriv_dev(pa < 90 ? pa : 180 - pa);
+  *dy = dr_deriv_dev(pa < 180 ? pa - 90 : 270 - pa);
+}
+// The same for an angle the compiler knows to be wave-uniform (readlane / readfirstlane): one scalar load and a few scalar instructions, no vector register.
+// Entry pa / 3 is dx | dy << 10 | (pa % 3) << 20 for the angles with a dx or dy (they lie at least 3 apart: no two share an entry), 3 << 20 for the rest.
+static __device__ const uint32_t dr_dxdy_tab[91] = {
+    0x300000, 0x0003ff, 0x000223, 0x000174, 0x200111, 0x2000d7, 0x2000b2, 0x200097, 0x200084, 0x200074, 0x200066, 0x300000, 0x00005a,
+    0x000050, 0x000047, 0x000040, 0x000039, 0x000033, 0x00002d, 0x100028, 0x100023, 0x10001f, 0x10001b, 0x100017, 0x100013, 0x10000f,
+    0x300000, 0x00000b, 0x000007, 0x000003, 0x300000, 0x0ffc03, 0x088c07, 0x05d00b, 0x24440f, 0x235c13, 0x22c817, 0x225c1b, 0x22101f,
+    0x21d023, 0x219828, 0x300000, 0x01682d, 0x014033, 0x011c39, 0x010040, 0x00e447, 0x00cc50, 0x00b45a, 0x10a066, 0x108c74, 0x107c84,
+    0x106c97, 0x105cb2, 0x104cd7, 0x103d11, 0x300000, 0x002d74, 0x001e23, 0x000fff, 0x300000, 0x000c00, 0x001c00, 0x002c00, 0x203c00,
+    0x204c00, 0x205c00, 0x206c00, 0x207c00, 0x208c00, 0x20a000, 0x300000, 0x00b400, 0x00cc00, 0x00e400, 0x010000, 0x011c00, 0x014000,
+    0x016800, 0x119800, 0x11d000, 0x121000, 0x125c00, 0x12c800, 0x135c00, 0x144400, 0x300000, 0x05d000, 0x088c00, 0x0ffc00, 0x300000 };
+__device__ __forceinline__ void dr_dxdy_uni(int pa, int *dx, int *dy) {
+  const int p = (unsigned)pa <= 270u ? pa : 0, k = (p * 683) >> 11;               // p / 3 for 0..270
+  const uint32_t e = dr_dxdy_tab[k];
+  const bool has = p - 3 * k == (int)(e >> 20);
+  *dx = has ? (int)(e & 1023) : 0; *dy = has ? (int)((e >> 10) & 1023) : 0;
 }
 
 // Raw (unfiltered) edges of the block at pixel (x,y) of `plane`: above[-1..2n-1], left[-1..2n-1]. (spec 7.11.2 steps 1-4)
@@ -174,9 +193,8 @@ __device__ inline void predict_block(const LDS FrameDev *f, int x, int y, int lo
     if (up_a) edge_upsample_dev(wa, n + (pa < 90 ? n : 0), bd, tmp);
     up_l = edge_upsample_sel_dev(n, n, ftype, pa - 180);
     if (up_l) edge_upsample_dev(wl, n + (pa > 180 ? n : 0), bd, tmp);
-    int dx = 0, dy = 0;
-    if (pa < 90) dx = dr_deriv_dev(pa); else if (pa > 90 && pa < 180) dx = dr_deriv_dev(180 - pa);
-    if (pa > 90 && pa < 180) dy = dr_deriv_dev(pa - 90); else if (pa > 180) dy = dr_deriv_dev(270 - pa);
+    int dx, dy;
+    dr_dxdy_dev(pa, &dx, &dy);
     for (int idx = LANE; idx < nn; idx += 64) {
       const int i = idx >> log2w, j = idx & (n - 1);
       int v;

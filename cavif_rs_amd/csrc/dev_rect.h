@@ -77,9 +77,8 @@ __device__ inline void predict_block_wh(const LDS FrameDev *f, int x, int y, int
     if (up_a) edge_upsample_dev(wa, w + (pa < 90 ? h : 0), bd, tmp);
     up_l = edge_upsample_sel_dev(w, h, ftype, pa - 180);
     if (up_l) edge_upsample_dev(wl_, h + (pa > 180 ? w : 0), bd, tmp);
-    int dx = 0, dy = 0;
-    if (pa < 90) dx = dr_deriv_dev(pa); else if (pa > 90 && pa < 180) dx = dr_deriv_dev(180 - pa);
-    if (pa > 90 && pa < 180) dy = dr_deriv_dev(pa - 90); else if (pa > 180) dy = dr_deriv_dev(270 - pa);
+    int dx, dy;
+    dr_dxdy_dev(pa, &dx, &dy);
     for (int idx = LANE; idx < nn; idx += 64) {
       const int i = idx >> wl, j = idx & (w - 1);
       int v;
