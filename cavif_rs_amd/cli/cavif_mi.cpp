@@ -1,6 +1,6 @@
 // cavif_mi -- the cavif command line (src/main.rs) on top of libmi_avif.so: same flags, path rules and report line;
 // the rayon fan-out over files (src/main.rs:223) becomes mi_ravif_encode_batch (one host thread per MI355X).
-//   cavif_mi [-Q n] [-s n] [-j n] [-f] [-o path] [-q] [--dirty-alpha] [--color ycbcr|rgb] [--depth 8|10|auto] [--jpeg-ycbcr] [--deep-png] IMAGES...
+//   cavif_mi [-Q n] [-s n] [-j n] [-f] [-o path] [-q] [--dirty-alpha] [--color ycbcr|rgb] [--depth 8|10|auto] [--jpeg-ycbcr] [--deep-png] [--color-managed] [--exif-orientation] IMAGES...
 // Input: PNG and baseline / progressive 8-bit JPEG, told apart by their first bytes as load_image does.  A loader thread does the serial half of the
 // decode -- inflate of a PNG (mi_png_parse), Huffman decoding of a JPEG (mi_jpeg_parse) -- and hands scanlines or coefficients to the encoder, which
 // finishes the picture on the GPU inside the batch that encodes it (mi_ravif_encode_sources): the loaders never touch a device.  Differences, deliberate:
@@ -8,7 +8,8 @@
 // default) codes a grey or YCbCr JPEG from the file's own Y, Cb, Cr instead of the RGB pixels a decoder makes of them; RGB-coloured JPEG files, PNG files and
 // everything under --color rgb go as without it.  `--deep-png` (off by default) codes a PNG file of bit depth 16 from all 16 bits of its samples instead of
 // their high bytes; a file with an alpha channel or tRNS goes that way only together with --dirty-alpha (the alpha cleaner is defined on 8-bit samples), every
-// other file as without the flag.
+// other file as without the flag.  `--exif-orientation` (off by default) turns every picture on the GPU as its file's EXIF orientation asks (a JPEG's APP1 Exif segment, a
+// PNG's eXIf chunk), so a portrait photo comes out upright; without it the stored rows are encoded as they are.  It combines with the three flags above.
 #include <sched.h>
 #include <sys/stat.h>
 #include <cerrno>
@@ -89,10 +90,13 @@ int host_threads() {
 }
 int usage(const char *msg) {
   fprintf(stderr, "error: %s\nusage: cavif_mi [-Q quality 1-100] [-s speed 1-10] [-j threads] [-f|--overwrite] [-o path] [-q] [--dirty-alpha]\n"
-                  "                [--color ycbcr|rgb] [--depth 8|10|auto] [--devices 0,1,..] [--rdo-passes 1|2] [--jpeg-ycbcr] [--deep-png] [--color-managed] IMAGES...   (\"-\" = stdin/stdout)\n"
+                  "                [--color ycbcr|rgb] [--depth 8|10|auto] [--devices 0,1,..] [--rdo-passes 1|2] [--jpeg-ycbcr] [--deep-png] [--color-managed]\n"
+                  "                [--exif-orientation] IMAGES...   (\"-\" = stdin/stdout)\n"
                   "  --color-managed  convert every file to sRGB by its own colour description (an ICC profile, or PNG gAMA / cHRM) on the GPU; a file whose profile\n"
                   "                   is unsupported or malformed is encoded unmanaged (one warning line unless -q).  With --jpeg-ycbcr a JPEG whose description\n"
-                  "                   asks for a conversion goes the RGB way: the conversion needs RGB.  Combines with --deep-png.\n", msg);
+                  "                   asks for a conversion goes the RGB way: the conversion needs RGB.  Combines with --deep-png.\n"
+                  "  --exif-orientation  turn every picture on the GPU as its file's EXIF orientation (tag 0x0112) asks; without it the stored rows are encoded as they are.\n"
+                  "                   Combines with --jpeg-ycbcr, --deep-png and --color-managed.\n", msg);
   return 1;
 }
 
@@ -106,13 +110,14 @@ int usage(const char *msg) {
 #include <sys/wait.h>
 static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 // one input file: where it goes, what its loader made of it (a JPEG leaves it as coefficients, a PNG as filtered scanlines) and how it is to be sent
-struct Job { std::string in_name, out_path; bool out_stdio = false; mi_jpeg_coeffs *jpeg = nullptr; mi_png_scanlines *png = nullptr; uint32_t w = 0, h = 0; bool ycbcr = false, deep = false, managed = false; std::string error; };
-// the source kind (MI_SOURCE_*) of a loaded job: its file type, then managed (which has switched ycbcr off), ycbcr / deep
-static int source_kind(const Job &j) {
+struct Job { std::string in_name, out_path; bool out_stdio = false; mi_jpeg_coeffs *jpeg = nullptr; mi_png_scanlines *png = nullptr; uint32_t w = 0, h = 0; bool ycbcr = false, deep = false, managed = false, oriented = false; std::string error; };
+// the source kind (MI_SOURCE_*) of a loaded job: its file type, then managed (which has switched ycbcr off), ycbcr / deep; --exif-orientation adds its modifier
+static int source_kind_plain(const Job &j) {
   if (j.jpeg) return j.managed ? MI_SOURCE_JPEG_MANAGED : j.ycbcr ? MI_SOURCE_JPEG_YCBCR : MI_SOURCE_JPEG;
   if (j.png) return j.managed ? (j.deep ? MI_SOURCE_PNG_DEEP_MANAGED : MI_SOURCE_PNG_MANAGED) : j.deep ? MI_SOURCE_PNG_DEEP : MI_SOURCE_PNG;
   return MI_SOURCE_HOST;
 }
+static int source_kind(const Job &j) { return source_kind_plain(j) | (j.oriented ? MI_SOURCE_ORIENTED : 0); }
 // --color-managed: what the parsed file says about its colour, probed (parsed, no tables) to learn whether it can be converted; the encoder bakes one transform per
 // distinct description.  True: a usable transform that is not the identity.  An unsupported or malformed profile: one warning line (unless quiet), false.
 static bool probe_managed(const Job &j, bool quiet) {
@@ -158,7 +163,7 @@ int main(int argc, char **argv) {
     }
   }
   float quality = 80.f; int speed = 4, threads = 0, depth = 0, color_model = 0, rdo_passes = 1;
-  bool overwrite = false, quiet = false, dirty_alpha = false, have_output = false, output_stdio = false, jpeg_ycbcr = false, deep_png = false, color_managed = false;
+  bool overwrite = false, quiet = false, dirty_alpha = false, have_output = false, output_stdio = false, jpeg_ycbcr = false, deep_png = false, color_managed = false, exif_orientation = false;
   std::string output; std::vector<std::string> images; std::vector<int> devices;
   // clap syntax (src/main.rs:45-110): --name value, --name=value, -n value, -nvalue, -n=value, combined short flags (-fq)
   std::vector<std::string> args;
@@ -196,6 +201,7 @@ int main(int argc, char **argv) {
     else if (a == "--jpeg-ycbcr") jpeg_ycbcr = true;                                                                                                   // extension: not a cavif flag
     else if (a == "--deep-png") deep_png = true;                                                                                                       // extension: not a cavif flag
     else if (a == "--color-managed") color_managed = true;                                                                                             // extension: not a cavif flag
+    else if (a == "--exif-orientation") exif_orientation = true;                                                                                       // extension: not a cavif flag
     else if (a == "--color") { const std::string v = value("--color"); if (v == "ycbcr") color_model = 0; else if (v == "rgb") color_model = 1; else return usage("bad color type"); }
     else if (a == "--rdo-passes") { rdo_passes = atoi(value("--rdo-passes")); if (rdo_passes < 1 || rdo_passes > 2) return usage("bad --rdo-passes (1 or 2)"); }   // extension: not a cavif flag
     else if (a == "--depth") { const std::string v = value("--depth"); depth = v == "8" ? 8 : v == "10" ? 10 : 0; if (v != "8" && v != "10" && v != "auto") return usage("bad depth"); }
@@ -253,6 +259,10 @@ int main(int argc, char **argv) {
       if (!st && is_jpeg && jpeg_ycbcr && color_model == 0 && mi_jpeg_coeffs_info(j.jpeg, &color, nullptr, nullptr) == MI_OK) j.ycbcr = color != 2;
       if (!st && color_managed) j.managed = probe_managed(j, quiet);
       if (j.managed) j.ycbcr = false;                               // the conversion needs RGB
+      if (!st && exif_orientation) {                                // the slot is the turned picture's: j.w x j.h name it from here on
+        int o = 1;
+        if ((is_jpeg ? mi_jpeg_coeffs_orientation(j.jpeg, &o) : mi_png_scanlines_orientation(j.png, &o)) == MI_OK) { j.oriented = true; mi_oriented_size(j.w, j.h, o, &j.w, &j.h); }
+      }
       if (st) j.error = st == MI_UNSUPPORTED ? "unsupported image format (this build reads PNG and baseline/progressive 8-bit JPEG)" :
                         st == MI_NO_DEVICE ? "no HIP device (this encoder has no CPU fallback)" : "corrupt image data";
     }

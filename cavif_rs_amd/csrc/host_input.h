@@ -1,6 +1,6 @@
 // host_input.h -- the input half of mi_avif.hip, the one translation unit every build names: the rules every slot-filling call shares and the calls through
 // which pixels reach a batch slot or leave it -- host pixels, pictures and planes in device memory, JPEG coefficients, PNG scanlines, 16-bit sources, resize
-// on input, decoded output.  Included there below struct mi_batch, the batch's lifecycle, its encode and its pool, so that the kernels keep the order of their
+// on input, colour management, orientation, decoded output.  Included there below struct mi_batch, the batch's lifecycle, its encode and its pool, so that the kernels keep the order of their
 // first launch site and the code object stays the one the sources gave before the split; the one-call entry points, the stream worker and the plane encoder follow it.
 #pragma once
 
@@ -912,6 +912,111 @@ int mi_batch_convert_colour(mi_batch *b, int first, int count, mi_colour_transfo
     i = j;
   }
   HIP_OK(hipGetLastError());
+  return MI_OK;
+}
+
+// ---- EXIF orientation on input: the file's tag 0x0112 read on the host (exif_reader.h), the picture turned on its way into the slot (dev_orient.h) ----
+int mi_exif_orientation(const uint8_t *exif, size_t len, int *orientation) {
+  if (!exif || !orientation) return MI_INVALID_ARGUMENT;
+  *orientation = exif_orientation(exif, len);
+  return MI_OK;
+}
+int mi_jpeg_coeffs_orientation(const mi_jpeg_coeffs *c, int *orientation) {
+  if (!c || !orientation) return MI_INVALID_ARGUMENT;
+  *orientation = c->jc.orientation;
+  return MI_OK;
+}
+int mi_png_scanlines_orientation(const mi_png_scanlines *p, int *orientation) {
+  if (!p || !orientation) return MI_INVALID_ARGUMENT;
+  *orientation = p->sl.orientation;
+  return MI_OK;
+}
+void mi_oriented_size(uint32_t w, uint32_t h, int orientation, uint32_t *ow, uint32_t *oh) { oriented_size(w, h, orientation, ow, oh); }
+
+}  // extern "C"
+
+// a source of sw x sh turned by `orientation` (1..8) has the batch's size
+static bool batch_oriented_fits(const mi_batch *b, uint32_t sw, uint32_t sh, int orientation) {
+  uint32_t ow, oh;
+  oriented_size(sw, sh, orientation, &ow, &oh);
+  return ow == b->w && oh == b->h;
+}
+// one orient_kernel launch on the batch's stream: `count` pictures described by s (8-bit; deep: packed uint16 samples) into slots (deep slots) [first, first + count); o = 2..8
+static int batch_orient(mi_batch *b, int first, int count, const IngestSrc &s, int o, bool deep) {
+  const dim3 grid((b->w + MI_ORIENT_TILE - 1) / MI_ORIENT_TILE, (b->h + MI_ORIENT_TILE - 1) / MI_ORIENT_TILE, (unsigned)count), block(MI_ORIENT_THREADS);
+  if (deep) {
+    uint16_t *const slots = mi_batch_device_input16(b, first);
+    if (!slots) return MI_ENCODING_ERROR;
+    if (b->channels == 4) hipLaunchKernelGGL((orient_kernel<4, uint16_t>), grid, block, 0, b->stream, s, o, slots);
+    else hipLaunchKernelGGL((orient_kernel<3, uint16_t>), grid, block, 0, b->stream, s, o, slots);
+  } else {
+    uint8_t *const slots = mi_batch_device_input(b, first);
+    if (b->channels == 4) hipLaunchKernelGGL((orient_kernel<4, uint8_t>), grid, block, 0, b->stream, s, o, slots);
+    else hipLaunchKernelGGL((orient_kernel<3, uint8_t>), grid, block, 0, b->stream, s, o, slots);
+  }
+  HIP_OK(hipGetLastError());
+  return MI_OK;
+}
+// a decoded source at the start of the scratch, packed, `channels` channels of `sample_bytes`: what the two handle forms below turn
+static IngestSrc orient_scratch_source(const mi_batch *b, uint32_t w, uint32_t h, int channels, size_t sample_bytes) {
+  IngestSrc s = resample_scratch_source(b, w, h, channels);
+  s.inner_stride *= sample_bytes; s.row_stride *= sample_bytes; s.image_stride *= sample_bytes;
+  return s;
+}
+
+extern "C" {
+
+// images [first, first + count) from pictures in the memory of the batch's device, of the batch's size (orientations 1..4) or of h x w (5..8): one orient_kernel
+// launch on the batch's stream, after whatever src->after_stream holds at this moment; orientation 1: mi_batch_upload_device
+int mi_batch_orient_device(mi_batch *b, int first, int count, const mi_device_pixels *src, int orientation) {
+  if (!batch_range_ok(b, first, count) || orientation < 1 || orientation > 8) return MI_INVALID_ARGUMENT;
+  if (orientation == 1) return mi_batch_upload_device(b, first, count, src);
+  const bool turn = orientation_turns(orientation);
+  IngestSrc s;
+  if (!batch_device_source(b, src, turn ? b->h : b->w, turn ? b->w : b->h, s)) return MI_INVALID_ARGUMENT;
+  (void)hipSetDevice(b->device);
+  if (int st = batch_join(b, src->after_stream)) return st;
+  if (int st = batch_orient(b, first, count, s, orientation, false)) return st;
+  batch_tag(b, first, count, MI_INPUT_RGB);
+  return MI_OK;
+}
+
+// one parsed JPEG into slot `index`, turned by `orientation` (0: as the file's Exif segment says): decoded into the scratch as three channels (mi_batch_upload_jpeg's
+// kernels; ycbcr: jpeg_ycc_kernel, the slot is tagged MI_INPUT_YCBCR), then orient_kernel; orientation 1: mi_batch_upload_jpeg / _jpeg_ycbcr.  Every check comes first.
+int mi_batch_upload_jpeg_oriented(mi_batch *b, int index, const mi_jpeg_coeffs *c, int orientation, int ycbcr) {
+  if (!batch_index_ok(b, index) || !c || orientation < 0 || orientation > 8) return MI_INVALID_ARGUMENT;
+  const JpegCoeffs &jc = c->jc;
+  const int o = orientation ? orientation : jc.orientation;
+  const bool ycc = ycbcr != 0;
+  if (!batch_oriented_fits(b, jc.w, jc.h, o) || (ycc && !batch_takes_ycbcr(b))) return MI_INVALID_ARGUMENT;
+  if (o == 1) return batch_upload_jpeg(b, index, c, ycc);
+  if (ycc && jc.color == JPEG_RGB) return MI_UNSUPPORTED;
+  (void)hipSetDevice(b->device);
+  if (int st = batch_reserve_scratch(b, (size_t)jc.w * jc.h * 3)) return st;
+  if (int st = batch_jpeg_decode(b, jc, b->d_rs_scratch.get(), 3, jc.w, ycc)) return st;
+  if (int st = batch_orient(b, index, 1, orient_scratch_source(b, jc.w, jc.h, 3, 1), o, false)) return st;
+  batch_tag(b, index, 1, ycc ? MI_INPUT_YCBCR : MI_INPUT_RGB);
+  return MI_OK;
+}
+
+// one parsed PNG into slot `index`, turned by `orientation` (0: as the file's eXIf chunk says): unfiltered and expanded into the scratch (RGBA when the file has alpha
+// or tRNS, else RGB; deep: a file of bit depth 16 as uint16 samples, on its way to the deep slot, kind MI_INPUT_RGB16), then orient_kernel; orientation 1:
+// mi_batch_upload_png / _png_deep.  Every check comes first: a refused call allocates nothing.
+int mi_batch_upload_png_oriented(mi_batch *b, int index, const mi_png_scanlines *p, int orientation, int deep) {
+  if (!batch_index_ok(b, index) || !p || orientation < 0 || orientation > 8) return MI_INVALID_ARGUMENT;
+  const PngScanlines &sl = p->sl;
+  const int o = orientation ? orientation : sl.orientation, channels = sl.has_alpha() ? 4 : 3;
+  const bool goes_deep = deep && png_goes_deep(p);
+  if (!batch_oriented_fits(b, sl.w, sl.h, o) || channels > b->channels) return MI_INVALID_ARGUMENT;      // alpha is never dropped
+  if (goes_deep && !batch_takes_deep(b, channels)) return MI_INVALID_ARGUMENT;
+  if (o == 1) return batch_upload_png(b, index, 1, &p, deep != 0);
+  if (goes_deep && !batch_deep(b)) return MI_ENCODING_ERROR;
+  (void)hipSetDevice(b->device);
+  const size_t sample_bytes = goes_deep ? 2 : 1;
+  if (int st = batch_reserve_scratch(b, (size_t)sl.w * sl.h * channels * sample_bytes)) return st;
+  if (int st = batch_png_expand(b, 1, &p, sl.w, sl.h, channels, b->d_rs_scratch.get(), goes_deep)) return st;
+  if (int st = batch_orient(b, index, 1, orient_scratch_source(b, sl.w, sl.h, channels, sample_bytes), o, goes_deep)) return st;
+  batch_tag(b, index, 1, goes_deep ? MI_INPUT_RGB16 : MI_INPUT_RGB);
   return MI_OK;
 }
 

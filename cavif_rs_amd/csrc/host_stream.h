@@ -11,7 +11,7 @@
 #define MI_STREAM_FIRST_RUN_DEN 1         /* 0.09 s of tile search each against 0.10 for 32: worker phase 1.24 -> 1.20 s on 256 files, profiles/r05zk_e2e_knobs.txt matrix 6) */
 
 // ---- the kinds of source (MI_SOURCE_*), as data: the handle a kind carries, the upload call it takes, and whether the file's own colour description is
-// applied after the upload (the managed kinds).  A new kind is a row here, a case in StreamWorker::stage and, where its upload call refuses more, a line in source_refusal.
+// applied after the upload (the managed kinds); MI_SOURCE_ORIENTED is a modifier on them, below.  A new kind is a row here, a case in StreamWorker::stage and, where its upload call refuses more, a line in source_refusal.
 enum SourceHandle : uint8_t { HANDLE_NONE, HANDLE_JPEG, HANDLE_PNG };
 enum UploadRoute : uint8_t { ROUTE_HOST, ROUTE_JPEG, ROUTE_JPEG_YCBCR, ROUTE_PNG, ROUTE_PNG_DEEP };   // pinned copy + mi_batch_upload_async, mi_batch_upload_jpeg, _jpeg_ycbcr, _png, _png_deep
 struct SourceKind { SourceHandle handle; UploadRoute route; bool managed; };
@@ -27,7 +27,13 @@ static constexpr SourceKind SOURCE_KINDS[] = {
 };
 static_assert(sizeof(SOURCE_KINDS) / sizeof(SOURCE_KINDS[0]) == 8 && MI_SOURCE_HOST == 0 && MI_SOURCE_JPEG == 1 && MI_SOURCE_PNG == 2 && MI_SOURCE_JPEG_YCBCR == 3 && MI_SOURCE_PNG_DEEP == 4 &&
               MI_SOURCE_JPEG_MANAGED == 5 && MI_SOURCE_PNG_MANAGED == 6 && MI_SOURCE_PNG_DEEP_MANAGED == 7, "one row per MI_SOURCE_*, in the enum's order");
-static const SourceKind *source_kind(int kind) { return kind >= 0 && kind < 8 ? &SOURCE_KINDS[kind] : nullptr; }      // nullptr: no such kind
+// One modifier on the kinds that carry a handle, not eight more rows: MI_SOURCE_ORIENTED (0x100) ORed into kinds 1..7 -- the picture is turned as its file says on its
+// way into the slot (the _oriented upload of its route), and desc names the oriented picture.  The row is found by kind & 0xFF.
+static bool source_oriented(int kind) { return (kind & MI_SOURCE_ORIENTED) != 0; }
+static const SourceKind *source_kind(int kind) {                 // nullptr: no such kind (8..255, any other bit, the flag on host pixels)
+  const int row = kind & 0xFF;
+  return kind >= 0 && (kind & ~(0xFF | MI_SOURCE_ORIENTED)) == 0 && row < 8 && !(source_oriented(kind) && row == MI_SOURCE_HOST) ? &SOURCE_KINDS[row] : nullptr;
+}
 // the colour description of a managed source (icc_reader.h: the kind travels beside the bytes; a view into the source's handle)
 static ColourDescription source_colour_description(const mi_image_source &src) {
   if (source_kind(src.kind)->handle == HANDLE_JPEG) return colour_description_of_icc(src.jpeg->jc.icc.data(), src.jpeg->jc.icc.size());
@@ -39,8 +45,10 @@ static int source_refusal(const mi_ravif_encoder &e, const mi_image_source &src)
   const mi_image_desc &x = src.desc;
   const SourceKind *const kind = source_kind(src.kind);
   if (!kind) return MI_INVALID_ARGUMENT;
-  const bool have = kind->handle == HANDLE_NONE ? x.pixels != nullptr : kind->handle == HANDLE_JPEG ? src.jpeg && src.jpeg->jc.w == x.width && src.jpeg->jc.h == x.height :
-                    src.png && src.png->sl.w == x.width && src.png->sl.h == x.height && !(x.channels == 3 && src.png->sl.has_alpha());
+  // the size desc names is the file's, or with MI_SOURCE_ORIENTED that of the file turned as it asks
+  auto fits = [&](uint32_t w, uint32_t h, int orientation) { uint32_t ow, oh; oriented_size(w, h, source_oriented(src.kind) ? orientation : 1, &ow, &oh); return ow == x.width && oh == x.height; };
+  const bool have = kind->handle == HANDLE_NONE ? x.pixels != nullptr : kind->handle == HANDLE_JPEG ? src.jpeg && fits(src.jpeg->jc.w, src.jpeg->jc.h, src.jpeg->jc.orientation) :
+                    src.png && fits(src.png->sl.w, src.png->sl.h, src.png->sl.orientation) && !(x.channels == 3 && src.png->sl.has_alpha());
   if (!have || !x.width || !x.height || (x.channels != 3 && x.channels != 4)) return MI_INVALID_ARGUMENT;
   if (kind->route == ROUTE_JPEG_YCBCR && !batch_takes_ycbcr(e, x.channels)) return MI_INVALID_ARGUMENT;      // the batch's rule first, then the file's colour, as in mi_batch_upload_jpeg_ycbcr
   if (kind->route == ROUTE_JPEG_YCBCR && src.jpeg->jc.color == JPEG_RGB) return MI_UNSUPPORTED;
@@ -78,7 +86,7 @@ static constexpr int NSLOT_MAX = 4, NSLOT = MI_STREAM_SLOTS_DEFAULT;
 static size_t est_bytes(uint32_t w, uint32_t h, int ch, size_t images) { return images * (size_t)w * h * (ch == 4 ? 110 : 82) + ((size_t)32 << 20); }   // arena + records + staging per pixel (measured on the planner)
 // what a batch object adds at its first JPEG image: MI_BATCH_JPEG_STAGED images' coefficients (at most three full planes of int16) pinned and on the device, one image's planes
 static size_t est_jpeg_bytes(uint32_t w, uint32_t h) { return ((size_t)w + 15) * ((size_t)h + 15) * (2 * MI_BATCH_JPEG_STAGED * 6 + 3) + ((size_t)3 << 20); }
-struct Slot { mi_batch *b = nullptr; std::future<mi_batch *> making; std::vector<size_t> idx; bool busy = false, jpeg = false, deep = false; size_t bytes = 0, png_bytes = 0; };
+struct Slot { mi_batch *b = nullptr; std::future<mi_batch *> making; std::vector<size_t> idx; bool busy = false, jpeg = false, deep = false; size_t bytes = 0, png_bytes = 0, scratch_bytes = 0; };
 struct Shape { uint32_t w, h; int ch; size_t cap; Slot slot[NSLOT_MAX]; int next = 0; size_t runs = 0, last_use = 0; };
 struct Baked { ColourKey key; mi_colour_transform *t; };
 using Sources = std::vector<mi_image_source>;                    // the fetched sources of one claim
@@ -105,7 +113,7 @@ struct StreamWorker {
     return baked.back().t;
   }
   void charge(Slot &sl, size_t extra) { sl.bytes += extra; live_bytes += extra; }      // what a slot's object holds on the device and pinned counts against the worker's budget
-  void reset_accounting(Slot &sl) { live_bytes -= std::min(live_bytes, sl.bytes); sl.bytes = 0; sl.jpeg = false; sl.deep = false; sl.png_bytes = 0; }
+  void reset_accounting(Slot &sl) { live_bytes -= std::min(live_bytes, sl.bytes); sl.bytes = 0; sl.jpeg = false; sl.deep = false; sl.png_bytes = 0; sl.scratch_bytes = 0; }
   // finish the slot's run, if any (its files and statuses go to the caller), and take an object that is being made: sl.b is the slot's object afterwards, or null
   void settle(Slot &sl) {
     if (sl.busy) {
@@ -158,8 +166,11 @@ struct StreamWorker {
   // stretch never reaches across a JPEG or PNG image's slot: the pinned staging there is stale); then the conversions of the managed sources.
   int stage(const Shape &sh, Slot &sl, const Sources &d, const Run &run) {
     auto source = [&](size_t k) -> const mi_image_source & { return d[run[k]]; };
-    const int rc = for_each_group(run.size(), [&](size_t k) { return source_kind(source(k).kind)->route; }, [&](size_t from, size_t to) -> int {
+    // (an oriented source's picture is decoded into the batch's scratch first: one picture of the slot's size, two bytes a sample on the deep route, joins the worker's budget)
+    auto charge_scratch = [&](bool deep_route) { const size_t need = (size_t)sh.w * sh.h * 4 * (deep_route ? 2 : 1) + ((size_t)1 << 20); if (need > sl.scratch_bytes) { charge(sl, need - sl.scratch_bytes); sl.scratch_bytes = need; } };
+    const int rc = for_each_group(run.size(), [&](size_t k) { return (int)source_kind(source(k).kind)->route | (source(k).kind & MI_SOURCE_ORIENTED); }, [&](size_t from, size_t to) -> int {
       const UploadRoute route = source_kind(source(from).kind)->route;
+      const bool oriented = source_oriented(source(from).kind);
       switch (route) {
       case ROUTE_HOST: {                                         // every image into the pinned staging, then one H2D
         const size_t row = (size_t)sh.w * sh.ch;
@@ -175,8 +186,10 @@ struct StreamWorker {
       }
       case ROUTE_JPEG: case ROUTE_JPEG_YCBCR:                    // coefficients to the batch's own staging, decoded into the slot on the batch's stream
         if (!sl.jpeg) { sl.jpeg = true; charge(sl, est_jpeg_bytes(sh.w, sh.h)); }
+        if (oriented) charge_scratch(false);
         for (size_t k = from; k < to; k++)
-          if (const int st = route == ROUTE_JPEG_YCBCR ? mi_batch_upload_jpeg_ycbcr(sl.b, (int)k, source(k).jpeg) : mi_batch_upload_jpeg(sl.b, (int)k, source(k).jpeg)) return st;
+          if (const int st = oriented ? mi_batch_upload_jpeg_oriented(sl.b, (int)k, source(k).jpeg, 0, route == ROUTE_JPEG_YCBCR) :
+                             route == ROUTE_JPEG_YCBCR ? mi_batch_upload_jpeg_ycbcr(sl.b, (int)k, source(k).jpeg) : mi_batch_upload_jpeg(sl.b, (int)k, source(k).jpeg)) return st;
         return MI_OK;
       case ROUTE_PNG: case ROUTE_PNG_DEEP: {                     // one call (one H2D, one launch per kernel); what the batch's PNG staging holds, pinned and on the device, joins the worker's budget
         std::vector<const mi_png_scanlines *> pngs;
@@ -184,6 +197,11 @@ struct StreamWorker {
         const size_t extra = 2 * (png_call_bytes((int)pngs.size(), pngs.data()) + ((size_t)1 << 20));
         if (extra > sl.png_bytes) { charge(sl, extra - sl.png_bytes); sl.png_bytes = extra; }
         if (route == ROUTE_PNG_DEEP && !sl.deep) { sl.deep = true; charge(sl, sh.cap * (size_t)sh.w * sh.h * sh.ch * 2); }   // the deep slots join the worker's budget
+        if (oriented) {                                          // one file a call: each goes through the scratch
+          charge_scratch(route == ROUTE_PNG_DEEP);
+          for (size_t k = from; k < to; k++) if (const int st = mi_batch_upload_png_oriented(sl.b, (int)k, source(k).png, 0, route == ROUTE_PNG_DEEP)) return st;
+          return MI_OK;
+        }
         return route == ROUTE_PNG_DEEP ? mi_batch_upload_png_deep(sl.b, (int)from, (int)pngs.size(), pngs.data()) : mi_batch_upload_png(sl.b, (int)from, (int)pngs.size(), pngs.data());
       }
       }

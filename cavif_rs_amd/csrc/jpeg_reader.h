@@ -3,13 +3,15 @@
 // sequential, and progressive with spectral selection + successive approximation).  No pixel arithmetic: dequantisation, the inverse DCT, chroma
 // upsampling and the colour transform are the kernels of dev_jpeg.h.  Written from ITU-T T.81 (markers: annex B; Huffman tables: annex C; sequential
 // decoding: annex F.2; progressive: annex G.2) and the JFIF / Adobe APP14 conventions; the APP2 segments of an embedded ICC profile (ICC.1 annex B.4) are
-// joined and kept for colour-managed input, and change neither the coefficients nor the status of any file.
+// joined and kept for colour-managed input, the orientation of the first APP1 Exif segment (exif_reader.h) for the oriented uploads (5i); both
+// change neither the coefficients nor the status of any file.
 // Stricter than libjpeg where that is simpler: a stream that ends before every block of every scan is decoded, a file without EOI, a component no scan
 // covered and a progressive file whose scans leave a coefficient short of full precision are MI_ENCODING_ERROR -- nothing partial is ever decoded.
 #pragma once
 #include <cstdint>
 #include <cstring>
 #include <vector>
+#include "exif_reader.h"
 
 namespace mi {
 
@@ -31,6 +33,7 @@ struct JpegCoeffs {
   size_t nblocks = 0;
   std::vector<int16_t> coef;        // nblocks x 64, natural (de-zigzagged) order, component after component, row-major over each block grid
   std::vector<uint8_t> icc;         // the embedded ICC profile (APP2 "ICC_PROFILE\0" segments joined by sequence number), empty = none
+  int orientation = 1;              // what the first APP1 "Exif\0\0" segment says (exif_reader.h), 1 = nothing: kept for the oriented uploads, no pixel depends on it
 };
 
 // APP2 "ICC_PROFILE\0" + sequence number (1..count) + count + bytes: the segments of one file in any order.  finish() joins them; a missing or duplicate
@@ -142,7 +145,7 @@ inline int jpeg_read_coeffs(const uint8_t *d, size_t len, JpegCoeffs &out) {
   if (len < 2 || d[0] != 0xFF || d[1] != 0xD8) return 2;
   uint16_t qt[4][64]; bool have_qt[4] = { false, false, false, false };
   std::vector<JpegHuff> huff(8);                                 // 0-3 DC, 4-7 AC
-  bool jfif = false, adobe = false, have_frame = false, progressive = false, saw_eoi = false;
+  bool jfif = false, adobe = false, have_frame = false, progressive = false, saw_eoi = false, have_exif = false;
   int adobe_transform = 0;
   JpegIccParts icc_parts;
   uint32_t restart_interval = 0;
@@ -170,7 +173,9 @@ inline int jpeg_read_coeffs(const uint8_t *d, size_t len, JpegCoeffs &out) {
     if (m == 0xE0) { if (n >= 12 && !memcmp(seg, "JFIF\0", 5)) jfif = true; }
     else if (m == 0xEE) { if (n >= 12 && !memcmp(seg, "Adobe", 5)) { adobe = true; adobe_transform = seg[11]; } }
     else if (m == 0xE2) icc_parts.add(seg, n);                   // ICC profile segments: kept for mi_jpeg_coeffs_icc, nothing else reads them
-    else if ((m >= 0xE1 && m <= 0xEF) || m == 0xFE) {}           // other APPn, COM: skipped
+    else if (m == 0xE1) {                                        // the first Exif segment: its orientation is kept, nothing else of it (XMP is APP1 as well: skipped)
+      if (!have_exif && n >= 6 && !memcmp(seg, "Exif\0\0", 6)) { have_exif = true; out.orientation = exif_orientation(seg, n); }
+    } else if ((m >= 0xE3 && m <= 0xEF) || m == 0xFE) {}         // other APPn, COM: skipped
     else if (m == 0xDB) {                                        // DQT
       for (size_t i = 0; i < n;) {
         const int pq = seg[i] >> 4, tq = seg[i] & 15; i++;

@@ -1,6 +1,6 @@
 // mi_avif.hip -- the entry points of include/mi_avif.h: the batch's lifecycle and its encode (K0 front end, pack + D2H, AVIF containers, timing), its
 // pool, the one-call entry points and the level-1 plane encoder.  Every call through which pixels reach a slot or leave it (host, device,
-// JPEG, PNG, 16-bit, resize, decoded output) is host_input.h, included below the pool; the stream fan-out (source kinds, per-device worker, mi_ravif_encode_sources /
+// JPEG, PNG, 16-bit, resize, colour management, orientation, decoded output) is host_input.h, included below the pool; the stream fan-out (source kinds, per-device worker, mi_ravif_encode_sources /
 // _stream / _batch) is host_stream.h, included below the one-call entry points.  The frame chain they all run (plans, arena, K1 tile search, K2 deblock,
 // K3 CDEF, K5 restoration, K4 tile entropy coding, readback) is host_frames.h.  One HIP stream per batch, no hidden device syncs
 // other than the two points where the host needs device results (alpha flags, tile lengths).
@@ -28,6 +28,7 @@
 #include "dev_deep.h"
 #include "icc_reader.h"
 #include "dev_colour.h"
+#include "dev_orient.h"
 #include "host_frames.h"
 
 // The product library reads no environment variables; probe builds (tools/) get MI_AVIF_TIMING=1 (-DMI_TUNING_KNOBS: host-side timeline on stderr)

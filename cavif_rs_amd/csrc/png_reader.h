@@ -2,7 +2,7 @@
 // every load_image pixel kind to RGBA8: RGB -> alpha 255, 16-bit -> high byte, gray -> r=g=b).
 // Host C++ over zlib's inflate; written from the PNG specification (chunks IHDR / PLTE / tRNS / IDAT / IEND, the five
 // scanline filters, Adam7).  The colour chunks before IDAT (iCCP, sRGB, gAMA, cHRM) are kept beside the scanlines for colour-managed input and
-// change neither the pixels nor the status of any file.  JPEG bytes get MI_UNSUPPORTED here: the reference's other input format has its own reader
+// change neither the pixels nor the status of any file; so is the orientation of the eXIf chunk (exif_reader.h).  JPEG bytes get MI_UNSUPPORTED here: the reference's other input format has its own reader
 // (jpeg_reader.h + dev_jpeg.h), and mi_image_decode_rgba picks between the two.
 #pragma once
 #include <algorithm>
@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <cstring>
 #include <vector>
+#include "exif_reader.h"
 
 namespace mi {
 
@@ -58,6 +59,7 @@ struct PngScanlines {
   // after png_resolve_colour, which inflates it: a file that is never asked about its colour never pays for that.
   int colour = 0; std::vector<uint8_t> icc; bool icc_oversize = false; double file_gamma = 0.0; bool has_chrm = false; double chrm[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
   std::vector<uint8_t> iccp_body; bool has_srgb = false, colour_resolved = false;
+  int orientation = 1;                                                            // what the file's eXIf chunk says (exif_reader.h), 1 = nothing; nothing in the pixel path reads it
   bool has_alpha() const { return ctype == 4 || ctype == 6 || has_trns; }
 };
 
@@ -106,7 +108,7 @@ inline int png_read_scanlines(const uint8_t *d, size_t len, PngScanlines &sl) {
   if (len < 8 + 25 || memcmp(d, sig, 8) != 0) return 2;
   size_t pos = 8;
   uint32_t w = 0, h = 0;
-  int depth = 0, ctype = 0, interlace = 0; bool have_ihdr = false;
+  int depth = 0, ctype = 0, interlace = 0; bool have_ihdr = false, have_exif = false;
   std::vector<uint8_t> idat, plte, trns;
   while (pos + 12 <= len) {
     const uint32_t n = png_be32(d + pos); const uint8_t *type = d + pos + 4, *body = d + pos + 8;
@@ -121,7 +123,9 @@ inline int png_read_scanlines(const uint8_t *d, size_t len, PngScanlines &sl) {
     else if (!memcmp(type, "tRNS", 4)) trns.assign(body, body + n);
     else if (!memcmp(type, "IDAT", 4)) idat.insert(idat.end(), body, body + n);
     else if (!memcmp(type, "IEND", 4)) break;
-    else if (idat.empty()) {                                   // the colour chunks come before IDAT; a broken one counts as absent and never as an error of the picture
+    else if (!memcmp(type, "eXIf", 4)) {                       // allowed before and after IDAT; the first one whose CRC holds counts, a broken one counts as absent
+      if (have_ihdr && !have_exif && png_be32(body + n) == (uint32_t)crc32_z(0, type, 4 + (size_t)n)) { have_exif = true; sl.orientation = exif_orientation(body, n); }
+    } else if (idat.empty()) {                                  // the colour chunks come before IDAT; a broken one counts as absent and never as an error of the picture
       if (!memcmp(type, "iCCP", 4)) { if (sl.iccp_body.empty()) sl.iccp_body.assign(body, body + n); }
       else if (!memcmp(type, "sRGB", 4)) sl.has_srgb = sl.has_srgb || n == 1;
       else if (!memcmp(type, "gAMA", 4)) { if (n == 4 && png_be32(body) != 0) sl.file_gamma = (double)png_be32(body) / 100000.0; }

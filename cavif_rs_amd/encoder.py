@@ -190,6 +190,14 @@ def load_library():
     L.mi_png_scanlines_colour.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.mi_jpeg_coeffs_icc.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.mi_batch_convert_colour.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.mi_exif_orientation.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_int)]
+    L.mi_jpeg_coeffs_orientation.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    L.mi_png_scanlines_orientation.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    L.mi_oriented_size.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.mi_oriented_size.restype = None
+    L.mi_batch_orient_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(_DevicePixels), C.c_int]
+    L.mi_batch_upload_jpeg_oriented.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
+    L.mi_batch_upload_png_oriented.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
     _LIB = L
     return L
 
@@ -231,8 +239,35 @@ def _decode(fn, data, device):
     return a
 
 
+def exif_orientation(exif):
+    """mi_exif_orientation: the orientation (1..8) an Exif blob asks for, with or without its leading b'Exif\\0\\0'; 1 for anything that is not a well-formed
+    tag 0x0112 in IFD0 (never an error)"""
+    exif = bytes(exif)
+    o = C.c_int(1)
+    st = load_library().mi_exif_orientation(exif, len(exif), C.byref(o))
+    if st:
+        raise AvifError(st)
+    return o.value
+
+
+def oriented_size(width, height, orientation):
+    """mi_oriented_size: (width, height) of a picture turned by `orientation`: they change places for 5..8"""
+    w, h = C.c_uint32(), C.c_uint32()
+    load_library().mi_oriented_size(int(width), int(height), int(orientation), C.byref(w), C.byref(h))
+    return w.value, h.value
+
+
+def _handle_orientation(fn, handle):
+    o = C.c_int(1)
+    st = fn(handle, C.byref(o))
+    if st:
+        raise AvifError(st)
+    return o.value
+
+
 def decode_jpeg(data, device=0):
-    """mi_jpeg_decode_rgba: JPEG bytes -> uint8 array (h, w, 4); Huffman decoding on the host, the rest on HIP device `device`."""
+    """mi_jpeg_decode_rgba: JPEG bytes -> uint8 array (h, w, 4); Huffman decoding on the host, the rest on HIP device `device`.  The file's EXIF orientation is
+    ignored: the rows are the sensor's."""
     return _decode(load_library().mi_jpeg_decode_rgba, data, device)
 
 
@@ -243,7 +278,8 @@ def load_rgba(data, device=0):
 
 class JpegCoeffs:
     """One parsed JPEG file (mi_jpeg_parse): quantised coefficients in host memory, `width`, `height`, `color` ('grey', 'ycbcr' or 'rgb': what the file's
-    components are) and `subsampling` ((hsub, vsub): luma samples per chroma sample).  Feeds BatchEncoder.upload_jpeg and encode_many; its pixels come
+    components are), `subsampling` ((hsub, vsub): luma samples per chroma sample) and `orientation` (1..8: what the file's first Exif segment asks for, 1 when it
+    says nothing; width and height are the stored ones).  Feeds BatchEncoder.upload_jpeg and encode_many; its pixels come
     into being on the device.  close() (or the garbage collector) frees it."""
     COLORS = ('grey', 'ycbcr', 'rgb')
 
@@ -264,6 +300,7 @@ class JpegCoeffs:
         p, n = C.c_void_p(), C.c_size_t()
         L.mi_jpeg_coeffs_icc(self._h, C.byref(p), C.byref(n))
         self.icc_profile = C.string_at(p.value, n.value) if p.value and n.value else None   # the file's APP2 ICC profile, or None
+        self.orientation = _handle_orientation(L.mi_jpeg_coeffs_orientation, self._h)
 
     def close(self):
         if getattr(self, '_h', None):
@@ -284,7 +321,8 @@ def parse_jpeg(data):
 
 class PngScanlines:
     """One parsed PNG file (mi_png_parse): the inflated scanlines in host memory, `width`, `height`, `has_alpha` (an alpha channel or a tRNS chunk),
-    `color_type` and `bit_depth` of the file (bit depth 16 is what upload_png(deep=True) sends through the deep slots).  Feeds
+    `color_type` and `bit_depth` of the file (bit depth 16 is what upload_png(deep=True) sends through the deep slots), `orientation` (1..8: what the file's
+    first eXIf chunk asks for, 1 when it says nothing).  Feeds
     BatchEncoder.upload_png and encode_many; the filters are undone and the pixels made on the device.  close() (or the garbage collector) frees it."""
 
     def __init__(self, data):
@@ -304,6 +342,7 @@ class PngScanlines:
         what, p, n, g, chrm = C.c_int(), C.c_void_p(), C.c_size_t(), C.c_double(), (C.c_double * 8)()
         L.mi_png_scanlines_colour(self._h, C.byref(what), C.byref(p), C.byref(n), C.byref(g), chrm)
         self.colour = (None, ('icc', C.string_at(p.value, n.value) if p.value else None), ('srgb',), ('gamma', g.value, tuple(chrm) if any(chrm) else None))[what.value]
+        self.orientation = _handle_orientation(L.mi_png_scanlines_orientation, self._h)
 
     def close(self):
         if getattr(self, '_h', None):
@@ -409,6 +448,7 @@ def _is_device_array(x):
 
 DECODED_WHICH = {'recon': 0, 'source': 1}                   # MI_DECODED_*
 SOURCE_HOST, SOURCE_JPEG, SOURCE_PNG, SOURCE_JPEG_YCBCR, SOURCE_PNG_DEEP, SOURCE_JPEG_MANAGED, SOURCE_PNG_MANAGED, SOURCE_PNG_DEEP_MANAGED = range(8)   # MI_SOURCE_*: what mi_ravif_encode_sources takes
+SOURCE_ORIENTED = 0x100                                  # MI_SOURCE_ORIENTED: ORed into kinds 1..7, the picture is turned as its file asks and desc names the oriented size
 _SOURCE_HANDLE_FIELD = {SOURCE_HOST: None, SOURCE_JPEG: 'jpeg', SOURCE_PNG: 'png', SOURCE_JPEG_YCBCR: 'jpeg', SOURCE_PNG_DEEP: 'png',      # the field of mi_image_source that carries
                         SOURCE_JPEG_MANAGED: 'jpeg', SOURCE_PNG_MANAGED: 'png', SOURCE_PNG_DEEP_MANAGED: 'png'}                      # the kind's handle (None: host pixels in desc)
 
@@ -904,20 +944,22 @@ class Encoder:
                 l = mid + 1
         return TargetResult(done[h][0], done[h][1], h, reached, tried)      # h is hi or a mid that reached the target: always encoded
 
-    def encode_jpeg(self, coeffs_or_bytes, ycbcr=True):
+    def encode_jpeg(self, coeffs_or_bytes, ycbcr=True, oriented=False):
         """a JPEG file (bytes or a JpegCoeffs) as an opaque picture, decoded on the device.  ycbcr=True: the frame is coded from the file's own Y, Cb, Cr
         (mi_batch_upload_jpeg_ycbcr: no conversion to RGB and back; a file whose colour is RGB raises Unsupported); ycbcr=False: from the RGB pixels
-        decode_jpeg gives, the file of encode_rgb over them.  One source of kind SOURCE_JPEG_YCBCR or SOURCE_JPEG through mi_ravif_encode_sources (a 3-channel slot)."""
+        decode_jpeg gives, the file of encode_rgb over them.  One source of kind SOURCE_JPEG_YCBCR or SOURCE_JPEG through mi_ravif_encode_sources (a 3-channel slot).
+        oriented=True: the picture is turned on the device as the file's EXIF orientation asks (SOURCE_ORIENTED); a portrait photo comes out upright."""
         c = coeffs_or_bytes if isinstance(coeffs_or_bytes, JpegCoeffs) else JpegCoeffs(coeffs_or_bytes)
         if not c._h:
             raise AvifError(4)
-        return _encode_sources(self, [(SOURCE_JPEG_YCBCR if ycbcr else SOURCE_JPEG, c, 3)], None)[0]
+        return _encode_sources(self, [((SOURCE_JPEG_YCBCR if ycbcr else SOURCE_JPEG) | (SOURCE_ORIENTED if oriented else 0), c, 3)], None)[0]
 
-    def encode_managed(self, data_or_handle, deep=False):
+    def encode_managed(self, data_or_handle, deep=False, oriented=False):
         """a PNG or JPEG file (bytes, a PngScanlines or a JpegCoeffs) converted to sRGB by its own colour description -- an ICC profile, or gAMA with an
         optional cHRM -- on the device, then encoded: a one-image batch, uploaded as upload_png / upload_jpeg do, then convert_colour.  Opaque or with alpha
         by the file.  deep=True sends a 16-bit PNG through its deep slot (the alpha rules of deep input apply).  A file whose profile is unsupported or
-        malformed is encoded unmanaged (as the stream fan-out and cavif_mi --color-managed do); a file that says nothing, or sRGB, is encoded as it is."""
+        malformed is encoded unmanaged (as the stream fan-out and cavif_mi --color-managed do); a file that says nothing, or sRGB, is encoded as it is.
+        oriented=True: the picture is turned as the file's EXIF orientation asks on its way into the slot (upload_jpeg / upload_png_oriented with the file's own)."""
         src = data_or_handle
         if not isinstance(src, (PngScanlines, JpegCoeffs)):
             src = bytes(src)
@@ -930,12 +972,16 @@ class Encoder:
             if ex.code not in (2, 3):
                 raise
             t = None
-        b = BatchEncoder(self, 1, src.width, src.height, 4 if isinstance(src, PngScanlines) and src.has_alpha else 3)
+        w, h = oriented_size(src.width, src.height, src.orientation if oriented else 1)
+        b = BatchEncoder(self, 1, w, h, 4 if isinstance(src, PngScanlines) and src.has_alpha else 3)
         try:
             if isinstance(src, PngScanlines):
-                b.upload_png(0, src, deep=deep)
+                if oriented:
+                    b.upload_png_oriented(0, src, deep=deep)
+                else:
+                    b.upload_png(0, src, deep=deep)
             else:
-                b.upload_jpeg(0, src)
+                b.upload_jpeg(0, src, orientation=0 if oriented else None)
             if t is not None:
                 b.convert_colour(0, t)
             b.encode()
@@ -1017,7 +1063,7 @@ def _source_kind(handle, jpeg_ycbcr, png_deep, managed):
     return SOURCE_JPEG_YCBCR if jpeg_ycbcr and handle.color != 'rgb' else SOURCE_JPEG
 
 
-def encode_many(encoder, images, devices=None, jpeg_ycbcr=False, png_deep=False, managed=False):
+def encode_many(encoder, images, devices=None, jpeg_ycbcr=False, png_deep=False, managed=False, oriented=False):
     """mi_ravif_encode_sources: the reference's files.into_par_iter() (src/main.rs:223) over the node's GPUs.
     images: list of HxWx3 / HxWx4 uint8 arrays (shapes may differ), JpegCoeffs objects (parse_jpeg; encoded as the RGBA pictures decode_jpeg
     gives, decoded on the device) and PngScanlines objects (parse_png; encoded as the RGBA pictures load_rgba gives, unfiltered and expanded on the
@@ -1026,13 +1072,15 @@ def encode_many(encoder, images, devices=None, jpeg_ycbcr=False, png_deep=False,
     managed=True: a parsed file is converted to sRGB by its own colour description after its upload (the source kinds SOURCE_*_MANAGED); a file whose
     profile is unsupported or malformed is coded unmanaged and raises nothing.  With jpeg_ycbcr, a JPEG whose profile gives a usable transform that is not
     the identity goes the RGB way (the conversion needs RGB), every other one keeps its YCbCr: cavif_mi's rule.  Host arrays are never converted.
+    oriented=True: a parsed file is turned on the device as its EXIF orientation asks (SOURCE_ORIENTED) and grouped into runs by its oriented shape; host arrays are
+    taken as they are.
     Returns a list of EncodedImage."""
     items = []
     for im in images:
         if isinstance(im, (JpegCoeffs, PngScanlines)):
             if not im._h:
                 raise AvifError(4)
-            items.append((_source_kind(im, jpeg_ycbcr, png_deep, managed), im, 4))
+            items.append((_source_kind(im, jpeg_ycbcr, png_deep, managed) | (SOURCE_ORIENTED if oriented else 0), im, 4))
             continue
         if _is_device_array(im):
             raise TypeError('encode_many takes host arrays, JpegCoeffs and PngScanlines; pixels in device memory go through BatchEncoder.upload_device')
@@ -1045,16 +1093,17 @@ def encode_many(encoder, images, devices=None, jpeg_ycbcr=False, png_deep=False,
 
 def _encode_sources(encoder, items, devices):
     """mi_ravif_encode_sources over (kind, object, channels of the slot) triples: SOURCE_HOST a contiguous uint8 array, SOURCE_JPEG / _JPEG_YCBCR a JpegCoeffs,
-    SOURCE_PNG / _PNG_DEEP a PngScanlines"""
+    SOURCE_PNG / _PNG_DEEP a PngScanlines; with SOURCE_ORIENTED desc names the oriented size"""
     L = load_library()
 
     def fetch(_user, i, src):
         (kind, it, channels), s = items[i], src.contents
         s.kind, s.jpeg, s.png = kind, None, None
-        field = _SOURCE_HANDLE_FIELD[kind]
+        field = _SOURCE_HANDLE_FIELD[kind & 0xFF]
         if field:
             setattr(s, field, it._h)
-            s.desc.pixels, s.desc.width, s.desc.height, s.desc.stride_px, s.desc.channels = None, it.width, it.height, it.width, channels
+            w, h = oriented_size(it.width, it.height, it.orientation if kind & SOURCE_ORIENTED else 1)
+            s.desc.pixels, s.desc.width, s.desc.height, s.desc.stride_px, s.desc.channels = None, w, h, w, channels
         else:
             s.desc.pixels, s.desc.width, s.desc.height, s.desc.stride_px, s.desc.channels = it.ctypes.data, it.shape[1], it.shape[0], it.shape[1], channels
         return 0
@@ -1116,12 +1165,17 @@ class BatchEncoder:
             raise AvifError(st)
         self._sources.append(pixels)
 
-    def upload_jpeg(self, index, coeffs, ycbcr=False):
+    def upload_jpeg(self, index, coeffs, ycbcr=False, orientation=None):
         """one parsed JPEG (parse_jpeg) of the batch's size into slot `index`: dequantisation, IDCT, upsampling and colour run on the batch's stream.
-        ycbcr=True: no colour step, the slot holds the file's own (Y, Cb, Cr) and is of input kind 1 (a file whose colour is RGB raises Unsupported)"""
+        ycbcr=True: no colour step, the slot holds the file's own (Y, Cb, Cr) and is of input kind 1 (a file whose colour is RGB raises Unsupported).
+        orientation (None: the file's is ignored): 1..8, or 0 for the file's own -- the picture is turned on the device (mi_batch_upload_jpeg_oriented) and it is
+        the turned picture that has the batch's size"""
         if not isinstance(coeffs, JpegCoeffs) or not coeffs._h:
             raise AvifError(4)
-        st = (self._L.mi_batch_upload_jpeg_ycbcr if ycbcr else self._L.mi_batch_upload_jpeg)(self._h, index, coeffs._h)
+        if orientation is not None:
+            st = self._L.mi_batch_upload_jpeg_oriented(self._h, index, coeffs._h, int(orientation), int(bool(ycbcr)))
+        else:
+            st = (self._L.mi_batch_upload_jpeg_ycbcr if ycbcr else self._L.mi_batch_upload_jpeg)(self._h, index, coeffs._h)
         if st:
             raise AvifError(st)
 
@@ -1163,6 +1217,26 @@ class BatchEncoder:
         st = (self._L.mi_batch_upload_png_deep if deep else self._L.mi_batch_upload_png)(self._h, first, len(handles), arr)
         if st:
             raise AvifError(st)
+
+    def upload_png_oriented(self, index, handle, orientation=0, deep=False):
+        """one parsed PNG into slot `index`, turned on the device by `orientation` (1..8, or 0: what the file's eXIf chunk asks for); the turned picture has the
+        batch's size.  deep=True: a file of bit depth 16 goes into its deep slot (input kind 2)"""
+        if not isinstance(handle, PngScanlines) or not handle._h:
+            raise AvifError(4)
+        st = self._L.mi_batch_upload_png_oriented(self._h, index, handle._h, int(orientation), int(bool(deep)))
+        if st:
+            raise AvifError(st)
+
+    def orient_device(self, first, pixels, orientation):
+        """upload_device for uint8 pictures that are turned by `orientation` (1..8) on their way into the slots: the array holds pictures of the batch's size
+        (1..4) or of h x w (5..8)"""
+        d, n, h, w, _ = _device_pixels(pixels, batched=True)
+        if oriented_size(w, h, orientation) != (self.w, self.h):
+            raise AvifError(4)
+        st = self._L.mi_batch_orient_device(self._h, first, n, C.byref(d), int(orientation))
+        if st:
+            raise AvifError(st)
+        self._sources.append(pixels)
 
     def convert_colour(self, first, transform, count=1):
         """mi_batch_convert_colour: the colour channels of slots first.. through a ColourTransform, in place, on the batch's stream after the uploads that filled

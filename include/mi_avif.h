@@ -121,10 +121,15 @@ int  mi_ravif_encode_stream(const mi_ravif_encoder *e, size_t n, mi_fetch_fn fet
  * colour description -- a JPEG's APP2 profile; a PNG's iCCP profile, else gAMA with an optional cHRM -- applied to the slot after the upload
  * (mi_batch_convert_colour below).  A file that says nothing or sRGB, and a file whose profile is unsupported or malformed, is encoded unmanaged with status MI_OK.
  * A worker bakes one transform per distinct description (cached by the description's bytes: hash, then compare); neighbours of a run that share it share a launch.
+ * MI_SOURCE_ORIENTED (0x100), ORed into kinds 1 to 7: the picture is turned as its file's EXIF orientation asks on its way into the slot (the _oriented upload of
+ * its kind below; for the managed kinds the conversion follows as before: a permutation of pixels and a map of each pixel commute).  desc.width / height then name the
+ * ORIENTED picture -- mi_oriented_size of the file's size and mi_jpeg_coeffs_orientation / mi_png_scanlines_orientation -- and runs are grouped by that shape; a source
+ * whose oriented size differs from them is MI_INVALID_ARGUMENT, for that image alone.  So is a kind of 8..255, any other bit, and the flag on kind 0.
  * mi_ravif_encode_stream is this call with MI_SOURCE_HOST throughout.  Pictures in device memory are not a kind here (a pointer belongs to one
  * device, the shared cursor hands images to any): they enter through mi_ravif_encode_device and mi_batch_upload_device. */
 enum { MI_SOURCE_HOST = 0, MI_SOURCE_JPEG = 1, MI_SOURCE_PNG = 2, MI_SOURCE_JPEG_YCBCR = 3, MI_SOURCE_PNG_DEEP = 4,
-       MI_SOURCE_JPEG_MANAGED = 5, MI_SOURCE_PNG_MANAGED = 6, MI_SOURCE_PNG_DEEP_MANAGED = 7 };
+       MI_SOURCE_JPEG_MANAGED = 5, MI_SOURCE_PNG_MANAGED = 6, MI_SOURCE_PNG_DEEP_MANAGED = 7,
+       MI_SOURCE_ORIENTED = 0x100 /* a modifier, ORed into kinds 1 to 7 */ };
 typedef struct mi_jpeg_coeffs mi_jpeg_coeffs;   /* opaque: one parsed file, host memory only */
 typedef struct mi_png_scanlines mi_png_scanlines;      /* opaque: one inflated file, host memory only */
 typedef struct mi_image_source {
@@ -188,7 +193,8 @@ void mi_png_scanlines_free(mi_png_scanlines *p);
  * Baseline / extended sequential and progressive Huffman files, 8 bit, one component or three at 4:4:4 / 4:2:2 / 4:2:0; arithmetic coding, lossless,
  * hierarchical, 12-bit, four-component files and other sampling ratios are MI_UNSUPPORTED, broken or incomplete streams MI_ENCODING_ERROR.  Huffman
  * decoding runs on the host, dequantisation + IDCT + chroma upsampling + YCbCr->RGB on HIP device `device`; the pixels are libjpeg's (integer "islow"
- * IDCT, "fancy" upsampling), embedded ICC profiles and EXIF orientation are ignored.  Data errors are reported before the device is looked at, then
+ * IDCT, "fancy" upsampling), embedded ICC profiles and EXIF orientation are ignored (this call still hands out the sensor's rows: orientation is applied by the
+ * oriented uploads below and by nothing else).  Data errors are reported before the device is looked at, then
  * MI_NO_DEVICE when there is no such device: no CPU fallback.  *rgba is malloc'd (mi_free), w*h*4 bytes.  Calls from many threads share a pool of at most 8
  * decode contexts per device (stream + staging; a call that finds all of them busy waits for one) that mi_release_cached() frees. */
 int  mi_jpeg_decode_rgba(const uint8_t *data, size_t len, int device, uint8_t **rgba, uint32_t *w, uint32_t *h);
@@ -359,6 +365,39 @@ size_t mi_colour_transform_table(const mi_colour_transform *t, int which, const 
 int  mi_png_scanlines_colour(const mi_png_scanlines *p, int *what, const uint8_t **icc, size_t *icc_len, double *file_gamma, double chrm8[8]);
 int  mi_jpeg_coeffs_icc(const mi_jpeg_coeffs *c, const uint8_t **icc, size_t *len);
 int  mi_batch_convert_colour(mi_batch *b, int first, int count, mi_colour_transform *t);
+/* ---- EXIF orientation on input (opt-in: without these calls, MI_SOURCE_ORIENTED or their arguments every slot holds the bytes it held before, and a file's
+ * orientation is ignored as it always was).  A camera file stores the sensor's rows and says in EXIF tag 0x0112 how to turn them for display; these calls turn the
+ * pixels on the device on their way into the slot, so the file that is written needs no irot / imir.  With S[row][column] a source of sw x sh and D[y][x] the slot:
+ *   1  D[y][x] = S[y][x]                 slot sw x sh          5  D[y][x] = S[x][y]                 slot sh x sw
+ *   2  D[y][x] = S[y][sw-1-x]            slot sw x sh          6  D[y][x] = S[sh-1-x][y]            slot sh x sw
+ *   3  D[y][x] = S[sh-1-y][sw-1-x]       slot sw x sh          7  D[y][x] = S[sh-1-x][sw-1-y]       slot sh x sw
+ *   4  D[y][x] = S[sh-1-y][x]            slot sw x sh          8  D[y][x] = S[x][sw-1-y]            slot sh x sw
+ * (what Pillow's ImageOps.exif_transpose gives): a permutation of pixels, so the slot's bytes are specified exactly.
+ * mi_exif_orientation: the orientation of an Exif blob, with or without a leading "Exif\0\0": TIFF header ("II*\0" or "MM\0*"), IFD0's entries only, tag 0x0112 of
+ * type SHORT and count 1 with a value of 1..8; anything else -- no tag, another type or count, 0, 9 and above, a truncated blob, an offset or an entry count that
+ * leaves the blob -- is 1.  Always MI_OK for non-null pointers: a file's orientation never makes the picture an error.  Never reads outside [exif, exif + len).
+ * mi_jpeg_coeffs_orientation: that of the first APP1 segment of a parsed JPEG that starts with "Exif\0\0"; mi_png_scanlines_orientation: that of the first eXIf chunk
+ * of a parsed PNG whose CRC holds (before or after IDAT); 1 when the file says nothing.  mi_oriented_size: width and height change places for 5..8 (either pointer may be NULL).
+ * mi_batch_orient_device: mi_batch_upload_device (source description, after_stream, ordering, lifetimes) for pictures of the batch's size (orientations 1..4) or of
+ * h x w (5..8), turned by `orientation` (1..8): one launch for all images of the call; 3 channels into an RGBA batch get alpha 255; kind MI_INPUT_RGB.
+ * mi_batch_upload_jpeg_oriented: one parsed JPEG into slot `index`, turned by `orientation` (1..8, or 0: the file's own); ycbcr != 0: the file's own (Y, Cb, Cr) as
+ * mi_batch_upload_jpeg_ycbcr stores them (kind MI_INPUT_YCBCR, that call's refusals), else mi_batch_upload_jpeg's pixels (kind MI_INPUT_RGB).
+ * mi_batch_upload_png_oriented: one parsed PNG likewise; deep != 0: a file of bit depth 16 goes into its deep slot as through mi_batch_upload_png_deep (kind
+ * MI_INPUT_RGB16, the alpha rules of deep input), every other file as through mi_batch_upload_png.  A file with an alpha channel or tRNS into a 3-channel batch is refused.
+ * The two handle calls decode the file into a device scratch of the batch (grown on demand, shared with the resize calls) and turn it into the slot from there, all on
+ * the batch's stream, no sync; the handle may be freed when the call returns.  Orientation 1 -- given, or read from the file -- takes the plain upload call of its kind,
+ * gives that call's bytes and touches no scratch.  The slot bytes of every other orientation are the plain call's bytes permuted by the map above.
+ * MI_INVALID_ARGUMENT: an orientation outside the call's range, a source whose oriented size is not the batch's, a range past the capacity, null pointers, 4 channels
+ * into a 3-channel batch, a refusal of the kind, a call between mi_batch_encode_async and mi_batch_wait; a refused call allocates nothing (mi_batch_footprint).
+ * MI_ENCODING_ERROR when staging or scratch cannot be allocated.  Orientation together with resize, the YCbCr planes of mi_batch_upload_device_ycbcr and
+ * mi_batch_upload_device16 are not built; an Exif blob passed through mi_ravif_encoder's exif field is written as it is and should not still carry an orientation other than 1. */
+int  mi_exif_orientation(const uint8_t *exif, size_t len, int *orientation);
+int  mi_jpeg_coeffs_orientation(const mi_jpeg_coeffs *c, int *orientation);
+int  mi_png_scanlines_orientation(const mi_png_scanlines *p, int *orientation);
+void mi_oriented_size(uint32_t w, uint32_t h, int orientation, uint32_t *ow, uint32_t *oh);
+int  mi_batch_orient_device(mi_batch *b, int first, int count, const mi_device_pixels *src, int orientation);
+int  mi_batch_upload_jpeg_oriented(mi_batch *b, int index, const mi_jpeg_coeffs *c, int orientation, int ycbcr);
+int  mi_batch_upload_png_oriented(mi_batch *b, int index, const mi_png_scanlines *p, int orientation, int deep);
 /* resize on input: the source has any size and is resampled into the slot on the batch's stream, no sync.  The pixels are exactly those of Pillow's
  * Image.resize((w, h), resample=filter, reducing_gap=None) on 8-bit pictures: coefficients in double on the host, 22-bit fixed-point taps, horizontal pass
  * first into an 8-bit intermediate, then the vertical one, a pass whose axis keeps its length skipped; 4-channel sources are premultiplied before the passes and
