@@ -9,6 +9,7 @@
 //                          specified exactly, in integers (include/mi_avif.h): BT.601 with Kr = 0.299, Kb = 0.114 rounded half up, or G, B, R.  Dividends
 //                          stay below 2^38 and every divisor is a compile-time constant: the divisions are multiply-high sequences.  A lane reads its pixel
 //                          with one 8-byte load (RGBA) or three halfword loads (RGB): a wavefront reads one contiguous run of 512 / 384 bytes of a slot row.
+//                          The same kernel reads a slot of kind MI_INPUT_YCBCR16: a scale per sample in place of the matrix.
 // No LDS, no scratch in any of them.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -114,8 +115,16 @@ template <int DC> __global__ void __launch_bounds__(64) png_expand16_kernel(cons
 //   RGB (planes G, B, R) and alpha:  p = floor((2 peak v + M) / (2 M))
 // half is folded into the chroma dividends (half * 3544 M, half * 2804 M): they run from 2 * 1772 M (2 * 1402 M) to 2^(bd+1) * 1772 M < 2^38, so the quotient
 // lies in [1, 2^bd] and only the upper clamp can act.
-struct FrontDeepParams { int depth, color_model; };
+// A slot of kind MI_INPUT_YCBCR16 (fp.ycc; filled by planes_ingest16_kernel, dev_planes.h) holds canonical (Y, Cb, Cr[, 65535]): no matrix,
+//   p0 = deep_scale(Y),  p_k = clamp(half + floor((2 peak (C_k - 32768) + M) / (2 M)), 0, peak)
+// with half and the centre folded into the dividend (half * 2 M - 65536 peak + M = 130815 at depth 8, 130047 at depth 10: positive, so only the upper clamp can
+// act).  Such an image is opaque: its fourth sample is not looked at, its alpha plane is peak and the flag stays 0.
+struct FrontDeepParams { int depth, color_model, ycc; };
 __device__ __forceinline__ uint32_t deep_scale(const uint32_t v, const uint32_t peak) { return (2u * peak * v + 65535u) / (2u * 65535u); }
+__device__ __forceinline__ uint32_t deep_scale_chroma(const uint32_t c, const uint32_t peak, const uint32_t half) {
+  const uint32_t q = (2u * peak * c + (half * (2u * 65535u) - 65536u * peak + 65535u)) / (2u * 65535u);
+  return q < peak ? q : peak;
+}
 template <int DC> __global__ __launch_bounds__(256) void frontend_deep_kernel(const uint16_t *pix, int w, int h, FrontDeepParams fp,
                                                                               uint16_t *p0, uint16_t *p1, uint16_t *p2, uint16_t *pa, int pw, int ph, int *alpha_flag) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
@@ -127,7 +136,8 @@ template <int DC> __global__ __launch_bounds__(256) void frontend_deep_kernel(co
   else { R = p[0]; G = p[1]; B = p[2]; }
   const uint32_t peak = (1u << fp.depth) - 1u, half = 1u << (fp.depth - 1);
   uint32_t o0, o1, o2;
-  if (fp.color_model == 1) { o0 = deep_scale(G, peak); o1 = deep_scale(B, peak); o2 = deep_scale(R, peak); }
+  if (fp.ycc) { o0 = deep_scale(R, peak); o1 = deep_scale_chroma(G, peak, half); o2 = deep_scale_chroma(B, peak, half); A = 65535u; }
+  else if (fp.color_model == 1) { o0 = deep_scale(G, peak); o1 = deep_scale(B, peak); o2 = deep_scale(R, peak); }
   else {
     constexpr long long M = 65535;
     const long long S = 299ll * R + 587ll * G + 114ll * B, k = 2ll * peak;

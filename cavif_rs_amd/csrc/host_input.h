@@ -120,12 +120,12 @@ int mi_batch_upload_async(mi_batch *b, int first, int count) {
   return MI_OK;
 }
 int mi_batch_set_input_kind(mi_batch *b, int first, int count, int kind) {
-  if (!batch_range_ok(b, first, count) || (kind != MI_INPUT_RGB && kind != MI_INPUT_YCBCR && kind != MI_INPUT_RGB16)) return MI_INVALID_ARGUMENT;
-  if (kind == MI_INPUT_YCBCR && !batch_takes_ycbcr(b)) return MI_INVALID_ARGUMENT;
-  // kind 2 tags what a HIP caller wrote through mi_batch_device_input16, the call that makes the deep slots: a batch without them has nothing to tag (and the
-  // set call allocates nothing); the slot may hold any alpha
-  if (kind == MI_INPUT_RGB16) {
-    if (!batch_takes_deep(b, b->channels)) return MI_INVALID_ARGUMENT;
+  if (!batch_range_ok(b, first, count) || kind < MI_INPUT_RGB || kind > MI_INPUT_YCBCR16) return MI_INVALID_ARGUMENT;
+  if ((kind == MI_INPUT_YCBCR || kind == MI_INPUT_YCBCR16) && !batch_takes_ycbcr(b)) return MI_INVALID_ARGUMENT;
+  // kinds 2 and 3 tag what a HIP caller wrote through mi_batch_device_input16, the call that makes the deep slots: a batch without them has nothing to tag (and
+  // the set call allocates nothing); a slot of kind 2 may hold any alpha, one of kind 3 is opaque whatever its fourth sample holds
+  if (kind == MI_INPUT_RGB16 || kind == MI_INPUT_YCBCR16) {
+    if (kind == MI_INPUT_RGB16 && !batch_takes_deep(b, b->channels)) return MI_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lk(b->staging_mu);
     if (!b->d_pixels16.get()) return MI_INVALID_ARGUMENT;
   }
@@ -411,6 +411,48 @@ int mi_batch_upload16(mi_batch *b, int index, const uint16_t *pixels, size_t str
     HIP_OK(hipStreamSynchronize(b->stream));
   } catch (const std::exception &) { return MI_ENCODING_ERROR; }
   batch_tag(b, index, 1, MI_INPUT_RGB16);
+  return MI_OK;
+}
+
+// ---- deep YCbCr planes (dev_planes.h) ----
+// the multiply-high form of one sample map of include/mi_avif.h for planes_ingest16_kernel: W = clamp(floor((65535 v + bias) / d), 0, 65535), where
+// full range has d = P = 2^bits - 1 and the rounding term (P - 1) / 2, narrow range d = 219 s (luma) | 224 s (chroma), s = 2^(bits - 8), and the rounding term
+// floor(d / 2); the dividend starts at -65535 * (0 | 2^(bits-1) | 16 s | 128 s) and chroma adds the centre, 32768 d.  |bias| stays below 2^29.
+static SampleMap16 make_sample_map16(int bits, bool chroma, bool narrow) {
+  const long long M = 65535, P = (1ll << bits) - 1, s = 1ll << (bits - 8);
+  const long long d = narrow ? (chroma ? 224 : 219) * s : P;
+  const long long zero = narrow ? (chroma ? 128 : 16) * s : chroma ? 1ll << (bits - 1) : 0;
+  const long long bias = -M * zero + (narrow ? d / 2 : (P - 1) / 2) + (chroma ? 32768 * d : 0);
+  uint32_t shift = 0;
+  while ((2ll << shift) <= d) shift++;                          // floor(log2 d); d is no power of two, so the magic number fits 32 bits
+  return SampleMap16{ (uint32_t)(((1ull << (32 + shift)) / (unsigned long long)d) + 1), (int32_t)bias, shift };
+}
+// images [first, first + count) from uint16 YCbCr planes in the memory of the batch's device: one planes_ingest16_kernel launch on the batch's stream, after
+// whatever src->after_stream holds at this moment; the slots are tagged MI_INPUT_YCBCR16.  Strides of 0 mean packed.  Every check comes before the deep slots
+// are made: a refused call allocates nothing.
+int mi_batch_upload_device_ycbcr16(mi_batch *b, int first, int count, const mi_device_planes16 *src) {
+  if (!batch_range_ok(b, first, count) || !src || !src->y || !src->cb || !batch_takes_ycbcr(b)) return MI_INVALID_ARGUMENT;
+  if (!((src->hsub == 1 && src->vsub == 1) || (src->hsub == 2 && (src->vsub == 1 || src->vsub == 2)))) return MI_INVALID_ARGUMENT;
+  if (src->bits < 8 || src->bits > 16 || (src->msb_aligned != 0 && src->msb_aligned != 1) || (src->narrow_range != 0 && src->narrow_range != 1)) return MI_INVALID_ARGUMENT;
+  if (((uintptr_t)src->y | (uintptr_t)src->cb | (uintptr_t)src->cr | src->y_row_stride | src->c_row_stride | src->y_image_stride | src->c_image_stride) & 1) return MI_INVALID_ARGUMENT;   // uint16 samples
+  Planes16Src s;
+  s.w = b->w; s.h = b->h; s.hsub = (uint32_t)src->hsub; s.vsub = (uint32_t)src->vsub;
+  s.cw = (b->w + s.hsub - 1) / s.hsub; s.ch = (b->h + s.vsub - 1) / s.vsub;
+  s.pairs = src->cr ? 0 : 1;
+  s.y = (const uint8_t *)src->y; s.cb = (const uint8_t *)src->cb; s.cr = src->cr ? (const uint8_t *)src->cr : s.cb;
+  const size_t packed_y = (size_t)b->w * 2, packed_c = (size_t)s.cw * (s.pairs ? 4 : 2);
+  s.y_row = src->y_row_stride ? src->y_row_stride : packed_y; s.c_row = src->c_row_stride ? src->c_row_stride : packed_c;
+  s.y_image = src->y_image_stride ? src->y_image_stride : s.y_row * b->h; s.c_image = src->c_image_stride ? src->c_image_stride : s.c_row * s.ch;
+  if (s.y_row < packed_y || s.c_row < packed_c) return MI_INVALID_ARGUMENT;
+  s.down = src->msb_aligned ? (uint32_t)(16 - src->bits) : 0u; s.mask = (1u << src->bits) - 1u;
+  s.ym = make_sample_map16(src->bits, false, src->narrow_range != 0); s.cm = make_sample_map16(src->bits, true, src->narrow_range != 0);
+  uint16_t *const slots = mi_batch_device_input16(b, first);
+  if (!slots) return MI_ENCODING_ERROR;
+  (void)hipSetDevice(b->device);
+  if (int st = batch_join(b, src->after_stream)) return st;
+  LAUNCH_BY_CHANNELS(b, b->channels, b->w, b->h, count, planes_ingest16_kernel, s, slots);
+  HIP_OK(hipGetLastError());
+  batch_tag(b, first, count, MI_INPUT_YCBCR16);
   return MI_OK;
 }
 

@@ -75,10 +75,10 @@ struct mi_batch {
   PinBuf<QualityRec> h_quality; size_t h_quality_bytes = 0;
   // decoded pixels (mi_batch_decode): one image of w*h*4 bytes on the device, made by the first call that decodes into host memory
   DevBuf<uint8_t> d_decoded; size_t d_decoded_cap = 0;
-  // what the bytes of each input slot mean (MI_INPUT_RGB / MI_INPUT_YCBCR): host state, set by whichever call last filled the slot, kept across encodes and
-  // mi_batch_set_count like the slot's contents
+  // what the samples of each input slot mean (MI_INPUT_RGB / _YCBCR in the 8-bit slots, MI_INPUT_RGB16 / _YCBCR16 in the deep ones): host state, set by
+  // whichever call last filled the slot, kept across encodes and mi_batch_set_count like the slot's contents
   std::vector<uint8_t> kinds;
-  // deep input: the slots of kind MI_INPUT_RGB16, cap * w*h*channels uint16 samples laid out like d_pixels; made by the first call that needs
+  // deep input: the slots of kinds MI_INPUT_RGB16 and MI_INPUT_YCBCR16, cap * w*h*channels uint16 samples laid out like d_pixels; made by the first call that needs
   // them (under staging_mu), never by a batch that sees no 16-bit source
   DevBuf<uint16_t> d_pixels16; size_t deep_bytes = 0;
 };
@@ -240,11 +240,11 @@ int mi_batch_encode_async(mi_batch *b) {
   for (int i = 0; i < b->n; i++) {
     FramePlan &p = b->fs.frames[i];
     uint16_t *alpha_stage = b->channels == 4 ? p.dev.fin[0] : nullptr;      // fin[0] is free until CDEF runs
-    if (b->kinds[i] == MI_INPUT_RGB16) {                        // its deep slot, through the 16-bit front end
+    if (b->kinds[i] == MI_INPUT_RGB16 || b->kinds[i] == MI_INPUT_YCBCR16) {   // its deep slot, through the 16-bit front end (kind 3: canonical YCbCr, no matrix)
       const uint16_t *deep = b->d_pixels16.get();
       if (!deep) return MI_INVALID_ARGUMENT;
       deep += (size_t)i * b->w * b->h * b->channels;
-      const FrontDeepParams dp{ b->depth, b->enc.color_model };
+      const FrontDeepParams dp{ b->depth, b->enc.color_model, b->kinds[i] == MI_INPUT_YCBCR16 };
       if (b->channels == 4) hipLaunchKernelGGL((frontend_deep_kernel<4>), dim3((p.pw + 255) / 256, p.ph), dim3(256), 0, s, deep, (int)b->w, (int)b->h, dp,
                                                p.dev.src[0], p.dev.src[1], p.dev.src[2], alpha_stage, p.pw, p.ph, d_alpha_flags + i);
       else hipLaunchKernelGGL((frontend_deep_kernel<3>), dim3((p.pw + 255) / 256, p.ph), dim3(256), 0, s, deep, (int)b->w, (int)b->h, dp,
@@ -520,6 +520,11 @@ int mi_ravif_encode_device16(const mi_ravif_encoder *e, const mi_device_pixels16
 int mi_ravif_encode_device_ycbcr(const mi_ravif_encoder *e, const mi_device_planes *src, uint32_t w, uint32_t h, mi_encoded_image *out) {
   if (!src || !src->y || !src->cb) return MI_INVALID_ARGUMENT;
   return encode_pooled(e, w, h, 3, out, [&](mi_batch *b) { return mi_batch_upload_device_ycbcr(b, 0, 1, src); });
+}
+// the same for uint16 planes (P010 / P016, planar 10- to 16-bit): mi_batch_upload_device_ycbcr16
+int mi_ravif_encode_device_ycbcr16(const mi_ravif_encoder *e, const mi_device_planes16 *src, uint32_t w, uint32_t h, mi_encoded_image *out) {
+  if (!src || !src->y || !src->cb) return MI_INVALID_ARGUMENT;
+  return encode_pooled(e, w, h, 3, out, [&](mi_batch *b) { return mi_batch_upload_device_ycbcr16(b, 0, 1, src); });
 }
 // the same for a picture of src_w x src_h that is resampled to w x h on the way in
 int mi_ravif_encode_device_resized(const mi_ravif_encoder *e, const mi_device_pixels *src, uint32_t src_w, uint32_t src_h, uint32_t w, uint32_t h, int filter, mi_encoded_image *out) {

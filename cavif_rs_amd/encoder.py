@@ -68,6 +68,10 @@ class _DevicePlanes(C.Structure):                      # mi_device_planes
                 ('c_row_stride', C.c_size_t), ('y_image_stride', C.c_size_t), ('c_image_stride', C.c_size_t), ('after_stream', C.c_void_p)]
 
 
+class _DevicePlanes16(C.Structure):                    # mi_device_planes16: _DevicePlanes for uint16 samples + what a sample means
+    _fields_ = _DevicePlanes._fields_ + [('bits', C.c_int), ('msb_aligned', C.c_int), ('narrow_range', C.c_int)]
+
+
 class _DeviceTarget(C.Structure):                      # mi_device_target: _DevicePixels with a writable pointer
     _fields_ = _DevicePixels._fields_
 
@@ -178,6 +182,8 @@ def load_library():
     L.mi_png_scanlines_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.mi_ravif_encode_device16.argtypes = [C.POINTER(_RavifEncoder), C.POINTER(_DevicePixels16), C.c_uint32, C.c_uint32, C.POINTER(_EncodedImage)]
     L.mi_ravif_encode_device_ycbcr.argtypes = [C.POINTER(_RavifEncoder), C.POINTER(_DevicePlanes), C.c_uint32, C.c_uint32, C.POINTER(_EncodedImage)]
+    L.mi_batch_upload_device_ycbcr16.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(_DevicePlanes16)]
+    L.mi_ravif_encode_device_ycbcr16.argtypes = [C.POINTER(_RavifEncoder), C.POINTER(_DevicePlanes16), C.c_uint32, C.c_uint32, C.POINTER(_EncodedImage)]
     L.mi_colour_transform_from_icc.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p)]
     L.mi_colour_transform_from_png.argtypes = [C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_void_p)]
     L.mi_colour_transform_free.argtypes = [C.c_void_p]
@@ -447,6 +453,7 @@ def _is_device_array(x):
 
 
 DECODED_WHICH = {'recon': 0, 'source': 1}                   # MI_DECODED_*
+INPUT_RGB, INPUT_YCBCR, INPUT_RGB16, INPUT_YCBCR16 = range(4)   # MI_INPUT_*: what the samples of a batch slot mean (BatchEncoder.input_kind)
 SOURCE_HOST, SOURCE_JPEG, SOURCE_PNG, SOURCE_JPEG_YCBCR, SOURCE_PNG_DEEP, SOURCE_JPEG_MANAGED, SOURCE_PNG_MANAGED, SOURCE_PNG_DEEP_MANAGED = range(8)   # MI_SOURCE_*: what mi_ravif_encode_sources takes
 SOURCE_ORIENTED = 0x100                                  # MI_SOURCE_ORIENTED: ORed into kinds 1..7, the picture is turned as its file asks and desc names the oriented size
 _SOURCE_HANDLE_FIELD = {SOURCE_HOST: None, SOURCE_JPEG: 'jpeg', SOURCE_PNG: 'png', SOURCE_JPEG_YCBCR: 'jpeg', SOURCE_PNG_DEEP: 'png',      # the field of mi_image_source that carries
@@ -527,15 +534,17 @@ def _widen16(a, bits=16, msb_aligned=False):
     return ((v << (16 - bits)) | (v >> (2 * bits - 16))).astype(np.uint16)
 
 
-def _plane_view(x, what):
-    """(pointer, shape, byte strides, device index or None) of a uint8 object with __cuda_array_interface__"""
+def _plane_view(x, what, item=1):
+    """(pointer, shape, byte strides, device index or None) of a uint8 (item 1) or little-endian uint16 (item 2) object with __cuda_array_interface__"""
     ai = x.__cuda_array_interface__
-    if ai.get('typestr') != '|u1':
-        raise TypeError('%s must be uint8 (got typestr %r)' % (what, ai.get('typestr')))
+    if ai.get('typestr') != ('|u1', '<u2')[item - 1]:
+        if ai.get('typestr') in ('|u1', '<u2'):
+            raise AvifError(4)                                     # the planes of one picture share their sample type
+        raise TypeError('%s must be uint8 or uint16 (got typestr %r)' % (what, ai.get('typestr')))
     shape = tuple(int(v) for v in ai['shape'])
     strides = ai.get('strides')
     if strides is None:
-        strides, acc = [], 1
+        strides, acc = [], item
         for n in reversed(shape):
             strides.insert(0, acc); acc *= n
     strides = tuple(int(v) for v in strides)
@@ -546,10 +555,12 @@ def _plane_view(x, what):
 
 def _device_planes(y, cb, cr, subsampling):
     """(_DevicePlanes, images, height, width, device index or None) of uint8 device arrays: y (N, H, W) or (H, W); cb and cr of the chroma extent
-    ceil(H / vsub) x ceil(W / hsub) with the same leading dimension, or cr=None and cb of shape (..., ch, cw, 2): interleaved (Cb, Cr) pairs.  Columns one byte
-    apart (pairs two); Cb and Cr share their row and image strides."""
+    ceil(H / vsub) x ceil(W / hsub) with the same leading dimension, or cr=None and cb of shape (..., ch, cw, 2): interleaved (Cb, Cr) pairs.  Columns one sample
+    apart (pairs two); Cb and Cr share their row and image strides.  uint16 planes (typestr '<u2', all of them) give a _DevicePlanes16 whose bits, msb_aligned
+    and narrow_range the caller fills in; a mix of uint8 and uint16 planes raises AvifError(4)."""
     hsub, vsub = (int(v) for v in subsampling)
-    yp, ys, yst, index = _plane_view(y, 'y')
+    item = 2 if y.__cuda_array_interface__.get('typestr') == '<u2' else 1
+    yp, ys, yst, index = _plane_view(y, 'y', item)
     if len(ys) not in (2, 3):
         raise AvifError(4)
     n = ys[0] if len(ys) == 3 else 1
@@ -558,21 +569,23 @@ def _device_planes(y, cb, cr, subsampling):
         raise AvifError(4)
     cdims = ((h + vsub - 1) // vsub, (w + hsub - 1) // hsub)
     lead = ys[:-2]
-    cp, cs, cst, _ = _plane_view(cb, 'cb')
-    d = _DevicePlanes()
+    cp, cs, cst, _ = _plane_view(cb, 'cb', item)
+    d = _DevicePlanes16() if item == 2 else _DevicePlanes()
+    if item == 2:
+        d.bits, d.msb_aligned, d.narrow_range = 16, 0, 0
     if cr is None:
-        if cs != lead + cdims + (2,) or cst[-1] != 1 or (cst[-2] != 2 and cdims[1] > 1):
+        if cs != lead + cdims + (2,) or cst[-1] != item or (cst[-2] != 2 * item and cdims[1] > 1):
             raise AvifError(4)
         cst = cst[:-1]
         d.cr = None
     else:
-        rp, rs, rst, _ = _plane_view(cr, 'cr')
-        if cs != lead + cdims or rs != cs or (cst[-1] != 1 and cdims[1] > 1):
+        rp, rs, rst, _ = _plane_view(cr, 'cr', item)
+        if cs != lead + cdims or rs != cs or (cst[-1] != item and cdims[1] > 1):
             raise AvifError(4)
-        if any(a != b_ for a, b_, m in zip(cst[:-1], rst[:-1], cs[:-1]) if m > 1) or (rst[-1] != 1 and cdims[1] > 1):
+        if any(a != b_ for a, b_, m in zip(cst[:-1], rst[:-1], cs[:-1]) if m > 1) or (rst[-1] != item and cdims[1] > 1):
             raise AvifError(4)                                     # one c_row_stride / c_image_stride serves both planes
         d.cr = rp
-    if yst[-1] != 1 and w > 1:
+    if yst[-1] != item and w > 1:
         raise AvifError(4)
     if n > 1 and (yst[0] == 0 or cst[0] == 0):
         raise AvifError(4)
@@ -583,6 +596,14 @@ def _device_planes(y, cb, cr, subsampling):
     if torch is not None and hasattr(torch, 'cuda') and torch.cuda.is_available():
         d.after_stream = torch.cuda.current_stream(index).cuda_stream or None
     return d, n, h, w, index
+
+
+def _planes16_fill(d, bits, msb_aligned, narrow_range):
+    """what the caller says about uint16 planes into a _DevicePlanes16; False for a _DevicePlanes, which has no such fields"""
+    if not isinstance(d, _DevicePlanes16):
+        return False
+    d.bits, d.msb_aligned, d.narrow_range = int(bits), int(bool(msb_aligned)), int(bool(narrow_range))
+    return True
 
 
 def _empty_like_device(x, shape):
@@ -991,18 +1012,20 @@ class Encoder:
             if t is not None:
                 t.close()
 
-    def encode_ycbcr_device(self, y, cb, cr=None, subsampling=(2, 2)):
-        """8-bit BT.601 full-range planes in device memory (objects with __cuda_array_interface__; see BatchEncoder.upload_device_ycbcr for the shapes) as
-        one opaque picture: mi_ravif_encode_device_ycbcr"""
+    def encode_ycbcr_device(self, y, cb, cr=None, subsampling=(2, 2), bits=16, msb_aligned=False, narrow_range=False):
+        """BT.601 planes in device memory (objects with __cuda_array_interface__; see BatchEncoder.upload_device_ycbcr for the shapes and for what bits,
+        msb_aligned and narrow_range say about uint16 planes) as one opaque picture: mi_ravif_encode_device_ycbcr for uint8 planes,
+        mi_ravif_encode_device_ycbcr16 for uint16 ones"""
         L = load_library()
         d, n, h, w, index = _device_planes(y, cb, cr, subsampling)
         if n != 1:
             raise AvifError(4)
+        deep = _planes16_fill(d, bits, msb_aligned, narrow_range)
         img = _EncodedImage()
         e = self._c()
         if index is not None:
             e.device = index                            # the pointers belong to that device
-        st = L.mi_ravif_encode_device_ycbcr(C.byref(e), C.byref(d), w, h, C.byref(img))
+        st = (L.mi_ravif_encode_device_ycbcr16 if deep else L.mi_ravif_encode_device_ycbcr)(C.byref(e), C.byref(d), w, h, C.byref(img))
         if st:
             raise AvifError(st)
         return _take(img)
@@ -1179,21 +1202,26 @@ class BatchEncoder:
         if st:
             raise AvifError(st)
 
-    def upload_device_ycbcr(self, first, y, cb, cr=None, subsampling=(2, 2)):
+    def upload_device_ycbcr(self, first, y, cb, cr=None, subsampling=(2, 2), bits=16, msb_aligned=False, narrow_range=False):
         """images first.. from 8-bit BT.601 full-range planes in device memory (objects with __cuda_array_interface__): y (N, H, W) or (H, W), cb and cr of
         ceil(H / vsub) x ceil(W / hsub) samples with subsampling = (hsub, vsub) one of (1, 1), (2, 1), (2, 2); cb of shape (..., ch, cw, 2) with cr=None:
         interleaved (Cb, Cr) pairs (NV12-style).  Chroma is upsampled as libjpeg does (centred siting); the slots are of input kind 1.  Enqueued on the
-        batch's stream after the work of torch's current stream; the objects are kept referenced until wait()."""
+        batch's stream after the work of torch's current stream; the objects are kept referenced until wait().
+        uint16 planes (typestr '<u2', all of them; a mix raises AvifError(4)) of the same shapes go through mi_batch_upload_device_ycbcr16 into deep slots of
+        input kind 3 (INPUT_YCBCR16): `bits` (8..16) of a sample count, its low bits or (msb_aligned, as in P010) its high bits, and narrow_range=True
+        expands "video" range (16..235 / 16..240 at 8 bits) to full range.  The three keywords say nothing about uint8 planes."""
         d, n, h, w, _ = _device_planes(y, cb, cr, subsampling)
         if (h, w) != (self.h, self.w):
             raise AvifError(4)
-        st = self._L.mi_batch_upload_device_ycbcr(self._h, first, n, C.byref(d))
+        deep = _planes16_fill(d, bits, msb_aligned, narrow_range)
+        st = (self._L.mi_batch_upload_device_ycbcr16 if deep else self._L.mi_batch_upload_device_ycbcr)(self._h, first, n, C.byref(d))
         if st:
             raise AvifError(st)
         self._sources.append((y, cb, cr))
 
     def input_kind(self, index):
-        """what the bytes of slot `index` mean: 0 RGB(A), 1 (Y, Cb, Cr[, 255]), 2 16-bit RGB(A) in the deep slot; set by whichever call last filled the slot"""
+        """what the samples of slot `index` mean: 0 RGB(A), 1 (Y, Cb, Cr[, 255]), 2 16-bit RGB(A) in the deep slot, 3 canonical 16-bit (Y, Cb, Cr[, 65535]) in
+        the deep slot (INPUT_YCBCR16); set by whichever call last filled the slot"""
         v = C.c_int()
         st = self._L.mi_batch_input_kind(self._h, index, C.byref(v))
         if st:
@@ -1291,7 +1319,8 @@ class BatchEncoder:
         return a
 
     def read_input16(self, index):
-        """the deep slot of image `index` as it is on the device now (blocking D2H): uint16 array (h, w, channels), full scale"""
+        """the deep slot of image `index` as it is on the device now (blocking D2H): uint16 array (h, w, channels), full scale -- (R, G, B[, A]) of input kind 2,
+        (Y, Cb, Cr[, 65535]) with chroma centred on 32768 of input kind 3"""
         a = np.empty((self.h, self.w, self.channels), np.uint16)
         st = self._L.mi_batch_read_input16(self._h, index, a.ctypes.data)
         if st:

@@ -246,8 +246,8 @@ int  mi_batch_upload_async(mi_batch *b, int first, int count);
  * three *_ycbcr calls tag theirs MI_INPUT_YCBCR; it survives encodes and mi_batch_set_count as the slot's contents do.  mi_batch_set_input_kind is for HIP
  * callers that write mi_batch_device_input themselves.  MI_INPUT_YCBCR is refused with MI_INVALID_ARGUMENT (by the set call and the *_ycbcr uploads alike)
  * when the encoder's colour model is RGB (color_model 1) and when the batch has 4 channels and alpha_mode 2 (premultiplied: defined on RGB colours).
- * mi_batch_set_input_kind: MI_INVALID_ARGUMENT as well for a range past the capacity, a kind not 0, 1 or 2 (MI_INPUT_RGB16: deep input, below; refused while the
- * batch has no deep slots), a call between mi_batch_encode_async and mi_batch_wait.
+ * mi_batch_set_input_kind: MI_INVALID_ARGUMENT as well for a range past the capacity, a kind not 0, 1, 2 or 3 (MI_INPUT_RGB16 and MI_INPUT_YCBCR16: deep
+ * input and deep YCbCr planes, below; both refused while the batch has no deep slots), a call between mi_batch_encode_async and mi_batch_wait.
  * mi_batch_upload_jpeg_ycbcr: mi_batch_upload_jpeg (staging, H2D, IDCT, ordering, lifetimes) ending in jpeg_ycc_kernel: the slot's pixels are
  * (Y, Cb', Cr') of a three-component YCbCr file, Cb' Cr' libjpeg's fancy-upsampled chroma -- exactly the triples whose 16.16 conversion mi_batch_upload_jpeg
  * stores -- and (Y, 128, 128) of a grey file.  A file whose colour is RGB (Adobe transform 0, or components named R G B): MI_UNSUPPORTED; a size mismatch, an
@@ -263,7 +263,7 @@ int  mi_batch_upload_async(mi_batch *b, int first, int count);
  *          x even: (3 v(i) + v(i-1) + 8) >> 4,  x odd: (3 v(i) + v(i+1) + 7) >> 4
  * MI_INVALID_ARGUMENT: null b / src / y / cb, another (hsub, vsub), a row stride below the packed row (w for y; cw, or 2 cw interleaved, for chroma), a
  * range past the capacity, a refusal of the kind, a call between mi_batch_encode_async and mi_batch_wait. */
-enum { MI_INPUT_RGB = 0, MI_INPUT_YCBCR = 1, MI_INPUT_RGB16 = 2 };
+enum { MI_INPUT_RGB = 0, MI_INPUT_YCBCR = 1, MI_INPUT_RGB16 = 2, MI_INPUT_YCBCR16 = 3 };
 int  mi_batch_set_input_kind(mi_batch *b, int first, int count, int kind);
 int  mi_batch_input_kind(mi_batch *b, int index, int *kind);
 int  mi_batch_upload_jpeg_ycbcr(mi_batch *b, int index, const mi_jpeg_coeffs *c);
@@ -321,6 +321,45 @@ int  mi_batch_upload_device16(mi_batch *b, int first, int count, const mi_device
 int  mi_batch_upload16(mi_batch *b, int index, const uint16_t *pixels, size_t stride_px, int channels);
 int  mi_batch_upload_png_deep(mi_batch *b, int first, int count, const mi_png_scanlines *const *png);
 int  mi_png_scanlines_info(const mi_png_scanlines *p, int *color_type, int *bit_depth);
+/* ---- deep YCbCr planes.  MI_INPUT_YCBCR16: the image is read from its deep slot (laid out as for MI_INPUT_RGB16: w*h*channels uint16 samples,
+ * rows packed), which holds (Y, Cb, Cr[, 65535]) in a CANONICAL 16-bit form: BT.601 full range, M = 65535, chroma centred on 32768.  Such an image is opaque
+ * exactly as MI_INPUT_YCBCR is: its fourth sample is never read, it never gets an alpha frame (mi_batch_uses_alpha 0), the clean alpha mode leaves it alone.
+ * The kind is taken where MI_INPUT_YCBCR is: it needs the YCbCr colour model and is refused in a 4-channel batch under alpha_mode 2; every refusal is
+ * MI_INVALID_ARGUMENT and allocates nothing.  mi_batch_set_input_kind(.., 3) tags what a HIP caller wrote through mi_batch_device_input16 and, like kind 2,
+ * is refused while the batch has no deep slots.  Kinds 0 to 3 mix freely in one batch.  mi_batch_convert_colour refuses a slot of this kind.
+ * All maps are exact integers, floor division towards minus infinity.  A source sample is first reduced to its `bits` (8..16) as mi_batch_upload_device16
+ * does -- masked to its low bits, or v >> (16 - bits) when msb_aligned -- giving v; P = 2^bits - 1, c = 2^(bits-1), s = 2^(bits-8).  Source to slot sample W:
+ *   full range    Y: W = floor((2 M v + P) / (2 P))
+ *                 C: W = clamp(32768 + floor((2 M (v - c) + P) / (2 P)), 0, M)
+ *   narrow range  Y: W = clamp(floor((2 M (v - 16 s) + 219 s) / (438 s)), 0, M)
+ *                 C: W = clamp(32768 + floor((2 M (v - 128 s) + 224 s) / (448 s)), 0, M)
+ * Slot sample to plane, bd = the batch's bit depth, peak = 2^bd - 1, half = 2^(bd-1):
+ *   p0  = floor((2 peak Y + M) / (2 M))
+ *   p_k = clamp(half + floor((2 peak (C_k - 32768) + M) / (2 M)), 0, peak)
+ * With bits == bd (8 or 10) a full-range sample reaches its plane as itself, luma and chroma (P010 full range at depth 10 is lossless on the way in); with
+ * bits = 8 the planes at depth 10 are those of MI_INPUT_YCBCR; neutral chroma c gives half for every `bits`.  The contract is this two-stage map: for 14 and 15
+ * bits into depth 10 it differs from one direct rounding at a few dozen values.  Samples past the picture replicate its edge.
+ * Chroma upsampling is done on W, not on source samples: every chroma sample is mapped first, then the formulas of mi_batch_upload_device_ycbcr above apply to
+ * the W values unchanged (libjpeg's h2v1 / h2v2 weights and rounding constants, planes of one or two samples' width replicated, edges clamped, centred siting;
+ * a sum reaches at most 16 M).  So a SUBSAMPLED 8-bit source sent through this call (bits = 8) does not give the 8-bit call's slot times 257: the rounding
+ * happens at 16 bits here.  A 4:4:4 one (no upsampling) gives the 8-bit call's planes and so its file.
+ * The files stay tagged matrix 6 (BT.601), full range, as the 8-bit path's are; narrow range is expanded, never signalled.
+ * mi_batch_upload_device_ycbcr16: mi_batch_upload_device_ycbcr (after_stream, ordering, lifetimes, image k's planes at y + k * y_image_stride and cb / cr +
+ * k * c_image_stride) for uint16 samples; strides in BYTES; one launch for all images of the call; the slots are tagged MI_INPUT_YCBCR16.
+ * MI_INVALID_ARGUMENT: null b / src / y / cb, another (hsub, vsub), bits outside 8..16, msb_aligned or narrow_range not 0 or 1, an odd pointer or stride, a
+ * row stride below the packed row (2 w for y; 2 cw, or 4 cw interleaved, for chroma), a range past the capacity, a refusal of the kind, a call between
+ * mi_batch_encode_async and mi_batch_wait -- all checked before the deep slots are made.  MI_ENCODING_ERROR when the deep slots cannot be allocated.
+ * mi_ravif_encode_device_ycbcr16: mi_ravif_encode_device_ycbcr for such planes.  Blocking, pooled. */
+typedef struct mi_device_planes16 {      /* mi_device_planes for uint16 samples */
+  const void *y, *cb, *cr;               /* cr == NULL: cb points at interleaved (Cb, Cr) uint16 pairs (P010 / P016-style) */
+  int hsub, vsub;                        /* (1,1), (2,1), (2,2) */
+  size_t y_row_stride, c_row_stride, y_image_stride, c_image_stride;   /* bytes, even; 0 = packed */
+  void *after_stream;
+  int bits, msb_aligned;                 /* 8..16; P010 = 10, 1 */
+  int narrow_range;                      /* 0 full, 1 narrow ("video") range, expanded by the maps above */
+} mi_device_planes16;
+int  mi_batch_upload_device_ycbcr16(mi_batch *b, int first, int count, const mi_device_planes16 *src);
+int  mi_ravif_encode_device_ycbcr16(const mi_ravif_encoder *e, const mi_device_planes16 *src, uint32_t w, uint32_t h, mi_encoded_image *out);
 int  mi_ravif_encode_device16(const mi_ravif_encoder *e, const mi_device_pixels16 *src, uint32_t w, uint32_t h, mi_encoded_image *out);
 /* ---- colour-managed input (opt-in: without these calls every slot holds the bytes it held before).  Every file this library writes is tagged
  * sRGB; a source that says something else about its colour is converted to sRGB in its slot, on the device, before it is encoded.
