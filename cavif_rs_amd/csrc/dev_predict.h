@@ -73,24 +73,38 @@ __device__ __forceinline__ void dr_dxdy_uni(int pa, int *dx, int *dy) {
 }
 
 // Raw (unfiltered) edges of the block at pixel (x,y) of `plane`: above[-1..2n-1], left[-1..2n-1]. (spec 7.11.2 steps 1-4)
+// In three steps, so that the head of a block search can send these loads off with its other loads (tile_search.h head_stage_*):
+//   edge_addr   pure: where sample i of the above edge and of the left edge of a w x h block comes from (sample offsets into the plane); i = w + h is the
+//               corner, every i beyond it the block's own first sample.  Every sample comes from one unconditional load per edge (addresses selected, not the loads): with no row above the
+//               left neighbour's sample, with no neighbour at all the block's own first sample
+//   (the loads: rec[ia], rec[il])
+//   edge_value  the values spec 7.11.2 puts where there is no neighbour at all
+struct EdgeAddr { int ia, il; };
+__device__ __forceinline__ EdgeAddr edge_addr(int rs, int mi_rows, int mi_cols, int x, int y, int w, int h, int have_left, int have_above, int have_ar, int have_bl, int i) {
+  const int max_x = mi_cols * 4 - 1, max_y = mi_rows * 4 - 1;
+  const int lim_a = imin_(max_x, x + (have_ar ? 2 * w : w) - 1), lim_l = imin_(max_y, y + (have_bl ? 2 * h : h) - 1);
+  const bool corner = i == w + h;
+  EdgeAddr e;
+  if (have_above) e.ia = (y - 1) * rs + (corner ? (have_left ? x - 1 : x) : imin_(lim_a, x + i));
+  else e.ia = y * rs + (have_left ? x - 1 : x);
+  if (have_left) e.il = imin_(lim_l, y + i) * rs + x - 1;
+  else e.il = (have_above ? y - 1 : y) * rs + x;
+  if (i > w + h) e.ia = e.il = y * rs + x;                       // a lane with no sample to fetch
+  return e;
+}
+__device__ __forceinline__ void edge_value(int bd, int have_left, int have_above, bool corner, uint16_t *a, uint16_t *l) {
+  if (!have_above && !have_left) { *a = (uint16_t)(corner ? (1 << (bd - 1)) : (1 << (bd - 1)) - 1); *l = (uint16_t)((1 << (bd - 1)) + 1); }
+}
 __device__ inline void load_edges(const LDS FrameDev *f, int plane, int x, int y, int n, int have_left, int have_above,
                                   int have_ar, int have_bl, LDS uint16_t *above /* +EDGE_OFF */, LDS uint16_t *left) {
-  const int bd = f->bd, rs = f->stride;
+  const int bd = f->bd, rs = f->stride, mi_rows = f->mi_rows, mi_cols = f->mi_cols;
   const uint16_t *rec = f->rec[plane];
-  const int max_x = f->mi_cols * 4 - 1, max_y = f->mi_rows * 4 - 1;
-  const int tot = 2 * n;
-  // index tot is the corner; every sample comes from one unconditional load per edge (addresses selected, not the loads)
-  const int na = x + (have_ar ? 2 * n : n) - 1, nl = y + (have_bl ? 2 * n : n) - 1;
-  const int lim_a = imin_(max_x, na), lim_l = imin_(max_y, nl);
+  const int tot = 2 * n;                                        // index tot is the corner
   for (int i = LANE; i <= tot; i += 64) {
     const bool corner = i == tot;
-    int ia, il;
-    if (have_above) ia = (y - 1) * rs + (corner ? (have_left ? x - 1 : x) : imin_(lim_a, x + i));
-    else ia = y * rs + (have_left ? x - 1 : x);                  // no row above: the left neighbour's sample (or, with no neighbour at all, any valid address)
-    if (have_left) il = imin_(lim_l, y + i) * rs + x - 1;
-    else il = (have_above ? y - 1 : y) * rs + x;
-    uint16_t a = rec[ia], l = rec[il];
-    if (!have_above && !have_left) { a = (uint16_t)(corner ? (1 << (bd - 1)) : (1 << (bd - 1)) - 1); l = (uint16_t)((1 << (bd - 1)) + 1); }
+    const EdgeAddr e = edge_addr(rs, mi_rows, mi_cols, x, y, n, n, have_left, have_above, have_ar, have_bl, i);
+    uint16_t a = rec[e.ia], l = rec[e.il];
+    edge_value(bd, have_left, have_above, corner, &a, &l);
     if (corner) { above[-1] = a; left[-1] = a; }
     else { above[i] = a; left[i] = l; }
   }

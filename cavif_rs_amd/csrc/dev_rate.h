@@ -5,47 +5,28 @@
 #pragma once
 #include "dev_common.h"
 
-// all_zero and dc_sign contexts from the level/dc maps left by the neighbours (inside the tile only)
-template <typename FP, typename TP> __device__ inline void txb_ctx_dev(FP f, TP t, int plane, int r4, int c4, int txs, int bs, int *skip_ctx, int *dc_ctx) {
-  const int w4 = 1 << txs, ms = f->mi_stride;
-  int top = 0, left = 0, dcs = 0, any_a = 0, any_l = 0;
-  const int k = LANE;
-  if (k < w4) {
-    // both neighbours with unconditional loads (clamped to the block's own cell where there is none): one round trip, not two
-    const bool ha = r4 - 1 >= t->mi_row_start && c4 + k < f->mi_cols, hl = c4 - 1 >= t->mi_col_start && r4 + k < f->mi_rows;
-    const int ia = ha ? (r4 - 1) * ms + c4 + k : r4 * ms + c4, il = hl ? (r4 + k) * ms + c4 - 1 : r4 * ms + c4;
-    const int la = f->m_lvl[plane][ia], da = f->m_dc[plane][ia], ll = f->m_lvl[plane][il], dl = f->m_dc[plane][il];
-    if (ha) { top = la; any_a = la | da; dcs += da == 1 ? -1 : (da == 2 ? 1 : 0); }
-    if (hl) { left = ll; any_l = ll | dl; dcs += dl == 1 ? -1 : (dl == 2 ? 1 : 0); }
-  }
-  top = wave_max_i32(top); left = wave_max_i32(left); dcs = wave_sum_i32(dcs);
-  any_a = wave_or_i32(any_a); any_l = wave_or_i32(any_l);
-  *dc_ctx = dcs < 0 ? 1 : (dcs > 0 ? 2 : 0);
-  if (plane == 0) {
-    int ctx;
-    if (bs == txs) ctx = 0;
-    else if (top == 0 && left == 0) ctx = 1;
-    else if (top == 0 || left == 0) ctx = 2 + (imax_(top, left) > 3);
-    else if (imax_(top, left) <= 3) ctx = 4;
-    else if (imin_(top, left) <= 3) ctx = 5;
-    else ctx = 6;
-    *skip_ctx = ctx;
-  } else {
-    *skip_ctx = 7 + (any_a != 0) + (any_l != 0) + (bs > txs ? 3 : 0);
-  }
+// all_zero and dc_sign contexts from the level/dc maps left by the neighbours (inside the tile only), in three steps so that a caller can send the loads off
+// together with its other loads and take the values when it needs them (the head of a block search, tile_search.h head_stage_*):
+//   txb_ctx_addr    pure: lane k's cell above and cell left of a w4 x h4 transform block, the block's own cell where there is no such neighbour (always addressable)
+//   txb_ctx_load    the four byte loads, unconditional: one round trip
+//   txb_ctx_reduce  the wave reductions; every lane returns the contexts
+struct TxbCtxAddr { int ia, il; bool ha, hl; };
+struct TxbCtxVal { int la, da, ll, dl; };
+__device__ __forceinline__ TxbCtxAddr txb_ctx_addr(int ms, int mi_rows, int mi_cols, int row_start, int col_start, int r4, int c4, int w4, int h4, int k) {
+  TxbCtxAddr a;
+  a.ha = k < w4 && r4 - 1 >= row_start && c4 + k < mi_cols; a.hl = k < h4 && c4 - 1 >= col_start && r4 + k < mi_rows;
+  a.ia = a.ha ? (r4 - 1) * ms + c4 + k : r4 * ms + c4; a.il = a.hl ? (r4 + k) * ms + c4 - 1 : r4 * ms + c4;
+  return a;
 }
-// all_zero / dc_sign contexts of a transform block of w4 x h4 cells inside a block (txb_ctx_dev with both dimensions); `whole`: the transform is the block
-template <typename FP, typename TP> __device__ inline void txb_ctx_wh(FP f, TP t, int plane, int r4, int c4, int w4, int h4, int whole, int *skip_ctx, int *dc_ctx) {
-  const int ms = f->mi_stride;
+template <typename FP> __device__ __forceinline__ TxbCtxVal txb_ctx_load(FP f, int plane, const TxbCtxAddr a) {
+  TxbCtxVal v;
+  v.la = f->m_lvl[plane][a.ia]; v.da = f->m_dc[plane][a.ia]; v.ll = f->m_lvl[plane][a.il]; v.dl = f->m_dc[plane][a.il];
+  return v;
+}
+__device__ __forceinline__ void txb_ctx_reduce(int plane, int whole, const TxbCtxAddr a, const TxbCtxVal v, int *skip_ctx, int *dc_ctx) {
   int top = 0, left = 0, dcs = 0, any_a = 0, any_l = 0;
-  const int k = LANE;
-  if (k < imax_(w4, h4)) {
-    const bool ha = k < w4 && r4 - 1 >= t->mi_row_start && c4 + k < f->mi_cols, hl = k < h4 && c4 - 1 >= t->mi_col_start && r4 + k < f->mi_rows;
-    const int ia = ha ? (r4 - 1) * ms + c4 + k : r4 * ms + c4, il = hl ? (r4 + k) * ms + c4 - 1 : r4 * ms + c4;
-    const int la = f->m_lvl[plane][ia], da = f->m_dc[plane][ia], ll = f->m_lvl[plane][il], dl = f->m_dc[plane][il];
-    if (ha) { top = la; any_a = la | da; dcs += da == 1 ? -1 : (da == 2 ? 1 : 0); }
-    if (hl) { left = ll; any_l = ll | dl; dcs += dl == 1 ? -1 : (dl == 2 ? 1 : 0); }
-  }
+  if (a.ha) { top = v.la; any_a = v.la | v.da; dcs += v.da == 1 ? -1 : (v.da == 2 ? 1 : 0); }
+  if (a.hl) { left = v.ll; any_l = v.ll | v.dl; dcs += v.dl == 1 ? -1 : (v.dl == 2 ? 1 : 0); }
   top = wave_max_i32(top); left = wave_max_i32(left); dcs = wave_sum_i32(dcs);
   any_a = wave_or_i32(any_a); any_l = wave_or_i32(any_l);
   *dc_ctx = dcs < 0 ? 1 : (dcs > 0 ? 2 : 0);
@@ -59,6 +40,15 @@ template <typename FP, typename TP> __device__ inline void txb_ctx_wh(FP f, TP t
     else ctx = 6;
     *skip_ctx = ctx;
   } else *skip_ctx = 7 + (any_a != 0) + (any_l != 0) + (whole ? 0 : 3);
+}
+// all_zero / dc_sign contexts of a transform block of w4 x h4 cells inside a block; `whole`: the transform is the block
+template <typename FP, typename TP> __device__ inline void txb_ctx_wh(FP f, TP t, int plane, int r4, int c4, int w4, int h4, int whole, int *skip_ctx, int *dc_ctx) {
+  const TxbCtxAddr a = txb_ctx_addr(f->mi_stride, f->mi_rows, f->mi_cols, t->mi_row_start, t->mi_col_start, r4, c4, w4, h4, LANE);
+  txb_ctx_reduce(plane, whole, a, txb_ctx_load(f, plane, a), skip_ctx, dc_ctx);
+}
+// the square form: a transform of size code `txs` in a block of size code `bs`
+template <typename FP, typename TP> __device__ inline void txb_ctx_dev(FP f, TP t, int plane, int r4, int c4, int txs, int bs, int *skip_ctx, int *dc_ctx) {
+  txb_ctx_wh(f, t, plane, r4, c4, 1 << txs, 1 << txs, bs == txs, skip_ctx, dc_ctx);
 }
 
 __device__ __forceinline__ int eob_to_pt(int eob) { return eob < 3 ? eob : (32 - __clz(eob - 1) + 1); }

@@ -7,19 +7,13 @@
 // raw edges of a w x h block: above[-1 .. w+h-1], left[-1 .. w+h-1] (oracle av1o_predict_intra_wh edge preparation)
 __device__ inline void load_edges_wh(const LDS FrameDev *f, int plane, int x, int y, int w, int h, int have_left, int have_above, int have_ar, int have_bl,
                                      LDS uint16_t *above, LDS uint16_t *left) {
-  const int bd = f->bd, rs = f->stride, tot = w + h;
+  const int bd = f->bd, rs = f->stride, tot = w + h, mi_rows = f->mi_rows, mi_cols = f->mi_cols;
   const uint16_t *rec = f->rec[plane];
-  const int max_x = f->mi_cols * 4 - 1, max_y = f->mi_rows * 4 - 1;
-  const int lim_a = imin_(max_x, x + (have_ar ? 2 * w : w) - 1), lim_l = imin_(max_y, y + (have_bl ? 2 * h : h) - 1);
   for (int i = LANE; i <= tot; i += 64) {
     const bool corner = i == tot;
-    int ia, il;
-    if (have_above) ia = (y - 1) * rs + (corner ? (have_left ? x - 1 : x) : imin_(lim_a, x + i));
-    else ia = y * rs + (have_left ? x - 1 : x);
-    if (have_left) il = imin_(lim_l, y + i) * rs + x - 1;
-    else il = (have_above ? y - 1 : y) * rs + x;
-    uint16_t a = rec[ia], l = rec[il];
-    if (!have_above && !have_left) { a = (uint16_t)(corner ? (1 << (bd - 1)) : (1 << (bd - 1)) - 1); l = (uint16_t)((1 << (bd - 1)) + 1); }
+    const EdgeAddr e = edge_addr(rs, mi_rows, mi_cols, x, y, w, h, have_left, have_above, have_ar, have_bl, i);
+    uint16_t a = rec[e.ia], l = rec[e.il];
+    edge_value(bd, have_left, have_above, corner, &a, &l);
     if (corner) { above[-1] = a; left[-1] = a; } else { above[i] = a; left[i] = l; }
   }
   WAVE_SYNC();
@@ -498,30 +492,37 @@ __device__ MI_K1_TRY_ATTR long long try_block_rect(const Ctx<MAXN, NW, TS> k, in
   const int iU = availU ? mi - ms : mi, iL = availL ? mi - 1 : mi;
   constexpr int SHAPE = BSR == BS_8X4 ? 1 : 2;                 // (decoded_before: the halves of the node in coding order)
   const int have_ar = can_ar && decoded_before(r, c, SHAPE, r - 1, c + w4), have_bl = can_bl && decoded_before(r, c, SHAPE, r + h4, c - 1);
-  const int amode = availU ? uni32(f->m_ymode[iU]) : DC_PRED, lmode = availL ? uni32(f->m_ymode[iL]) : DC_PRED;
-  const int uvU = f->np > 1 ? uni32(f->m_uvmode[iU]) : 0, uvL = f->np > 1 ? uni32(f->m_uvmode[iL]) : 0;
+  // the neighbour context as one batch of unconditional loads, and behind it the loads of the wave's staging role (waves 0..2 a plane each, wave 3 the psychovisual
+  // references), before anything waits: one round trip for the whole head, as in try_block
+  const int v_ymU = f->m_ymode[iU], v_ymL = f->m_ymode[iL];
+  const int v_uvU = f->np > 1 ? f->m_uvmode[iU] : 0, v_uvL = f->np > 1 ? f->m_uvmode[iL] : 0;
   const int v_skU = f->m_skip[iU], v_skL = f->m_skip[iL], v_skUL = f->m_skip[availU && availL ? mi - ms - 1 : mi];        // bit 0 = skip, the rest = segment id
+  const int v_txU = f->m_txsize[iU], v_txL = f->m_txsize[iL];
+  PH_BEGIN();
+  const bool stager = W < f->np;
+  HeadStage<W_, H_> hs;
+  int hp_a = 0, hp_sv4 = 0;
+  if (stager) head_stage_issue<W_, H_>(f, t, W, r, c, availL, availU, have_ar, have_bl, hs);
+  if (W == NW - 1) {
+    const int l2 = LANE < 2 ? LANE : 0;
+    hp_a = (int)f->act[(y >> 3) * (f->pw >> 3) + (x >> 3)];
+    hp_sv4 = (int)f->svar4[(r + (HL == 3 ? l2 : 0)) * ms + c + (WL == 3 ? l2 : 0)];
+  }
+  const int amode = availU ? uni32(v_ymU) : DC_PRED, lmode = availL ? uni32(v_ymL) : DC_PRED;
+  const int uvU = uni32(v_uvU), uvL = uni32(v_uvL);
   const int nb_skip = (availU ? uni32(v_skU) & 1 : 0) + (availL ? uni32(v_skL) & 1 : 0);
   const int seg_nb = (availU && availL ? (uni32(v_skUL) >> 1) + 1 : 0) | ((availU ? (uni32(v_skU) >> 1) + 1 : 0) << 4) | ((availL ? (uni32(v_skL) >> 1) + 1 : 0) << 8);   // as in try_block
-  const int nb_txU = availU ? uni32(f->m_txsize[iU]) : -1, nb_txL = availL ? uni32(f->m_txsize[iL]) : -1;
+  const int nb_txU = availU ? uni32(v_txU) : -1, nb_txL = availL ? uni32(v_txL) : -1;
   const uint16_t *ycost = k.cost() + CDF_KF_Y + (intra_mode_ctx(amode) * 5 + intra_mode_ctx(lmode)) * CDF_KF_Y_STRIDE;
   const int ftype_y = IS_SMOOTH_(amode) || IS_SMOOTH_(lmode);
   const int ftype_uv = f->np > 1 && ((availU && IS_SMOOTH_(uvU)) || (availL && IS_SMOOTH_(uvL)));
   LDS uint16_t *wa = S->wa + EDGE_OFF, *wl = S->wl + EDGE_OFF;
-  PH_BEGIN();
 
   // ---- stage the source block, the raw edges and the transform contexts of every plane (plane p by wave p % NW), the psychovisual references
-  for (int p = 0; p < f->np; p++) if (p % NW == W) {
-    int sc_, dc_;
-    txb_ctx_wh(f, t, p, r, c, w4, h4, 1, &sc_, &dc_);
-    if (LANE == 0) { SH->sctx[p] = sc_; SH->dctx[p] = dc_; }
-    const uint16_t *g = f->src[p] + (size_t)y * f->stride + x;
-    for (int idx = LANE; idx < NN; idx += 64) SH->srcb[p][idx] = g[(idx >> WL) * f->stride + (idx & (W_ - 1))];
-    load_edges_wh(f, p, x, y, W_, H_, availL, availU, have_ar, have_bl, SH->ra[p] + EDGE_OFF, SH->rl[p] + EDGE_OFF);
-  }
+  if (stager) head_stage_consume<W_, H_, true>(f, SH, W, availL, availU, hs);
   if (W == NW - 1) {
-    const int a = (int)f->act[(y >> 3) * (f->pw >> 3) + (x >> 3)];
-    if (LANE < 2) SH->psv4[LANE] = (int)f->svar4[(r + (HL == 3 ? LANE : 0)) * ms + c + (WL == 3 ? LANE : 0)];
+    const int a = hp_a;
+    if (LANE < 2) SH->psv4[LANE] = hp_sv4;
     if (LANE == 0) { SH->pact[0] = a; SH->cact = a; SH->seg_nb = seg_nb; }
     seg_select(f, SH, a);
   }
@@ -657,13 +658,13 @@ __device__ MI_K1_TRY_ATTR long long try_block_rect(const Ctx<MAXN, NW, TS> k, in
       int sub_any = 0;
       if (W == 0) for (int idx = LANE; idx < NN; idx += 64) { const int q = W_ == 8 ? ((idx & 7) >> 2) : (idx >> 4), i = (idx >> WL) & 3, j = idx & 3; SH->ssrc[q * 16 + i * 4 + j] = SH->srcb[0][idx]; }
       if (W == 1 && LANE < 4) {
-        // outer neighbour contexts of the two halves (txb_ctx_wh's loads): lane = 2 * half + (0: above, 1: left); level | dc << 8 | available << 16.  The second half's
-        // inner neighbour (the first half) comes from the chain.
+        // outer neighbour contexts of the two halves (txb_ctx_wh's cells, kept by the block's head in SH->nb_top / nb_left): lane = 2 * half + (0: above, 1: left);
+        // level | dc << 8 | available << 16.  The second half's inner neighbour (the first half) comes from the chain.
         const int q = LANE >> 1, side = LANE & 1, rr = r + (H_ == 8 ? q : 0), cc = c + (W_ == 8 ? q : 0);
         const bool inner = q == 1 && (side == 0 ? H_ == 8 : W_ == 8);
         const bool have = !inner && (side == 0 ? (rr - 1 >= t->mi_row_start && cc < f->mi_cols) : (cc - 1 >= t->mi_col_start && rr < f->mi_rows));
-        const int ia = have ? (side == 0 ? (rr - 1) * ms + cc : rr * ms + cc - 1) : rr * ms + cc;
-        const int l = f->m_lvl[0][ia], d = f->m_dc[0][ia];
+        const int kk = inner ? 0 : q;                               // the cell of the block's above row / left column that lies beside this half
+        const int l = side == 0 ? SH->nb_top[kk][0] : SH->nb_left[kk][0], d = side == 0 ? SH->nb_top[kk][1] : SH->nb_left[kk][1];
         sub[8 + LANE] = have ? (l | (d << 8) | (1 << 16)) : 0;
       }
       WG_SYNC();
@@ -1028,7 +1029,7 @@ __device__ MI_K1_TRY_ATTR long long try_block_rect(const Ctx<MAXN, NW, TS> k, in
     fill_rect<WL, HL>(f->m_skip, ms, r, c, skip | (seg_fin << 1));
     if (skip) for (int p = 0; p < f->np; p++) { fill_rect<WL, HL>(f->m_lvl[p], ms, r, c, 0); fill_rect<WL, HL>(f->m_dc[p], ms, r, c, 0); }
   }
-  total_j += ((long long)k.cost()[CDF_SKIP + nb_skip * CDF_SKIP_STRIDE + skip] * f->rdmult + 256) >> 9;
+  total_j += ((long long)SH->part_cost[40 + nb_skip * 2 + skip] * f->rdmult + 256) >> 9;
   WG_SYNC();
   return total_j;
 }

@@ -92,7 +92,8 @@ template <int N> struct SharedScratch {          // shared by the waves of the t
   long long satd[13], dsd[7][6];
   long long wbest_j[4], cj[16][2], pbest_j[2];
   int order[13], wbest_e[4], pbest_c[2], calpha[2][2], ldelta[7];
-  uint16_t part_cost[40];                          // the partition symbols the walker prices (part_cost_idx): the slice of the rate table it needs, per frame / tile like the coefficient slices
+  uint16_t part_cost[46];                          // the partition symbols the walker prices (part_cost_idx): the slice of the rate table it needs, per frame / tile like the coefficient slices;
+                                                   // [40 + 2 * context + flag]: the skip flag's rates, which every block search adds at its end (a round trip to L2 per block before)
   uint16_t lpred[N <= 32 ? 768 : 4];               // final luma predictions of the surviving modes, n*n samples each (three at 16x16, up to seven at 8x8 / 4x4)
   long long ca_sse[2][2]; int ca_idx[2][2];                  // CfL alpha search, [plane][half of the alpha range]
   int lm_mode, lm_delta, lm_tx, lm_eob, ceob[2], sctx[3], dctx[3];
@@ -369,6 +370,60 @@ __device__ inline void commit_plane(const LDS FrameDev *f, int plane, int r, int
   if (LANE == 0) f->m_eob[plane][r * f->mi_stride + c] = (uint16_t)eob;
 }
 
+// ---- the head of a block search: address, then issue, then consume ----
+// What a staging wave fetches for its plane of a w x h block -- the neighbour cells of the transform contexts, the source samples, the raw edges -- has addresses
+// that depend on nothing but the block's position, so all of it leaves as ONE batch of unconditional loads into registers (head_stage_issue) and is reduced and
+// stored to LDS afterwards (head_stage_consume).  Called one after the other, txb_ctx_dev, the source loop and load_edges were a load, a wait and an LDS store each:
+// four to five round trips to L2 with the whole workgroup waiting at the barrier behind them.  A lane with nothing to fetch reads the block's own first sample / cell.
+template <int W_, int H_> struct HeadStage {
+  static constexpr int NN = W_ * H_, NS = (NN + 63) / 64, NE = (W_ + H_ + 64) / 64;
+  TxbCtxAddr ca; TxbCtxVal cv;
+  uint16_t src[NS], ea[NE], el[NE];
+};
+template <int W_, int H_> __device__ __forceinline__ void head_stage_issue(const LDS FrameDev *f, const LDS TileB *t, int p, int r, int c, int have_left, int have_above,
+                                                                            int have_ar, int have_bl, HeadStage<W_, H_> &h) {
+  using H = HeadStage<W_, H_>;
+  const int rs = f->stride, x = c * 4, y = r * 4, mi_rows = f->mi_rows, mi_cols = f->mi_cols;
+  const uint16_t *g = f->src[p] + (size_t)y * rs + x, *rec = f->rec[p];
+  h.ca = txb_ctx_addr(f->mi_stride, mi_rows, mi_cols, t->mi_row_start, t->mi_col_start, r, c, W_ >> 2, H_ >> 2, LANE);
+  int so[H::NS]; EdgeAddr e[H::NE];
+#pragma unroll
+  for (int i = 0; i < H::NS; i++) { const int idx = LANE + 64 * i < H::NN ? LANE + 64 * i : 0; so[i] = (idx / W_) * rs + (idx % W_); }
+#pragma unroll
+  for (int i = 0; i < H::NE; i++) e[i] = edge_addr(rs, mi_rows, mi_cols, x, y, W_, H_, have_left, have_above, have_ar, have_bl, LANE + 64 * i);
+  h.cv = txb_ctx_load(f, p, h.ca);
+#pragma unroll
+  for (int i = 0; i < H::NS; i++) h.src[i] = g[so[i]];
+#pragma unroll
+  for (int i = 0; i < H::NE; i++) { h.ea[i] = rec[e[i].ia]; h.el[i] = rec[e[i].il]; }
+}
+// `keep_nb`: the luma cells' (level, dc) pairs also go to SH->nb_top / nb_left, 0 where there is no neighbour -- the luma transform-size trial prices its sub-blocks against them
+// (the block's own commits in between touch the block's cells only, so what was read here still holds there)
+template <int W_, int H_, bool keep_nb, typename SHT> __device__ __forceinline__ void head_stage_consume(const LDS FrameDev *f, LDS SHT *SH, int p, int have_left, int have_above, const HeadStage<W_, H_> &h) {
+  using H = HeadStage<W_, H_>;
+  constexpr int tot = W_ + H_;
+  int sc_, dc_;                                              // all-zero / dc-sign contexts depend on the neighbours only
+  txb_ctx_reduce(p, 1, h.ca, h.cv, &sc_, &dc_);
+  if constexpr (keep_nb) if (p == 0) {
+    if (LANE < (W_ >> 2)) { SH->nb_top[LANE][0] = (uint8_t)(h.ca.ha ? h.cv.la : 0); SH->nb_top[LANE][1] = (uint8_t)(h.ca.ha ? h.cv.da : 0); }
+    if (LANE < (H_ >> 2)) { SH->nb_left[LANE][0] = (uint8_t)(h.ca.hl ? h.cv.ll : 0); SH->nb_left[LANE][1] = (uint8_t)(h.ca.hl ? h.cv.dl : 0); }
+  }
+#pragma unroll
+  for (int i = 0; i < H::NS; i++) if (LANE + 64 * i < H::NN) SH->srcb[p][LANE + 64 * i] = h.src[i];
+  LDS uint16_t *above = SH->ra[p] + EDGE_OFF, *left = SH->rl[p] + EDGE_OFF;
+  const int bd = f->bd;
+#pragma unroll
+  for (int i = 0; i < H::NE; i++) {
+    const int ii = LANE + 64 * i;
+    uint16_t a = h.ea[i], l = h.el[i];
+    edge_value(bd, have_left, have_above, ii == tot, &a, &l);
+    if (ii == tot) { above[-1] = a; left[-1] = a; }
+    else if (ii < tot) { above[ii] = a; left[ii] = l; }
+  }
+  SH->sctx[p] = sc_; SH->dctx[p] = dc_;                      // every lane the same value: the region ends with unconditional stores (the EXEC hazard)
+  WAVE_SYNC();
+}
+
 #include "dev_rect.h"
 
 // `budget`: the caller only needs to know whether the block's cost stays below it (split trials: cost of the
@@ -394,6 +449,21 @@ __device__ MI_K1_TRY_ATTR long long try_block(const Ctx<MAXN, NW, TS> k, int r, 
   const int v_skU = f->m_skip[iU], v_skL = f->m_skip[iL], v_txU = f->m_txsize[iU], v_txL = f->m_txsize[iL];
   const int v_skUL = f->m_skip[availU && availL ? mi - ms - 1 : mi];                                  // (segment id of the above-left neighbour)
   const int have_ar = can_ar && decoded_before(r, c, 0, r - 1, c + n4), have_bl = can_bl && decoded_before(r, c, 0, r + n4, c - 1);
+  PH_BEGIN();
+  // The loads of the wave's role in staging the block go out behind that batch, before anything waits for it (consumed below, "stage the source block"): waves 1..3
+  // a plane each, wave 0 the psychovisual references.  One round trip per wave for the whole head.
+  static_assert(NW == 4, "the head deals its staging roles to four wavefronts (as every launch has: host_frames.h MI_LAUNCH_)");
+  constexpr int psy_cp = n >= 8 ? n / 8 : 1, psy_ncell = psy_cp * psy_cp;
+  const bool stager = W >= 1 && W - 1 < f->np;
+  HeadStage<n, n> hs;
+  int hp_a = 0, hp_sv = 0, hp_sv4 = 0;
+  if (stager) head_stage_issue<n, n>(f, t, W - 1, r, c, availL, availU, have_ar, have_bl, hs);
+  if (W == 0) {
+    const int l = LANE < psy_ncell ? LANE : 0, l4 = LANE < 4 ? LANE : 0;
+    const int cell = ((y >> 3) + l / psy_cp) * (f->pw >> 3) + (x >> 3) + l % psy_cp;
+    hp_a = (int)f->act[cell]; hp_sv = (int)(n == 4 ? f->svar4[mi] : f->svar8[cell]);
+    if constexpr (BS == 1) hp_sv4 = (int)f->svar4[(r + (l4 >> 1)) * ms + c + (l4 & 1)];
+  }
   const int amode = availU ? uni32(v_ymU) : DC_PRED, lmode = availL ? uni32(v_ymL) : DC_PRED;
   const int nb_skip = (availU ? uni32(v_skU) & 1 : 0) + (availL ? uni32(v_skL) & 1 : 0);              // skip context (bit 0 of the map)
   // neighbours' segment ids + 1 (0 = outside the tile), packed: needed again when the block's skip flag is known -- parked in LDS, not in registers
@@ -403,26 +473,14 @@ __device__ MI_K1_TRY_ATTR long long try_block(const Ctx<MAXN, NW, TS> k, int r, 
   const int ftype_y = IS_SMOOTH_(amode) || IS_SMOOTH_(lmode);                                           // DC_PRED (no neighbour) is not smooth
   const int ftype_uv = f->np > 1 && ((availU && IS_SMOOTH_(uni32(v_uvU))) || (availL && IS_SMOOTH_(uni32(v_uvL))));
   LDS uint16_t *wa = S->wa + EDGE_OFF, *wl = S->wl + EDGE_OFF;
-  PH_BEGIN();
 
-  // ---- stage the source block and the raw edges of every plane (plane p by wave p % NW) ----
-  for (int p = 0; p < f->np; p++) if ((p + 1) % NW == W) {      // waves 1..3: wave 0 carries the longest candidate chains below
-    int sc_, dc_;                                            // all-zero / dc-sign contexts depend on the neighbours only
-    txb_ctx_dev(f, t, p, r, c, BS, BS, &sc_, &dc_);
-    if (LANE == 0) { SH->sctx[p] = sc_; SH->dctx[p] = dc_; }
-    const uint16_t *g = f->src[p] + (size_t)y * f->stride + x;
-    for (int idx = LANE; idx < nn; idx += 64) SH->srcb[p][idx] = g[(idx / n) * f->stride + (idx % n)];
-    load_edges(f, p, x, y, n, availL, availU, have_ar, have_bl, SH->ra[p] + EDGE_OFF, SH->rl[p] + EDGE_OFF);
-  }
+  // ---- stage the source block and the raw edges of every plane: what the loads above brought ----
+  if (stager) head_stage_consume<n, n, (BS > 0)>(f, SH, W - 1, availL, availU, hs);      // waves 1..3: wave 0 carries the longest candidate chains below
   if (W == 0) {                                               // wave 0 stages no plane: the block's psychovisual references
-    constexpr int cp = n >= 8 ? n / 8 : 1, ncell = cp * cp;
-    const int cw = f->pw >> 3;
-    int a = 0;
-    if (LANE < ncell) {
-      const int cell = ((y >> 3) + LANE / cp) * cw + (x >> 3) + LANE % cp;
-      a = (int)f->act[cell]; SH->pact[LANE] = a; SH->psv[LANE] = (int)(n == 4 ? f->svar4[mi] : f->svar8[cell]);
-    }
-    if (BS == 1 && LANE < 4) SH->psv4[LANE] = (int)f->svar4[(r + (LANE >> 1)) * ms + c + (LANE & 1)];
+    constexpr int ncell = psy_ncell;
+    const int a = LANE < ncell ? hp_a : 0;
+    if (LANE < ncell) { SH->pact[LANE] = a; SH->psv[LANE] = hp_sv; }
+    if (BS == 1 && LANE < 4) SH->psv4[LANE] = hp_sv4;
     const int tot = wave_sum_i32(a);
     const int cact = (tot + ncell / 2) / ncell;
     if (LANE == 0) { SH->cact = cact; SH->seg_nb = seg_nb; }
@@ -701,22 +759,16 @@ __device__ MI_K1_TRY_ATTR long long try_block(const Ctx<MAXN, NW, TS> k, int r, 
         auto tr_done_ = []() {};
 #endif
         PH(13);
-        // ---- stage 0, all waves: the sub-sources; wave 0: outer neighbour contexts, the 4x4 source variances (depth 2 of a 16x16 block)
-        // and the decoded flags of the cells right of / below the block that a sub-block's above-right / below-left edge may reach
+        // ---- stage 0, all waves: the sub-sources; wave 0: the 4x4 source variances (depth 2 of a 16x16 block) and the decoded flags of the cells right of / below the
+        // block that a sub-block's above-right / below-left edge may reach.  (The outer neighbour contexts, SH->nb_top / nb_left, are there since the block's head.)
+        int v_psv16 = 0;
+        if constexpr (hn == 4 && n == 16) if (W == 0) v_psv16 = (int)f->svar4[(r + ((LANE & 15) >> 2)) * ms + c + (LANE & 3)];      // sent off before the copy below
         for (int q = W; q < G * G; q += NW) {
           const int so = (q / G) * hn * n + (q % G) * hn;
           for (int idx = LANE; idx < hnn; idx += 64) ssrc[q * hnn + idx] = SH->srcb[0][so + (idx / hn) * n + (idx % hn)];
         }
         if (W == 0) {
-          if (LANE < n4) {
-            const int k2 = LANE;
-            const bool ha = availU && c + k2 < f->mi_cols, hl = availL && r + k2 < f->mi_rows;         // unconditional loads, one batch
-            const int ia = ha ? (r - 1) * ms + c + k2 : mi, il = hl ? (r + k2) * ms + c - 1 : mi;
-            const int la = f->m_lvl[0][ia], da = f->m_dc[0][ia], ll = f->m_lvl[0][il], dl2 = f->m_dc[0][il];
-            SH->nb_top[k2][0] = (uint8_t)(ha ? la : 0); SH->nb_top[k2][1] = (uint8_t)(ha ? da : 0);
-            SH->nb_left[k2][0] = (uint8_t)(hl ? ll : 0); SH->nb_left[k2][1] = (uint8_t)(hl ? dl2 : 0);
-          }
-          if (hn == 4 && n == 16 && LANE < 16) psv16[LANE] = (int)f->svar4[(r + (LANE >> 2)) * ms + c + (LANE & 3)];
+          if (hn == 4 && n == 16 && LANE < 16) psv16[LANE] = v_psv16;
           if (LANE >= 1 && LANE < G) {
             const bool ca = c + n4 < t->mi_col_end, cb = r + n4 < t->mi_row_end;
             sfl_r[LANE] = ca && decoded_before(r, c, 0, r + LANE * half - 1, c + n4); sfl_b[LANE] = cb && decoded_before(r, c, 0, r + n4, c + LANE * half - 1);
@@ -1508,7 +1560,7 @@ __device__ MI_K1_TRY_ATTR long long try_block(const Ctx<MAXN, NW, TS> k, int r, 
     if (skip) for (int p = 0; p < f->np; p++) { fill_map_dev(f->m_lvl[p], ms, r, c, n4, 0); fill_map_dev(f->m_dc[p], ms, r, c, n4, 0); }
   }
   const int sctx = nb_skip;
-  total_j += ((long long)k.cost()[CDF_SKIP + sctx * CDF_SKIP_STRIDE + skip] * f->rdmult + 256) >> 9;
+  total_j += ((long long)SH->part_cost[40 + sctx * 2 + skip] * f->rdmult + 256) >> 9;
   if (f->seg_n && !skip) total_j += ((long long)k.cost()[CDF_SEG_ID + seg_ctx * CDF_SEG_ID_STRIDE + seg_symbol(seg_own, seg_p, f->seg_n)] * f->rdmult + 256) >> 9;
   PH(11);
   WG_SYNC();
@@ -1525,13 +1577,13 @@ template <int MAXN, int BS, int NW, int TS> __device__ __forceinline__ long long
 // ---- area snapshot (NONE-vs-SPLIT comparison), kept in the workgroup's HBM scratch; whole workgroup ----
 // Wave p copies plane p (reconstruction + levels, four samples per lane: 8- and 16-byte accesses), the last wave the 17 mode-info byte maps (one
 // row of the area per lane, the map's pointer picked out of the LDS frame descriptor) and the eob maps.  m_decoded is not part of a snapshot.
-template <int BYTES> __device__ __forceinline__ void copy_row_(void *dst, const void *src) {
-  if constexpr (BYTES == 1) *(uint8_t *)dst = *(const uint8_t *)src;
-  else if constexpr (BYTES == 2) *(uint16_t *)dst = *(const uint16_t *)src;
-  else if constexpr (BYTES == 4) *(uint32_t *)dst = *(const uint32_t *)src;
-  else if constexpr (BYTES == 8) *(uint2 *)dst = *(const uint2 *)src;
-  else { for (int i = 0; i < BYTES / 16; i++) ((uint4 *)dst)[i] = ((const uint4 *)src)[i]; }
-}
+// (plain vector types, not uint2 / uint4: arrays of those structs stay in scratch instead of registers)
+typedef uint32_t copy_u32x2 __attribute__((vector_size(8))); typedef uint32_t copy_u32x4 __attribute__((vector_size(16))); typedef uint32_t copy_u32x8 __attribute__((vector_size(32), aligned(16)));
+template <int BYTES> struct CopyRow {             // the register type of one row of a map's area: loaded whole, stored whole
+  static_assert(BYTES == 1 || BYTES == 2 || BYTES == 4 || BYTES == 8 || BYTES == 16 || BYTES == 32, "a row of 1 .. 16 cells of one or two bytes");
+  using T = typename std::conditional<BYTES == 1, uint8_t, typename std::conditional<BYTES == 2, uint16_t, typename std::conditional<BYTES == 4, uint32_t,
+            typename std::conditional<BYTES == 8, copy_u32x2, typename std::conditional<BYTES == 16, copy_u32x4, copy_u32x8>::type>::type>::type>::type>::type;
+};
 static_assert(offsetof(FrameDev, m_eob) - offsetof(FrameDev, m_bsize) == 18 * sizeof(void *), "area_copy_dev indexes m_bsize .. m_dc[2] as one array of 18 map pointers");
 template <int BS, int NW> __device__ inline void area_copy_dev(const LDS FrameDev *f, uint8_t *snap, int r, int c, int save) {
   constexpr int n = 4 << BS, n4 = 1 << BS, Q = n / 4;
@@ -1542,31 +1594,54 @@ template <int BS, int NW> __device__ inline void area_copy_dev(const LDS FrameDe
   uint8_t *smaps = snap + 3 * n * n * 6;                     // 17 byte-maps [n4*n4]
   uint8_t *seob = smaps + 18 * n4 * n4;                      // [3][n4*n4] uint16
   const int W = NW > 1 ? WAVE_ID : 0, np = f->np, rs = f->stride, ms = f->mi_stride;
+  // Every copy: the addresses, then ALL of the wave's loads, then its stores -- a load that follows a store waits for it to be issued, and the copies used to go
+  // unit by unit.  A lane without a unit of its own repeats unit 0 (the same bytes to the same place): no divergent region, nothing conditional around the stores.
+  constexpr int PU = n * Q, PB = PU > 256 ? 4 : (PU + 63) / 64;            // a plane's units of four samples; units per lane and batch (24 registers at the most)
   for (int p = W; p < np; p += NW) {
     uint16_t *gr = f->rec[p] + (size_t)(r * 4) * rs + c * 4;
     int32_t *gc = f->coef[p] + (size_t)(r * 4) * rs + c * 4;
-    uint2 *srec = (uint2 *)(snap + (size_t)p * n * n * 2);
-    uint4 *scoef = (uint4 *)(snap + 3 * n * n * 2 + (size_t)p * n * n * 4);
-    for (int u = LANE; u < n * Q; u += 64) {
-      const int o = (u / Q) * rs + 4 * (u % Q);
-      if (save) { srec[u] = *(const uint2 *)(gr + o); scoef[u] = *(const uint4 *)(gc + o); }
-      else { *(uint2 *)(gr + o) = srec[u]; *(uint4 *)(gc + o) = scoef[u]; }
+    copy_u32x2 *srec = (copy_u32x2 *)(snap + (size_t)p * n * n * 2);
+    copy_u32x4 *scoef = (copy_u32x4 *)(snap + 3 * n * n * 2 + (size_t)p * n * n * 4);
+    for (int b = 0; b < PU; b += 64 * PB) {
+      int u[PB], o[PB]; copy_u32x2 rv[PB]; copy_u32x4 cv[PB];
+#pragma unroll
+      for (int j = 0; j < PB; j++) { u[j] = b + 64 * j + LANE < PU ? b + 64 * j + LANE : 0; o[j] = (u[j] / Q) * rs + 4 * (u[j] % Q); }
+      if (save) {
+#pragma unroll
+        for (int j = 0; j < PB; j++) { rv[j] = *(const copy_u32x2 *)(gr + o[j]); cv[j] = *(const copy_u32x4 *)(gc + o[j]); }
+#pragma unroll
+        for (int j = 0; j < PB; j++) { srec[u[j]] = rv[j]; scoef[u[j]] = cv[j]; }
+      } else {
+#pragma unroll
+        for (int j = 0; j < PB; j++) { rv[j] = srec[u[j]]; cv[j] = scoef[u[j]]; }
+#pragma unroll
+        for (int j = 0; j < PB; j++) { *(copy_u32x2 *)(gr + o[j]) = rv[j]; *(copy_u32x4 *)(gc + o[j]) = cv[j]; }
+      }
     }
   }
   if (W == NW - 1) {
     const LDS unsigned long long *mp = (const LDS unsigned long long *)&f->m_bsize;     // 18 pointers: ... m_cfl_av, m_decoded (skipped), m_txsize, angles, m_lvl[3], m_dc[3]
-    for (int u = LANE; u < 17 * n4; u += 64) {
-      const int m = u / n4, row = u - m * n4, mi = m + (m >= 8);
-      if (np == 1 && (mi == 13 || mi == 14 || mi == 16 || mi == 17)) continue;             // 4:0:0: no chroma context maps
-      uint8_t *g = (uint8_t *)mp[mi] + (r + row) * ms + c, *sp = smaps + m * n4 * n4 + row * n4;
-      if (save) copy_row_<n4>(sp, g); else copy_row_<n4>(g, sp);
-    }
     const LDS unsigned long long *ep = (const LDS unsigned long long *)&f->m_eob[0];
-    for (int u = LANE; u < np * n4; u += 64) {
-      const int p = u / n4, row = u - p * n4;
-      uint8_t *g = (uint8_t *)((uint16_t *)ep[p] + (r + row) * ms + c), *sp = seob + (p * n4 * n4 + row * n4) * 2;
-      if (save) copy_row_<2 * n4>(sp, g); else copy_row_<2 * n4>(g, sp);
+    constexpr int MB = (17 * n4 + 63) / 64;                                             // map rows per lane: 1 (8x8), 2 (16x16) ... 5 (64x64)
+    static_assert(3 * n4 <= 64, "one eob row per lane");
+    using MRow = typename CopyRow<n4>::T; using ERow = typename CopyRow<2 * n4>::T;
+    uint8_t *mg[MB], *msp[MB]; MRow mv[MB];
+#pragma unroll
+    for (int j = 0; j < MB; j++) {
+      const int u0 = LANE + 64 * j, m0 = u0 / n4, mi0 = m0 + (m0 >= 8);
+      const bool idle = u0 >= 17 * n4 || (np == 1 && (mi0 == 13 || mi0 == 14 || mi0 == 16 || mi0 == 17));     // 4:0:0: no chroma context maps
+      const int u = idle ? 0 : u0, m = u / n4, row = u - m * n4, mi = m + (m >= 8);
+      mg[j] = (uint8_t *)mp[mi] + (r + row) * ms + c; msp[j] = smaps + m * n4 * n4 + row * n4;
     }
+    const int eu = LANE < np * n4 ? LANE : 0, epl = eu / n4, erow = eu - epl * n4;
+    uint8_t *eg = (uint8_t *)((uint16_t *)ep[epl] + (r + erow) * ms + c), *esp = seob + (epl * n4 * n4 + erow * n4) * 2;
+    ERow ev;
+#pragma unroll
+    for (int j = 0; j < MB; j++) mv[j] = *(const MRow *)(save ? mg[j] : msp[j]);
+    ev = *(const ERow *)(save ? eg : esp);
+#pragma unroll
+    for (int j = 0; j < MB; j++) *(MRow *)(save ? msp[j] : mg[j]) = mv[j];
+    *(ERow *)(save ? esp : eg) = ev;
   }
   WG_SYNC();
 #if MI_PROFILE
@@ -1584,7 +1659,7 @@ template <typename SHT> __device__ inline void load_part_cost(LDS SHT *SH, const
   if (tid < 40) {
     const int bs = tid < 16 ? 1 : 2 + (tid - 16) / 8, e = tid < 16 ? tid : (tid - 16) % 8, ctx = tid < 16 ? e >> 2 : e >> 1, part = tid < 16 ? (e & 3) : ((e & 1) ? 3 : 0);
     SH->part_cost[tid] = cost[CDF_PARTITION + ((bs - 1) * 4 + ctx) * CDF_PARTITION_STRIDE + part];
-  }
+  } else if (tid < 46) SH->part_cost[tid] = cost[CDF_SKIP + ((tid - 40) >> 1) * CDF_SKIP_STRIDE + ((tid - 40) & 1)];
 }
 // partition context of a node of size code `bs` from the block-size codes above / left of it (spec 8.3.2: is the above block narrower, the left block lower than the node)
 __device__ __forceinline__ int part_ctx_of(int bs, int availU, int availL, int code_above, int code_left) {
@@ -1729,9 +1804,10 @@ template <int MAXN, int MAXBS, int BS, int NW> struct RdPart {
           {
             long long j = uni64(part_j(k.sh(), f, BS, pctx, 2));
             for (int k2 = 0; k2 < 2 && j < j_best; k2++) j += uni64(PH_SIZE(5, (try_block_rect<MAXN, BS_4X8, NW>(k, r, c + k2, j_best - j))));
-            if (j < j_best) { j_best = j; rect_won = 2; area_copy_dev<BS, NW>(f, best_snap, r, c, 1); }
+            if (j < j_best) { j_best = j; rect_won = 2; }     // the candidate evaluated last: the frame holds it, nothing to save and nothing to put back
           }
-          if (rect_won) { area_copy_dev<BS, NW>(f, best_snap, r, c, 0); return 1; }   // 1: the later siblings' trial results are stale
+          if (rect_won == 1) area_copy_dev<BS, NW>(f, best_snap, r, c, 0);
+          if (rect_won) return 1;                              // 1: the later siblings' trial results are stale
           if (have_split) area_copy_dev<BS, NW>(f, split_snap, r, c, 0);
         }
         if (j_split < j_none && !DBG_IS(f, 7) && !DBG_IS(f, 8) && !(DBG_IS(f, 10) && BS == 1)) do_split = 1;
@@ -1813,9 +1889,10 @@ template <int MAXN, int MAXBS, int BS, int NW> struct RdPartBU {
       {
         long long j = uni64(part_j(k.sh(), f, BS, pctx, 2));
         for (int k2 = 0; k2 < 2 && j < j_best; k2++) j += uni64(PH_SIZE(5, (try_block_rect<MAXN, BS_4X8, NW>(k, r, c + k2, j_best - j))));
-        if (j < j_best) { j_best = j; rect_won = 2; area_copy_dev<BS, NW>(f, best_snap, r, c, 1); }
+        if (j < j_best) { j_best = j; rect_won = 2; }         // the candidate evaluated last: the frame holds it, nothing to save and nothing to put back
       }
-      if (rect_won) { area_copy_dev<BS, NW>(f, best_snap, r, c, 0); return j_best; }
+      if (rect_won == 1) area_copy_dev<BS, NW>(f, best_snap, r, c, 0);
+      if (rect_won) return j_best;
       if (have_split) { area_copy_dev<BS, NW>(f, split_snap, r, c, 0); return j_split; }
     }
     if (must_split || j_split < j_none) return j_split;
