@@ -88,6 +88,110 @@ class _ImageQuality(C.Structure):
 _FETCH_SOURCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.POINTER(_ImageSource))
 _RELEASE = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t)
 
+# The prototypes load_library() gives the functions of include/mi_avif.h: name -> (restype, argtypes); tests/test_abi.py holds the argument counts against the
+# header.  _STATUS: the function returns an mi status, 0 or an AvifError code (a plain int: callers check it with _ok, tests and tools compare it themselves).
+# C.c_int on a function the header declares void is ctypes' default, left as it is: nobody reads the value.
+_STATUS = 'mi status'
+_P, _I, _Z, _U8, _U32, _D, _S = C.c_void_p, C.c_int, C.c_size_t, C.c_uint8, C.c_uint32, C.c_double, C.c_char_p
+_PP, _PI, _PZ, _PU32, _PD = C.POINTER(_P), C.POINTER(_I), C.POINTER(_Z), C.POINTER(_U32), C.POINTER(_D)
+_BYTES, _PLANES = C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.POINTER(C.c_uint16))      # a buffer, or three planes, the library allocates
+_ENC, _OUT, _CFG, _QUAL = C.POINTER(_RavifEncoder), C.POINTER(_EncodedImage), C.POINTER(_Av1Config), C.POINTER(_ImageQuality)
+_PROTOTYPES = {
+    'mi_version': (_S, []),
+    'mi_quality_to_quantizer': (_I, [C.c_float]),
+    'mi_av1_tweaks_from_preset': (_STATUS, [_U8, _U8, _CFG]),
+    'mi_rgb_to_ycbcr': (_I, [C.POINTER(_U8), _I, C.POINTER(C.c_uint16)]),
+    'mi_av1_encode_planes': (_STATUS, [_CFG, _PP, _PZ, _BYTES, _PZ, _PLANES]),
+    'mi_ravif_encoder_default': (_I, [_ENC]),
+    'mi_ravif_encode_rgba': (_STATUS, [_ENC, _P, _U32, _U32, _Z, _OUT]),
+    'mi_ravif_encode_rgb': (_STATUS, [_ENC, _P, _U32, _U32, _Z, _OUT]),
+    'mi_ravif_encode_raw_planes_8': (_STATUS, [_ENC, _U32, _U32, _P, _P, _U8, _U8, _OUT]),
+    'mi_ravif_encode_raw_planes_10': (_STATUS, [_ENC, _U32, _U32, _P, _P, _U8, _U8, _OUT]),
+    'mi_batch_create': (_P, [_ENC, _I, _U32, _U32, _I]),
+    'mi_batch_upload': (_STATUS, [_P, _I, _P, _Z]),
+    'mi_batch_input': (_P, [_P, _I]),
+    'mi_batch_upload_async': (_STATUS, [_P, _I, _I]),
+    'mi_batch_set_count': (_STATUS, [_P, _I]),
+    'mi_batch_encode': (_STATUS, [_P]),
+    'mi_batch_encode_async': (_STATUS, [_P]),
+    'mi_batch_wait': (_STATUS, [_P]),
+    'mi_batch_get': (_STATUS, [_P, _I, _OUT]),
+    'mi_batch_get_recon': (_STATUS, [_P, _I, _I, _PLANES]),
+    'mi_batch_stage_ms': (_D, [_P, _I]),
+    'mi_batch_num_tiles': (_I, [_P]),
+    'mi_batch_tile_clocks': (_STATUS, [_P, _P]),
+    'mi_batch_phase_profile': (_STATUS, [_P, _P]),
+    'mi_batch_destroy': (_I, [_P]),
+    'mi_avif_serialize': (_Z, [_P, _Z, _P, _Z, _U32, _U32, _U8, _U8, _I, _P, _Z, _BYTES]),
+    'mi_free': (_I, [_P]),
+    'mi_jpeg_decode_rgba': (_STATUS, [_S, _Z, _I, _BYTES, _PU32, _PU32]),
+    'mi_image_decode_rgba': (_STATUS, [_S, _Z, _I, _BYTES, _PU32, _PU32]),
+    'mi_jpeg_parse': (_STATUS, [_S, _Z, _PP, _PU32, _PU32]),
+    'mi_jpeg_coeffs_free': (None, [_P]),
+    'mi_batch_device_input': (_P, [_P, _I]),
+    'mi_batch_read_input': (_STATUS, [_P, _I, _P]),
+    'mi_batch_upload_device': (_STATUS, [_P, _I, _I, C.POINTER(_DevicePixels)]),
+    'mi_batch_upload_jpeg': (_STATUS, [_P, _I, _P]),
+    'mi_png_parse': (_STATUS, [_S, _Z, _PP, _PU32, _PU32, _PI]),
+    'mi_png_scanlines_free': (None, [_P]),
+    'mi_batch_upload_png': (_STATUS, [_P, _I, _I, _PP]),
+    'mi_ravif_encode_device': (_STATUS, [_ENC, C.POINTER(_DevicePixels), _U32, _U32, _OUT]),
+    'mi_batch_resize_device': (_STATUS, [_P, _I, _I, C.POINTER(_DevicePixels), _U32, _U32, _I]),
+    'mi_batch_resize_jpeg': (_STATUS, [_P, _I, _P, _I]),
+    'mi_batch_resize_png': (_STATUS, [_P, _I, _P, _I]),
+    'mi_ravif_encode_device_resized': (_STATUS, [_ENC, C.POINTER(_DevicePixels), _U32, _U32, _U32, _U32, _I, _OUT]),
+    'mi_batch_measure': (_STATUS, [_P]),
+    'mi_batch_get_quality': (_STATUS, [_P, _I, _QUAL]),
+    'mi_batch_get_source': (_STATUS, [_P, _I, _I, _PLANES]),
+    'mi_quality_psnr_db': (_D, [_QUAL]),
+    'mi_quality_ssim_db': (_D, [_QUAL]),
+    'mi_batch_uses_alpha': (_STATUS, [_P, _I, _PI]),
+    'mi_batch_decode_device': (_STATUS, [_P, _I, _I, _I, C.POINTER(_DeviceTarget)]),
+    'mi_batch_decode': (_STATUS, [_P, _I, _I, _I, _P]),
+    'mi_ravif_encode_sources': (_STATUS, [_ENC, _Z, _FETCH_SOURCE, _RELEASE, _P, _OUT, _PI, _PI, _I]),
+    'mi_batch_set_input_kind': (_STATUS, [_P, _I, _I, _I]),
+    'mi_batch_input_kind': (_STATUS, [_P, _I, _PI]),
+    'mi_batch_upload_jpeg_ycbcr': (_STATUS, [_P, _I, _P]),
+    'mi_jpeg_coeffs_info': (_STATUS, [_P, _PI, _PI, _PI]),
+    'mi_batch_upload_device_ycbcr': (_STATUS, [_P, _I, _I, C.POINTER(_DevicePlanes)]),
+    'mi_batch_device_input16': (_P, [_P, _I]),
+    'mi_batch_read_input16': (_STATUS, [_P, _I, _P]),
+    'mi_batch_footprint': (_Z, [_P]),
+    'mi_batch_upload_device16': (_STATUS, [_P, _I, _I, C.POINTER(_DevicePixels16)]),
+    'mi_batch_upload16': (_STATUS, [_P, _I, _P, _Z, _I]),
+    'mi_batch_upload_png_deep': (_STATUS, [_P, _I, _I, _PP]),
+    'mi_png_scanlines_info': (_STATUS, [_P, _PI, _PI]),
+    'mi_ravif_encode_device16': (_STATUS, [_ENC, C.POINTER(_DevicePixels16), _U32, _U32, _OUT]),
+    'mi_ravif_encode_device_ycbcr': (_STATUS, [_ENC, C.POINTER(_DevicePlanes), _U32, _U32, _OUT]),
+    'mi_batch_upload_device_ycbcr16': (_STATUS, [_P, _I, _I, C.POINTER(_DevicePlanes16)]),
+    'mi_ravif_encode_device_ycbcr16': (_STATUS, [_ENC, C.POINTER(_DevicePlanes16), _U32, _U32, _OUT]),
+    'mi_colour_transform_from_icc': (_STATUS, [_S, _Z, _PP]),
+    'mi_colour_transform_from_png': (_STATUS, [_D, _PD, _PP]),
+    'mi_colour_transform_free': (None, [_P]),
+    'mi_colour_transform_is_identity': (_I, [_P]),
+    'mi_colour_probe_icc': (_STATUS, [_S, _Z, _PI]),
+    'mi_colour_probe_png': (_STATUS, [_D, _PD, _PI]),
+    'mi_colour_transform_table': (_Z, [_P, _I, _PP]),
+    'mi_png_scanlines_colour': (_STATUS, [_P, _PI, _PP, _PZ, _PD, _PD]),
+    'mi_jpeg_coeffs_icc': (_STATUS, [_P, _PP, _PZ]),
+    'mi_batch_convert_colour': (_STATUS, [_P, _I, _I, _P]),
+    'mi_exif_orientation': (_STATUS, [_S, _Z, _PI]),
+    'mi_jpeg_coeffs_orientation': (_STATUS, [_P, _PI]),
+    'mi_png_scanlines_orientation': (_STATUS, [_P, _PI]),
+    'mi_oriented_size': (None, [_U32, _U32, _I, _PU32, _PU32]),
+    'mi_batch_orient_device': (_STATUS, [_P, _I, _I, C.POINTER(_DevicePixels), _I]),
+    'mi_batch_upload_jpeg_oriented': (_STATUS, [_P, _I, _P, _I, _I]),
+    'mi_batch_upload_png_oriented': (_STATUS, [_P, _I, _P, _I, _I]),
+}
+# declared in the header and left without a prototype: their callers (tests, tools) pass ctypes values of their own
+_UNBOUND = ('mi_device_count', 'mi_png_decode_rgba', 'mi_ravif_encode_batch', 'mi_ravif_encode_stream', 'mi_release_cached')
+
+
+def _ok(st):
+    """the status of a C call: 0, or the AvifError it stands for"""
+    if st:
+        raise AvifError(st)
+
 
 def library_path():
     return os.environ.get('MI_AVIF_LIB') or os.path.join(_HERE, 'libmi_avif.so')
@@ -102,108 +206,11 @@ def load_library():
     if not os.path.exists(path):
         raise ImportError('libmi_avif.so is missing: run `python -c "import __graft_entry__ as g; g.build()"` (hipcc --offload-arch=gfx950)')
     L = C.CDLL(path)
-    L.mi_version.restype = C.c_char_p
-    L.mi_quality_to_quantizer.argtypes = [C.c_float]
-    L.mi_av1_tweaks_from_preset.argtypes = [C.c_uint8, C.c_uint8, C.POINTER(_Av1Config)]
-    L.mi_rgb_to_ycbcr.argtypes = [C.POINTER(C.c_uint8), C.c_int, C.POINTER(C.c_uint16)]
-    L.mi_av1_encode_planes.argtypes = [C.POINTER(_Av1Config), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
-                                       C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t), C.POINTER(C.POINTER(C.c_uint16))]
-    L.mi_ravif_encoder_default.argtypes = [C.POINTER(_RavifEncoder)]
-    for fn in (L.mi_ravif_encode_rgba, L.mi_ravif_encode_rgb):
-        fn.argtypes = [C.POINTER(_RavifEncoder), C.c_void_p, C.c_uint32, C.c_uint32, C.c_size_t, C.POINTER(_EncodedImage)]
-    L.mi_ravif_encode_raw_planes_8.argtypes = [C.POINTER(_RavifEncoder), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint8, C.c_uint8, C.POINTER(_EncodedImage)]
-    L.mi_ravif_encode_raw_planes_10.argtypes = L.mi_ravif_encode_raw_planes_8.argtypes
-    L.mi_batch_create.argtypes = [C.POINTER(_RavifEncoder), C.c_int, C.c_uint32, C.c_uint32, C.c_int]
-    L.mi_batch_create.restype = C.c_void_p
-    L.mi_batch_upload.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
-    L.mi_batch_input.argtypes = [C.c_void_p, C.c_int]
-    L.mi_batch_input.restype = C.c_void_p
-    L.mi_batch_upload_async.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    L.mi_batch_set_count.argtypes = [C.c_void_p, C.c_int]
-    L.mi_batch_encode.argtypes = [C.c_void_p]
-    L.mi_batch_encode_async.argtypes = [C.c_void_p]
-    L.mi_batch_wait.argtypes = [C.c_void_p]
-    L.mi_batch_get.argtypes = [C.c_void_p, C.c_int, C.POINTER(_EncodedImage)]
-    L.mi_batch_get_recon.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.POINTER(C.c_uint16))]
-    L.mi_batch_stage_ms.argtypes = [C.c_void_p, C.c_int]
-    L.mi_batch_stage_ms.restype = C.c_double
-    L.mi_batch_num_tiles.argtypes = [C.c_void_p]
-    L.mi_batch_tile_clocks.argtypes = [C.c_void_p, C.c_void_p]
-    if hasattr(L, 'mi_batch_phase_profile'):
-        L.mi_batch_phase_profile.argtypes = [C.c_void_p, C.c_void_p]
-    L.mi_batch_destroy.argtypes = [C.c_void_p]
-    L.mi_avif_serialize.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint8,
-                                    C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.POINTER(C.c_uint8))]
-    L.mi_avif_serialize.restype = C.c_size_t
-    L.mi_free.argtypes = [C.c_void_p]
-    for fn in (L.mi_jpeg_decode_rgba, L.mi_image_decode_rgba):
-        fn.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    L.mi_jpeg_parse.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    L.mi_jpeg_coeffs_free.argtypes = [C.c_void_p]
-    L.mi_jpeg_coeffs_free.restype = None
-    L.mi_batch_device_input.argtypes = [C.c_void_p, C.c_int]
-    L.mi_batch_device_input.restype = C.c_void_p
-    L.mi_batch_read_input.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    L.mi_batch_upload_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(_DevicePixels)]
-    L.mi_batch_upload_jpeg.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    L.mi_png_parse.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
-    L.mi_png_scanlines_free.argtypes = [C.c_void_p]
-    L.mi_png_scanlines_free.restype = None
-    L.mi_batch_upload_png.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-    L.mi_ravif_encode_device.argtypes = [C.POINTER(_RavifEncoder), C.POINTER(_DevicePixels), C.c_uint32, C.c_uint32, C.POINTER(_EncodedImage)]
-    L.mi_batch_resize_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(_DevicePixels), C.c_uint32, C.c_uint32, C.c_int]
-    L.mi_batch_resize_jpeg.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-    L.mi_batch_resize_png.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-    L.mi_ravif_encode_device_resized.argtypes = [C.POINTER(_RavifEncoder), C.POINTER(_DevicePixels), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_EncodedImage)]
-    L.mi_batch_measure.argtypes = [C.c_void_p]
-    L.mi_batch_get_quality.argtypes = [C.c_void_p, C.c_int, C.POINTER(_ImageQuality)]
-    L.mi_batch_get_source.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.POINTER(C.c_uint16))]
-    for fn in (L.mi_quality_psnr_db, L.mi_quality_ssim_db):
-        fn.argtypes = [C.POINTER(_ImageQuality)]
-        fn.restype = C.c_double
-    L.mi_batch_uses_alpha.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-    L.mi_batch_decode_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(_DeviceTarget)]
-    L.mi_batch_decode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
-    L.mi_ravif_encode_sources.argtypes = [C.POINTER(_RavifEncoder), C.c_size_t, _FETCH_SOURCE, _RELEASE, C.c_void_p, C.POINTER(_EncodedImage),
-                                          C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
-    L.mi_batch_set_input_kind.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
-    L.mi_batch_input_kind.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-    L.mi_batch_upload_jpeg_ycbcr.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    L.mi_jpeg_coeffs_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.mi_batch_upload_device_ycbcr.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(_DevicePlanes)]
-    L.mi_batch_device_input16.argtypes = [C.c_void_p, C.c_int]
-    L.mi_batch_device_input16.restype = C.c_void_p
-    L.mi_batch_read_input16.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    L.mi_batch_footprint.argtypes = [C.c_void_p]
-    L.mi_batch_footprint.restype = C.c_size_t
-    L.mi_batch_upload_device16.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(_DevicePixels16)]
-    L.mi_batch_upload16.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int]
-    L.mi_batch_upload_png_deep.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-    L.mi_png_scanlines_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.mi_ravif_encode_device16.argtypes = [C.POINTER(_RavifEncoder), C.POINTER(_DevicePixels16), C.c_uint32, C.c_uint32, C.POINTER(_EncodedImage)]
-    L.mi_ravif_encode_device_ycbcr.argtypes = [C.POINTER(_RavifEncoder), C.POINTER(_DevicePlanes), C.c_uint32, C.c_uint32, C.POINTER(_EncodedImage)]
-    L.mi_batch_upload_device_ycbcr16.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(_DevicePlanes16)]
-    L.mi_ravif_encode_device_ycbcr16.argtypes = [C.POINTER(_RavifEncoder), C.POINTER(_DevicePlanes16), C.c_uint32, C.c_uint32, C.POINTER(_EncodedImage)]
-    L.mi_colour_transform_from_icc.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p)]
-    L.mi_colour_transform_from_png.argtypes = [C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_void_p)]
-    L.mi_colour_transform_free.argtypes = [C.c_void_p]
-    L.mi_colour_transform_free.restype = None
-    L.mi_colour_transform_is_identity.argtypes = [C.c_void_p]
-    L.mi_colour_probe_icc.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_int)]
-    L.mi_colour_probe_png.argtypes = [C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int)]
-    L.mi_colour_transform_table.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
-    L.mi_colour_transform_table.restype = C.c_size_t
-    L.mi_png_scanlines_colour.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    L.mi_jpeg_coeffs_icc.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
-    L.mi_batch_convert_colour.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    L.mi_exif_orientation.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_int)]
-    L.mi_jpeg_coeffs_orientation.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
-    L.mi_png_scanlines_orientation.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
-    L.mi_oriented_size.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    L.mi_oriented_size.restype = None
-    L.mi_batch_orient_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(_DevicePixels), C.c_int]
-    L.mi_batch_upload_jpeg_oriented.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
-    L.mi_batch_upload_png_oriented.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
+    for name, (restype, argtypes) in _PROTOTYPES.items():
+        if name == 'mi_batch_phase_profile' and not hasattr(L, name):      # only a profiling build exports it
+            continue
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = (C.c_int if restype is _STATUS else restype), argtypes
     _LIB = L
     return L
 
@@ -218,9 +225,7 @@ def quality_to_quantizer(quality):
 
 def tweaks_from_preset(speed, quantizer):
     c = _Av1Config()
-    st = load_library().mi_av1_tweaks_from_preset(speed, quantizer, C.byref(c))
-    if st:
-        raise AvifError(st)
+    _ok(load_library().mi_av1_tweaks_from_preset(speed, quantizer, C.byref(c)))
     return {k: getattr(c, k) for k in ('part_min', 'part_max', 'complex_pred_modes', 'sgr_full', 'encode_bottomup', 'rdo_tx_decision',
                                        'reduced_tx_set', 'fine_directional_intra', 'fast_deblock', 'lrf', 'cdef', 'inter_tx_split',
                                        'tx_domain_rate', 'min_tile_size')}
@@ -237,9 +242,7 @@ def _decode(fn, data, device):
     data = bytes(data)
     out = C.POINTER(C.c_uint8)()
     w, h = C.c_uint32(), C.c_uint32()
-    st = fn(data, len(data), int(device), C.byref(out), C.byref(w), C.byref(h))
-    if st:
-        raise AvifError(st)
+    _ok(fn(data, len(data), int(device), C.byref(out), C.byref(w), C.byref(h)))
     a = np.ctypeslib.as_array(out, shape=(h.value, w.value, 4)).copy()
     load_library().mi_free(out)
     return a
@@ -250,9 +253,7 @@ def exif_orientation(exif):
     tag 0x0112 in IFD0 (never an error)"""
     exif = bytes(exif)
     o = C.c_int(1)
-    st = load_library().mi_exif_orientation(exif, len(exif), C.byref(o))
-    if st:
-        raise AvifError(st)
+    _ok(load_library().mi_exif_orientation(exif, len(exif), C.byref(o)))
     return o.value
 
 
@@ -265,9 +266,7 @@ def oriented_size(width, height, orientation):
 
 def _handle_orientation(fn, handle):
     o = C.c_int(1)
-    st = fn(handle, C.byref(o))
-    if st:
-        raise AvifError(st)
+    _ok(fn(handle, C.byref(o)))
     return o.value
 
 
@@ -282,35 +281,14 @@ def load_rgba(data, device=0):
     return _decode(load_library().mi_image_decode_rgba, data, device)
 
 
-class JpegCoeffs:
-    """One parsed JPEG file (mi_jpeg_parse): quantised coefficients in host memory, `width`, `height`, `color` ('grey', 'ycbcr' or 'rgb': what the file's
-    components are), `subsampling` ((hsub, vsub): luma samples per chroma sample) and `orientation` (1..8: what the file's first Exif segment asks for, 1 when it
-    says nothing; width and height are the stored ones).  Feeds BatchEncoder.upload_jpeg and encode_many; its pixels come
-    into being on the device.  close() (or the garbage collector) frees it."""
-    COLORS = ('grey', 'ycbcr', 'rgb')
-
-    def __init__(self, data):
-        L = load_library()
-        data = bytes(data)
-        h = C.c_void_p()
-        w, ht = C.c_uint32(), C.c_uint32()
-        st = L.mi_jpeg_parse(data, len(data), C.byref(h), C.byref(w), C.byref(ht))
-        if st:
-            raise AvifError(st)
-        self._L, self._h, self.width, self.height = L, h.value, w.value, ht.value
-        color, hs, vs = C.c_int(), C.c_int(), C.c_int()
-        st = L.mi_jpeg_coeffs_info(self._h, C.byref(color), C.byref(hs), C.byref(vs))
-        if st:
-            raise AvifError(st)
-        self.color, self.subsampling = self.COLORS[color.value], (hs.value, vs.value)
-        p, n = C.c_void_p(), C.c_size_t()
-        L.mi_jpeg_coeffs_icc(self._h, C.byref(p), C.byref(n))
-        self.icc_profile = C.string_at(p.value, n.value) if p.value and n.value else None   # the file's APP2 ICC profile, or None
-        self.orientation = _handle_orientation(L.mi_jpeg_coeffs_orientation, self._h)
+class _Handle:
+    """Owner of one C object: `_h` (None once it is freed) of library `_L`, released by the C function `_free` names.  close() may be called any number of
+    times, and on an object whose __init__ raised before it had a handle; the garbage collector and a `with` block close too."""
+    _free = None
 
     def close(self):
         if getattr(self, '_h', None):
-            self._L.mi_jpeg_coeffs_free(self._h)
+            getattr(self._L, self._free)(self._h)
             self._h = None
 
     def __del__(self):
@@ -318,6 +296,43 @@ class JpegCoeffs:
             self.close()
         except Exception:
             pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def _live(x, T):
+    """the C handle of `x`, which must be a T (a class, or a tuple of them) that has not been closed"""
+    if not isinstance(x, T) or not x._h:
+        raise AvifError(4)
+    return x._h
+
+
+class JpegCoeffs(_Handle):
+    """One parsed JPEG file (mi_jpeg_parse): quantised coefficients in host memory, `width`, `height`, `color` ('grey', 'ycbcr' or 'rgb': what the file's
+    components are), `subsampling` ((hsub, vsub): luma samples per chroma sample) and `orientation` (1..8: what the file's first Exif segment asks for, 1 when it
+    says nothing; width and height are the stored ones).  Feeds BatchEncoder.upload_jpeg and encode_many; its pixels come
+    into being on the device.  close() (or the garbage collector) frees it."""
+    COLORS = ('grey', 'ycbcr', 'rgb')
+    _free = 'mi_jpeg_coeffs_free'
+
+    def __init__(self, data):
+        L = load_library()
+        data = bytes(data)
+        h = C.c_void_p()
+        w, ht = C.c_uint32(), C.c_uint32()
+        _ok(L.mi_jpeg_parse(data, len(data), C.byref(h), C.byref(w), C.byref(ht)))
+        self._L, self._h, self.width, self.height = L, h.value, w.value, ht.value
+        color, hs, vs = C.c_int(), C.c_int(), C.c_int()
+        _ok(L.mi_jpeg_coeffs_info(self._h, C.byref(color), C.byref(hs), C.byref(vs)))
+        self.color, self.subsampling = self.COLORS[color.value], (hs.value, vs.value)
+        p, n = C.c_void_p(), C.c_size_t()
+        L.mi_jpeg_coeffs_icc(self._h, C.byref(p), C.byref(n))                               # status unread: a live handle with both outputs has nothing to refuse
+        self.icc_profile = C.string_at(p.value, n.value) if p.value and n.value else None   # the file's APP2 ICC profile, or None
+        self.orientation = _handle_orientation(L.mi_jpeg_coeffs_orientation, self._h)
 
 
 def parse_jpeg(data):
@@ -325,41 +340,29 @@ def parse_jpeg(data):
     return JpegCoeffs(data)
 
 
-class PngScanlines:
+class PngScanlines(_Handle):
     """One parsed PNG file (mi_png_parse): the inflated scanlines in host memory, `width`, `height`, `has_alpha` (an alpha channel or a tRNS chunk),
     `color_type` and `bit_depth` of the file (bit depth 16 is what upload_png(deep=True) sends through the deep slots), `orientation` (1..8: what the file's
     first eXIf chunk asks for, 1 when it says nothing).  Feeds
     BatchEncoder.upload_png and encode_many; the filters are undone and the pixels made on the device.  close() (or the garbage collector) frees it."""
+    _free = 'mi_png_scanlines_free'
 
     def __init__(self, data):
         L = load_library()
         data = bytes(data)
         h = C.c_void_p()
         w, ht, alpha = C.c_uint32(), C.c_uint32(), C.c_int()
-        st = L.mi_png_parse(data, len(data), C.byref(h), C.byref(w), C.byref(ht), C.byref(alpha))
-        if st:
-            raise AvifError(st)
+        _ok(L.mi_png_parse(data, len(data), C.byref(h), C.byref(w), C.byref(ht), C.byref(alpha)))
         self._L, self._h, self.width, self.height, self.has_alpha = L, h.value, w.value, ht.value, bool(alpha.value)
         ct, bd = C.c_int(), C.c_int()
-        L.mi_png_scanlines_info(self._h, C.byref(ct), C.byref(bd))
+        L.mi_png_scanlines_info(self._h, C.byref(ct), C.byref(bd))                          # status unread: it refuses a null handle only
         self.color_type, self.bit_depth = ct.value, bd.value
         # what the file says about its colour: None, ('icc', bytes), ('srgb',) or ('gamma', file_gamma, the eight cHRM values or None); a profile that inflates
-        # beyond 4 MiB shows as ('icc', None)
+        # beyond 4 MiB shows as ('icc', None): the call's status (Unsupported for such a profile) is left unread, the file itself still encodes
         what, p, n, g, chrm = C.c_int(), C.c_void_p(), C.c_size_t(), C.c_double(), (C.c_double * 8)()
         L.mi_png_scanlines_colour(self._h, C.byref(what), C.byref(p), C.byref(n), C.byref(g), chrm)
         self.colour = (None, ('icc', C.string_at(p.value, n.value) if p.value else None), ('srgb',), ('gamma', g.value, tuple(chrm) if any(chrm) else None))[what.value]
         self.orientation = _handle_orientation(L.mi_png_scanlines_orientation, self._h)
-
-    def close(self):
-        if getattr(self, '_h', None):
-            self._L.mi_png_scanlines_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def parse_png(data):
@@ -372,11 +375,12 @@ def _colour_of(handle):
     return handle.colour if isinstance(handle, PngScanlines) else ('icc', handle.icc_profile) if handle.icc_profile else None
 
 
-class ColourTransform:
+class ColourTransform(_Handle):
     """A colour description baked into a transform to sRGB (mi_colour_transform): host state, applied to batch slots on the device by
     BatchEncoder.convert_colour.  from_icc(bytes): an ICC v2 / v4 RGB matrix/TRC profile (any other well-formed profile raises Unsupported, a malformed one
     EncodingError); from_png(gamma, chrm=None): a gAMA value with the eight cHRM values or None; for_source(handle): what a PngScanlines or JpegCoeffs says
     about itself (the identity when it says nothing).  `is_identity`: converting is a no-op.  close() (or the garbage collector) frees it."""
+    _free = 'mi_colour_transform_free'
 
     def __init__(self, handle):
         self._L, self._h = load_library(), handle
@@ -387,9 +391,7 @@ class ColourTransform:
         L = load_library()
         profile = bytes(profile)
         h = C.c_void_p()
-        st = L.mi_colour_transform_from_icc(profile, len(profile), C.byref(h))
-        if st:
-            raise AvifError(st)
+        _ok(L.mi_colour_transform_from_icc(profile, len(profile), C.byref(h)))
         return cls(h.value)
 
     @classmethod
@@ -401,9 +403,7 @@ class ColourTransform:
             if len(chrm) != 8:
                 raise AvifError(4)
             c = (C.c_double * 8)(*[float(v) for v in chrm])
-        st = L.mi_colour_transform_from_png(float(gamma), c, C.byref(h))
-        if st:
-            raise AvifError(st)
+        _ok(L.mi_colour_transform_from_png(float(gamma), c, C.byref(h)))
         return cls(h.value)
 
     @classmethod
@@ -427,25 +427,15 @@ class ColourTransform:
         a = np.frombuffer(C.string_at(p.value, n * np.dtype(dt).itemsize), dtype=dt).copy()
         return a.reshape(3, -1) if which in (0, 1, 3) else a
 
-    def close(self):
-        if getattr(self, '_h', None):
-            self._L.mi_colour_transform_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 RESAMPLE_FILTERS = {'box': 0, 'bilinear': 1, 'bicubic': 2, 'lanczos': 3}       # MI_RESAMPLE_*: Pillow's filters of the same names
 
 
-def _resample_filter(name):
-    if name not in RESAMPLE_FILTERS:
+def _named(table, name):
+    """the C constant `name` stands for in RESAMPLE_FILTERS or DECODED_WHICH"""
+    if name not in table:
         raise AvifError(4)
-    return RESAMPLE_FILTERS[name]
+    return table[name]
 
 
 def _is_device_array(x):
@@ -460,10 +450,32 @@ _SOURCE_HANDLE_FIELD = {SOURCE_HOST: None, SOURCE_JPEG: 'jpeg', SOURCE_PNG: 'png
                         SOURCE_JPEG_MANAGED: 'jpeg', SOURCE_PNG_MANAGED: 'png', SOURCE_PNG_DEEP_MANAGED: 'png'}                      # the kind's handle (None: host pixels in desc)
 
 
-def _decoded_which(name):
-    if name not in DECODED_WHICH:
+def _cai(x, item, what):
+    """(pointer, shape, byte strides, device index or None) of an object with __cuda_array_interface__ whose samples are uint8 (item 1) or little-endian uint16
+    (item 2); `what` is the TypeError's text for any other typestr, with a %r for it.  Strides left out are those of a C-contiguous array.  A null pointer,
+    a negative stride and an empty or missing dimension raise AvifError(4)."""
+    ai = x.__cuda_array_interface__
+    if ai.get('typestr') != ('|u1', '<u2')[item - 1]:
+        raise TypeError(what % (ai.get('typestr'),))
+    shape = tuple(int(v) for v in ai['shape'])
+    strides = ai.get('strides')
+    if strides is None:
+        strides, acc = [], item
+        for n in reversed(shape):
+            strides.insert(0, acc); acc *= n
+    strides = tuple(int(v) for v in strides)
+    if not ai['data'][0] or not shape or min(shape) < 1 or min(strides) < 0:
         raise AvifError(4)
-    return DECODED_WHICH[name]
+    return ai['data'][0], shape, strides, getattr(getattr(x, 'device', None), 'index', None)
+
+
+def _after_stream(index):
+    """torch's current stream on device `index`, for the after_stream of a device view: None for the default stream and for a caller without torch, which is
+    never imported here -- only a caller that has torch can hand over torch's work"""
+    torch = sys.modules.get('torch')
+    if torch is not None and hasattr(torch, 'cuda') and torch.cuda.is_available():
+        return torch.cuda.current_stream(index).cuda_stream or None
+    return None
 
 
 def _device_pixels(x, batched=False, writable=False, deep_ok=False):
@@ -476,24 +488,13 @@ def _device_pixels(x, batched=False, writable=False, deep_ok=False):
     if writable and ai['data'][1]:
         raise ValueError('the target array is read-only')
     deep = ai.get('typestr') == '<u2' and deep_ok and not writable
-    if ai.get('typestr') != '|u1' and not deep:
-        raise TypeError('device pixels must be uint8%s (got typestr %r): rounding floats is the caller\'s decision' % (' or uint16' if deep_ok else '', ai.get('typestr'),))
     item = 2 if deep else 1
-    shape = tuple(int(v) for v in ai['shape'])
-    strides = ai.get('strides')
-    if strides is None:
-        strides, acc = [], item
-        for n in reversed(shape):
-            strides.insert(0, acc); acc *= n
-    strides = tuple(int(v) for v in strides)
+    ptr, shape, strides, index = _cai(x, item, 'device pixels must be uint8%s (got typestr %%r): rounding floats is the caller\'s decision' % (' or uint16' if deep_ok else ''))
     if len(shape) == 4 and batched:
         n, img_stride, shape, strides = shape[0], strides[0], shape[1:], strides[1:]
     elif len(shape) == 3:
         n, img_stride = 1, 0
     else:
-        raise AvifError(4)
-    ptr = ai['data'][0]
-    if not ptr or min(strides) < 0 or img_stride < 0 or min(shape) < 1 or n < 1:
         raise AvifError(4)
     if shape[0] in (3, 4) and shape[2] not in (3, 4):
         (c, h, w), (sc, sh, sw) = shape, strides
@@ -515,11 +516,8 @@ def _device_pixels(x, batched=False, writable=False, deep_ok=False):
         raise AvifError(4)
     if n > 1 and img_stride == 0:
         raise AvifError(4)
-    torch = sys.modules.get('torch')                               # never imported here: only a caller that has torch can hand over torch's work
-    if torch is not None and hasattr(torch, 'cuda') and torch.cuda.is_available():
-        idx = getattr(getattr(x, 'device', None), 'index', None)
-        d.after_stream = torch.cuda.current_stream(idx).cuda_stream or None
-    return d, n, h, w, getattr(getattr(x, 'device', None), 'index', None)
+    d.after_stream = _after_stream(index)
+    return d, n, h, w, index
 
 
 def _widen16(a, bits=16, msb_aligned=False):
@@ -534,25 +532,6 @@ def _widen16(a, bits=16, msb_aligned=False):
     return ((v << (16 - bits)) | (v >> (2 * bits - 16))).astype(np.uint16)
 
 
-def _plane_view(x, what, item=1):
-    """(pointer, shape, byte strides, device index or None) of a uint8 (item 1) or little-endian uint16 (item 2) object with __cuda_array_interface__"""
-    ai = x.__cuda_array_interface__
-    if ai.get('typestr') != ('|u1', '<u2')[item - 1]:
-        if ai.get('typestr') in ('|u1', '<u2'):
-            raise AvifError(4)                                     # the planes of one picture share their sample type
-        raise TypeError('%s must be uint8 or uint16 (got typestr %r)' % (what, ai.get('typestr')))
-    shape = tuple(int(v) for v in ai['shape'])
-    strides = ai.get('strides')
-    if strides is None:
-        strides, acc = [], item
-        for n in reversed(shape):
-            strides.insert(0, acc); acc *= n
-    strides = tuple(int(v) for v in strides)
-    if not ai['data'][0] or not shape or min(shape) < 1 or min(strides) < 0:
-        raise AvifError(4)
-    return ai['data'][0], shape, strides, getattr(getattr(x, 'device', None), 'index', None)
-
-
 def _device_planes(y, cb, cr, subsampling):
     """(_DevicePlanes, images, height, width, device index or None) of uint8 device arrays: y (N, H, W) or (H, W); cb and cr of the chroma extent
     ceil(H / vsub) x ceil(W / hsub) with the same leading dimension, or cr=None and cb of shape (..., ch, cw, 2): interleaved (Cb, Cr) pairs.  Columns one sample
@@ -560,7 +539,12 @@ def _device_planes(y, cb, cr, subsampling):
     and narrow_range the caller fills in; a mix of uint8 and uint16 planes raises AvifError(4)."""
     hsub, vsub = (int(v) for v in subsampling)
     item = 2 if y.__cuda_array_interface__.get('typestr') == '<u2' else 1
-    yp, ys, yst, index = _plane_view(y, 'y', item)
+
+    def view(x, what):
+        if x.__cuda_array_interface__.get('typestr') == ('<u2', '|u1')[item - 1]:
+            raise AvifError(4)                                     # the planes of one picture share their sample type
+        return _cai(x, item, what + ' must be uint8 or uint16 (got typestr %r)')
+    yp, ys, yst, index = view(y, 'y')
     if len(ys) not in (2, 3):
         raise AvifError(4)
     n = ys[0] if len(ys) == 3 else 1
@@ -569,7 +553,7 @@ def _device_planes(y, cb, cr, subsampling):
         raise AvifError(4)
     cdims = ((h + vsub - 1) // vsub, (w + hsub - 1) // hsub)
     lead = ys[:-2]
-    cp, cs, cst, _ = _plane_view(cb, 'cb', item)
+    cp, cs, cst, _ = view(cb, 'cb')
     d = _DevicePlanes16() if item == 2 else _DevicePlanes()
     if item == 2:
         d.bits, d.msb_aligned, d.narrow_range = 16, 0, 0
@@ -579,7 +563,7 @@ def _device_planes(y, cb, cr, subsampling):
         cst = cst[:-1]
         d.cr = None
     else:
-        rp, rs, rst, _ = _plane_view(cr, 'cr', item)
+        rp, rs, rst, _ = view(cr, 'cr')
         if cs != lead + cdims or rs != cs or (cst[-1] != item and cdims[1] > 1):
             raise AvifError(4)
         if any(a != b_ for a, b_, m in zip(cst[:-1], rst[:-1], cs[:-1]) if m > 1) or (rst[-1] != item and cdims[1] > 1):
@@ -592,9 +576,7 @@ def _device_planes(y, cb, cr, subsampling):
     d.y, d.cb, d.hsub, d.vsub = yp, cp, hsub, vsub
     d.y_row_stride, d.c_row_stride = (yst[-2] if h > 1 else 0), (cst[-2] if cdims[0] > 1 else 0)
     d.y_image_stride, d.c_image_stride = (yst[0] if n > 1 else 0), (cst[0] if n > 1 else 0)
-    torch = sys.modules.get('torch')                               # never imported here: only a caller that has torch can hand over torch's work
-    if torch is not None and hasattr(torch, 'cuda') and torch.cuda.is_available():
-        d.after_stream = torch.cuda.current_stream(index).cuda_stream or None
+    d.after_stream = _after_stream(index)
     return d, n, h, w, index
 
 
@@ -716,9 +698,7 @@ def encode_planes(planes, bit_depth=8, quantizer=121, speed=4, mono=False, matri
     c.width, c.height, c.bit_depth, c.quantizer, c.chroma, c.pixel_range = w, h, bit_depth, quantizer, int(mono), 1
     c.has_color_desc = 0 if mono else 1
     c.primaries, c.transfer, c.matrix = 1, 13, matrix
-    st = L.mi_av1_tweaks_from_preset(speed, quantizer, C.byref(c))
-    if st:
-        raise AvifError(st)
+    _ok(L.mi_av1_tweaks_from_preset(speed, quantizer, C.byref(c)))
     c.tiles_override, c.device = tiles, device
     for k, v in over.items():
         setattr(c, k, v)
@@ -729,9 +709,7 @@ def encode_planes(planes, bit_depth=8, quantizer=121, speed=4, mono=False, matri
     obu = C.POINTER(C.c_uint8)()
     n = C.c_size_t()
     rec = (C.POINTER(C.c_uint16) * 3)()
-    st = L.mi_av1_encode_planes(C.byref(c), ptrs, strides, C.byref(obu), C.byref(n), rec if want_recon else None)
-    if st:
-        raise AvifError(st)
+    _ok(L.mi_av1_encode_planes(C.byref(c), ptrs, strides, C.byref(obu), C.byref(n), rec if want_recon else None))
     data = bytes(bytearray(obu[:n.value]))
     L.mi_free(obu)
     recon = []
@@ -806,23 +784,44 @@ class Encoder:
             e.exif, e.exif_len = C.cast(self._exif_buf, C.c_void_p), len(self.exif)
         return e
 
+    def _call_once(self, fn, index, *args):
+        """one of the C entry points that encode a picture in a single call, fn(encoder, *args, image out), on device `index` where the picture's pointers name
+        one (None: on this encoder's)"""
+        e, img = self._c(), _EncodedImage()
+        if index is not None:
+            e.device = index                            # the pointers belong to that device
+        _ok(fn(C.byref(e), *args, C.byref(img)))
+        return _take(img)
+
     def _encode_device(self, px, channels, bits=16, msb_aligned=False):
         L = load_library()
         d, _, h, w, index = _device_pixels(px, deep_ok=True)
         if d.channels != channels:
             raise AvifError(4)
-        img = _EncodedImage()
-        e = self._c()
-        if index is not None:
-            e.device = index                            # the pointer belongs to that device
-        if isinstance(d, _DevicePixels16):              # uint16 samples: through the deep slot
+        deep = isinstance(d, _DevicePixels16)           # uint16 samples: through the deep slot
+        if deep:
             d.bits, d.msb_aligned = int(bits), int(bool(msb_aligned))
-            st = L.mi_ravif_encode_device16(C.byref(e), C.byref(d), w, h, C.byref(img))
+        return self._call_once(L.mi_ravif_encode_device16 if deep else L.mi_ravif_encode_device, index, C.byref(d), w, h)
+
+    def _one_image(self, pixels):
+        """(a one-image BatchEncoder that holds `pixels`, whether they came from device memory): RGB or RGBA by their channels, a host array or a device array,
+        whose batch is made on the array's own device.  The caller closes the batch."""
+        dev = _is_device_array(pixels)
+        if dev:
+            d, _, h, w, index = _device_pixels(pixels)
+            channels, enc = d.channels, (self if index is None else self.with_device(index))
         else:
-            st = L.mi_ravif_encode_device(C.byref(e), C.byref(d), w, h, C.byref(img))
-        if st:
-            raise AvifError(st)
-        return _take(img)
+            pixels = np.ascontiguousarray(pixels, dtype=np.uint8)
+            if pixels.ndim != 3 or pixels.shape[2] not in (3, 4):
+                raise AvifError(4)
+            (h, w, channels), enc = pixels.shape, self
+        b = BatchEncoder(enc, 1, w, h, channels)
+        try:
+            (b.upload_device if dev else b.upload)(0, pixels)
+        except BaseException:
+            b.close()
+            raise
+        return b, dev
 
     def _encode(self, px, channels, bits=16, msb_aligned=False):
         if _is_device_array(px):                        # pixels in HBM (a torch tensor, ...): never through the host
@@ -831,25 +830,16 @@ class Encoder:
             a = _widen16(np.ascontiguousarray(px), bits, msb_aligned)
             if a.ndim != 3 or a.shape[2] != channels:
                 raise AvifError(4)
-            b = BatchEncoder(self, 1, a.shape[1], a.shape[0], channels)
-            try:
+            with BatchEncoder(self, 1, a.shape[1], a.shape[0], channels) as b:
                 b.upload(0, a)
                 b.encode()
                 return b.get(0)
-            finally:
-                b.close()
         L = load_library()
         a = np.ascontiguousarray(px, dtype=np.uint8)
         if a.ndim != 3 or a.shape[2] != channels:
             raise AvifError(4)
         h, w, _ = a.shape
-        img = _EncodedImage()
-        e = self._c()
-        fn = L.mi_ravif_encode_rgba if channels == 4 else L.mi_ravif_encode_rgb
-        st = fn(C.byref(e), a.ctypes.data, w, h, w, C.byref(img))
-        if st:
-            raise AvifError(st)
-        return _take(img)
+        return self._call_once(L.mi_ravif_encode_rgba if channels == 4 else L.mi_ravif_encode_rgb, None, a.ctypes.data, w, h, w)
 
     def encode_resized(self, source, size, filter='lanczos'):
         """`source` resampled to size = (width, height) on the device, then encoded: the file of encode_rgb / encode_rgba over the pixels Pillow's
@@ -857,52 +847,30 @@ class Encoder:
         size; encoded as RGB or RGBA by its channels), a JpegCoeffs (RGB) or a PngScanlines (RGBA when the file has alpha or tRNS, else RGB).
         filter: 'box', 'bilinear', 'bicubic' or 'lanczos'."""
         L = load_library()
-        f = _resample_filter(filter)
+        f = _named(RESAMPLE_FILTERS, filter)
         w, h = int(size[0]), int(size[1])
         if w < 1 or h < 1:
             raise AvifError(4)
         if _is_device_array(source):
             d, _, sh, sw, index = _device_pixels(source)
-            img = _EncodedImage()
-            e = self._c()
-            if index is not None:
-                e.device = index                        # the pointer belongs to that device
-            st = L.mi_ravif_encode_device_resized(C.byref(e), C.byref(d), sw, sh, w, h, f, C.byref(img))
-            if st:
-                raise AvifError(st)
-            return _take(img)
+            return self._call_once(L.mi_ravif_encode_device_resized, index, C.byref(d), sw, sh, w, h, f)
         if isinstance(source, JpegCoeffs):
             channels = 3
         elif isinstance(source, PngScanlines):
             channels = 4 if source.has_alpha else 3
         else:
             raise TypeError('encode_resized takes a device array, a JpegCoeffs or a PngScanlines (host pixels: resize them where they are)')
-        b = BatchEncoder(self, 1, w, h, channels)       # the handle forms go through a one-image batch
-        try:
+        with BatchEncoder(self, 1, w, h, channels) as b:   # the handle forms go through a one-image batch
             (b.resize_jpeg if isinstance(source, JpegCoeffs) else b.resize_png)(0, source, filter)
             b.encode()
             return b.get(0)
-        finally:
-            b.close()
 
     def encode_measured(self, pixels):
         """(EncodedImage, ImageQuality) of an RGB or RGBA picture (host array or device array, by its channels): the file of encode_rgb / encode_rgba and the
         quality metrics of its reconstruction against the planes the encoder saw, computed on the device (mi_batch_measure); through a one-image batch"""
-        if _is_device_array(pixels):
-            d, _, h, w, index = _device_pixels(pixels)
-            channels, enc = d.channels, (self if index is None else self.with_device(index))
-        else:
-            pixels = np.ascontiguousarray(pixels, dtype=np.uint8)
-            if pixels.ndim != 3 or pixels.shape[2] not in (3, 4):
-                raise AvifError(4)
-            (h, w, channels), enc = pixels.shape, self
-        b = BatchEncoder(enc, 1, w, h, channels)
-        try:
-            (b.upload_device if _is_device_array(pixels) else b.upload)(0, pixels)
+        with self._one_image(pixels)[0] as b:
             b.encode()
             return b.get(0), b.measure()[0]
-        finally:
-            b.close()
 
     def encode_decoded(self, pixels):
         """(EncodedImage, decoded, premultiplied) of an RGB or RGBA picture (host array or device array, by its channels): the file of encode_rgb / encode_rgba
@@ -910,27 +878,16 @@ class Encoder:
         reconstruction (mi_batch_decode / _decode_device).  A numpy array in gives a numpy array out; a device array in gives a device array of
         the same library (torch, cupy) on the same device out, and only the file crosses to the host.  `premultiplied`: the colours are stored premultiplied
         by alpha (the file says so); nothing here undoes that.  Through a one-image batch."""
-        if _is_device_array(pixels):
-            d, _, h, w, index = _device_pixels(pixels)
-            channels, enc = d.channels, (self if index is None else self.with_device(index))
-        else:
-            pixels = np.ascontiguousarray(pixels, dtype=np.uint8)
-            if pixels.ndim != 3 or pixels.shape[2] not in (3, 4):
-                raise AvifError(4)
-            (h, w, channels), enc = pixels.shape, self
-        b = BatchEncoder(enc, 1, w, h, channels)
-        try:
-            (b.upload_device if _is_device_array(pixels) else b.upload)(0, pixels)
+        b, dev = self._one_image(pixels)
+        with b:
             b.encode()
             alpha = b.uses_alpha(0)
-            if _is_device_array(pixels):
-                out = _empty_like_device(pixels, (h, w, 4 if alpha else 3))
+            if dev:
+                out = _empty_like_device(pixels, (b.h, b.w, 4 if alpha else 3))
                 b.decode_into(0, out)
             else:
                 out = b.decoded(0)
             return b.get(0), out, bool(alpha and self.alpha_mode == 2)
-        finally:
-            b.close()
 
     def encode_to_target(self, pixels, target_db, metric='ssim', lo=1, hi=100):
         """The smallest integer quality in [lo, hi] whose encode reaches `target_db` in `metric`: 'ssim' (ImageQuality.ssim_db) or 'psnr' (ImageQuality.psnr_db).
@@ -971,8 +928,7 @@ class Encoder:
         decode_jpeg gives, the file of encode_rgb over them.  One source of kind SOURCE_JPEG_YCBCR or SOURCE_JPEG through mi_ravif_encode_sources (a 3-channel slot).
         oriented=True: the picture is turned on the device as the file's EXIF orientation asks (SOURCE_ORIENTED); a portrait photo comes out upright."""
         c = coeffs_or_bytes if isinstance(coeffs_or_bytes, JpegCoeffs) else JpegCoeffs(coeffs_or_bytes)
-        if not c._h:
-            raise AvifError(4)
+        _live(c, JpegCoeffs)
         return _encode_sources(self, [((SOURCE_JPEG_YCBCR if ycbcr else SOURCE_JPEG) | (SOURCE_ORIENTED if oriented else 0), c, 3)], None)[0]
 
     def encode_managed(self, data_or_handle, deep=False, oriented=False):
@@ -985,32 +941,30 @@ class Encoder:
         if not isinstance(src, (PngScanlines, JpegCoeffs)):
             src = bytes(src)
             src = PngScanlines(src) if src[:8] == b'\x89PNG\r\n\x1a\n' else JpegCoeffs(src)
-        if not src._h:
-            raise AvifError(4)
+        _live(src, (PngScanlines, JpegCoeffs))
         try:
             t = ColourTransform.for_source(src)
         except AvifError as ex:
             if ex.code not in (2, 3):
                 raise
             t = None
-        w, h = oriented_size(src.width, src.height, src.orientation if oriented else 1)
-        b = BatchEncoder(self, 1, w, h, 4 if isinstance(src, PngScanlines) and src.has_alpha else 3)
         try:
-            if isinstance(src, PngScanlines):
-                if oriented:
-                    b.upload_png_oriented(0, src, deep=deep)
+            w, h = oriented_size(src.width, src.height, src.orientation if oriented else 1)
+            with BatchEncoder(self, 1, w, h, 4 if isinstance(src, PngScanlines) and src.has_alpha else 3) as b:
+                if isinstance(src, PngScanlines):
+                    if oriented:
+                        b.upload_png_oriented(0, src, deep=deep)
+                    else:
+                        b.upload_png(0, src, deep=deep)
                 else:
-                    b.upload_png(0, src, deep=deep)
-            else:
-                b.upload_jpeg(0, src, orientation=0 if oriented else None)
-            if t is not None:
-                b.convert_colour(0, t)
-            b.encode()
-            return b.get(0)
+                    b.upload_jpeg(0, src, orientation=0 if oriented else None)
+                if t is not None:
+                    b.convert_colour(0, t)
+                b.encode()
+                return b.get(0)
         finally:
-            b.close()
             if t is not None:
-                t.close()
+                t.close()                               # on every path, after the batch that referenced it
 
     def encode_ycbcr_device(self, y, cb, cr=None, subsampling=(2, 2), bits=16, msb_aligned=False, narrow_range=False):
         """BT.601 planes in device memory (objects with __cuda_array_interface__; see BatchEncoder.upload_device_ycbcr for the shapes and for what bits,
@@ -1021,14 +975,7 @@ class Encoder:
         if n != 1:
             raise AvifError(4)
         deep = _planes16_fill(d, bits, msb_aligned, narrow_range)
-        img = _EncodedImage()
-        e = self._c()
-        if index is not None:
-            e.device = index                            # the pointers belong to that device
-        st = (L.mi_ravif_encode_device_ycbcr16 if deep else L.mi_ravif_encode_device_ycbcr)(C.byref(e), C.byref(d), w, h, C.byref(img))
-        if st:
-            raise AvifError(st)
-        return _take(img)
+        return self._call_once(L.mi_ravif_encode_device_ycbcr16 if deep else L.mi_ravif_encode_device_ycbcr, index, C.byref(d), w, h)
 
     def encode_rgba(self, rgba, bits=16, msb_aligned=False):   # :243; uint16 arrays (host or device) are coded from all `bits` of their samples (deep input)
         return self._encode(rgba, 4, bits, msb_aligned)
@@ -1037,7 +984,6 @@ class Encoder:
         return self._encode(rgb, 3, bits, msb_aligned)
 
     def _raw(self, fn, dt, yuv, alpha, width, height, color_pixel_range, matrix_coefficients):
-        L = load_library()
         a = np.ascontiguousarray(yuv, dtype=dt).reshape(-1)
         if a.size < width * height * 3:
             raise AvifError(1)                          # Error::TooFewPixels
@@ -1046,12 +992,7 @@ class Encoder:
             al = np.ascontiguousarray(alpha, dtype=dt).reshape(-1)
             if al.size < width * height:
                 raise AvifError(1)
-        img = _EncodedImage()
-        e = self._c()
-        st = fn(C.byref(e), width, height, a.ctypes.data, al.ctypes.data if al is not None else None, color_pixel_range, matrix_coefficients, C.byref(img))
-        if st:
-            raise AvifError(st)
-        return _take(img)
+        return self._call_once(fn, None, width, height, a.ctypes.data, al.ctypes.data if al is not None else None, color_pixel_range, matrix_coefficients)
 
     def encode_raw_planes_8_bit(self, width, height, planes, alpha, color_pixel_range=1, matrix_coefficients=6):   # :366
         return self._raw(load_library().mi_ravif_encode_raw_planes_8, np.uint8, planes, alpha, width, height, color_pixel_range, matrix_coefficients)
@@ -1101,8 +1042,7 @@ def encode_many(encoder, images, devices=None, jpeg_ycbcr=False, png_deep=False,
     items = []
     for im in images:
         if isinstance(im, (JpegCoeffs, PngScanlines)):
-            if not im._h:
-                raise AvifError(4)
+            _live(im, (JpegCoeffs, PngScanlines))
             items.append((_source_kind(im, jpeg_ycbcr, png_deep, managed) | (SOURCE_ORIENTED if oriented else 0), im, 4))
             continue
         if _is_device_array(im):
@@ -1135,14 +1075,14 @@ def _encode_sources(encoder, items, devices):
     dev = (C.c_int * len(devices))(*devices) if devices else None
     e = encoder._c()
     st = L.mi_ravif_encode_sources(C.byref(e), len(items), _FETCH_SOURCE(fetch), _RELEASE(), None, out, status, dev, len(devices) if devices else 0)
-    res = [_take(o) if s == 0 else None for o, s in zip(out, status)]
-    if st:
-        raise AvifError(st)
+    res = [_take(o) if s == 0 else None for o, s in zip(out, status)]      # before the call's own status is looked at: every output that was made is taken, its buffer freed
+    _ok(st)
     return res
 
 
-class BatchEncoder:
+class BatchEncoder(_Handle):
     """Device-resident batch (the reference's files.into_par_iter(), src/main.rs:223): upload once, encode many."""
+    _free = 'mi_batch_destroy'
 
     def __init__(self, encoder, n_images, width, height, channels=3):
         self._L = load_library()
@@ -1162,15 +1102,11 @@ class BatchEncoder:
             a = _widen16(np.ascontiguousarray(pixels), bits, msb_aligned)
             if a.ndim != 3 or a.shape[:2] != (self.h, self.w) or a.shape[2] not in (3, 4):
                 raise AvifError(4)
-            st = self._L.mi_batch_upload16(self._h, index, a.ctypes.data, self.w, a.shape[2])
-            if st:
-                raise AvifError(st)
+            _ok(self._L.mi_batch_upload16(self._h, index, a.ctypes.data, self.w, a.shape[2]))
             return
         a = np.ascontiguousarray(pixels, dtype=np.uint8)
         assert a.shape == (self.h, self.w, self.channels)
-        st = self._L.mi_batch_upload(self._h, index, a.ctypes.data, self.w)
-        if st:
-            raise AvifError(st)
+        _ok(self._L.mi_batch_upload(self._h, index, a.ctypes.data, self.w))
 
     def upload_device(self, first, pixels, bits=16, msb_aligned=False):
         """images first.. from an object with __cuda_array_interface__ (a torch tensor of the batch's device): uint8 (H, W, C), (C, H, W), (N, H, W, C) or
@@ -1179,13 +1115,10 @@ class BatchEncoder:
         d, n, h, w, _ = _device_pixels(pixels, batched=True, deep_ok=True)
         if (h, w) != (self.h, self.w):
             raise AvifError(4)
-        if isinstance(d, _DevicePixels16):
+        deep = isinstance(d, _DevicePixels16)
+        if deep:
             d.bits, d.msb_aligned = int(bits), int(bool(msb_aligned))
-            st = self._L.mi_batch_upload_device16(self._h, first, n, C.byref(d))
-        else:
-            st = self._L.mi_batch_upload_device(self._h, first, n, C.byref(d))
-        if st:
-            raise AvifError(st)
+        _ok((self._L.mi_batch_upload_device16 if deep else self._L.mi_batch_upload_device)(self._h, first, n, C.byref(d)))
         self._sources.append(pixels)
 
     def upload_jpeg(self, index, coeffs, ycbcr=False, orientation=None):
@@ -1193,14 +1126,11 @@ class BatchEncoder:
         ycbcr=True: no colour step, the slot holds the file's own (Y, Cb, Cr) and is of input kind 1 (a file whose colour is RGB raises Unsupported).
         orientation (None: the file's is ignored): 1..8, or 0 for the file's own -- the picture is turned on the device (mi_batch_upload_jpeg_oriented) and it is
         the turned picture that has the batch's size"""
-        if not isinstance(coeffs, JpegCoeffs) or not coeffs._h:
-            raise AvifError(4)
+        h = _live(coeffs, JpegCoeffs)
         if orientation is not None:
-            st = self._L.mi_batch_upload_jpeg_oriented(self._h, index, coeffs._h, int(orientation), int(bool(ycbcr)))
+            _ok(self._L.mi_batch_upload_jpeg_oriented(self._h, index, h, int(orientation), int(bool(ycbcr))))
         else:
-            st = (self._L.mi_batch_upload_jpeg_ycbcr if ycbcr else self._L.mi_batch_upload_jpeg)(self._h, index, coeffs._h)
-        if st:
-            raise AvifError(st)
+            _ok((self._L.mi_batch_upload_jpeg_ycbcr if ycbcr else self._L.mi_batch_upload_jpeg)(self._h, index, h))
 
     def upload_device_ycbcr(self, first, y, cb, cr=None, subsampling=(2, 2), bits=16, msb_aligned=False, narrow_range=False):
         """images first.. from 8-bit BT.601 full-range planes in device memory (objects with __cuda_array_interface__): y (N, H, W) or (H, W), cb and cr of
@@ -1214,46 +1144,34 @@ class BatchEncoder:
         if (h, w) != (self.h, self.w):
             raise AvifError(4)
         deep = _planes16_fill(d, bits, msb_aligned, narrow_range)
-        st = (self._L.mi_batch_upload_device_ycbcr16 if deep else self._L.mi_batch_upload_device_ycbcr)(self._h, first, n, C.byref(d))
-        if st:
-            raise AvifError(st)
+        _ok((self._L.mi_batch_upload_device_ycbcr16 if deep else self._L.mi_batch_upload_device_ycbcr)(self._h, first, n, C.byref(d)))
         self._sources.append((y, cb, cr))
 
     def input_kind(self, index):
         """what the samples of slot `index` mean: 0 RGB(A), 1 (Y, Cb, Cr[, 255]), 2 16-bit RGB(A) in the deep slot, 3 canonical 16-bit (Y, Cb, Cr[, 65535]) in
         the deep slot (INPUT_YCBCR16); set by whichever call last filled the slot"""
         v = C.c_int()
-        st = self._L.mi_batch_input_kind(self._h, index, C.byref(v))
-        if st:
-            raise AvifError(st)
+        _ok(self._L.mi_batch_input_kind(self._h, index, C.byref(v)))
         return v.value
 
     def set_input_kind(self, first, count, kind):
         """mi_batch_set_input_kind: for callers that write device_input() themselves"""
-        st = self._L.mi_batch_set_input_kind(self._h, first, count, int(kind))
-        if st:
-            raise AvifError(st)
+        _ok(self._L.mi_batch_set_input_kind(self._h, first, count, int(kind)))
 
     def upload_png(self, first, handles, deep=False):
         """parsed PNG files (parse_png) of the batch's size into slots first..: one H2D, the scanline filters and the sample expansion run on the batch's
         stream, one launch per kernel for all of them.  A file with alpha or tRNS into a 3-channel batch raises InvalidArgument.
         deep=True: files of bit depth 16 fill their deep slots with both bytes of every sample (input kind 2); every other file goes as before."""
         handles = [handles] if isinstance(handles, PngScanlines) else list(handles)
-        if not handles or any(not isinstance(p, PngScanlines) or not p._h for p in handles):
+        if not handles:
             raise AvifError(4)
-        arr = (C.c_void_p * len(handles))(*[p._h for p in handles])
-        st = (self._L.mi_batch_upload_png_deep if deep else self._L.mi_batch_upload_png)(self._h, first, len(handles), arr)
-        if st:
-            raise AvifError(st)
+        arr = (C.c_void_p * len(handles))(*[_live(p, PngScanlines) for p in handles])
+        _ok((self._L.mi_batch_upload_png_deep if deep else self._L.mi_batch_upload_png)(self._h, first, len(handles), arr))
 
     def upload_png_oriented(self, index, handle, orientation=0, deep=False):
         """one parsed PNG into slot `index`, turned on the device by `orientation` (1..8, or 0: what the file's eXIf chunk asks for); the turned picture has the
         batch's size.  deep=True: a file of bit depth 16 goes into its deep slot (input kind 2)"""
-        if not isinstance(handle, PngScanlines) or not handle._h:
-            raise AvifError(4)
-        st = self._L.mi_batch_upload_png_oriented(self._h, index, handle._h, int(orientation), int(bool(deep)))
-        if st:
-            raise AvifError(st)
+        _ok(self._L.mi_batch_upload_png_oriented(self._h, index, _live(handle, PngScanlines), int(orientation), int(bool(deep))))
 
     def orient_device(self, first, pixels, orientation):
         """upload_device for uint8 pictures that are turned by `orientation` (1..8) on their way into the slots: the array holds pictures of the batch's size
@@ -1261,47 +1179,31 @@ class BatchEncoder:
         d, n, h, w, _ = _device_pixels(pixels, batched=True)
         if oriented_size(w, h, orientation) != (self.w, self.h):
             raise AvifError(4)
-        st = self._L.mi_batch_orient_device(self._h, first, n, C.byref(d), int(orientation))
-        if st:
-            raise AvifError(st)
+        _ok(self._L.mi_batch_orient_device(self._h, first, n, C.byref(d), int(orientation)))
         self._sources.append(pixels)
 
     def convert_colour(self, first, transform, count=1):
         """mi_batch_convert_colour: the colour channels of slots first.. through a ColourTransform, in place, on the batch's stream after the uploads that filled
         them; 8-bit and deep slots alike, alpha untouched, the input kind unchanged.  The identity transform launches nothing.  A YCbCr slot, a range past the
         capacity or a call in flight raises InvalidArgument.  The transform is kept referenced until wait()."""
-        if not isinstance(transform, ColourTransform) or not transform._h:
-            raise AvifError(4)
-        st = self._L.mi_batch_convert_colour(self._h, first, count, transform._h)
-        if st:
-            raise AvifError(st)
+        _ok(self._L.mi_batch_convert_colour(self._h, first, count, _live(transform, ColourTransform)))
         self._sources.append(transform)
 
     def resize_device(self, first, pixels, filter='lanczos'):
         """upload_device for pictures of any size (taken from the array): resampled into the slots on the batch's stream, the pixels of Pillow's
         Image.resize((w, h), resample=filter, reducing_gap=None); filter: 'box', 'bilinear', 'bicubic' or 'lanczos'"""
         d, n, h, w, _ = _device_pixels(pixels, batched=True)
-        st = self._L.mi_batch_resize_device(self._h, first, n, C.byref(d), w, h, _resample_filter(filter))
-        if st:
-            raise AvifError(st)
+        _ok(self._L.mi_batch_resize_device(self._h, first, n, C.byref(d), w, h, _named(RESAMPLE_FILTERS, filter)))
         self._sources.append(pixels)
 
     def resize_jpeg(self, index, coeffs, filter='lanczos'):
         """upload_jpeg for a file of any size: decoded and resampled into slot `index` on the batch's stream"""
-        if not isinstance(coeffs, JpegCoeffs) or not coeffs._h:
-            raise AvifError(4)
-        st = self._L.mi_batch_resize_jpeg(self._h, index, coeffs._h, _resample_filter(filter))
-        if st:
-            raise AvifError(st)
+        _ok(self._L.mi_batch_resize_jpeg(self._h, index, _live(coeffs, JpegCoeffs), _named(RESAMPLE_FILTERS, filter)))
 
     def resize_png(self, index, scanlines, filter='lanczos'):
         """upload_png for one file of any size: unfiltered, expanded and resampled into slot `index` on the batch's stream.  A file with alpha or tRNS into
         a 3-channel batch raises InvalidArgument."""
-        if not isinstance(scanlines, PngScanlines) or not scanlines._h:
-            raise AvifError(4)
-        st = self._L.mi_batch_resize_png(self._h, index, scanlines._h, _resample_filter(filter))
-        if st:
-            raise AvifError(st)
+        _ok(self._L.mi_batch_resize_png(self._h, index, _live(scanlines, PngScanlines), _named(RESAMPLE_FILTERS, filter)))
 
     def device_input(self, index):
         """device address (int) of the HBM input slot of image `index`: h * w * channels bytes, rows packed"""
@@ -1312,19 +1214,16 @@ class BatchEncoder:
 
     def read_input(self, index):
         """the slot of image `index` as it is on the device now (blocking D2H): uint8 array (h, w, channels)"""
-        a = np.empty((self.h, self.w, self.channels), np.uint8)
-        st = self._L.mi_batch_read_input(self._h, index, a.ctypes.data)
-        if st:
-            raise AvifError(st)
-        return a
+        return self._read(self._L.mi_batch_read_input, np.uint8, index)
 
     def read_input16(self, index):
         """the deep slot of image `index` as it is on the device now (blocking D2H): uint16 array (h, w, channels), full scale -- (R, G, B[, A]) of input kind 2,
         (Y, Cb, Cr[, 65535]) with chroma centred on 32768 of input kind 3"""
-        a = np.empty((self.h, self.w, self.channels), np.uint16)
-        st = self._L.mi_batch_read_input16(self._h, index, a.ctypes.data)
-        if st:
-            raise AvifError(st)
+        return self._read(self._L.mi_batch_read_input16, np.uint16, index)
+
+    def _read(self, fn, dtype, index):
+        a = np.empty((self.h, self.w, self.channels), dtype)
+        _ok(fn(self._h, index, a.ctypes.data))
         return a
 
     def pinned_input(self, index):
@@ -1336,86 +1235,65 @@ class BatchEncoder:
 
     def upload_async(self, first=0, count=None):
         """enqueue pinned host -> HBM for a range of images on the batch's stream (returns at once)"""
-        st = self._L.mi_batch_upload_async(self._h, first, self.n if count is None else count)
-        if st:
-            raise AvifError(st)
+        _ok(self._L.mi_batch_upload_async(self._h, first, self.n if count is None else count))
 
     def set_count(self, n_images):
-        st = self._L.mi_batch_set_count(self._h, n_images)
-        if st:
-            raise AvifError(st)
+        _ok(self._L.mi_batch_set_count(self._h, n_images))
         self.count = n_images
 
     def encode(self):
         st = self._L.mi_batch_encode(self._h)
-        self._sources = []
-        if st:
-            raise AvifError(st)
+        self._sources = []                           # the run is over whatever its status: nothing reads them any more
+        _ok(st)
 
     def encode_async(self):
-        st = self._L.mi_batch_encode_async(self._h)
-        if st:
-            raise AvifError(st)
+        _ok(self._L.mi_batch_encode_async(self._h))
 
     def wait(self):
         st = self._L.mi_batch_wait(self._h)
-        self._sources = []
-        if st:
-            raise AvifError(st)
+        self._sources = []                           # as in encode()
+        _ok(st)
 
     def get(self, index):
         img = _EncodedImage()
-        st = self._L.mi_batch_get(self._h, index, C.byref(img))
-        if st:
-            raise AvifError(st)
+        _ok(self._L.mi_batch_get(self._h, index, C.byref(img)))
         return _take(img)
 
-    def recon(self, index, alpha=False):
-        rec = (C.POINTER(C.c_uint16) * 3)()
-        st = self._L.mi_batch_get_recon(self._h, index, int(alpha), rec)
-        if st:
-            raise AvifError(st)
+    def _planes(self, fn, index, alpha):
+        """copies of the up to three planes fn allocates for image `index` (its alpha frame when `alpha`)"""
+        planes = (C.POINTER(C.c_uint16) * 3)()
+        _ok(fn(self._h, index, int(alpha), planes))
         out = []
-        for i in range(3):
-            if rec[i]:
-                out.append(np.ctypeslib.as_array(rec[i], shape=(self.h, self.w)).copy())
-                self._L.mi_free(rec[i])
+        for p in planes:
+            if p:
+                out.append(np.ctypeslib.as_array(p, shape=(self.h, self.w)).copy())
+                self._L.mi_free(p)
         return out
+
+    def recon(self, index, alpha=False):
+        return self._planes(self._L.mi_batch_get_recon, index, alpha)
 
     def source(self, index, alpha=False):
         """the planes the encoder saw (mi_batch_get_source): what recon() is compared with"""
-        src = (C.POINTER(C.c_uint16) * 3)()
-        st = self._L.mi_batch_get_source(self._h, index, int(alpha), src)
-        if st:
-            raise AvifError(st)
-        out = []
-        for i in range(3):
-            if src[i]:
-                out.append(np.ctypeslib.as_array(src[i], shape=(self.h, self.w)).copy())
-                self._L.mi_free(src[i])
-        return out
+        return self._planes(self._L.mi_batch_get_source, index, alpha)
 
     def uses_alpha(self, index):
         """whether image `index` of the last encode carries an alpha frame (an RGBA batch's image that is not fully opaque)"""
         v = C.c_int()
-        st = self._L.mi_batch_uses_alpha(self._h, index, C.byref(v))
-        if st:
-            raise AvifError(st)
+        _ok(self._L.mi_batch_uses_alpha(self._h, index, C.byref(v)))
         return bool(v.value)
 
     def decoded(self, index, channels=None, which='recon'):
         """image `index` of the last encode as 8-bit pixels, uint8 array (h, w, c): the final reconstruction (which='recon': what a decoder of the file shows)
         or the source planes (which='source': what the encoder saw) through the inverse colour transform, on the device, then one D2H.
         channels: 3, 4 (A = 255 for an opaque image) or None = 4 if the image uses alpha, else 3; 3 for an image that uses alpha raises InvalidArgument."""
-        w = _decoded_which(which)
+        w = _named(DECODED_WHICH, which)
         if channels is None:
             channels = 4 if self.uses_alpha(index) else 3
         if channels not in (3, 4):
             raise AvifError(4)
         a = np.empty((self.h, self.w, channels), np.uint8)
-        st = self._L.mi_batch_decode(self._h, index, w, channels, a.ctypes.data)
-        if st:
-            raise AvifError(st)
+        _ok(self._L.mi_batch_decode(self._h, index, w, channels, a.ctypes.data))
         return a
 
     def decode_into(self, first, target, which='recon'):
@@ -1425,21 +1303,15 @@ class BatchEncoder:
         d, n, h, w, _ = _device_pixels(target, batched=True, writable=True)
         if (h, w) != (self.h, self.w):
             raise AvifError(4)
-        st = self._L.mi_batch_decode_device(self._h, first, n, _decoded_which(which), C.byref(d))
-        if st:
-            raise AvifError(st)
+        _ok(self._L.mi_batch_decode_device(self._h, first, n, _named(DECODED_WHICH, which), C.byref(d)))
 
     def measure(self):
         """mi_batch_measure + mi_batch_get_quality: the ImageQuality of every image of the last encode, computed on the device"""
-        st = self._L.mi_batch_measure(self._h)
-        if st:
-            raise AvifError(st)
+        _ok(self._L.mi_batch_measure(self._h))
         out = []
         for i in range(self.count):
             q = _ImageQuality()
-            st = self._L.mi_batch_get_quality(self._h, i, C.byref(q))
-            if st:
-                raise AvifError(st)
+            _ok(self._L.mi_batch_get_quality(self._h, i, C.byref(q)))
             pq = lambda p: PlaneQuality(p.sse, p.ssim_sum, p.ssim_windows)
             out.append(ImageQuality(q.width, q.height, q.depth, [pq(q.color[p]) for p in range(q.color_planes)], pq(q.alpha) if q.has_alpha else None))
         return out
@@ -1453,25 +1325,10 @@ class BatchEncoder:
 
     def tile_clocks(self):
         a = np.zeros((self.num_tiles(), 4), dtype=np.uint64)
-        st = self._L.mi_batch_tile_clocks(self._h, a.ctypes.data)
-        if st:
-            raise AvifError(st)
+        _ok(self._L.mi_batch_tile_clocks(self._h, a.ctypes.data))
         return a
 
     def phase_profile(self):
         a = np.zeros((max(self.num_tiles(), 2048), 4, 32), dtype=np.uint64)      # rows: tile jobs (K4 profile) or persistent workgroups (K1 profile); unused rows stay zero
-        st = self._L.mi_batch_phase_profile(self._h, a.ctypes.data)
-        if st:
-            raise AvifError(st)
+        _ok(self._L.mi_batch_phase_profile(self._h, a.ctypes.data))
         return a
-
-    def close(self):
-        if self._h:
-            self._L.mi_batch_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

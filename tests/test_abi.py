@@ -25,6 +25,41 @@ def test_library_exports_all_declared_symbols():
     assert b'gfx950' in L.mi_version()
 
 
+def _declared_prototypes():
+    """{function: number of parameters} of every declaration in include/mi_avif.h; function-pointer parameters are typedefs there, so no declaration nests
+    parentheses"""
+    hdr = open(os.path.join(ROOT, 'include', 'mi_avif.h')).read()
+    hdr = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
+    hdr = re.sub(r'//[^\n]*', '', hdr)
+    found = re.findall(r'\b(mi_[a-z0-9_]+)\s*\(([^()]*)\)\s*;', hdr)
+    assert len(found) == len(set(n for n, _ in found))
+    return {n: 0 if a.strip() in ('', 'void') else a.count(',') + 1 for n, a in found}
+
+
+def test_every_declared_function_is_bound_or_listed_unbound():
+    """the binding's prototype table and its _UNBOUND list cover include/mi_avif.h, each function in exactly one of them (needs no library)"""
+    from cavif_rs_amd import encoder as E
+    declared = _declared_prototypes()
+    assert sorted(declared) == _declared_symbols()                     # the declaration pattern misses none
+    assert len(declared) >= 89
+    assert len(set(E._UNBOUND)) == len(E._UNBOUND)
+    for n in declared:
+        assert (n in E._PROTOTYPES) != (n in E._UNBOUND), '%s: in the prototype table or in _UNBOUND, and in one of them only' % n
+    assert set(E._UNBOUND) <= set(declared)
+
+
+def test_prototype_table_matches_the_header():
+    """ctypes accepts a prototype with the wrong number of arguments silently: every entry has as many argtypes as the header declares parameters"""
+    from cavif_rs_amd import encoder as E
+    declared = _declared_prototypes()
+    for n, (restype, argtypes) in E._PROTOTYPES.items():
+        if n == 'mi_batch_phase_profile':                              # a profiling build's extra export: not in the header
+            assert n not in declared
+            continue
+        assert n in declared, '%s is not declared in include/mi_avif.h' % n
+        assert len(argtypes) == declared[n], '%s: %d argtypes, %d parameters declared' % (n, len(argtypes), declared[n])
+
+
 def test_container_matches_oracle(oracle):
     """mi_avif_serialize (avif-serialize stand-in) is byte-identical to the oracle's container writer."""
     import cavif_rs_amd as m
