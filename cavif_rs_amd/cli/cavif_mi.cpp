@@ -1,6 +1,6 @@
 // cavif_mi -- the cavif command line (src/main.rs) on top of libmi_avif.so: same flags, path rules and report line;
 // the rayon fan-out over files (src/main.rs:223) becomes mi_ravif_encode_batch (one host thread per MI355X).
-//   cavif_mi [-Q n] [-s n] [-j n] [-f] [-o path] [-q] [--dirty-alpha] [--color ycbcr|rgb] [--depth 8|10|auto] [--jpeg-ycbcr] [--deep-png] [--color-managed] [--exif-orientation] IMAGES...
+//   cavif_mi [-Q n] [-s n] [-j n] [-f] [-o path] [-q] [--dirty-alpha] [--color ycbcr|rgb] [--depth 8|10|auto] [--jpeg-ycbcr] [--deep-png] [--color-managed] [--exif-orientation] [--mixed-sizes] IMAGES...
 // Input: PNG and baseline / progressive 8-bit JPEG, told apart by their first bytes as load_image does.  A loader thread does the serial half of the
 // decode -- inflate of a PNG (mi_png_parse), Huffman decoding of a JPEG (mi_jpeg_parse) -- and hands scanlines or coefficients to the encoder, which
 // finishes the picture on the GPU inside the batch that encodes it (mi_ravif_encode_sources): the loaders never touch a device.  Differences, deliberate:
@@ -10,6 +10,8 @@
 // their high bytes; a file with an alpha channel or tRNS goes that way only together with --dirty-alpha (the alpha cleaner is defined on 8-bit samples), every
 // other file as without the flag.  `--exif-orientation` (off by default) turns every picture on the GPU as its file's EXIF orientation asks (a JPEG's APP1 Exif segment, a
 // PNG's eXIf chunk), so a portrait photo comes out upright; without it the stored rows are encoded as they are.  It combines with the three flags above.
+// `--mixed-sizes` (off by default) lets the encoder put pictures of different sizes into one run on the GPU (mi_ravif_encoder.mixed_runs) instead of one run
+// per size: a matter of speed on a directory whose files all differ in size; the files written are the same.
 #include <sched.h>
 #include <sys/stat.h>
 #include <cerrno>
@@ -91,12 +93,13 @@ int host_threads() {
 int usage(const char *msg) {
   fprintf(stderr, "error: %s\nusage: cavif_mi [-Q quality 1-100] [-s speed 1-10] [-j threads] [-f|--overwrite] [-o path] [-q] [--dirty-alpha]\n"
                   "                [--color ycbcr|rgb] [--depth 8|10|auto] [--devices 0,1,..] [--rdo-passes 1|2] [--jpeg-ycbcr] [--deep-png] [--color-managed]\n"
-                  "                [--exif-orientation] IMAGES...   (\"-\" = stdin/stdout)\n"
+                  "                [--exif-orientation] [--mixed-sizes] IMAGES...   (\"-\" = stdin/stdout)\n"
                   "  --color-managed  convert every file to sRGB by its own colour description (an ICC profile, or PNG gAMA / cHRM) on the GPU; a file whose profile\n"
                   "                   is unsupported or malformed is encoded unmanaged (one warning line unless -q).  With --jpeg-ycbcr a JPEG whose description\n"
                   "                   asks for a conversion goes the RGB way: the conversion needs RGB.  Combines with --deep-png.\n"
                   "  --exif-orientation  turn every picture on the GPU as its file's EXIF orientation (tag 0x0112) asks; without it the stored rows are encoded as they are.\n"
-                  "                   Combines with --jpeg-ycbcr, --deep-png and --color-managed.\n", msg);
+                  "                   Combines with --jpeg-ycbcr, --deep-png and --color-managed.\n"
+                  "  --mixed-sizes    encode pictures of different sizes in one run on the GPU; the files written are the same.\n", msg);
   return 1;
 }
 
@@ -163,7 +166,7 @@ int main(int argc, char **argv) {
     }
   }
   float quality = 80.f; int speed = 4, threads = 0, depth = 0, color_model = 0, rdo_passes = 1;
-  bool overwrite = false, quiet = false, dirty_alpha = false, have_output = false, output_stdio = false, jpeg_ycbcr = false, deep_png = false, color_managed = false, exif_orientation = false;
+  bool overwrite = false, quiet = false, dirty_alpha = false, have_output = false, output_stdio = false, jpeg_ycbcr = false, deep_png = false, color_managed = false, exif_orientation = false, mixed_sizes = false;
   std::string output; std::vector<std::string> images; std::vector<int> devices;
   // clap syntax (src/main.rs:45-110): --name value, --name=value, -n value, -nvalue, -n=value, combined short flags (-fq)
   std::vector<std::string> args;
@@ -201,6 +204,7 @@ int main(int argc, char **argv) {
     else if (a == "--jpeg-ycbcr") jpeg_ycbcr = true;                                                                                                   // extension: not a cavif flag
     else if (a == "--deep-png") deep_png = true;                                                                                                       // extension: not a cavif flag
     else if (a == "--color-managed") color_managed = true;                                                                                             // extension: not a cavif flag
+    else if (a == "--mixed-sizes") mixed_sizes = true;                                                                                                 // extension: not a cavif flag
     else if (a == "--exif-orientation") exif_orientation = true;                                                                                       // extension: not a cavif flag
     else if (a == "--color") { const std::string v = value("--color"); if (v == "ycbcr") color_model = 0; else if (v == "rgb") color_model = 1; else return usage("bad color type"); }
     else if (a == "--rdo-passes") { rdo_passes = atoi(value("--rdo-passes")); if (rdo_passes < 1 || rdo_passes > 2) return usage("bad --rdo-passes (1 or 2)"); }   // extension: not a cavif flag
@@ -232,7 +236,7 @@ int main(int argc, char **argv) {
   mi_ravif_encoder enc; mi_ravif_encoder_default(&enc);
   enc.quality = quality;
   enc.alpha_quality = std::fmin((quality + 100.f) / 2.f, quality + quality / 4.f + 2.f);                                   // :115
-  enc.speed = (uint8_t)speed; enc.depth = (uint8_t)depth; enc.color_model = (uint8_t)color_model; enc.rdo_passes = rdo_passes;
+  enc.speed = (uint8_t)speed; enc.depth = (uint8_t)depth; enc.color_model = (uint8_t)color_model; enc.rdo_passes = rdo_passes; enc.mixed_runs = mixed_sizes ? 1 : 0;
   enc.alpha_mode = dirty_alpha ? 0 : 1;
   // -j absent or 0: the reference resolves `threads: None` to rayon::current_num_threads() = the host's logical cores (ravif/src/av1encoder.rs:665-668), which bounds
   // the tile target min(T, w*h / min_tile_size^2): the same file on the same host gets the same tiles from `cavif` and from `cavif_mi`

@@ -332,8 +332,10 @@ static int queue_fit(SearchQueue &q, size_t nitems, size_t snap_need, hipStream_
   if (snap_need > q.snap_bytes) { q.snap_bytes = snap_need; HIP_OK(q.d_snap.alloc(snap_need)); }
   return MI_OK;
 }
-static int search_reserve(SearchQueue &q, const std::vector<FramePlan> &frames, int device, hipStream_t s) {
-  size_t per_class[5] = { 0, 0, 0, 0, 0 }, items = 0, snap_need = 0;
+// what the queue of a launch over `frames` needs at most: its work items and the bytes of area snapshots (host only: the grids are asked from the runtime, nothing is launched)
+static int search_demand(const std::vector<FramePlan> &frames, int device, hipStream_t s, size_t &items, size_t &snap_need) {
+  size_t per_class[5] = { 0, 0, 0, 0, 0 };
+  items = snap_need = 0;
   for (const FramePlan &p : frames) { per_class[std::max(p.maxbs, 2)] += (size_t)p.sb_rows * p.sb_cols; items += (size_t)p.sb_rows * p.sb_cols; }
   const int mode = search_mode(frames);
   for (int cls = 2; cls <= 4; cls++) for (int tools : { mode >> 1, (mode >> 1) & ~2 }) {        // a run with fewer frames may run the other instantiation (search_mode)
@@ -341,6 +343,11 @@ static int search_reserve(SearchQueue &q, const std::vector<FramePlan> &frames, 
     HIP_OK(launch_search(cls, (mode & 1) != 0, tools, nullptr, nullptr, nullptr, (int)per_class[cls], nullptr, nullptr, &grid, device, s));
     snap_need = std::max(snap_need, (size_t)grid * k1_snap_bytes(cls));
   }
+  return MI_OK;
+}
+static int search_reserve(SearchQueue &q, const std::vector<FramePlan> &frames, int device, hipStream_t s) {
+  size_t items = 0, snap_need = 0;
+  if (int st = search_demand(frames, device, s, items, snap_need)) return st;
   return queue_fit(q, items, snap_need, s);
 }
 static int search_enqueue(SearchQueue &q, const std::vector<FramePlan> &frames, const std::vector<TileJob> &jobs, const int class_begin[6], const FrameDev *d_frames, const TileJob *d_jobs, int device, hipStream_t s) {
@@ -388,27 +395,35 @@ struct FrameSet {
   int device = 0;
   std::vector<FramePlan> frames; std::vector<TileJob> jobs; int class_begin[6] = { 0, 0, 0, 0, 0, 0 };   // jobs grouped by block-size class (one K1 / K4 instantiation per class)
   DevBuf<uint8_t> d_arena; size_t arena_bytes = 0, aux_bytes = 0;       // aux: pre-carry units + symbol records
-  DevBuf<FrameDev> d_frames; DevBuf<TileJob> d_jobs; DevBuf<uint16_t> d_precarry; uint32_t pre_cap = 0;
+  DevBuf<FrameDev> d_frames; DevBuf<TileJob> d_jobs; DevBuf<uint16_t> d_precarry; uint32_t pre_cap = 0, pre_run = 0;   // pre-carry units per tile job: reserved (the worst case's largest tile), of the placed frames (theirs)
   DevBuf<uint32_t> d_recbuf; uint32_t rec_cap = 0;                      // K4's symbol records: three rotating superblock buffers per tile
   DevBuf<unsigned long long> d_prof;                                    // profiling builds: per tile job (K4) / per persistent workgroup (K1)
   PinBuf<FrameDev> h_frames; PinBuf<TileJob> h_jobs; PinBuf<uint32_t> h_lens; PinBuf<int> h_lf;   // pinned: H2D sources; tile lengths, deblock levels + segment indices (13 per frame)
   SearchQueue queue;
-  size_t tiles_cap = 0, payload_worst = 0;                              // reserved: tile jobs, the sum of their output capacities
+  size_t tiles_cap = 0, payload_worst = 0, frames_cap = 0;              // reserved: tile jobs, the sum of their output capacities, frames
   uint8_t *d_records = nullptr; size_t records_cap = 0;                 // MI_FRAME_RECORD_BYTES per (frame, plane) of the worst case, behind the frames' arenas: what a stage outside
                                                                         // the chain reports per plane (the quality metrics, dev_quality.h); never touched by an encode
   int max_mi_cells = 0, max_sb = 0, max_lr = 0, max_cells = 0, max_tiles = 1;   // launch maxima of the placed frames
 
+  // What a set of planned frames asks of the objects reserve() makes: the one count behind reserve(), which sizes them, and fits(), which holds a set against them
+  struct Demand { size_t arena = 0, tiles = 0, payload = 0, items = 0, snap = 0; uint32_t max_cap = 0; int max_np = 1; };
+  static int demand(std::vector<FramePlan> &set, int dev, hipStream_t s, Demand &d) {
+    d = Demand();
+    for (auto &p : set) {
+      const uint32_t cap = tile_capacity(p);
+      d.arena += align_up(carve(p, nullptr, cap), 4096); d.tiles += (size_t)p.ntiles; d.max_cap = std::max(d.max_cap, cap); d.max_np = std::max(d.max_np, p.np);
+      d.payload += (size_t)p.ntiles * cap;
+    }
+    return search_demand(set, dev, s, d.items, d.snap);
+  }
   // allocates everything for the worst case `worst` (geometry planned): no (device-synchronising) reallocation inside an encode
   int reserve(std::vector<FramePlan> worst, int dev, hipStream_t s) {
     device = dev;
-    size_t total = 0; uint32_t max_cap = 0; int max_np = 1;
-    tiles_cap = payload_worst = 0;
-    for (auto &p : worst) {
-      const uint32_t cap = tile_capacity(p);
-      total += align_up(carve(p, nullptr, cap), 4096); tiles_cap += (size_t)p.ntiles; max_cap = std::max(max_cap, cap); max_np = std::max(max_np, p.np);
-      payload_worst += (size_t)p.ntiles * cap;
-    }
-    pre_cap = max_cap; rec_cap = MI_K4_SB_RECORDS(max_np);
+    Demand d;
+    if (int st = demand(worst, dev, s, d)) return st;
+    size_t total = d.arena; const uint32_t max_cap = d.max_cap;
+    tiles_cap = d.tiles; payload_worst = d.payload; frames_cap = worst.size();
+    pre_cap = pre_run = max_cap; rec_cap = MI_K4_SB_RECORDS(d.max_np);
     const size_t records_off = total;
     records_cap = worst.size() * 3; total += align_up(records_cap * MI_FRAME_RECORD_BYTES, 4096);
     arena_bytes = total; aux_bytes = tiles_cap * (size_t)max_cap * 2 + tiles_cap * 3 * (size_t)rec_cap * 4;
@@ -424,7 +439,17 @@ struct FrameSet {
     HIP_OK(h_lf.alloc(worst.size() * 13));
     HIP_OK(h_frames.alloc(worst.size()));
     HIP_OK(h_jobs.alloc(tiles_cap));
-    return search_reserve(queue, worst, device, s);
+    return queue_fit(queue, d.items, d.snap, s);
+  }
+  // `set` (geometry planned) runs in what reserve() made: the frames' arenas stay in front of the records, and every quantity reserve() sized for its worst case
+  // holds the set's -- frames, tile jobs, payload capacities, the jobs' pre-carry units (one stride for all jobs: the largest tile capacity) and symbol records,
+  // the queue's items and snapshots.  Allocates and launches nothing
+  bool fits(std::vector<FramePlan> set, hipStream_t s) const {
+    Demand d;
+    if (set.empty() || demand(set, device, s, d) != MI_OK) return false;
+    const size_t records_off = arena_bytes - align_up(records_cap * MI_FRAME_RECORD_BYTES, 4096);
+    return set.size() <= frames_cap && d.arena <= records_off && d.tiles <= tiles_cap && d.payload <= payload_worst && d.tiles * (size_t)d.max_cap <= tiles_cap * (size_t)pre_cap &&
+           MI_K4_SB_RECORDS(d.max_np) <= rec_cap && d.items <= queue.items_cap && d.snap <= queue.snap_bytes;
   }
   // carves the arena for `frames`, fills their descriptors, builds the grouped job list (tile_base indexes it) and the launch maxima; host only
   void place() {
@@ -443,8 +468,9 @@ struct FrameSet {
       }
     }
     class_begin[5] = (int)jobs.size();
-    max_mi_cells = max_sb = max_lr = max_cells = 0; max_tiles = 1;
+    max_mi_cells = max_sb = max_lr = max_cells = 0; max_tiles = 1; pre_run = 0;
     for (const FramePlan &p : frames) {
+      pre_run = std::max(pre_run, p.dev.tile_out_cap);
       max_mi_cells = std::max(max_mi_cells, p.mi_cols * p.mi_rows * 4); max_sb = std::max(max_sb, p.sb_cols * p.sb_rows);
       max_cells = std::max(max_cells, (p.pw / 8) * (p.ph / 8)); max_tiles = std::max(max_tiles, p.ntiles);
       if (p.cfg.lrf) max_lr = std::max(max_lr, lr_units_host(p.cfg.width) * lr_units_host(p.cfg.height));
@@ -479,7 +505,7 @@ struct FrameSet {
       HIP_OK(launch_loop_filters(d_frames.get(), nframes, max_mi_cells, max_sb, max_lr, s, ev ? ev[3] : nullptr));
       if (ev) HIP_OK(hipEventRecord(ev[4], s));
       for (int cls = 2; cls <= 4; cls++)
-        HIP_OK(launch_entropy(cls, d_frames.get(), d_jobs.get() + class_begin[cls], class_begin[cls + 1] - class_begin[cls], d_precarry.get() + (size_t)class_begin[cls] * (size_t)pre_cap, pre_cap,
+        HIP_OK(launch_entropy(cls, d_frames.get(), d_jobs.get() + class_begin[cls], class_begin[cls + 1] - class_begin[cls], d_precarry.get() + (size_t)class_begin[cls] * (size_t)pre_run, pre_run,
                               d_recbuf.get() + (size_t)class_begin[cls] * 3 * (size_t)rec_cap, rec_cap, s));
     }
     HIP_OK(hipGetLastError());

@@ -40,11 +40,29 @@ static const auto staging_grow = [](auto &buf /* DevBuf or PinBuf */, size_t &ca
 // ---- the rules the slot-filling calls share ----
 // images [first, first + count) are slots of the batch, and the one-index form (what a call that may run beside an encode in flight asks); the same of a batch
 // with no encode in flight (what every call that fills slots on the stream asks), and its one-index form; the same against the images of a completed encode
-static bool batch_has_slots(const mi_batch *b, int first, int count) { return b && first >= 0 && count >= 1 && first <= b->cap - count; }
+static bool batch_has_slots(const mi_batch *b, int first, int count) { return b && first >= 0 && count >= 1 && first <= batch_slots(b) - count; }
 static bool batch_has_slot(const mi_batch *b, int index) { return batch_has_slots(b, index, 1); }
 static bool batch_range_ok(const mi_batch *b, int first, int count) { return batch_has_slots(b, first, count) && !b->in_flight; }
 static bool batch_index_ok(const mi_batch *b, int index) { return batch_range_ok(b, index, 1); }
 static bool batch_encoded_ok(const mi_batch *b, int first, int count) { return b && !b->in_flight && b->encoded && first >= 0 && count >= 1 && first <= b->n - count; }
+
+// the same for the calls that take a range and describe its pictures with one size: every slot of the range has it (w x h on return)
+static bool batch_range_sized(const mi_batch *b, int first, int count, uint32_t &w, uint32_t &h) {
+  if (!batch_range_ok(b, first, count) || !slots_one_size(b, first, count)) return false;
+  w = slot_w(b, first); h = slot_h(b, first);
+  return true;
+}
+// the bytes of slots [first, first + count): they lie back to back
+static size_t batch_range_samples(const mi_batch *b, int first, int count) { return slot_at(b, first + count - 1) + slot_samples(b, first + count - 1) - slot_at(b, first); }
+
+// fn(from, to) for every maximal stretch [from, to) of neighbours in [0, n) whose key(k) is equal, in index order; the first status that is not MI_OK ends the walk and is returned
+template <class Key, class Fn> static int for_each_group(size_t n, Key key, Fn fn) {
+  for (size_t k = 0, k1; k < n; k = k1) {
+    for (k1 = k + 1; k1 < n && key(k1) == key(k);) k1++;
+    if (const int rc = fn(k, k1)) return rc;
+  }
+  return MI_OK;
+}
 
 // the batch's stream waits for whatever `after_stream` (a producer's or a consumer's hipStream_t, or null) holds at this moment; the event is made on first use
 static int batch_join(mi_batch *b, void *after_stream) {
@@ -84,7 +102,7 @@ template <class Desc, class Dev> static bool strided_resolve(const Desc &src, ui
 // the slot of image `index` in device memory: uint8_t the 8-bit slots, uint16_t the deep ones (made by the first call: nullptr = could not be allocated)
 template <class T> static T *batch_slot(mi_batch *b, int index) {
   if (!batch_has_slot(b, index)) return nullptr;
-  const size_t at = (size_t)index * b->w * b->h * b->channels;
+  const size_t at = slot_at(b, index);
   if constexpr (sizeof(T) == 1) return b->d_pixels.get() + at;
   else { uint16_t *const deep = batch_deep(b); return deep ? deep + at : nullptr; }
 }
@@ -95,7 +113,7 @@ template <class T> static int batch_read_slot(mi_batch *b, int index, T *dst) {
   if (!src) return MI_ENCODING_ERROR;                         // the deep slots could not be made (the 8-bit ones exist since mi_batch_create)
   (void)hipSetDevice(b->device);
   HIP_OK(hipStreamSynchronize(b->stream));
-  HIP_OK(hipMemcpy(dst, src, (size_t)b->w * b->h * b->channels * sizeof(T), hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(dst, src, slot_samples(b, index) * sizeof(T), hipMemcpyDeviceToHost));
   return MI_OK;
 }
 
@@ -108,14 +126,13 @@ uint8_t *mi_batch_input(mi_batch *b, int index) {
     std::lock_guard<std::mutex> lk(b->staging_mu);
     if (!b->h_pixels.get()) { (void)hipSetDevice(b->device); if (b->h_pixels.alloc(b->pixel_bytes) != hipSuccess) return nullptr; }
   }
-  return b->h_pixels.get() + (size_t)index * b->w * b->h * b->channels;
+  return b->h_pixels.get() + slot_at(b, index);
 }
 // enqueue the H2D of images [first, first + count) from the pinned staging on the batch's stream; returns at once
 int mi_batch_upload_async(mi_batch *b, int first, int count) {
   if (!batch_has_slots(b, first, count) || !mi_batch_input(b, first)) return MI_INVALID_ARGUMENT;
   (void)hipSetDevice(b->device);
-  const size_t img = (size_t)b->w * b->h * b->channels;
-  HIP_OK(hipMemcpyAsync(b->d_pixels.get() + first * img, b->h_pixels.get() + first * img, count * img, hipMemcpyHostToDevice, b->stream));
+  HIP_OK(hipMemcpyAsync(b->d_pixels.get() + slot_at(b, first), b->h_pixels.get() + slot_at(b, first), batch_range_samples(b, first, count), hipMemcpyHostToDevice, b->stream));
   batch_tag(b, first, count, MI_INPUT_RGB);
   return MI_OK;
 }
@@ -139,10 +156,10 @@ int mi_batch_input_kind(mi_batch *b, int index, int *kind) {
 }
 int mi_batch_upload(mi_batch *b, int index, const uint8_t *pixels, size_t stride_px) {
   if (!batch_has_slot(b, index) || !pixels) return MI_INVALID_ARGUMENT;
-  const size_t row = (size_t)b->w * b->channels;
+  const size_t row = (size_t)slot_w(b, index) * b->channels;
   uint8_t *dst = mi_batch_input(b, index);
   if (!dst) return MI_ENCODING_ERROR;
-  for (uint32_t y = 0; y < b->h; y++) memcpy(dst + y * row, pixels + (size_t)y * stride_px * b->channels, row);
+  for (uint32_t y = 0; y < slot_h(b, index); y++) memcpy(dst + y * row, pixels + (size_t)y * stride_px * b->channels, row);
   if (int st = mi_batch_upload_async(b, index, 1)) return st;
   HIP_OK(hipStreamSynchronize(b->stream));
   return MI_OK;
@@ -332,12 +349,12 @@ static bool batch_device_source(const mi_batch *b, const mi_device_pixels *src, 
   return strided_resolve(*src, w, h, 1, false, s);
 }
 int mi_batch_upload_device(mi_batch *b, int first, int count, const mi_device_pixels *src) {
-  IngestSrc s;
-  if (!batch_range_ok(b, first, count) || !batch_device_source(b, src, b->w, b->h, s)) return MI_INVALID_ARGUMENT;
+  IngestSrc s; uint32_t w, h;
+  if (!batch_range_sized(b, first, count, w, h) || !batch_device_source(b, src, w, h, s)) return MI_INVALID_ARGUMENT;
   (void)hipSetDevice(b->device);
   if (int st = batch_join(b, src->after_stream)) return st;
   uint8_t *const slots = mi_batch_device_input(b, first);
-  LAUNCH_BY_CHANNELS(b, b->channels, b->w, b->h, count, ingest_kernel, s, slots);
+  LAUNCH_BY_CHANNELS(b, b->channels, w, h, count, ingest_kernel, s, slots);
   HIP_OK(hipGetLastError());
   batch_tag(b, first, count, MI_INPUT_RGB);
   return MI_OK;
@@ -345,21 +362,22 @@ int mi_batch_upload_device(mi_batch *b, int first, int count, const mi_device_pi
 // images [first, first + count) from 8-bit YCbCr planes in the memory of the batch's device: one planes_ingest_kernel launch on the batch's stream, after
 // whatever src->after_stream holds at this moment; the slots are tagged MI_INPUT_YCBCR.  Strides of 0 mean packed.
 int mi_batch_upload_device_ycbcr(mi_batch *b, int first, int count, const mi_device_planes *src) {
-  if (!batch_range_ok(b, first, count) || !src || !src->y || !src->cb || !batch_takes_ycbcr(b)) return MI_INVALID_ARGUMENT;
+  uint32_t w, h;
+  if (!batch_range_sized(b, first, count, w, h) || !src || !src->y || !src->cb || !batch_takes_ycbcr(b)) return MI_INVALID_ARGUMENT;
   if (!((src->hsub == 1 && src->vsub == 1) || (src->hsub == 2 && (src->vsub == 1 || src->vsub == 2)))) return MI_INVALID_ARGUMENT;
   PlanesSrc s;
-  s.w = b->w; s.h = b->h; s.hsub = (uint32_t)src->hsub; s.vsub = (uint32_t)src->vsub;
-  s.cw = (b->w + s.hsub - 1) / s.hsub; s.ch = (b->h + s.vsub - 1) / s.vsub;
+  s.w = w; s.h = h; s.hsub = (uint32_t)src->hsub; s.vsub = (uint32_t)src->vsub;
+  s.cw = (w + s.hsub - 1) / s.hsub; s.ch = (h + s.vsub - 1) / s.vsub;
   s.cpitch = src->cr ? 1 : 2;
   s.y = (const uint8_t *)src->y; s.cb = (const uint8_t *)src->cb; s.cr = src->cr ? (const uint8_t *)src->cr : s.cb + 1;
   const size_t packed_c = (size_t)s.cw * s.cpitch;
-  s.y_row = src->y_row_stride ? src->y_row_stride : b->w; s.c_row = src->c_row_stride ? src->c_row_stride : packed_c;
-  s.y_image = src->y_image_stride ? src->y_image_stride : s.y_row * b->h; s.c_image = src->c_image_stride ? src->c_image_stride : s.c_row * s.ch;
-  if (s.y_row < b->w || s.c_row < packed_c) return MI_INVALID_ARGUMENT;
+  s.y_row = src->y_row_stride ? src->y_row_stride : w; s.c_row = src->c_row_stride ? src->c_row_stride : packed_c;
+  s.y_image = src->y_image_stride ? src->y_image_stride : s.y_row * h; s.c_image = src->c_image_stride ? src->c_image_stride : s.c_row * s.ch;
+  if (s.y_row < w || s.c_row < packed_c) return MI_INVALID_ARGUMENT;
   (void)hipSetDevice(b->device);
   if (int st = batch_join(b, src->after_stream)) return st;
   uint8_t *const slots = mi_batch_device_input(b, first);
-  LAUNCH_BY_CHANNELS(b, b->channels, b->w, b->h, count, planes_ingest_kernel, s, slots);
+  LAUNCH_BY_CHANNELS(b, b->channels, w, h, count, planes_ingest_kernel, s, slots);
   HIP_OK(hipGetLastError());
   batch_tag(b, first, count, MI_INPUT_YCBCR);
   return MI_OK;
@@ -372,18 +390,19 @@ int mi_batch_read_input16(mi_batch *b, int index, uint16_t *dst) { return batch_
 // images [first, first + count) from uint16 pictures in the memory of the batch's device: one ingest16_kernel launch on the batch's stream, after whatever
 // src->after_stream holds at this moment; the slots are tagged MI_INPUT_RGB16.  Every check comes before the deep slots are made: a refused call allocates nothing.
 int mi_batch_upload_device16(mi_batch *b, int first, int count, const mi_device_pixels16 *src) {
-  if (!batch_range_ok(b, first, count) || !src || !src->dev) return MI_INVALID_ARGUMENT;
+  uint32_t w, h;
+  if (!batch_range_sized(b, first, count, w, h) || !src || !src->dev) return MI_INVALID_ARGUMENT;
   if ((src->layout != 0 && src->layout != 1) || !batch_takes_deep(b, src->channels)) return MI_INVALID_ARGUMENT;   // alpha is never dropped; the alpha rules of the kind
   if (src->bits < 8 || src->bits > 16 || (src->msb_aligned != 0 && src->msb_aligned != 1)) return MI_INVALID_ARGUMENT;
   if (((uintptr_t)src->dev | src->row_stride | src->pixel_or_plane_stride | src->image_stride) & 1) return MI_INVALID_ARGUMENT;   // uint16 samples
   Ingest16Src s;
-  s.w = b->w; s.h = b->h; s.bits = src->bits; s.msb_aligned = src->msb_aligned;
-  if (!strided_resolve(*src, b->w, b->h, 2, false, s)) return MI_INVALID_ARGUMENT;
+  s.w = w; s.h = h; s.bits = src->bits; s.msb_aligned = src->msb_aligned;
+  if (!strided_resolve(*src, w, h, 2, false, s)) return MI_INVALID_ARGUMENT;
   uint16_t *const slots = mi_batch_device_input16(b, first);
   if (!slots) return MI_ENCODING_ERROR;
   (void)hipSetDevice(b->device);
   if (int st = batch_join(b, src->after_stream)) return st;
-  LAUNCH_BY_CHANNELS(b, b->channels, b->w, b->h, count, ingest16_kernel, s, slots);
+  LAUNCH_BY_CHANNELS(b, b->channels, w, h, count, ingest16_kernel, s, slots);
   HIP_OK(hipGetLastError());
   batch_tag(b, first, count, MI_INPUT_RGB16);
   return MI_OK;
@@ -392,22 +411,23 @@ int mi_batch_upload_device16(mi_batch *b, int first, int count, const mi_device_
 // copy that carries A = 65535), then the stream is waited for.  No pinned staging of its own.
 int mi_batch_upload16(mi_batch *b, int index, const uint16_t *pixels, size_t stride_px, int channels) {
   if (!batch_index_ok(b, index) || !pixels || !batch_takes_deep(b, channels)) return MI_INVALID_ARGUMENT;
-  if (stride_px == 0) stride_px = b->w;
-  if (stride_px < b->w) return MI_INVALID_ARGUMENT;
+  const uint32_t w = slot_w(b, index), h = slot_h(b, index);
+  if (stride_px == 0) stride_px = w;
+  if (stride_px < w) return MI_INVALID_ARGUMENT;
   uint16_t *const slot = mi_batch_device_input16(b, index);
   if (!slot) return MI_ENCODING_ERROR;
   (void)hipSetDevice(b->device);
-  const size_t row = (size_t)b->w * b->channels * sizeof(uint16_t);
+  const size_t row = (size_t)w * b->channels * sizeof(uint16_t);
   try {                                                       // nothing may unwind through the C ABI
     std::vector<uint16_t> wide;
     if (channels != b->channels) {
-      wide.resize((size_t)b->w * b->h * 4);
-      for (uint32_t y = 0; y < b->h; y++) for (uint32_t x = 0; x < b->w; x++) {
-        const uint16_t *q = pixels + ((size_t)y * stride_px + x) * 3; uint16_t *o = wide.data() + ((size_t)y * b->w + x) * 4;
+      wide.resize((size_t)w * h * 4);
+      for (uint32_t y = 0; y < h; y++) for (uint32_t x = 0; x < w; x++) {
+        const uint16_t *q = pixels + ((size_t)y * stride_px + x) * 3; uint16_t *o = wide.data() + ((size_t)y * w + x) * 4;
         o[0] = q[0]; o[1] = q[1]; o[2] = q[2]; o[3] = 65535;
       }
-      HIP_OK(hipMemcpyAsync(slot, wide.data(), row * b->h, hipMemcpyHostToDevice, b->stream));
-    } else HIP_OK(hipMemcpy2DAsync(slot, row, pixels, stride_px * channels * sizeof(uint16_t), row, b->h, hipMemcpyHostToDevice, b->stream));
+      HIP_OK(hipMemcpyAsync(slot, wide.data(), row * h, hipMemcpyHostToDevice, b->stream));
+    } else HIP_OK(hipMemcpy2DAsync(slot, row, pixels, stride_px * channels * sizeof(uint16_t), row, h, hipMemcpyHostToDevice, b->stream));
     HIP_OK(hipStreamSynchronize(b->stream));
   } catch (const std::exception &) { return MI_ENCODING_ERROR; }
   batch_tag(b, index, 1, MI_INPUT_RGB16);
@@ -431,18 +451,19 @@ static SampleMap16 make_sample_map16(int bits, bool chroma, bool narrow) {
 // whatever src->after_stream holds at this moment; the slots are tagged MI_INPUT_YCBCR16.  Strides of 0 mean packed.  Every check comes before the deep slots
 // are made: a refused call allocates nothing.
 int mi_batch_upload_device_ycbcr16(mi_batch *b, int first, int count, const mi_device_planes16 *src) {
-  if (!batch_range_ok(b, first, count) || !src || !src->y || !src->cb || !batch_takes_ycbcr(b)) return MI_INVALID_ARGUMENT;
+  uint32_t w, h;
+  if (!batch_range_sized(b, first, count, w, h) || !src || !src->y || !src->cb || !batch_takes_ycbcr(b)) return MI_INVALID_ARGUMENT;
   if (!((src->hsub == 1 && src->vsub == 1) || (src->hsub == 2 && (src->vsub == 1 || src->vsub == 2)))) return MI_INVALID_ARGUMENT;
   if (src->bits < 8 || src->bits > 16 || (src->msb_aligned != 0 && src->msb_aligned != 1) || (src->narrow_range != 0 && src->narrow_range != 1)) return MI_INVALID_ARGUMENT;
   if (((uintptr_t)src->y | (uintptr_t)src->cb | (uintptr_t)src->cr | src->y_row_stride | src->c_row_stride | src->y_image_stride | src->c_image_stride) & 1) return MI_INVALID_ARGUMENT;   // uint16 samples
   Planes16Src s;
-  s.w = b->w; s.h = b->h; s.hsub = (uint32_t)src->hsub; s.vsub = (uint32_t)src->vsub;
-  s.cw = (b->w + s.hsub - 1) / s.hsub; s.ch = (b->h + s.vsub - 1) / s.vsub;
+  s.w = w; s.h = h; s.hsub = (uint32_t)src->hsub; s.vsub = (uint32_t)src->vsub;
+  s.cw = (w + s.hsub - 1) / s.hsub; s.ch = (h + s.vsub - 1) / s.vsub;
   s.pairs = src->cr ? 0 : 1;
   s.y = (const uint8_t *)src->y; s.cb = (const uint8_t *)src->cb; s.cr = src->cr ? (const uint8_t *)src->cr : s.cb;
-  const size_t packed_y = (size_t)b->w * 2, packed_c = (size_t)s.cw * (s.pairs ? 4 : 2);
+  const size_t packed_y = (size_t)w * 2, packed_c = (size_t)s.cw * (s.pairs ? 4 : 2);
   s.y_row = src->y_row_stride ? src->y_row_stride : packed_y; s.c_row = src->c_row_stride ? src->c_row_stride : packed_c;
-  s.y_image = src->y_image_stride ? src->y_image_stride : s.y_row * b->h; s.c_image = src->c_image_stride ? src->c_image_stride : s.c_row * s.ch;
+  s.y_image = src->y_image_stride ? src->y_image_stride : s.y_row * h; s.c_image = src->c_image_stride ? src->c_image_stride : s.c_row * s.ch;
   if (s.y_row < packed_y || s.c_row < packed_c) return MI_INVALID_ARGUMENT;
   s.down = src->msb_aligned ? (uint32_t)(16 - src->bits) : 0u; s.mask = (1u << src->bits) - 1u;
   s.ym = make_sample_map16(src->bits, false, src->narrow_range != 0); s.cm = make_sample_map16(src->bits, true, src->narrow_range != 0);
@@ -450,7 +471,7 @@ int mi_batch_upload_device_ycbcr16(mi_batch *b, int first, int count, const mi_d
   if (!slots) return MI_ENCODING_ERROR;
   (void)hipSetDevice(b->device);
   if (int st = batch_join(b, src->after_stream)) return st;
-  LAUNCH_BY_CHANNELS(b, b->channels, b->w, b->h, count, planes_ingest16_kernel, s, slots);
+  LAUNCH_BY_CHANNELS(b, b->channels, w, h, count, planes_ingest16_kernel, s, slots);
   HIP_OK(hipGetLastError());
   batch_tag(b, first, count, MI_INPUT_YCBCR16);
   return MI_OK;
@@ -465,17 +486,18 @@ int mi_batch_uses_alpha(mi_batch *b, int index, int *uses_alpha) {
 // One decoded_kernel launch over the frame descriptors the encode staged (still on the device, like the planes: nothing after mi_batch_wait writes them until
 // the next encode), after whatever dst->after_stream holds at this moment, then the batch's stream is waited for.  Strides of 0 mean packed.
 int mi_batch_decode_device(mi_batch *b, int first, int count, int which, const mi_device_target *dst) {
-  if (!batch_encoded_ok(b, first, count) || !dst || !dst->dev) return MI_INVALID_ARGUMENT;
+  if (!batch_encoded_ok(b, first, count) || !slots_one_size(b, first, count) || !dst || !dst->dev) return MI_INVALID_ARGUMENT;
+  const uint32_t w = slot_w(b, first), h = slot_h(b, first);
   if ((which != MI_DECODED_RECON && which != MI_DECODED_SOURCE) || (dst->layout != 0 && dst->layout != 1) || (dst->channels != 3 && dst->channels != 4)) return MI_INVALID_ARGUMENT;
   if ((size_t)b->n * (b->channels == 4 ? 2 : 1) != b->fs.frames.size()) return MI_INVALID_ARGUMENT;
   if (dst->channels == 3 && b->channels == 4)
     for (int i = first; i < first + count; i++) if (b->alpha_flags[i]) return MI_INVALID_ARGUMENT;      // alpha is never dropped
   DecodedDst d;
   d.first = first; d.n = b->n; d.alpha_frames = b->channels == 4; d.source = which == MI_DECODED_SOURCE;
-  if (!strided_resolve(*dst, b->w, b->h, 1, true, d)) return MI_INVALID_ARGUMENT;
+  if (!strided_resolve(*dst, w, h, 1, true, d)) return MI_INVALID_ARGUMENT;
   (void)hipSetDevice(b->device);
   if (int st = batch_join(b, dst->after_stream)) return st;
-  const dim3 grid = grid_by_four(b->w, b->h, count);
+  const dim3 grid = grid_by_four(w, h, count);
   const FrameDev *const frames = b->fs.d_frames.get();
   const bool rgb_model = b->fs.frames[first].cfg.matrix == 0;
   if (b->depth == 8) {
@@ -494,12 +516,12 @@ int mi_batch_decode(mi_batch *b, int index, int which, int channels, uint8_t *ds
   if (!batch_encoded_ok(b, index, 1) || !dst || (channels != 3 && channels != 4)) return MI_INVALID_ARGUMENT;
   if ((which != MI_DECODED_RECON && which != MI_DECODED_SOURCE) || (channels == 3 && b->channels == 4 && b->alpha_flags[index])) return MI_INVALID_ARGUMENT;   // before the scratch exists: a refused call allocates nothing
   (void)hipSetDevice(b->device);
-  if (!staging_grow(b->d_decoded, b->d_decoded_cap, (size_t)b->w * b->h * 4)) return MI_ENCODING_ERROR;
+  if (!staging_grow(b->d_decoded, b->d_decoded_cap, slot_px(b, index) * 4)) return MI_ENCODING_ERROR;     // (one image: follows the largest picture asked for)
   mi_device_target t;
   memset(&t, 0, sizeof(t));
   t.dev = b->d_decoded.get(); t.layout = 0; t.channels = channels;
   if (const int st = mi_batch_decode_device(b, index, 1, which, &t)) return st;
-  HIP_OK(hipMemcpy(dst, b->d_decoded.get(), (size_t)b->w * b->h * channels, hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(dst, b->d_decoded.get(), slot_px(b, index) * channels, hipMemcpyDeviceToHost));
   return MI_OK;
 }
 
@@ -527,10 +549,10 @@ static int batch_jpeg_decode(mi_batch *b, const JpegCoeffs &jc, uint8_t *d_out, 
 static int batch_upload_jpeg(mi_batch *b, int index, const mi_jpeg_coeffs *c, bool ycc) {
   if (!batch_index_ok(b, index) || !c) return MI_INVALID_ARGUMENT;
   const JpegCoeffs &jc = c->jc;
-  if (jc.w != b->w || jc.h != b->h || (ycc && !batch_takes_ycbcr(b))) return MI_INVALID_ARGUMENT;
+  if (jc.w != slot_w(b, index) || jc.h != slot_h(b, index) || (ycc && !batch_takes_ycbcr(b))) return MI_INVALID_ARGUMENT;
   if (ycc && jc.color == JPEG_RGB) return MI_UNSUPPORTED;
   (void)hipSetDevice(b->device);
-  if (int st = batch_jpeg_decode(b, jc, mi_batch_device_input(b, index), b->channels, b->w, ycc)) return st;
+  if (int st = batch_jpeg_decode(b, jc, mi_batch_device_input(b, index), b->channels, slot_w(b, index), ycc)) return st;
   batch_tag(b, index, 1, ycc ? MI_INPUT_YCBCR : MI_INPUT_RGB);
   return MI_OK;
 }
@@ -591,8 +613,9 @@ static bool batch_reserve_png(mi_batch *b, size_t bytes) {
 // images [first, first + count) from parsed PNG files of the batch's size: descriptors, palettes and scanlines into the batch's pinned staging, one H2D, then
 // png_unfilter_kernel (one workgroup per pass that has a filtered row, all images in one launch) and png_expand_kernel on the batch's stream, no sync.
 // The staging keeps the calls since the stream last drained; when the next one does not fit, the stream is waited for and the staging starts over, grown to the call.
-// (the body, shared with mi_batch_resize_png: `count` checked files of w x h into packed pictures of `channels` channels, back to back from `slots` on)
-static int batch_png_expand(mi_batch *b, int count, const mi_png_scanlines *const *png, uint32_t w, uint32_t h, int channels, void *slots, bool deep = false) {
+// (the body, shared with mi_batch_resize_png: `count` checked files, each of its own size, into packed pictures of `channels` channels, back to back from `slots` on: one
+// staging, one copy and one unfilter launch for the call -- its grid runs over per-image pass descriptors -- and one expand launch per stretch of equal-sized neighbours)
+static int batch_png_expand(mi_batch *b, int count, const mi_png_scanlines *const *png, int channels, void *slots, bool deep = false) {
   const size_t need = png_call_bytes(count, png);
   if (b->png_used + need > b->h_png_cap || b->png_used + need > b->d_png_cap) {
     HIP_OK(hipStreamSynchronize(b->stream));                  // earlier calls' copies and kernels may still use the buffers that start over or are replaced
@@ -633,8 +656,16 @@ static int batch_png_expand(mi_batch *b, int count, const mi_png_scanlines *cons
     hipLaunchKernelGGL(png_unfilter_kernel, dim3(npass), dim3(64 * waves), 0, b->stream, db, (const PngPassDev *)(db + at));
   }
   const uint8_t *const cdb = db; const PngImageDev *const imgs_dev = (const PngImageDev *)(db + at + img_at);
-  if (deep) LAUNCH_BY_CHANNELS(b, channels, w, h, count, png_expand16_kernel, cdb, imgs_dev, w, h, (uint16_t *)slots);      // files of bit depth 16 into deep slots: both bytes of every sample
-  else LAUNCH_BY_CHANNELS(b, channels, w, h, count, png_expand_kernel, cdb, imgs_dev, w, h, (uint8_t *)slots);
+  size_t out_at = 0;                                            // samples from `slots` to the stretch's first picture
+  const int rc = for_each_group((size_t)count, [&](size_t k) { return ((uint64_t)png[k]->sl.w << 32) | png[k]->sl.h; }, [&](size_t from, size_t to) -> int {
+    const uint32_t w = png[from]->sl.w, h = png[from]->sl.h; const int n = (int)(to - from);
+    const PngImageDev *const stretch = imgs_dev + from;
+    if (deep) { uint16_t *const out = (uint16_t *)slots + out_at; LAUNCH_BY_CHANNELS(b, channels, w, h, n, png_expand16_kernel, cdb, stretch, w, h, out); }      // files of bit depth 16 into deep slots: both bytes of every sample
+    else { uint8_t *const out = (uint8_t *)slots + out_at; LAUNCH_BY_CHANNELS(b, channels, w, h, n, png_expand_kernel, cdb, stretch, w, h, out); }
+    out_at += (size_t)n * w * h * channels;
+    return MI_OK;
+  });
+  if (rc != MI_OK) return rc;
   HIP_OK(hipGetLastError());
   return MI_OK;
 }
@@ -654,18 +685,18 @@ static int batch_upload_png(mi_batch *b, int first, int count, const mi_png_scan
   auto goes_deep = [&](const mi_png_scanlines *p) { return deep_handles && png_goes_deep(p); };
   bool any_deep = false;
   for (int i = 0; i < count; i++) {
-    if (!png[i] || png[i]->sl.w != b->w || png[i]->sl.h != b->h) return MI_INVALID_ARGUMENT;
+    if (!png[i] || png[i]->sl.w != slot_w(b, first + i) || png[i]->sl.h != slot_h(b, first + i)) return MI_INVALID_ARGUMENT;
     if (b->channels == 3 && png[i]->sl.has_alpha()) return MI_INVALID_ARGUMENT;      // alpha is never dropped
     if (goes_deep(png[i])) { any_deep = true; if (!batch_takes_deep(b, png[i]->sl.has_alpha() ? 4 : 3)) return MI_INVALID_ARGUMENT; }
   }
   if (any_deep && !batch_deep(b)) return MI_ENCODING_ERROR;
   (void)hipSetDevice(b->device);
-  for (int i = 0; i < count;) {
+  for (int i = 0; i < count;) {                                 // stretches of neighbours that go the same way; in a mixed layout a stretch may hold several sizes
     const bool deep = goes_deep(png[i]);
     int j = i + 1;
     while (j < count && goes_deep(png[j]) == deep) j++;
     void *const slots = deep ? (void *)mi_batch_device_input16(b, first + i) : (void *)mi_batch_device_input(b, first + i);
-    if (int st = batch_png_expand(b, j - i, png + i, b->w, b->h, b->channels, slots, deep)) return st;
+    if (int st = batch_png_expand(b, j - i, png + i, b->channels, slots, deep)) return st;
     batch_tag(b, first + i, j - i, deep ? MI_INPUT_RGB16 : MI_INPUT_RGB);
     i = j;
   }
@@ -738,8 +769,9 @@ static int batch_reserve_scratch(mi_batch *b, size_t bytes) {
 // which the caller has reserved up to inter_at + resample_inter_bytes().  Stream order serialises the users of the scratch.  No sync.
 static size_t resample_inter_bytes(int count, uint32_t src_h, uint32_t dst_w) { return (size_t)count * src_h * align_up(dst_w, 4) * 4; }
 static int batch_resample(mi_batch *b, int first, int count, const IngestSrc &s, int filter, size_t inter_at) {
-  const uint32_t key[5] = { s.w, s.h, b->w, b->h, (uint32_t)filter + 1 };
-  const size_t h_bytes = resample_axis_bytes(s.w, b->w, filter), need = align_up(h_bytes + resample_axis_bytes(s.h, b->h, filter), 256);
+  const uint32_t dw = slot_w(b, first), dh = slot_h(b, first);    // the slots' size (one for the range: the callers have checked)
+  const uint32_t key[5] = { s.w, s.h, dw, dh, (uint32_t)filter + 1 };
+  const size_t h_bytes = resample_axis_bytes(s.w, dw, filter), need = align_up(h_bytes + resample_axis_bytes(s.h, dh, filter), 256);
   size_t at = b->rs_key_at;
   if (memcmp(key, b->rs_key, sizeof(key)) != 0) {
     if (b->rs_used + need > b->h_rs_cap || b->rs_used + need > b->d_rs_cap) {
@@ -749,21 +781,21 @@ static int batch_resample(mi_batch *b, int first, int count, const IngestSrc &s,
     }
     at = b->rs_used; b->rs_used += need;
     uint8_t *const hb = b->h_rs.get() + at;
-    resample_axis(s.w, b->w, filter, (uint32_t *)hb, (int32_t *)(hb + align_up((size_t)b->w * 8, 16)));
-    resample_axis(s.h, b->h, filter, (uint32_t *)(hb + h_bytes), (int32_t *)(hb + h_bytes + align_up((size_t)b->h * 8, 16)));
+    resample_axis(s.w, dw, filter, (uint32_t *)hb, (int32_t *)(hb + align_up((size_t)dw * 8, 16)));
+    resample_axis(s.h, dh, filter, (uint32_t *)(hb + h_bytes), (int32_t *)(hb + h_bytes + align_up((size_t)dh * 8, 16)));
     HIP_OK(hipMemcpyAsync(b->d_rs.get() + at, hb, need, hipMemcpyHostToDevice, b->stream));
     memcpy(b->rs_key, key, sizeof(key)); b->rs_key_at = at;
   }
   const uint8_t *const db = b->d_rs.get() + at;
   const uint32_t *const hbounds = (const uint32_t *)db, *const vbounds = (const uint32_t *)(db + h_bytes);
-  const int32_t *const htaps = (const int32_t *)(db + align_up((size_t)b->w * 8, 16)), *const vtaps = (const int32_t *)(db + h_bytes + align_up((size_t)b->h * 8, 16));
-  const uint32_t pitch = (uint32_t)align_up(b->w, 4);
+  const int32_t *const htaps = (const int32_t *)(db + align_up((size_t)dw * 8, 16)), *const vtaps = (const int32_t *)(db + h_bytes + align_up((size_t)dh * 8, 16));
+  const uint32_t pitch = (uint32_t)align_up(dw, 4);
   uint32_t *const inter = (uint32_t *)(b->d_rs_scratch.get() + inter_at);
-  hipLaunchKernelGGL(resample_h_kernel, dim3((b->w + MI_RS_TW - 1) / MI_RS_TW, (s.h + MI_RS_TH - 1) / MI_RS_TH, (unsigned)count), dim3(64 * MI_RS_TH), 0, b->stream,
-                     s, hbounds, htaps, b->w, pitch, inter);
+  hipLaunchKernelGGL(resample_h_kernel, dim3((dw + MI_RS_TW - 1) / MI_RS_TW, (s.h + MI_RS_TH - 1) / MI_RS_TH, (unsigned)count), dim3(64 * MI_RS_TH), 0, b->stream,
+                     s, hbounds, htaps, dw, pitch, inter);
   uint8_t *const slots = mi_batch_device_input(b, first);
   const int alpha = s.channels == 4 ? 1 : 0;
-  LAUNCH_BY_CHANNELS(b, b->channels, b->w, b->h, count, resample_v_kernel, (const uint32_t *)inter, s.h, pitch, vbounds, vtaps, b->w, b->h, alpha, slots);
+  LAUNCH_BY_CHANNELS(b, b->channels, dw, dh, count, resample_v_kernel, (const uint32_t *)inter, s.h, pitch, vbounds, vtaps, dw, dh, alpha, slots);
   HIP_OK(hipGetLastError());
   batch_tag(b, first, count, MI_INPUT_RGB);
   return MI_OK;
@@ -773,11 +805,11 @@ static bool resample_extent_ok(uint32_t w, uint32_t h) { return w >= 1 && h >= 1
 
 // images [first, first + count) from pictures of src_w x src_h in the memory of the batch's device; of the batch's own size: mi_batch_upload_device
 int mi_batch_resize_device(mi_batch *b, int first, int count, const mi_device_pixels *src, uint32_t src_w, uint32_t src_h, int filter) {
-  IngestSrc s;
-  if (!batch_range_ok(b, first, count) || !resample_filter_known(filter) || !resample_extent_ok(src_w, src_h) || !batch_device_source(b, src, src_w, src_h, s)) return MI_INVALID_ARGUMENT;
-  if (src_w == b->w && src_h == b->h) return mi_batch_upload_device(b, first, count, src);
+  IngestSrc s; uint32_t w, h;
+  if (!batch_range_sized(b, first, count, w, h) || !resample_filter_known(filter) || !resample_extent_ok(src_w, src_h) || !batch_device_source(b, src, src_w, src_h, s)) return MI_INVALID_ARGUMENT;
+  if (src_w == w && src_h == h) return mi_batch_upload_device(b, first, count, src);
   (void)hipSetDevice(b->device);
-  if (int st = batch_reserve_scratch(b, resample_inter_bytes(count, src_h, b->w))) return st;
+  if (int st = batch_reserve_scratch(b, resample_inter_bytes(count, src_h, w))) return st;
   if (int st = batch_join(b, src->after_stream)) return st;
   return batch_resample(b, first, count, s, filter, 0);
 }
@@ -794,11 +826,11 @@ static IngestSrc resample_scratch_source(const mi_batch *b, uint32_t w, uint32_t
 int mi_batch_resize_jpeg(mi_batch *b, int index, const mi_jpeg_coeffs *c, int filter) {
   if (!batch_index_ok(b, index) || !c || !resample_filter_known(filter)) return MI_INVALID_ARGUMENT;
   const JpegCoeffs &jc = c->jc;
-  if (jc.w == b->w && jc.h == b->h) return mi_batch_upload_jpeg(b, index, c);
+  if (jc.w == slot_w(b, index) && jc.h == slot_h(b, index)) return mi_batch_upload_jpeg(b, index, c);
   if (!resample_extent_ok(jc.w, jc.h)) return MI_INVALID_ARGUMENT;
   (void)hipSetDevice(b->device);
   const size_t inter_at = align_up((size_t)jc.w * jc.h * 3, 256);
-  if (int st = batch_reserve_scratch(b, inter_at + resample_inter_bytes(1, jc.h, b->w))) return st;
+  if (int st = batch_reserve_scratch(b, inter_at + resample_inter_bytes(1, jc.h, slot_w(b, index)))) return st;
   if (int st = batch_jpeg_decode(b, jc, b->d_rs_scratch.get(), 3, jc.w)) return st;
   return batch_resample(b, index, 1, resample_scratch_source(b, jc.w, jc.h, 3), filter, inter_at);
 }
@@ -809,12 +841,12 @@ int mi_batch_resize_png(mi_batch *b, int index, const mi_png_scanlines *p, int f
   if (!batch_index_ok(b, index) || !p || !resample_filter_known(filter)) return MI_INVALID_ARGUMENT;
   const int channels = p->sl.has_alpha() ? 4 : 3;
   if (channels > b->channels) return MI_INVALID_ARGUMENT;     // alpha is never dropped
-  if (p->sl.w == b->w && p->sl.h == b->h) return mi_batch_upload_png(b, index, 1, &p);
+  if (p->sl.w == slot_w(b, index) && p->sl.h == slot_h(b, index)) return mi_batch_upload_png(b, index, 1, &p);
   if (!resample_extent_ok(p->sl.w, p->sl.h)) return MI_INVALID_ARGUMENT;
   (void)hipSetDevice(b->device);
   const size_t inter_at = align_up((size_t)p->sl.w * p->sl.h * channels, 256);
-  if (int st = batch_reserve_scratch(b, inter_at + resample_inter_bytes(1, p->sl.h, b->w))) return st;
-  if (int st = batch_png_expand(b, 1, &p, p->sl.w, p->sl.h, channels, b->d_rs_scratch.get())) return st;
+  if (int st = batch_reserve_scratch(b, inter_at + resample_inter_bytes(1, p->sl.h, slot_w(b, index)))) return st;
+  if (int st = batch_png_expand(b, 1, &p, channels, b->d_rs_scratch.get())) return st;
   return batch_resample(b, index, 1, resample_scratch_source(b, p->sl.w, p->sl.h, channels), filter, inter_at);
 }
 
@@ -930,7 +962,7 @@ int mi_jpeg_coeffs_icc(const mi_jpeg_coeffs *c, const uint8_t **icc, size_t *len
 }
 
 // The colour channels of slots [first, first + count) through `t`, in place, on the batch's stream (after the uploads that filled them): one launch per run of
-// slots of one kind, all images of a run in grid z.  Every check comes first; a refused call and the identity transform launch and allocate nothing.
+// slots of one kind and size, all images of a run in grid z.  Every check comes first; a refused call and the identity transform launch and allocate nothing.
 int mi_batch_convert_colour(mi_batch *b, int first, int count, mi_colour_transform *t) {
   if (!batch_range_ok(b, first, count) || !t) return MI_INVALID_ARGUMENT;
   for (int i = first; i < first + count; i++) if (b->kinds[i] != MI_INPUT_RGB && b->kinds[i] != MI_INPUT_RGB16) return MI_INVALID_ARGUMENT;
@@ -938,11 +970,11 @@ int mi_batch_convert_colour(mi_batch *b, int first, int count, mi_colour_transfo
   (void)hipSetDevice(b->device);
   ColourDev d;
   if (!colour_on_device(t, b->device, d)) return MI_ENCODING_ERROR;
-  const uint32_t w = b->w, h = b->h, row_groups = (h + MI_COLOUR_ROWS - 1) / MI_COLOUR_ROWS;    // a workgroup runs down MI_COLOUR_ROWS rows
   for (int i = first; i < first + count;) {
     const int kind = b->kinds[i];
+    const uint32_t w = slot_w(b, i), h = slot_h(b, i), row_groups = (h + MI_COLOUR_ROWS - 1) / MI_COLOUR_ROWS;    // a workgroup runs down MI_COLOUR_ROWS rows
     int j = i + 1;
-    while (j < first + count && b->kinds[j] == kind) j++;
+    while (j < first + count && b->kinds[j] == kind && slot_w(b, j) == w && slot_h(b, j) == h) j++;
     if (kind == MI_INPUT_RGB) {
       uint8_t *const slots = mi_batch_device_input(b, i);
       LAUNCH_BY_CHANNELS(b, b->channels, w, row_groups, j - i, colour_convert_kernel, d, slots, w, h);
@@ -977,15 +1009,15 @@ void mi_oriented_size(uint32_t w, uint32_t h, int orientation, uint32_t *ow, uin
 
 }  // extern "C"
 
-// a source of sw x sh turned by `orientation` (1..8) has the batch's size
-static bool batch_oriented_fits(const mi_batch *b, uint32_t sw, uint32_t sh, int orientation) {
+// a source of sw x sh turned by `orientation` (1..8) has the size of slot `index`
+static bool batch_oriented_fits(const mi_batch *b, int index, uint32_t sw, uint32_t sh, int orientation) {
   uint32_t ow, oh;
   oriented_size(sw, sh, orientation, &ow, &oh);
-  return ow == b->w && oh == b->h;
+  return ow == slot_w(b, index) && oh == slot_h(b, index);
 }
 // one orient_kernel launch on the batch's stream: `count` pictures described by s (8-bit; deep: packed uint16 samples) into slots (deep slots) [first, first + count); o = 2..8
 static int batch_orient(mi_batch *b, int first, int count, const IngestSrc &s, int o, bool deep) {
-  const dim3 grid((b->w + MI_ORIENT_TILE - 1) / MI_ORIENT_TILE, (b->h + MI_ORIENT_TILE - 1) / MI_ORIENT_TILE, (unsigned)count), block(MI_ORIENT_THREADS);
+  const dim3 grid((slot_w(b, first) + MI_ORIENT_TILE - 1) / MI_ORIENT_TILE, (slot_h(b, first) + MI_ORIENT_TILE - 1) / MI_ORIENT_TILE, (unsigned)count), block(MI_ORIENT_THREADS);     // the slots' size (one for the range)
   if (deep) {
     uint16_t *const slots = mi_batch_device_input16(b, first);
     if (!slots) return MI_ENCODING_ERROR;
@@ -1011,11 +1043,12 @@ extern "C" {
 // images [first, first + count) from pictures in the memory of the batch's device, of the batch's size (orientations 1..4) or of h x w (5..8): one orient_kernel
 // launch on the batch's stream, after whatever src->after_stream holds at this moment; orientation 1: mi_batch_upload_device
 int mi_batch_orient_device(mi_batch *b, int first, int count, const mi_device_pixels *src, int orientation) {
-  if (!batch_range_ok(b, first, count) || orientation < 1 || orientation > 8) return MI_INVALID_ARGUMENT;
+  uint32_t w, h;
+  if (!batch_range_sized(b, first, count, w, h) || orientation < 1 || orientation > 8) return MI_INVALID_ARGUMENT;
   if (orientation == 1) return mi_batch_upload_device(b, first, count, src);
   const bool turn = orientation_turns(orientation);
   IngestSrc s;
-  if (!batch_device_source(b, src, turn ? b->h : b->w, turn ? b->w : b->h, s)) return MI_INVALID_ARGUMENT;
+  if (!batch_device_source(b, src, turn ? h : w, turn ? w : h, s)) return MI_INVALID_ARGUMENT;
   (void)hipSetDevice(b->device);
   if (int st = batch_join(b, src->after_stream)) return st;
   if (int st = batch_orient(b, first, count, s, orientation, false)) return st;
@@ -1030,7 +1063,7 @@ int mi_batch_upload_jpeg_oriented(mi_batch *b, int index, const mi_jpeg_coeffs *
   const JpegCoeffs &jc = c->jc;
   const int o = orientation ? orientation : jc.orientation;
   const bool ycc = ycbcr != 0;
-  if (!batch_oriented_fits(b, jc.w, jc.h, o) || (ycc && !batch_takes_ycbcr(b))) return MI_INVALID_ARGUMENT;
+  if (!batch_oriented_fits(b, index, jc.w, jc.h, o) || (ycc && !batch_takes_ycbcr(b))) return MI_INVALID_ARGUMENT;
   if (o == 1) return batch_upload_jpeg(b, index, c, ycc);
   if (ycc && jc.color == JPEG_RGB) return MI_UNSUPPORTED;
   (void)hipSetDevice(b->device);
@@ -1049,14 +1082,14 @@ int mi_batch_upload_png_oriented(mi_batch *b, int index, const mi_png_scanlines 
   const PngScanlines &sl = p->sl;
   const int o = orientation ? orientation : sl.orientation, channels = sl.has_alpha() ? 4 : 3;
   const bool goes_deep = deep && png_goes_deep(p);
-  if (!batch_oriented_fits(b, sl.w, sl.h, o) || channels > b->channels) return MI_INVALID_ARGUMENT;      // alpha is never dropped
+  if (!batch_oriented_fits(b, index, sl.w, sl.h, o) || channels > b->channels) return MI_INVALID_ARGUMENT;      // alpha is never dropped
   if (goes_deep && !batch_takes_deep(b, channels)) return MI_INVALID_ARGUMENT;
   if (o == 1) return batch_upload_png(b, index, 1, &p, deep != 0);
   if (goes_deep && !batch_deep(b)) return MI_ENCODING_ERROR;
   (void)hipSetDevice(b->device);
   const size_t sample_bytes = goes_deep ? 2 : 1;
   if (int st = batch_reserve_scratch(b, (size_t)sl.w * sl.h * channels * sample_bytes)) return st;
-  if (int st = batch_png_expand(b, 1, &p, sl.w, sl.h, channels, b->d_rs_scratch.get(), goes_deep)) return st;
+  if (int st = batch_png_expand(b, 1, &p, channels, b->d_rs_scratch.get(), goes_deep)) return st;
   if (int st = batch_orient(b, index, 1, orient_scratch_source(b, sl.w, sl.h, channels, sample_bytes), o, goes_deep)) return st;
   batch_tag(b, index, 1, goes_deep ? MI_INPUT_RGB16 : MI_INPUT_RGB);
   return MI_OK;

@@ -1,5 +1,5 @@
 // host_stream.h -- the stream fan-out of mi_avif.hip: the source kinds as a table, what one call's workers share (StreamCall), the per-device worker
-// (StreamWorker: resident batch objects per image shape, their byte budget and eviction, the staging of a run) and the three entry points over them,
+// (StreamWorker: resident batch objects per image shape -- or, with mixed_runs, one rotation per channel count for pictures of any size --, their byte budget and eviction, the staging of a run) and the three entry points over them,
 // mi_ravif_encode_sources / _stream / _batch.  Included there below host_input.h, the pool and the one-call entry points; host code only, no kernel is launched here.
 #pragma once
 
@@ -56,15 +56,6 @@ static int source_refusal(const mi_ravif_encoder &e, const mi_image_source &src)
   return MI_OK;
 }
 
-// fn(from, to) for every maximal stretch [from, to) of neighbours in [0, n) whose key(k) is equal, in index order; the first status that is not MI_OK ends the walk and is returned
-template <class Key, class Fn> static int for_each_group(size_t n, Key key, Fn fn) {
-  for (size_t k = 0, k1; k < n; k = k1) {
-    for (k1 = k + 1; k1 < n && key(k1) == key(k);) k1++;
-    if (const int rc = fn(k, k1)) return rc;
-  }
-  return MI_OK;
-}
-
 // ---- what the workers of one mi_ravif_encode_sources call share ----
 struct StreamCall {
   const mi_ravif_encoder *e; size_t n; mi_fetch_source_fn fetch; mi_release_fn release; void *user; mi_encoded_image *out;
@@ -87,10 +78,13 @@ static size_t est_bytes(uint32_t w, uint32_t h, int ch, size_t images) { return 
 // what a batch object adds at its first JPEG image: MI_BATCH_JPEG_STAGED images' coefficients (at most three full planes of int16) pinned and on the device, one image's planes
 static size_t est_jpeg_bytes(uint32_t w, uint32_t h) { return ((size_t)w + 15) * ((size_t)h + 15) * (2 * MI_BATCH_JPEG_STAGED * 6 + 3) + ((size_t)3 << 20); }
 struct Slot { mi_batch *b = nullptr; std::future<mi_batch *> making; std::vector<size_t> idx; bool busy = false, jpeg = false, deep = false; size_t bytes = 0, png_bytes = 0, scratch_bytes = 0; };
-struct Shape { uint32_t w, h; int ch; size_t cap; Slot slot[NSLOT_MAX]; int next = 0; size_t runs = 0, last_use = 0; };
+struct Shape { uint32_t w, h; int ch; size_t cap; Slot slot[NSLOT_MAX]; int next = 0; size_t runs = 0, last_use = 0; bool mixed = false; };
+// mixed runs (mi_ravif_encoder.mixed_runs == 1): one rotation per channel count whose objects are made for `cap` pictures of this reference size and
+// hold runs of pictures of any sizes that fit what such an object reserves (mi_batch_fits); the bench's own batch, under MI_SLOT_BYTES for both channel counts
+static constexpr uint32_t MI_MIXED_REF_W = 1920, MI_MIXED_REF_H = 1080;
 struct Baked { ColourKey key; mi_colour_transform *t; };
 using Sources = std::vector<mi_image_source>;                    // the fetched sources of one claim
-using Run = std::vector<size_t>;                                 // indices into them: neighbours of one shape, staged together
+using Run = std::vector<size_t>;                                 // indices into them: neighbours of one shape (or, in a mixed run, of sizes that fit one object together), staged together
 
 struct StreamWorker {
   StreamCall &call; const int dev; mi_ravif_encoder enc; size_t budget = (size_t)48 << 30;
@@ -156,40 +150,60 @@ struct StreamWorker {
     });
   }
   Shape &shape_for(const mi_image_desc &x) {
-    for (auto &c : shapes) if (c->w == x.width && c->h == x.height && c->ch == x.channels) return *c;
+    for (auto &c : shapes) if (!c->mixed && c->w == x.width && c->h == x.height && c->ch == x.channels) return *c;
     const size_t per = est_bytes(x.width, x.height, x.channels, 1);
     const size_t cap = std::max<size_t>(1, std::min(call.max_run, MI_SLOT_BYTES / per));
     shapes.emplace_back(new Shape{ x.width, x.height, x.channels, cap, {}, 0, 0, 0 });
     return *shapes.back();
+  }
+  // the rotation of mixed objects for `channels`, made on first use
+  Shape &mixed_shape_for(int channels) {
+    for (auto &c : shapes) if (c->mixed && c->ch == channels) return *c;
+    const size_t per = est_bytes(MI_MIXED_REF_W, MI_MIXED_REF_H, channels, 1);
+    const size_t cap = std::max<size_t>(1, std::min(call.max_run, MI_SLOT_BYTES / per));
+    shapes.emplace_back(new Shape{ MI_MIXED_REF_W, MI_MIXED_REF_H, channels, cap, {}, 0, 0, 0 });
+    shapes.back()->mixed = true;
+    return *shapes.back();
+  }
+  // an object of the mixed rotation to ask mi_batch_fits of (all of a rotation's objects reserve the same; the call reads what mi_batch_create fixed, so an object with a
+  // run in flight serves): the first one that exists, else the next slot's, made now and waited for.  nullptr: it could not be made
+  mi_batch *mixed_probe(Shape &sh, bool host_staging, size_t png_staging) {
+    for (Slot &sl : sh.slot) if (sl.b) return sl.b;
+    Slot &sl = sh.slot[sh.next];
+    ensure_slot(sh, sh.next, host_staging, png_staging);
+    if (sl.making.valid()) sl.b = sl.making.get();
+    if (!sl.b) reset_accounting(sl);
+    return sl.b;
   }
   // The uploads of a run into the slot's object, enqueued on its stream in index order, one stretch of neighbours that take the same upload call at a time (a host
   // stretch never reaches across a JPEG or PNG image's slot: the pinned staging there is stale); then the conversions of the managed sources.
   int stage(const Shape &sh, Slot &sl, const Sources &d, const Run &run) {
     auto source = [&](size_t k) -> const mi_image_source & { return d[run[k]]; };
     // (an oriented source's picture is decoded into the batch's scratch first: one picture of the slot's size, two bytes a sample on the deep route, joins the worker's budget)
-    auto charge_scratch = [&](bool deep_route) { const size_t need = (size_t)sh.w * sh.h * 4 * (deep_route ? 2 : 1) + ((size_t)1 << 20); if (need > sl.scratch_bytes) { charge(sl, need - sl.scratch_bytes); sl.scratch_bytes = need; } };
+    auto charge_scratch = [&](bool deep_route, const mi_image_desc &x) { const size_t need = (size_t)x.width * x.height * 4 * (deep_route ? 2 : 1) + ((size_t)1 << 20); if (need > sl.scratch_bytes) { charge(sl, need - sl.scratch_bytes); sl.scratch_bytes = need; } };
     const int rc = for_each_group(run.size(), [&](size_t k) { return (int)source_kind(source(k).kind)->route | (source(k).kind & MI_SOURCE_ORIENTED); }, [&](size_t from, size_t to) -> int {
       const UploadRoute route = source_kind(source(from).kind)->route;
       const bool oriented = source_oriented(source(from).kind);
       switch (route) {
       case ROUTE_HOST: {                                         // every image into the pinned staging, then one H2D
-        const size_t row = (size_t)sh.w * sh.ch;
-        for (size_t k = from; k < to; k++) {
+        for (size_t k = from; k < to; k++) {                      // (a slot has its source's size: the shape's, or in a mixed run the one mi_batch_set_sizes gave it)
           const mi_image_desc &x = source(k).desc;
+          const size_t row = (size_t)x.width * sh.ch;
           uint8_t *dst = mi_batch_input(sl.b, (int)k);
           if (!dst) return MI_ENCODING_ERROR;
           const size_t sp = x.stride_px ? x.stride_px : x.width;
-          if (sp == x.width) memcpy(dst, x.pixels, row * sh.h);
-          else for (uint32_t y = 0; y < sh.h; y++) memcpy(dst + y * row, x.pixels + (size_t)y * sp * sh.ch, row);
+          if (sp == x.width) memcpy(dst, x.pixels, row * x.height);
+          else for (uint32_t y = 0; y < x.height; y++) memcpy(dst + y * row, x.pixels + (size_t)y * sp * sh.ch, row);
         }
         return mi_batch_upload_async(sl.b, (int)from, (int)(to - from));
       }
       case ROUTE_JPEG: case ROUTE_JPEG_YCBCR:                    // coefficients to the batch's own staging, decoded into the slot on the batch's stream
         if (!sl.jpeg) { sl.jpeg = true; charge(sl, est_jpeg_bytes(sh.w, sh.h)); }
-        if (oriented) charge_scratch(false);
-        for (size_t k = from; k < to; k++)
+        for (size_t k = from; k < to; k++) {
+          if (oriented) charge_scratch(false, source(k).desc);
           if (const int st = oriented ? mi_batch_upload_jpeg_oriented(sl.b, (int)k, source(k).jpeg, 0, route == ROUTE_JPEG_YCBCR) :
                              route == ROUTE_JPEG_YCBCR ? mi_batch_upload_jpeg_ycbcr(sl.b, (int)k, source(k).jpeg) : mi_batch_upload_jpeg(sl.b, (int)k, source(k).jpeg)) return st;
+        }
         return MI_OK;
       case ROUTE_PNG: case ROUTE_PNG_DEEP: {                     // one call (one H2D, one launch per kernel); what the batch's PNG staging holds, pinned and on the device, joins the worker's budget
         std::vector<const mi_png_scanlines *> pngs;
@@ -198,7 +212,7 @@ struct StreamWorker {
         if (extra > sl.png_bytes) { charge(sl, extra - sl.png_bytes); sl.png_bytes = extra; }
         if (route == ROUTE_PNG_DEEP && !sl.deep) { sl.deep = true; charge(sl, sh.cap * (size_t)sh.w * sh.h * sh.ch * 2); }   // the deep slots join the worker's budget
         if (oriented) {                                          // one file a call: each goes through the scratch
-          charge_scratch(route == ROUTE_PNG_DEEP);
+          for (size_t k = from; k < to; k++) charge_scratch(route == ROUTE_PNG_DEEP, source(k).desc);
           for (size_t k = from; k < to; k++) if (const int st = mi_batch_upload_png_oriented(sl.b, (int)k, source(k).png, 0, route == ROUTE_PNG_DEEP)) return st;
           return MI_OK;
         }
@@ -224,7 +238,12 @@ struct StreamWorker {
     ensure_slot(sh, j, any_host, png_run);                       // (nothing to do for a slot that has an object, with a run in flight or not)
     settle(sl);                                                  // the slot's previous run, if any
     if (!sl.b) reset_accounting(sl);                             // the object could not be made: nothing of it is resident
-    int rc = sl.b ? mi_batch_set_count(sl.b, (int)run.size()) : MI_ENCODING_ERROR;
+    int rc = MI_ENCODING_ERROR;
+    if (sl.b && sh.mixed) {                                      // the run's own sizes, laid into what the object reserved (run() has asked mi_batch_fits)
+      std::vector<uint32_t> ws, hs;
+      for (size_t k : run) { ws.push_back(d[k].desc.width); hs.push_back(d[k].desc.height); }
+      rc = mi_batch_set_sizes(sl.b, (int)run.size(), ws.data(), hs.data());
+    } else if (sl.b) rc = mi_batch_set_count(sl.b, (int)run.size());
     if (call.timing) fprintf(stderr, "[mi_avif %8.1f ms] dev %d: slot %d ready\n", call.since(), dev, j);
     if (rc == MI_OK) {
       rc = stage(sh, sl, d, run);
@@ -255,15 +274,31 @@ struct StreamWorker {
       const size_t i1 = std::min(call.n, i0 + want);
       Sources d(i1 - i0);
       Run run; Shape *run_shape = nullptr;
-      auto flush = [&](bool more) { if (!run.empty()) { submit(*run_shape, d, run, i0, more); run.clear(); } };
+      std::vector<uint32_t> run_w, run_h;                        // a mixed run's sizes so far
+      auto flush = [&](bool more) { if (!run.empty()) { submit(*run_shape, d, run, i0, more); run.clear(); run_w.clear(); run_h.clear(); } };
       for (size_t i = i0; i < i1; i++) {
         mi_image_source &src = d[i - i0];
         if (const int rc = call.fetch(call.user, i, &src)) { call.st[i] = rc; continue; }
         if (const int why = source_refusal(*call.e, src)) { call.st[i] = why; if (call.release) call.release(call.user, i); continue; }
+        const SourceKind &kind = *source_kind(src.kind);
+        if (enc.mixed_runs == 1) {
+          // a mixed run grows in arrival order while the object's reserve takes the sizes so far; a picture that does not fit it alone goes the per-shape way below
+          Shape &mx = mixed_shape_for(src.desc.channels);
+          const mi_batch *probe = mixed_probe(mx, kind.route == ROUTE_HOST, kind.handle == HANDLE_PNG ? mx.cap * png_call_bytes(1, &src.png) : 0);
+          if (probe && mi_batch_fits(probe, 1, &src.desc.width, &src.desc.height) == MI_OK) {
+            if (&mx != run_shape || run.size() >= mx.cap) flush(true);
+            run_w.push_back(src.desc.width); run_h.push_back(src.desc.height);
+            if (run_w.size() > 1 && mi_batch_fits(probe, (int)run_w.size(), run_w.data(), run_h.data()) != MI_OK) {
+              flush(true);
+              run_w.push_back(src.desc.width); run_h.push_back(src.desc.height);
+            }
+            run_shape = &mx; run.push_back(i - i0);
+            continue;
+          }
+        }
         Shape &sh = shape_for(src.desc);
         if (&sh != run_shape || run.size() >= sh.cap) flush(true);
         run_shape = &sh; run.push_back(i - i0);
-        const SourceKind &kind = *source_kind(src.kind);
         if (run.size() == 1) ensure_slot(sh, sh.next, kind.route == ROUTE_HOST, kind.handle == HANDLE_PNG ? sh.cap * png_call_bytes(1, &src.png) : 0);   // made in the background while the rest of the run arrives
       }
       if (call.timing) fprintf(stderr, "[mi_avif %8.1f ms] dev %d: images %zu..%zu fetched\n", call.since(), dev, i0, i1);

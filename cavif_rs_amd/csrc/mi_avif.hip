@@ -45,12 +45,15 @@ using namespace mi;
 
 // ================================================================ batch object
 struct mi_batch {
-  mi_ravif_encoder enc{}; int n = 0; uint32_t w = 0, h = 0; int channels = 3, device = 0, depth = 10;
+  mi_ravif_encoder enc{}; int n = 0; uint32_t w = 0, h = 0; int channels = 3, device = 0, depth = 10;     // w x h: the reference size, what the batch was created for
+  // the layout: per slot its width, height and the sample offset of its first sample in the slot arrays (8-bit, deep, pinned staging, cleaned pixels
+  // alike).  Uniform: cap slots of w x h at i * w * h * channels.  Mixed (mi_batch_set_sizes): the n pictures of the run back to back, the slots behind them empty
+  std::vector<uint32_t> slot_w, slot_h; std::vector<size_t> slot_at; bool mixed = false; size_t run_px = 0;       // run_px: the pixels of the run's n pictures
   std::vector<uint8_t> exif;                                       // the batch's own copy of enc.exif (the caller's buffer need not outlive mi_batch_create)
   hipStream_t stream = nullptr;
   int cap = 0;                                                     // images the batch was created for (n = images of the current run <= cap)
   DevBuf<uint8_t> d_pixels; size_t pixel_bytes = 0;               // cap * w*h*channels
-  std::mutex staging_mu; PinBuf<uint8_t> h_pixels;                                        // pinned staging of the same size: the H2D source (async, no pageable copies); made by the first mi_batch_input (a batch fed
+  std::mutex staging_mu; PinBuf<uint8_t> h_pixels;                                        // pinned staging of the same size and layout: the H2D source (async, no pageable copies); made by the first mi_batch_input (a batch fed
                                                                    // JPEG coefficients, PNG scanlines or device pixels alone never pins it: pinning and unpinning 265 MB costs ~0.1 s)
   DevBuf<int> d_alpha_flags; PinBuf<int> h_alpha; std::vector<int> alpha_flags;      // h_alpha: pinned D2H target
   DevBuf<uint8_t> d_clean, d_clean_tmp; DevBuf<unsigned long long> d_alpha_acc;       // dirty-alpha cleaner (RGBA, UnassociatedClean)
@@ -84,23 +87,65 @@ struct mi_batch {
 };
 static_assert(sizeof(QualityRec) <= MI_FRAME_RECORD_BYTES, "FrameSet reserves MI_FRAME_RECORD_BYTES per (frame, plane)");
 
-static void batch_plan(mi_batch *b) {
-  // (re)build frame plans: colour for every image [0, n), then (RGBA input) one alpha frame per image [n, 2n) -- whether an alpha
-  // frame is used is decided on the device (FrameDev::active)
-  b->fs.frames.clear();
+// ---- the layout's accessors: nothing below reads b->w / b->h for a slot ----
+static uint32_t slot_w(const mi_batch *b, int i) { return b->slot_w[i]; }
+static uint32_t slot_h(const mi_batch *b, int i) { return b->slot_h[i]; }
+static size_t slot_px(const mi_batch *b, int i) { return (size_t)b->slot_w[i] * b->slot_h[i]; }
+static size_t slot_samples(const mi_batch *b, int i) { return slot_px(b, i) * b->channels; }
+static size_t slot_at(const mi_batch *b, int i) { return b->slot_at[i]; }
+static int batch_slots(const mi_batch *b) { return b->mixed ? b->n : b->cap; }                   // the slots that can be addressed
+// slots [first, first + count) have one size (the calls that describe their pictures with one size ask this)
+static bool slots_one_size(const mi_batch *b, int first, int count) {
+  for (int i = first + 1; i < first + count; i++) if (b->slot_w[i] != b->slot_w[first] || b->slot_h[i] != b->slot_h[first]) return false;
+  return true;
+}
+static void batch_layout_uniform(mi_batch *b) {
+  b->mixed = false;
+  b->slot_w.assign(b->cap, b->w); b->slot_h.assign(b->cap, b->h); b->slot_at.resize(b->cap);
+  for (int i = 0; i < b->cap; i++) b->slot_at[i] = (size_t)i * b->w * b->h * b->channels;
+  b->run_px = (size_t)b->n * b->w * b->h;
+}
+
+
+// The filters address samples inside a plane with 32-bit offsets (row * stride + column): a padded plane must stay below 2^31 samples.  That is 60 x the largest picture
+// any AV1 level allows (level 6.x: 35.6 MPix); beyond it the entry points answer MI_INVALID_ARGUMENT instead of filtering the wrong samples.
+static bool mi_plane_too_large(uint32_t w, uint32_t h) {
+  const uint64_t pw = ((uint64_t)w + 63) & ~63ull, ph = ((uint64_t)h + 63) & ~63ull;
+  return (pw + 64) * (ph + 64) >= (1ull << 31);
+}
+
+// frame plans of n pictures of the given sizes: colour for every image [0, n), then (RGBA input) one alpha frame per image [n, 2n) -- whether an alpha
+// frame is used is decided on the device (FrameDev::active)
+static std::vector<FramePlan> batch_plans(const mi_batch *b, int n, const uint32_t *ws, const uint32_t *hs) {
+  std::vector<FramePlan> frames;
   const int quantizer = quality_to_quantizer(b->enc.quality), aquant = quality_to_quantizer(b->enc.alpha_quality);
   auto make = [&](int image, bool alpha) {
     FramePlan p; p.image = image; p.is_alpha = alpha;
     mi_av1_config &c = p.cfg;
-    c.width = b->w; c.height = b->h; c.bit_depth = (uint8_t)b->depth; c.quantizer = (uint8_t)(alpha ? aquant : quantizer);
+    c.width = ws[image]; c.height = hs[image]; c.bit_depth = (uint8_t)b->depth; c.quantizer = (uint8_t)(alpha ? aquant : quantizer);
     c.chroma = alpha ? 1 : 0; c.pixel_range = 1; c.threads = b->enc.threads; c.device = b->device; c.tiles_override = b->enc.tiles_override; c.rdo_passes = (uint8_t)(b->enc.rdo_passes == 2 ? 2 : 1);
     c.has_color_desc = alpha ? 0 : 1; c.primaries = 1; c.transfer = 13; c.matrix = b->enc.color_model == 1 ? 0 : 6;
     tweaks_from_preset(b->enc.speed, c.quantizer, &c);
     plan_geometry(p);
     return p;
   };
-  for (int i = 0; i < b->n; i++) b->fs.frames.push_back(make(i, false));
-  if (b->channels == 4) for (int i = 0; i < b->n; i++) b->fs.frames.push_back(make(i, true));
+  for (int i = 0; i < n; i++) frames.push_back(make(i, false));
+  if (b->channels == 4) for (int i = 0; i < n; i++) frames.push_back(make(i, true));
+  return frames;
+}
+static void batch_plan(mi_batch *b) { b->fs.frames = batch_plans(b, b->n, b->slot_w.data(), b->slot_h.data()); }      // (re)build the plans of the run's pictures
+
+// The status mi_batch_set_sizes gives a layout (mi_batch_fits hands it out as it is): host arithmetic over the plans, nothing is allocated, launched or changed
+static int batch_layout_status(const mi_batch *b, int n, const uint32_t *ws, const uint32_t *hs) {
+  if (!b || !ws || !hs || n < 1) return MI_INVALID_ARGUMENT;
+  for (int i = 0; i < n; i++) if (ws[i] < 1 || hs[i] < 1 || ws[i] > 65536 || hs[i] > 65536 || mi_plane_too_large(ws[i], hs[i])) return MI_INVALID_ARGUMENT;
+  if (n > b->cap) return MI_UNSUPPORTED;
+  size_t px = 0;
+  for (int i = 0; i < n; i++) px += (size_t)ws[i] * hs[i];
+  if (px > (size_t)b->cap * b->w * b->h) return MI_UNSUPPORTED;                                  // the slot arrays
+  if (b->channels == 4 && b->enc.alpha_mode == 1)                                              // the cleaner's one-image scratch
+    for (int i = 0; i < n; i++) if ((size_t)ws[i] * hs[i] > (size_t)b->w * b->h) return MI_UNSUPPORTED;
+  try { return b->fs.fits(batch_plans(b, n, ws, hs), b->stream) ? MI_OK : MI_UNSUPPORTED; } catch (const std::exception &) { return MI_ENCODING_ERROR; }
 }
 
 // allocate for the worst case: every image has an alpha frame when channels == 4
@@ -139,12 +184,6 @@ size_t mi_avif_serialize(const uint8_t *color, size_t color_len, const uint8_t *
   return v.size();
 }
 
-// The filters address samples inside a plane with 32-bit offsets (row * stride + column): a padded plane must stay below 2^31 samples.  That is 60 x the largest picture
-// any AV1 level allows (level 6.x: 35.6 MPix); beyond it the entry points answer MI_INVALID_ARGUMENT instead of filtering the wrong samples.
-static bool mi_plane_too_large(uint32_t w, uint32_t h) {
-  const uint64_t pw = ((uint64_t)w + 63) & ~63ull, ph = ((uint64_t)h + 63) & ~63ull;
-  return (pw + 64) * (ph + 64) >= (1ull << 31);
-}
 mi_batch *mi_batch_create(const mi_ravif_encoder *e, int n_images, uint32_t w, uint32_t h, int channels) {
   if (!e || n_images < 1 || w < 1 || h < 1 || w > 65536 || h > 65536 || (channels != 3 && channels != 4) || e->alpha_mode > 2) return nullptr;
   if (mi_plane_too_large(w, h)) return nullptr;
@@ -160,6 +199,7 @@ mi_batch *mi_batch_create(const mi_ravif_encoder *e, int n_images, uint32_t w, u
   b->enc.exif = b->exif.empty() ? nullptr : b->exif.data(); b->enc.exif_len = b->exif.size();
   b->alpha_flags.assign(n_images, 0);
   b->kinds.assign(n_images, MI_INPUT_RGB);
+  batch_layout_uniform(b);
   b->pixel_bytes = (size_t)n_images * w * h * channels;
   bool ok = hipStreamCreate(&b->stream) == hipSuccess && b->d_pixels.alloc(b->pixel_bytes) == hipSuccess &&
             b->d_alpha_flags.alloc(n_images) == hipSuccess;
@@ -181,6 +221,27 @@ int mi_batch_set_count(mi_batch *b, int n_images) {
   if (!b || b->in_flight || n_images < 1 || n_images > b->cap) return MI_INVALID_ARGUMENT;
   b->n = n_images; b->alpha_flags.assign(n_images, 0);
   b->encoded = b->measured = false;
+  if (b->mixed) std::fill(b->kinds.begin(), b->kinds.end(), (uint8_t)MI_INPUT_RGB);              // back from a mixed layout: the slots moved, their contents are unspecified
+  batch_layout_uniform(b);
+  return MI_OK;
+}
+
+// ---- mixed-size layouts: the run's pictures differ in size and share what the batch reserved for cap pictures of w x h ----
+int mi_batch_fits(const mi_batch *b, int n_images, const uint32_t *widths, const uint32_t *heights) { return batch_layout_status(b, n_images, widths, heights); }
+int mi_batch_set_sizes(mi_batch *b, int n_images, const uint32_t *widths, const uint32_t *heights) {
+  if (b && b->in_flight) return MI_INVALID_ARGUMENT;
+  if (const int st = batch_layout_status(b, n_images, widths, heights)) return st;
+  b->n = n_images; b->alpha_flags.assign(n_images, 0);
+  b->encoded = b->measured = false;
+  std::fill(b->kinds.begin(), b->kinds.end(), (uint8_t)MI_INPUT_RGB);
+  b->mixed = true; b->run_px = 0;
+  b->slot_w.assign(b->cap, 0); b->slot_h.assign(b->cap, 0); b->slot_at.assign(b->cap, 0);
+  for (int i = 0; i < n_images; i++) { b->slot_w[i] = widths[i]; b->slot_h[i] = heights[i]; b->slot_at[i] = b->run_px * b->channels; b->run_px += (size_t)widths[i] * heights[i]; }
+  return MI_OK;
+}
+int mi_batch_image_size(const mi_batch *b, int index, uint32_t *w, uint32_t *h) {
+  if (!b || !w || !h || index < 0 || index >= batch_slots(b)) return MI_INVALID_ARGUMENT;
+  *w = slot_w(b, index); *h = slot_h(b, index);
   return MI_OK;
 }
 
@@ -220,40 +281,43 @@ int mi_batch_encode_async(mi_batch *b) {
   FrontParams fp{ fc.sy_r, fc.sy_g, fc.sy_b, fc.scale, fc.kcb, fc.kcr, fc.shift, b->depth, b->enc.color_model, b->channels, 0 };
   const uint8_t *front_src = d_pixels;
   if (d_clean && b->enc.alpha_mode == 2) {                  // convert_alpha_8bit: Premultiplied (av1encoder.rs:282-296)
-    const size_t npx = (size_t)b->n * b->w * b->h;
+    const size_t npx = b->run_px;
     hipLaunchKernelGGL(premultiply_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, s, d_pixels, d_clean, npx);
     HIP_OK(hipGetLastError());
     front_src = d_clean;
   } else if (d_clean) {                                     // convert_alpha_8bit: UnassociatedClean (av1encoder.rs:277-281)
     HIP_OK(hipMemsetAsync(d_alpha_acc, 0, sizeof(unsigned long long) * 4 * b->n, s));
-    const dim3 g((b->w + 255) / 256, b->h), blk(256);
+    const dim3 blk(256);
     for (int i = 0; i < b->n; i++) {
       if (b->kinds[i] != MI_INPUT_RGB) continue;                // opaque (YCbCr, or a deep image with A = 65535): the passes would be copies; the front end reads the slot itself
-      const uint8_t *in = d_pixels + (size_t)i * b->w * b->h * 4; uint8_t *outp = d_clean + (size_t)i * b->w * b->h * 4;
-      hipLaunchKernelGGL(alpha_scan_kernel, g, blk, 0, s, in, (int)b->w, (int)b->h, d_alpha_acc + 4 * i);
-      hipLaunchKernelGGL(alpha_rewrite_kernel, g, blk, 0, s, in, d_clean_tmp, (int)b->w, (int)b->h, d_alpha_acc + 4 * i, 0);
-      hipLaunchKernelGGL(alpha_rewrite_kernel, g, blk, 0, s, (const uint8_t *)d_clean_tmp, outp, (int)b->w, (int)b->h, d_alpha_acc + 4 * i, 1);
+      const int w = (int)slot_w(b, i), h = (int)slot_h(b, i);
+      const dim3 g((w + 255) / 256, h);
+      const uint8_t *in = d_pixels + slot_at(b, i); uint8_t *outp = d_clean + slot_at(b, i);
+      hipLaunchKernelGGL(alpha_scan_kernel, g, blk, 0, s, in, w, h, d_alpha_acc + 4 * i);
+      hipLaunchKernelGGL(alpha_rewrite_kernel, g, blk, 0, s, in, d_clean_tmp, w, h, d_alpha_acc + 4 * i, 0);
+      hipLaunchKernelGGL(alpha_rewrite_kernel, g, blk, 0, s, (const uint8_t *)d_clean_tmp, outp, w, h, d_alpha_acc + 4 * i, 1);
     }
     HIP_OK(hipGetLastError());
     front_src = d_clean;
   }
   for (int i = 0; i < b->n; i++) {
     FramePlan &p = b->fs.frames[i];
+    const int w = (int)slot_w(b, i), h = (int)slot_h(b, i);
     uint16_t *alpha_stage = b->channels == 4 ? p.dev.fin[0] : nullptr;      // fin[0] is free until CDEF runs
     if (b->kinds[i] == MI_INPUT_RGB16 || b->kinds[i] == MI_INPUT_YCBCR16) {   // its deep slot, through the 16-bit front end (kind 3: canonical YCbCr, no matrix)
       const uint16_t *deep = b->d_pixels16.get();
       if (!deep) return MI_INVALID_ARGUMENT;
-      deep += (size_t)i * b->w * b->h * b->channels;
+      deep += slot_at(b, i);
       const FrontDeepParams dp{ b->depth, b->enc.color_model, b->kinds[i] == MI_INPUT_YCBCR16 };
-      if (b->channels == 4) hipLaunchKernelGGL((frontend_deep_kernel<4>), dim3((p.pw + 255) / 256, p.ph), dim3(256), 0, s, deep, (int)b->w, (int)b->h, dp,
+      if (b->channels == 4) hipLaunchKernelGGL((frontend_deep_kernel<4>), dim3((p.pw + 255) / 256, p.ph), dim3(256), 0, s, deep, w, h, dp,
                                                p.dev.src[0], p.dev.src[1], p.dev.src[2], alpha_stage, p.pw, p.ph, d_alpha_flags + i);
-      else hipLaunchKernelGGL((frontend_deep_kernel<3>), dim3((p.pw + 255) / 256, p.ph), dim3(256), 0, s, deep, (int)b->w, (int)b->h, dp,
+      else hipLaunchKernelGGL((frontend_deep_kernel<3>), dim3((p.pw + 255) / 256, p.ph), dim3(256), 0, s, deep, w, h, dp,
                               p.dev.src[0], p.dev.src[1], p.dev.src[2], alpha_stage, p.pw, p.ph, d_alpha_flags + i);
       continue;
     }
     fp.ycc = b->kinds[i] == MI_INPUT_YCBCR;
     hipLaunchKernelGGL(frontend_kernel, dim3((p.pw + 255) / 256, p.ph), dim3(256), 0, s,
-                       (fp.ycc ? d_pixels : front_src) + (size_t)i * b->w * b->h * b->channels, (int)b->w, (int)b->h, (int)b->w, fp,
+                       (fp.ycc ? d_pixels : front_src) + slot_at(b, i), w, h, w, fp,
                        p.dev.src[0], p.dev.src[1], p.dev.src[2], alpha_stage, p.pw, p.ph, d_alpha_flags + i);
   }
   HIP_OK(hipGetLastError());
@@ -315,7 +379,7 @@ int mi_batch_wait(mi_batch *b) {
     if (b->channels == 4 && b->alpha_flags[i]) alpha = &b->fs.frames[b->n + i];
     const FramePlan &col = b->fs.frames[i];
     b->files[i] = avif_container(col.obu.data(), col.obu.size(), alpha ? alpha->obu.data() : nullptr, alpha ? alpha->obu.size() : 0,
-                                 b->w, b->h, b->depth, col.cfg.matrix, b->enc.alpha_mode == 2, b->enc.exif, b->enc.exif_len);
+                                 slot_w(b, i), slot_h(b, i), b->depth, col.cfg.matrix, b->enc.alpha_mode == 2, b->enc.exif, b->enc.exif_len);
     b->color_sz[i] = col.obu.size(); b->alpha_sz[i] = alpha ? alpha->obu.size() : 0;
   }
   HIP_OK(hipEventRecord(b->ev[7], s));
@@ -345,9 +409,10 @@ int mi_batch_get_recon(mi_batch *b, int index, int alpha, uint16_t *planes[3]) {
   if (!alpha) p = &b->fs.frames[index]; else if (b->channels == 4 && b->alpha_flags[index]) p = &b->fs.frames[b->n + index];
   if (!p) return MI_INVALID_ARGUMENT;
   for (int i = 0; i < 3; i++) planes[i] = nullptr;
+  const size_t w = slot_w(b, index), h = slot_h(b, index);
   for (int i = 0; i < p->np; i++) {
-    planes[i] = (uint16_t *)malloc((size_t)b->w * b->h * 2);
-    HIP_OK(hipMemcpy2D(planes[i], (size_t)b->w * 2, p->cfg.lrf ? p->dev.lrp[i] : p->dev.fin[i], (size_t)p->pw * 2, (size_t)b->w * 2, b->h, hipMemcpyDeviceToHost));
+    planes[i] = (uint16_t *)malloc(w * h * 2);
+    HIP_OK(hipMemcpy2D(planes[i], w * 2, p->cfg.lrf ? p->dev.lrp[i] : p->dev.fin[i], (size_t)p->pw * 2, w * 2, h, hipMemcpyDeviceToHost));
   }
   return MI_OK;
 }
@@ -359,9 +424,10 @@ int mi_batch_get_source(mi_batch *b, int index, int alpha, uint16_t *planes[3]) 
   if (!alpha) p = &b->fs.frames[index]; else if (b->channels == 4 && b->alpha_flags[index]) p = &b->fs.frames[b->n + index];
   if (!p) return MI_INVALID_ARGUMENT;
   for (int i = 0; i < 3; i++) planes[i] = nullptr;
+  const size_t w = slot_w(b, index), h = slot_h(b, index);
   for (int i = 0; i < p->np; i++) {
-    planes[i] = (uint16_t *)malloc((size_t)b->w * b->h * 2);
-    HIP_OK(hipMemcpy2D(planes[i], (size_t)b->w * 2, p->dev.src[i], (size_t)p->pw * 2, (size_t)b->w * 2, b->h, hipMemcpyDeviceToHost));
+    planes[i] = (uint16_t *)malloc(w * h * 2);
+    HIP_OK(hipMemcpy2D(planes[i], w * 2, p->dev.src[i], (size_t)p->pw * 2, w * 2, h, hipMemcpyDeviceToHost));
   }
   return MI_OK;
 }
@@ -391,7 +457,7 @@ int mi_batch_measure(mi_batch *b) {
 int mi_batch_get_quality(mi_batch *b, int index, mi_image_quality *out) {
   if (!b || !out || index < 0 || index >= b->n || !b->encoded || !b->measured) return MI_INVALID_ARGUMENT;
   memset(out, 0, sizeof(*out));
-  out->width = b->w; out->height = b->h; out->depth = (uint8_t)b->depth; out->color_planes = (uint8_t)b->fs.frames[index].np;
+  out->width = slot_w(b, index); out->height = slot_h(b, index); out->depth = (uint8_t)b->depth; out->color_planes = (uint8_t)b->fs.frames[index].np;
   out->has_alpha = (b->channels == 4 && b->alpha_flags[index]) ? 1 : 0;
   auto put = [&](mi_plane_quality &q, size_t frame, int plane) {
     const QualityRec &r = b->h_quality.get()[3 * frame + plane];
@@ -457,8 +523,7 @@ static mi_batch *pool_acquire(const mi_ravif_encoder *e, int cap, uint32_t w, ui
   b->exif.clear();
   if (e->exif && e->exif_len) b->exif.assign(e->exif, e->exif + e->exif_len);
   b->enc.exif = b->exif.empty() ? nullptr : b->exif.data(); b->enc.exif_len = b->exif.size();
-  b->n = b->cap; b->alpha_flags.assign(b->cap, 0);
-  b->encoded = b->measured = false;
+  (void)mi_batch_set_count(b, b->cap);                          // every image, the uniform layout
   return b;
 }
 static void pool_release(mi_batch *b) {

@@ -39,7 +39,7 @@ class _Av1Config(C.Structure):
 class _RavifEncoder(C.Structure):
     _fields_ = [('quality', C.c_float), ('alpha_quality', C.c_float), ('speed', C.c_uint8), ('color_model', C.c_uint8),
                 ('depth', C.c_uint8), ('alpha_mode', C.c_uint8), ('threads', C.c_int32),
-                ('exif', C.c_void_p), ('exif_len', C.c_size_t), ('device', C.c_int32), ('tiles_override', C.c_int32), ('rdo_passes', C.c_int32)]
+                ('exif', C.c_void_p), ('exif_len', C.c_size_t), ('device', C.c_int32), ('tiles_override', C.c_int32), ('rdo_passes', C.c_int32), ('mixed_runs', C.c_int32)]
 
 
 class _EncodedImage(C.Structure):
@@ -182,6 +182,9 @@ _PROTOTYPES = {
     'mi_batch_orient_device': (_STATUS, [_P, _I, _I, C.POINTER(_DevicePixels), _I]),
     'mi_batch_upload_jpeg_oriented': (_STATUS, [_P, _I, _P, _I, _I]),
     'mi_batch_upload_png_oriented': (_STATUS, [_P, _I, _P, _I, _I]),
+    'mi_batch_set_sizes': (_STATUS, [_P, _I, _PU32, _PU32]),
+    'mi_batch_fits': (_STATUS, [_P, _I, _PU32, _PU32]),
+    'mi_batch_image_size': (_STATUS, [_P, _I, _PU32, _PU32]),
 }
 # declared in the header and left without a prototype: their callers (tests, tools) pass ctypes values of their own
 _UNBOUND = ('mi_device_count', 'mi_png_decode_rgba', 'mi_ravif_encode_batch', 'mi_ravif_encode_stream', 'mi_release_cached')
@@ -728,6 +731,7 @@ class Encoder:
         self.color_model, self.depth, self.alpha_mode, self.threads = 0, 0, 1, None
         self.device, self.tiles_override = 0, 0
         self.rdo_passes = 1
+        self.mixed_runs = 0
         self.exif = None
 
     def _copy(self, **kw):
@@ -774,11 +778,14 @@ class Encoder:
         assert n in (1, 2)
         return self._copy(rdo_passes=int(n))
 
+    def with_mixed_runs(self, on=True):                 # extension (not in ravif): encode_many lets a run hold pictures of different sizes; the files are unchanged
+        return self._copy(mixed_runs=1 if on else 0)
+
     def _c(self):
         e = _RavifEncoder()
         e.quality, e.alpha_quality, e.speed, e.color_model, e.depth, e.alpha_mode = self.quality, self.alpha_quality, self.speed, self.color_model, self.depth, self.alpha_mode
         e.threads = self.threads or 0
-        e.device, e.tiles_override, e.rdo_passes = self.device, self.tiles_override, self.rdo_passes
+        e.device, e.tiles_override, e.rdo_passes, e.mixed_runs = self.device, self.tiles_override, self.rdo_passes, self.mixed_runs
         if self.exif:
             self._exif_buf = C.create_string_buffer(self.exif, len(self.exif))   # must outlive every call made with `e`
             e.exif, e.exif_len = C.cast(self._exif_buf, C.c_void_p), len(self.exif)
@@ -1032,6 +1039,7 @@ def encode_many(encoder, images, devices=None, jpeg_ycbcr=False, png_deep=False,
     images: list of HxWx3 / HxWx4 uint8 arrays (shapes may differ), JpegCoeffs objects (parse_jpeg; encoded as the RGBA pictures decode_jpeg
     gives, decoded on the device) and PngScanlines objects (parse_png; encoded as the RGBA pictures load_rgba gives, unfiltered and expanded on the
     device).  jpeg_ycbcr=True: a JpegCoeffs whose colour is not RGB is coded from the file's own Y, Cb, Cr (source kind SOURCE_JPEG_YCBCR) instead.
+    An encoder made with_mixed_runs() lets a run hold pictures of different sizes (mi_ravif_encoder.mixed_runs); the files are the same.
     png_deep=True: a PngScanlines goes as source kind SOURCE_PNG_DEEP: a file of bit depth 16 is coded from all 16 bits of its samples.
     managed=True: a parsed file is converted to sRGB by its own colour description after its upload (the source kinds SOURCE_*_MANAGED); a file whose
     profile is unsupported or malformed is coded unmanaged and raises nothing.  With jpeg_ycbcr, a JPEG whose profile gives a usable transform that is not
@@ -1091,29 +1099,65 @@ class BatchEncoder(_Handle):
         self._h = self._L.mi_batch_create(C.byref(e), n_images, width, height, channels)
         if not self._h:
             raise AvifError(5 if self._L.mi_device_count() <= encoder.device else 4)
-        self.n, self.w, self.h, self.channels = n_images, width, height, channels
-        self.count = n_images                        # images of the next run (set_count)
+        self.n, self.w, self.h, self.channels = n_images, width, height, channels      # w x h: the reference size (every slot's, until set_sizes)
+        self.count = n_images                        # images of the next run (set_count, set_sizes)
+        self._mixed = False                          # set_sizes laid the run out: its slots are [0, count)
         self._sources = []                           # device arrays handed to upload_device: alive until the run that reads them has been waited for
+
+    @staticmethod
+    def _size_arrays(sizes):
+        sizes = [(int(w), int(h)) for w, h in sizes]
+        if any(w < 0 or h < 0 or w >= 1 << 32 or h >= 1 << 32 for w, h in sizes):
+            raise AvifError(4)
+        n = len(sizes)
+        return n, (C.c_uint32 * max(n, 1))(*[w for w, _ in sizes]), (C.c_uint32 * max(n, 1))(*[h for _, h in sizes])
+
+    def set_sizes(self, sizes):
+        """mi_batch_set_sizes: the next run holds len(sizes) pictures of sizes[i] = (width, height), laid back to back into what the batch reserved for its n
+        pictures of w x h; nothing is allocated.  The slots' contents are unspecified afterwards and their kinds 0.  Raises Unsupported for a layout that does not
+        fit (fits() asks without raising), InvalidArgument for a malformed one or with an encode in flight.  set_count(n) returns to n pictures of w x h."""
+        n, ws, hs = self._size_arrays(sizes)
+        _ok(self._L.mi_batch_set_sizes(self._h, n, ws, hs))
+        self.count, self._mixed = n, True
+
+    def fits(self, sizes):
+        """mi_batch_fits: whether set_sizes(sizes) would take the layout (False: Unsupported; a malformed layout raises InvalidArgument); changes nothing"""
+        n, ws, hs = self._size_arrays(sizes)
+        st = self._L.mi_batch_fits(self._h, n, ws, hs)
+        if st == 2:
+            return False
+        _ok(st)
+        return True
+
+    def image_size(self, index):
+        """(width, height) of slot `index` now: the batch's own in a uniform batch, the picture's after set_sizes"""
+        w, h = C.c_uint32(), C.c_uint32()
+        _ok(self._L.mi_batch_image_size(self._h, index, C.byref(w), C.byref(h)))
+        return w.value, h.value
+
+    def _hw(self, index):
+        w, h = self.image_size(index)
+        return h, w
 
     def upload(self, index, pixels, bits=16, msb_aligned=False):
         """host pixels (h, w, channels) uint8 into the slot of `index`; a uint16 array -- (h, w, 3) or (h, w, 4), `bits` significant bits -- into its deep slot
         (input kind 2: coded from all 16 bits)"""
         if getattr(pixels, 'dtype', None) == np.uint16:
             a = _widen16(np.ascontiguousarray(pixels), bits, msb_aligned)
-            if a.ndim != 3 or a.shape[:2] != (self.h, self.w) or a.shape[2] not in (3, 4):
+            if a.ndim != 3 or a.shape[:2] != self._hw(index) or a.shape[2] not in (3, 4):
                 raise AvifError(4)
-            _ok(self._L.mi_batch_upload16(self._h, index, a.ctypes.data, self.w, a.shape[2]))
+            _ok(self._L.mi_batch_upload16(self._h, index, a.ctypes.data, a.shape[1], a.shape[2]))
             return
         a = np.ascontiguousarray(pixels, dtype=np.uint8)
-        assert a.shape == (self.h, self.w, self.channels)
-        _ok(self._L.mi_batch_upload(self._h, index, a.ctypes.data, self.w))
+        assert a.shape == self._hw(index) + (self.channels,)
+        _ok(self._L.mi_batch_upload(self._h, index, a.ctypes.data, a.shape[1]))
 
     def upload_device(self, first, pixels, bits=16, msb_aligned=False):
         """images first.. from an object with __cuda_array_interface__ (a torch tensor of the batch's device): uint8 (H, W, C), (C, H, W), (N, H, W, C) or
         (N, C, H, W), any strides a view has.  Enqueued on the batch's stream after the work of torch's current stream; the object is kept referenced until wait().
         uint16 arrays of the same shapes fill the deep slots (input kind 2); `bits` (8..16) of a sample count, its low ones or (msb_aligned) its high ones."""
         d, n, h, w, _ = _device_pixels(pixels, batched=True, deep_ok=True)
-        if (h, w) != (self.h, self.w):
+        if (h, w) != self._hw(first):
             raise AvifError(4)
         deep = isinstance(d, _DevicePixels16)
         if deep:
@@ -1141,7 +1185,7 @@ class BatchEncoder(_Handle):
         input kind 3 (INPUT_YCBCR16): `bits` (8..16) of a sample count, its low bits or (msb_aligned, as in P010) its high bits, and narrow_range=True
         expands "video" range (16..235 / 16..240 at 8 bits) to full range.  The three keywords say nothing about uint8 planes."""
         d, n, h, w, _ = _device_planes(y, cb, cr, subsampling)
-        if (h, w) != (self.h, self.w):
+        if (h, w) != self._hw(first):
             raise AvifError(4)
         deep = _planes16_fill(d, bits, msb_aligned, narrow_range)
         _ok((self._L.mi_batch_upload_device_ycbcr16 if deep else self._L.mi_batch_upload_device_ycbcr)(self._h, first, n, C.byref(d)))
@@ -1177,7 +1221,7 @@ class BatchEncoder(_Handle):
         """upload_device for uint8 pictures that are turned by `orientation` (1..8) on their way into the slots: the array holds pictures of the batch's size
         (1..4) or of h x w (5..8)"""
         d, n, h, w, _ = _device_pixels(pixels, batched=True)
-        if oriented_size(w, h, orientation) != (self.w, self.h):
+        if oriented_size(w, h, orientation) != self.image_size(first):
             raise AvifError(4)
         _ok(self._L.mi_batch_orient_device(self._h, first, n, C.byref(d), int(orientation)))
         self._sources.append(pixels)
@@ -1222,7 +1266,7 @@ class BatchEncoder(_Handle):
         return self._read(self._L.mi_batch_read_input16, np.uint16, index)
 
     def _read(self, fn, dtype, index):
-        a = np.empty((self.h, self.w, self.channels), dtype)
+        a = np.empty(self._hw(index) + (self.channels,), dtype)
         _ok(fn(self._h, index, a.ctypes.data))
         return a
 
@@ -1231,15 +1275,15 @@ class BatchEncoder(_Handle):
         ptr = self._L.mi_batch_input(self._h, index)
         if not ptr:
             raise AvifError(4)
-        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(self.h, self.w, self.channels))
+        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=self._hw(index) + (self.channels,))
 
     def upload_async(self, first=0, count=None):
         """enqueue pinned host -> HBM for a range of images on the batch's stream (returns at once)"""
-        _ok(self._L.mi_batch_upload_async(self._h, first, self.n if count is None else count))
+        _ok(self._L.mi_batch_upload_async(self._h, first, (self.count - first if self._mixed else self.n) if count is None else count))
 
     def set_count(self, n_images):
         _ok(self._L.mi_batch_set_count(self._h, n_images))
-        self.count = n_images
+        self.count, self._mixed = n_images, False
 
     def encode(self):
         st = self._L.mi_batch_encode(self._h)
@@ -1266,7 +1310,7 @@ class BatchEncoder(_Handle):
         out = []
         for p in planes:
             if p:
-                out.append(np.ctypeslib.as_array(p, shape=(self.h, self.w)).copy())
+                out.append(np.ctypeslib.as_array(p, shape=self._hw(index)).copy())
                 self._L.mi_free(p)
         return out
 
@@ -1292,7 +1336,7 @@ class BatchEncoder(_Handle):
             channels = 4 if self.uses_alpha(index) else 3
         if channels not in (3, 4):
             raise AvifError(4)
-        a = np.empty((self.h, self.w, channels), np.uint8)
+        a = np.empty(self._hw(index) + (channels,), np.uint8)
         _ok(self._L.mi_batch_decode(self._h, index, w, channels, a.ctypes.data))
         return a
 
@@ -1301,7 +1345,7 @@ class BatchEncoder(_Handle):
         (C, H, W), (N, H, W, C) or (N, C, H, W), C = 3 or 4, any strides a view has: bytes the view does not address are left alone.  The write is ordered
         after the work of torch's current stream; the pixels are in place when the call returns."""
         d, n, h, w, _ = _device_pixels(target, batched=True, writable=True)
-        if (h, w) != (self.h, self.w):
+        if (h, w) != self._hw(first):
             raise AvifError(4)
         _ok(self._L.mi_batch_decode_device(self._h, first, n, _named(DECODED_WHICH, which), C.byref(d)))
 

@@ -77,6 +77,10 @@ typedef struct mi_ravif_encoder {
   int32_t tiles_override;
   int32_t rdo_passes;             /* extension: see mi_av1_config.rdo_passes (exactly 2 = two passes; anything else = one pass, ravif's behaviour).  The struct must be
                                      zero-initialised or come from mi_ravif_encoder_default: both structs have grown at the tail and may grow again */
+  int32_t mixed_runs;             /* extension, read by mi_ravif_encode_sources / _stream / _batch alone: exactly 1 lets a run hold pictures of different sizes (one
+                                     rotation of batch objects per channel count, made for 32 x 1920 x 1080 at most and filled through mi_batch_set_sizes below, instead
+                                     of one per shape); ANY other value keeps runs of one shape.  The files are the same either way.  It means nothing to a batch and is no
+                                     part of the pool's key */
 } mi_ravif_encoder;
 
 typedef struct mi_encoded_image { uint8_t *avif_file; size_t avif_len, color_byte_size, alpha_byte_size; } mi_encoded_image;
@@ -452,7 +456,31 @@ enum { MI_RESAMPLE_BOX = 0, MI_RESAMPLE_BILINEAR = 1, MI_RESAMPLE_BICUBIC = 2, M
 int  mi_batch_resize_device(mi_batch *b, int first, int count, const mi_device_pixels *src, uint32_t src_w, uint32_t src_h, int filter);
 int  mi_batch_resize_jpeg(mi_batch *b, int index, const mi_jpeg_coeffs *c, int filter);
 int  mi_batch_resize_png(mi_batch *b, int index, const mi_png_scanlines *p, int filter);
-int  mi_batch_set_count(mi_batch *b, int n_images);                                       /* images of the next run (<= the count the batch was created for) */
+int  mi_batch_set_count(mi_batch *b, int n_images);                                       /* images of the next run (<= the count the batch was created for), each of the batch's w x h */
+/* ---- mixed-size layouts: the pictures of a run differ in size.  A batch is made as before, mi_batch_create(e, cap, W, H, channels); everything it
+ * reserves for cap pictures of W x H -- the slot arrays, the arena, tile jobs, payload and pre-carry capacity, symbol records, the search queue's items and snapshots,
+ * the alpha flags -- is the room a mixed layout may use.  Pictures are coded independently: every file equals, byte for byte, the file its picture gets alone.
+ * mi_batch_set_sizes: lays n_images pictures of widths[i] x heights[i] into that room.  Slot i of the 8-bit slot array (and of the deep one, the pinned staging alike)
+ * starts at sample offset sum over k < i of w_k * h_k * channels: rows packed, slots back to back, so a stretch of equal-sized slots is laid out exactly like a uniform
+ * batch from its first slot on.  Allocates nothing (mi_batch_footprint is unchanged), launches nothing.  Afterwards the contents of all slots are unspecified, every
+ * slot's kind is MI_INPUT_RGB, the records of the last encode are gone, and slots [0, n_images) are the batch's slots: an index past them is a range past the capacity.
+ * mi_batch_set_count(b, n) returns the batch to n pictures of W x H (contents unspecified when it follows a mixed layout; after a uniform one as before).
+ * Wherever a call's contract above says "the batch's width and height" it means the slot's: the size checks of mi_batch_upload_jpeg* / _png*, the destination of the
+ * resize calls, the oriented size of the orient calls, the pictures of mi_batch_decode*, mi_batch_get_recon / _get_source and mi_image_quality.width / height.  The
+ * calls that take a range and describe its pictures with one size -- mi_batch_upload_device[16], _upload_device_ycbcr[16], _resize_device, _orient_device and
+ * _decode_device -- need all slots of the range to have one size, else MI_INVALID_ARGUMENT; mi_batch_upload_png[_deep] takes one handle per slot, each of its slot's
+ * size; mi_batch_upload_async and mi_batch_convert_colour work on any range.
+ * Statuses.  MI_INVALID_ARGUMENT: null pointers, n_images < 1, a zero extent or one above 65536, a picture whose padded plane reaches 2^31 samples, and (set_sizes
+ * only) a call between mi_batch_encode_async and mi_batch_wait.  MI_UNSUPPORTED: a well-formed layout that does not fit what the batch reserved -- n_images > cap,
+ * sum of w * h > cap * W * H, or a dry run of the actual frames exceeding any quantity the reserve sized for its worst case: arena bytes (these go by PADDED pixels:
+ * each extent rounded up to 64), tile jobs, the sum of payload capacities, jobs x the largest tile capacity against the pre-carry and record buffers, work items and
+ * snapshot bytes; in a 4-channel batch under alpha_mode 1 also a picture of more than W * H pixels (the cleaner's one-image scratch).  MI_OK otherwise: a layout that
+ * fits encodes, and a picture larger than W x H is taken when everything reserved suffices (one 4K photograph in a batch made for 32 x 1080p).
+ * mi_batch_fits: the status mi_batch_set_sizes would give; touches no device and changes nothing, and may be asked while an encode is in flight.
+ * mi_batch_image_size: the current size of slot `index` (W, H in a uniform batch); MI_INVALID_ARGUMENT for null pointers and an index that is no slot. */
+int  mi_batch_set_sizes(mi_batch *b, int n_images, const uint32_t *widths, const uint32_t *heights);
+int  mi_batch_fits(const mi_batch *b, int n_images, const uint32_t *widths, const uint32_t *heights);
+int  mi_batch_image_size(const mi_batch *b, int index, uint32_t *w, uint32_t *h);
 int  mi_batch_encode(mi_batch *b);                                                        /* the hot path over all resident images */
 /* split form: enqueue the GPU work and return; wait = sync + one packed D2H + OBU/container assembly.  Two batches
  * driven alternately overlap one batch's entropy coding / loop filters with the next batch's tile search. */
