@@ -4,7 +4,9 @@
 //                          (CDF row, symbol, alphabet) or a literal -- in the superblock's record buffer; a transform block's coefficient
 //                          symbols are written by all lanes at once (contexts depend on the level map only, exclusive scans place them);
 //   adapters (MI_K4_ADAPTERS waves)  own disjoint sets of CDF rows (a row's state depends only on the symbols coded through that row, never on
-//                          the coder state): each turns ITS records into bounds records in place (read the row, pick fl / fh, adapt);
+//                          the coder state): each turns ITS records into bounds records in place (read the row, pick fl / fh, adapt).  The same
+//                          independence holds inside a wave: its four rows of 16 lanes are four adapters working on four different CDF rows in one
+//                          step (k4_row_group), so that nothing per record is wave-uniform -- i.e. scalar -- work (k4_adapt_sb);
 //   coder (last wave)      runs the range recurrence of the finished records on the scalar unit and leaves `low` -- a sum -- to its 64 lanes: prefix sum of the
 //                          shifts, every symbol's contribution added into a ring of byte accumulators in LDS (RangeEncDev below).
 // While the coder works on superblock k the adapters convert k + 1 and the producer writes k + 2; one workgroup barrier per superblock.
@@ -95,53 +97,80 @@ __device__ __forceinline__ int wave_excl_scan_i32(int v, int *total) {
 #define MI_BALLOT64(p) __builtin_amdgcn_ballot_w64(p)
 #endif
 __device__ __forceinline__ unsigned long long k4_ballot(bool p) { return MI_BALLOT64(p); }
-// Adapter `a` over one superblock's records: only its own rows' records are visited (ballot of the chunk, lowest set bit first).  The row sits in a
-// register (lane i = entry i, lane nsyms = the adaptation counter) and stays there while consecutive records name it.
-#ifndef MI_BITSET0_64                                    /* clears bit `j` of a 64-bit scalar mask: one instruction instead of the four of m &= m - 1 (K4 -0.45 ms, profiles/r06R_*) */
-#define MI_BITSET0_64(m, j) asm("s_bitset0_b64 %0, %1" : "+s"(m) : "s"(j))
-#endif
+// which of its owner wave's four 16-lane groups adapts a CDF row (tests/helpers/k4_grouped_streams.py row_group mirrors it): the bits of (context index + table block)
+// above the one k4_row_owner<2> takes, turned by the table block -- chosen on the oracle's symbol histograms for the lowest share of the busiest (wave, group) with two
+// and with four adapters (tools/k4_group_balance.py, profiles/k4_grouped_adapters.md; the hottest single row is the floor: 36 % of a 1080p tile's symbols).
+// Static: the records of one row always meet in one group, in coding order.
+__device__ __forceinline__ int k4_row_group(uint32_t row) { return (int)((((row / 5u + row / 210u) >> 1) + row / 210u) & 3u); }
+__device__ __forceinline__ int k4_popc64(unsigned long long m) { return __builtin_popcountll(m); }
+// Adapter `a` over one superblock's records.  The wave's four rows of 16 lanes are four adapters of their own: per chunk of 64 records (lane = record) every record
+// of this wave's rows is filed under its group (k4_row_group) at its rank among the chunk's records of that group -- four ballots, a popcount -- into a per-wave
+// table in LDS; at step t each group takes its t-th record (one broadcast read), reads its row from the tables (lane e = entry e; fl, fh and the counter as
+// broadcast reads: the tables are current, every step stores its row), adapts it and leaves the bounds record in the table slot, from where the record's own lane
+// fetches it for one coalesced store per chunk.  Nothing per record is wave-uniform any more: the step loop's counter and branch are the scalar unit's only work.
+// The counter stays out of the lanes (entry nsyms - 1 never changes: its lane stores the counter instead), so 16 lanes hold every alphabet.
+// Groups that have run out of records in a chunk compute on record 0 of row 0 and store into a per-lane sink.
 template <int NA> __device__ __forceinline__ void k4_adapt_sb(LDS uint16_t *cdf, uint32_t *buf, int n_in, int a) {
-  const int n = uni32(n_in), i = LANE;
-  int row = -1, v = 0;
+  __shared__ uint32_t k4_group_recs[NA * (4 * 64 + 32)];                    // per adapter: [group][rank in the chunk], then a 16-bit sink per lane for the stores of idle lanes
+  const int n = uni32(n_in), i = LANE, G = i >> 4, e = i & 15;
+  LDS uint32_t *const tab = (LDS uint32_t *)k4_group_recs + a * (4 * 64 + 32);
+  LDS uint32_t *const gtab = tab + G * 64;                                  // the group this lane adapts for
+  LDS uint16_t *const sink = (LDS uint16_t *)(tab + 4 * 64) + i;
   uint32_t nx = n > 0 ? buf[imin_(i, n - 1)] : 0u;
   for (int cb = 0; cb < n; cb += 64) {
     const uint32_t rv = cb + i < n ? nx : 0x80000000u;
     if (cb + 64 < n) nx = buf[imin_(cb + 64 + i, n - 1)];                    // the next chunk's load flies behind this chunk's chain (its records of this adapter's rows are nobody else's to change)
     const bool mine = (rv >> 30) == 0u && k4_row_owner<NA>(rv & 0xFFFFu) == a;
-    unsigned long long todo = k4_ballot(mine);
-    uint32_t outv = rv;
-    while (todo) {
-      const int j = __builtin_ctzll(todo); MI_BITSET0_64(todo, j);
-      const uint32_t rec = (uint32_t)__builtin_amdgcn_readlane((int)rv, j);
-      const int r = (int)(rec & 0xFFFFu);
-      uint32_t out;
-      if (__builtin_expect((rec & 0x20000000u) != 0u, 0)) {  // partition node at the frame edge (rare: kept off the straight path): P(the partitions that split this way), not adapted
-        const int cv = cdf[r + imin_(i, 10)];
-        uint32_t psum = 0;
+    const int g = k4_row_group(rv & 0xFFFFu);
+    const unsigned long long m0 = k4_ballot(mine && g == 0), m1 = k4_ballot(mine && g == 1), m2 = k4_ballot(mine && g == 2), m3 = k4_ballot(mine && g == 3);
+    const int nsteps = uni32(imax_(imax_(k4_popc64(m0), k4_popc64(m1)), imax_(k4_popc64(m2), k4_popc64(m3))));   // the longest group's records: wave-uniform
+    if (nsteps == 0) continue;
+    const bool any_edge = k4_ballot(mine && (rv & 0x20000000u) != 0u) != 0ull;                             // partition nodes at the frame edge are rare: a wave-uniform branch per chunk
+    const unsigned long long gm = g == 0 ? m0 : (g == 1 ? m1 : (g == 2 ? m2 : m3)), Gm = G == 0 ? m0 : (G == 1 ? m1 : (G == 2 ? m2 : m3));
+    const int slot = g * 64 + k4_popc64(gm & ((1ull << i) - 1ull)), have = k4_popc64(Gm);
+    if (mine) tab[slot] = rv;
+    WAVE_SYNC();
+    uint32_t raw = gtab[0], rec = 0 < have ? raw : 0u;
+    for (int t = 0; t < nsteps; t++) {
+      // (every conditional below selects between values already computed: as branches they would each cost the scalar unit an EXEC save and restore)
+      raw = gtab[imin_(t + 1, 63)];                          // the next step's record flies behind this step: it is there before the row is (no wait at the loop's head)
+      const int r = (int)(rec & 0xFFFFu), s = (int)((rec >> 16) & 15u), nsyms = (int)((rec >> 20) & 15u) + 1;   // (an edge record: s = has_cols, nsyms = 1)
+      const int v = cdf[r + imin_(e, nsyms - 1)];
+      const uint32_t fl6 = (uint32_t)cdf[r + imax_(s - 1, 0)] >> 6, fh6 = (uint32_t)cdf[r + s] >> 6, top6 = 512u;
+      const int cnt = cdf[r + nsyms];
+      const uint32_t lo6 = s > 0 ? fl6 : top6;
+      uint32_t out = K4_BOUNDS(lo6, fh6, nsyms - 1 - s);
+      const bool last = e == nsyms - 1;
+      const int at = last ? nsyms : e;
+      LDS uint16_t *const own = cdf + r + at;
+      LDS uint16_t *dst = ((t < have) & (e < nsyms)) ? own : sink;     // idle groups and lanes past the row store into the sink
+      if (any_edge) {                                        // P(the partitions that split this way) from the row as it stands, not adapted: lane q holds cv[q - 1] - cv[q], a row sum
+        const bool edge = (rec & 0x20000000u) != 0u;
+        const int cv = cdf[r + imin_(e, 9)];                                  // (a partition row of 10)
+        const int up = DPP_(0, cv, 0x111, 0xF), diff = up - cv, zero = 0;     // row_shr:1
         const uint32_t set = (rec & 0x10000u) ? 0x2DCu : 0x17Au;              // has_cols: partitions 2, 3, 4, 6, 7, 9; else 1, 3, 4, 5, 6, 8
-#pragma unroll
-        for (int q = 1; q < 10; q++) if ((set >> q) & 1u) psum += (uint32_t)__builtin_amdgcn_readlane(cv, q - 1) - (uint32_t)__builtin_amdgcn_readlane(cv, q);
-        out = K4_BOUNDS(psum >> 6, 0, 0);
-      } else {
-        const int s = (int)((rec >> 16) & 15u), nsyms = (int)((rec >> 20) & 15u) + 1;
-        if (r != row) { v = cdf[r + imin_(i, nsyms)]; row = r; }
-        const uint32_t fl0 = (uint32_t)__builtin_amdgcn_readlane(v, s - 1), fh = (uint32_t)__builtin_amdgcn_readlane(v, s);   // (s = 0: v_readlane takes the lane modulo 64, the value is not used)
-        const int cnt = __builtin_amdgcn_readlane(v, nsyms);
-        out = K4_BOUNDS(s > 0 ? fl0 >> 6 : 512u, fh >> 6, nsyms - 1 - s);
-        // spec 8.3.2, one step for every entry: rate = 3 + (cnt > 15) + (cnt > 31) + min(floor(log2(nsyms)), 2); cnt <= 32.  Written without a branch:
-        // entries below the symbol move up by (32768 - v) >> rate, the others down by v >> rate; entry nsyms - 1 stays, entry nsyms counts.
-        const int rate = 4 + (nsyms > 3) + (cnt >> 4);
-        const bool below = i < s;
-        const int t = below ? 32768 - v : v, sh = t >> rate;
-        const int moved = below ? v + sh : v - sh;
-        const int va = i == nsyms ? imin_(cnt + 1, 32) : (i < nsyms - 1 ? moved : v);
-        if (i <= nsyms) cdf[r + i] = (uint16_t)va;            // (entry nsyms - 1 is rewritten unchanged; storing every symbol's row is CHEAPER than writing a row back when
-                                                              // another one comes -- K4 +0.2 ms with that, profiles/r06R_ab_k4_adapter_diet.txt)
-        v = va;
+        const bool in_set = ((set >> e) & 1u) != 0u;
+        int ps = in_set ? diff : zero;
+        ps += DPP_(0, ps, 0xB1, 0xF); ps += DPP_(0, ps, 0x4E, 0xF); ps += DPP_(0, ps, 0x141, 0xF); ps += DPP_(0, ps, 0x140, 0xF);   // the sum in all 16 lanes of the row
+        const uint32_t eout = K4_BOUNDS((uint32_t)ps >> 6, 0, 0), sout = out;
+        out = edge ? eout : sout;
+        LDS uint16_t *const kept = dst;
+        dst = edge ? sink : kept;
       }
-      outv = i == j ? out : outv;
+      // spec 8.3.2, one step for every entry: rate = 3 + (cnt > 15) + (cnt > 31) + min(floor(log2(nsyms)), 2); cnt <= 32.  Written without a branch:
+      // entries below the symbol move up by (32768 - v) >> rate, the others down by v >> rate; entry nsyms - 1 stays: its lane stores the counter behind it.
+      const int rate = 4 + (nsyms > 3) + ((cnt >> 4) & 3);   // (the mask: an idle group reads some entry of row 0 for a counter)
+      const bool below = e < s;
+      const int inv = 32768 - v, tt = below ? inv : v, sh = tt >> rate;
+      const int up_ = v + sh, dn_ = v - sh, cnt1 = imin_(cnt + 1, 32), moved = below ? up_ : dn_, va = last ? cnt1 : moved;
+      WAVE_SYNC();
+      *dst = (uint16_t)va;                                   // (storing every symbol's row was measured cheaper than writing it back on a row change, profiles/r06R_ab_k4_adapter_diet.txt)
+      gtab[t] = out;                                         // all 16 lanes the same word; both stores unconditional: no divergent region in the step (the EXEC hazard)
+      rec = t + 1 < have ? raw : 0u;
+      WAVE_SYNC();
     }
-    if (mine) buf[cb + i] = outv;
+    if (mine) buf[cb + i] = tab[slot];
+    WAVE_SYNC();
   }
 }
 // The coder over one superblock's finished records.
