@@ -1,6 +1,6 @@
 // cavif_mi -- the cavif command line (src/main.rs) on top of libmi_avif.so: same flags, path rules and report line;
 // the rayon fan-out over files (src/main.rs:223) becomes mi_ravif_encode_batch (one host thread per MI355X).
-//   cavif_mi [-Q n] [-s n] [-j n] [-f] [-o path] [-q] [--dirty-alpha] [--color ycbcr|rgb] [--depth 8|10|auto] [--jpeg-ycbcr] [--deep-png] [--color-managed] [--exif-orientation] [--mixed-sizes] IMAGES...
+//   cavif_mi [-Q n] [-s n] [-j n] [-f] [-o path] [-q] [--dirty-alpha] [--color ycbcr|rgb] [--depth 8|10|auto] [--jpeg-ycbcr] [--deep-png] [--color-managed] [--exif-orientation] [--mixed-sizes] [--fit WxH] [--resize-filter f] IMAGES...
 // Input: PNG and baseline / progressive 8-bit JPEG, told apart by their first bytes as load_image does.  A loader thread does the serial half of the
 // decode -- inflate of a PNG (mi_png_parse), Huffman decoding of a JPEG (mi_jpeg_parse) -- and hands scanlines or coefficients to the encoder, which
 // finishes the picture on the GPU inside the batch that encodes it (mi_ravif_encode_sources): the loaders never touch a device.  Differences, deliberate:
@@ -12,6 +12,10 @@
 // PNG's eXIf chunk), so a portrait photo comes out upright; without it the stored rows are encoded as they are.  It combines with the three flags above.
 // `--mixed-sizes` (off by default) lets the encoder put pictures of different sizes into one run on the GPU (mi_ravif_encoder.mixed_runs) instead of one run
 // per size: a matter of speed on a directory whose files all differ in size; the files written are the same.
+// `--fit WxH` (off by default; `--fit N` = NxN, an extent of 0 = no bound on that axis) scales every picture that is larger than the box down to mi_fit_size of its
+// size -- with --exif-orientation, of its oriented size -- on the GPU on its way in (MI_SOURCE_RESIZED), with `--resize-filter box|bilinear|bicubic|lanczos` (default
+// lanczos): the pixels of Pillow's Image.resize.  A file that fits goes exactly as without the flag.  It combines with --exif-orientation, --jpeg-ycbcr, --color-managed
+// (the conversion follows the resize) and --mixed-sizes; with --deep-png a 16-bit file that must be resized is coded from its high bytes (one warning line per run).
 #include <sched.h>
 #include <sys/stat.h>
 #include <cerrno>
@@ -93,13 +97,17 @@ int host_threads() {
 int usage(const char *msg) {
   fprintf(stderr, "error: %s\nusage: cavif_mi [-Q quality 1-100] [-s speed 1-10] [-j threads] [-f|--overwrite] [-o path] [-q] [--dirty-alpha]\n"
                   "                [--color ycbcr|rgb] [--depth 8|10|auto] [--devices 0,1,..] [--rdo-passes 1|2] [--jpeg-ycbcr] [--deep-png] [--color-managed]\n"
-                  "                [--exif-orientation] [--mixed-sizes] IMAGES...   (\"-\" = stdin/stdout)\n"
+                  "                [--exif-orientation] [--mixed-sizes] [--fit WxH] [--resize-filter box|bilinear|bicubic|lanczos] IMAGES...   (\"-\" = stdin/stdout)\n"
                   "  --color-managed  convert every file to sRGB by its own colour description (an ICC profile, or PNG gAMA / cHRM) on the GPU; a file whose profile\n"
                   "                   is unsupported or malformed is encoded unmanaged (one warning line unless -q).  With --jpeg-ycbcr a JPEG whose description\n"
                   "                   asks for a conversion goes the RGB way: the conversion needs RGB.  Combines with --deep-png.\n"
                   "  --exif-orientation  turn every picture on the GPU as its file's EXIF orientation (tag 0x0112) asks; without it the stored rows are encoded as they are.\n"
                   "                   Combines with --jpeg-ycbcr, --deep-png and --color-managed.\n"
-                  "  --mixed-sizes    encode pictures of different sizes in one run on the GPU; the files written are the same.\n", msg);
+                  "  --mixed-sizes    encode pictures of different sizes in one run on the GPU; the files written are the same.\n"
+                  "  --fit WxH        scale every picture that is larger than the box down to fit it, aspect ratio kept, on the GPU (N = NxN; an extent of 0 = no bound on that\n"
+                  "                   axis); a file that fits is encoded as without the flag.  --resize-filter picks the filter (default lanczos).  Combines with\n"
+                  "                   --exif-orientation (the box holds the turned picture), --jpeg-ycbcr, --color-managed and --mixed-sizes; with --deep-png a 16-bit file\n"
+                  "                   that must be resized is coded from its high bytes.\n", msg);
   return 1;
 }
 
@@ -113,14 +121,14 @@ int usage(const char *msg) {
 #include <sys/wait.h>
 static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 // one input file: where it goes, what its loader made of it (a JPEG leaves it as coefficients, a PNG as filtered scanlines) and how it is to be sent
-struct Job { std::string in_name, out_path; bool out_stdio = false; mi_jpeg_coeffs *jpeg = nullptr; mi_png_scanlines *png = nullptr; uint32_t w = 0, h = 0; bool ycbcr = false, deep = false, managed = false, oriented = false; std::string error; };
-// the source kind (MI_SOURCE_*) of a loaded job: its file type, then managed (which has switched ycbcr off), ycbcr / deep; --exif-orientation adds its modifier
+struct Job { std::string in_name, out_path; bool out_stdio = false; mi_jpeg_coeffs *jpeg = nullptr; mi_png_scanlines *png = nullptr; uint32_t w = 0, h = 0; bool ycbcr = false, deep = false, managed = false, oriented = false, resized = false; int resize_filter = 0; std::string error; };
+// the source kind (MI_SOURCE_*) of a loaded job: its file type, then managed (which has switched ycbcr off), ycbcr / deep; --exif-orientation and --fit add their modifiers
 static int source_kind_plain(const Job &j) {
   if (j.jpeg) return j.managed ? MI_SOURCE_JPEG_MANAGED : j.ycbcr ? MI_SOURCE_JPEG_YCBCR : MI_SOURCE_JPEG;
   if (j.png) return j.managed ? (j.deep ? MI_SOURCE_PNG_DEEP_MANAGED : MI_SOURCE_PNG_MANAGED) : j.deep ? MI_SOURCE_PNG_DEEP : MI_SOURCE_PNG;
   return MI_SOURCE_HOST;
 }
-static int source_kind(const Job &j) { return source_kind_plain(j) | (j.oriented ? MI_SOURCE_ORIENTED : 0); }
+static int source_kind(const Job &j) { return source_kind_plain(j) | (j.oriented ? MI_SOURCE_ORIENTED : 0) | (j.resized ? MI_SOURCE_RESIZED : 0); }
 // --color-managed: what the parsed file says about its colour, probed (parsed, no tables) to learn whether it can be converted; the encoder bakes one transform per
 // distinct description.  True: a usable transform that is not the identity.  An unsupported or malformed profile: one warning line (unless quiet), false.
 static bool probe_managed(const Job &j, bool quiet) {
@@ -166,7 +174,9 @@ int main(int argc, char **argv) {
     }
   }
   float quality = 80.f; int speed = 4, threads = 0, depth = 0, color_model = 0, rdo_passes = 1;
-  bool overwrite = false, quiet = false, dirty_alpha = false, have_output = false, output_stdio = false, jpeg_ycbcr = false, deep_png = false, color_managed = false, exif_orientation = false, mixed_sizes = false;
+  bool overwrite = false, quiet = false, dirty_alpha = false, have_output = false, output_stdio = false, jpeg_ycbcr = false, deep_png = false, color_managed = false, exif_orientation = false, mixed_sizes = false, have_fit = false;
+  uint32_t fit_w = 0, fit_h = 0; int resize_filter = MI_RESAMPLE_LANCZOS3;
+  std::atomic<bool> deep_resized{ false };
   std::string output; std::vector<std::string> images; std::vector<int> devices;
   // clap syntax (src/main.rs:45-110): --name value, --name=value, -n value, -nvalue, -n=value, combined short flags (-fq)
   std::vector<std::string> args;
@@ -206,6 +216,18 @@ int main(int argc, char **argv) {
     else if (a == "--color-managed") color_managed = true;                                                                                             // extension: not a cavif flag
     else if (a == "--mixed-sizes") mixed_sizes = true;                                                                                                 // extension: not a cavif flag
     else if (a == "--exif-orientation") exif_orientation = true;                                                                                       // extension: not a cavif flag
+    else if (a == "--fit") {                                                                                                                           // extension: not a cavif flag
+      // N | WxH, decimal extents up to 65536; 0 = no bound on that axis, but not on both
+      const std::string v = value("--fit"); const size_t x = v.find('x');
+      auto extent = [](const std::string &t, uint32_t *out) { if (t.empty() || t.size() > 5 || t.find_first_not_of("0123456789") != std::string::npos) return false; const long n = atol(t.c_str()); *out = (uint32_t)n; return n <= 65536; };
+      if (!(x == std::string::npos ? extent(v, &fit_w) && (fit_h = fit_w, true) : extent(v.substr(0, x), &fit_w) && extent(v.substr(x + 1), &fit_h)) || (fit_w == 0 && fit_h == 0))
+        return usage("bad --fit (N or WxH, extents up to 65536, 0 = no bound on that axis)");
+      have_fit = true;
+    } else if (a == "--resize-filter") {                                                                                                               // extension: not a cavif flag
+      const std::string v = value("--resize-filter");
+      if (v == "box") resize_filter = MI_RESAMPLE_BOX; else if (v == "bilinear") resize_filter = MI_RESAMPLE_BILINEAR; else if (v == "bicubic") resize_filter = MI_RESAMPLE_BICUBIC;
+      else if (v == "lanczos") resize_filter = MI_RESAMPLE_LANCZOS3; else return usage("bad --resize-filter (box, bilinear, bicubic or lanczos)");
+    }
     else if (a == "--color") { const std::string v = value("--color"); if (v == "ycbcr") color_model = 0; else if (v == "rgb") color_model = 1; else return usage("bad color type"); }
     else if (a == "--rdo-passes") { rdo_passes = atoi(value("--rdo-passes")); if (rdo_passes < 1 || rdo_passes > 2) return usage("bad --rdo-passes (1 or 2)"); }   // extension: not a cavif flag
     else if (a == "--depth") { const std::string v = value("--depth"); depth = v == "8" ? 8 : v == "10" ? 10 : 0; if (v != "8" && v != "10" && v != "auto") return usage("bad depth"); }
@@ -267,6 +289,14 @@ int main(int argc, char **argv) {
         int o = 1;
         if ((is_jpeg ? mi_jpeg_coeffs_orientation(j.jpeg, &o) : mi_png_scanlines_orientation(j.png, &o)) == MI_OK) { j.oriented = true; mi_oriented_size(j.w, j.h, o, &j.w, &j.h); }
       }
+      if (!st && have_fit) {                                        // a picture larger than the box: the slot is the fitted picture's, the file is resampled on its way in
+        uint32_t fw, fh;
+        mi_fit_size(j.w, j.h, fit_w, fit_h, &fw, &fh);
+        if (fw != j.w || fh != j.h) {
+          j.resized = true; j.resize_filter = resize_filter; j.w = fw; j.h = fh;
+          if (j.deep) { j.deep = false; deep_resized = true; }        // resizing deep sources is not built: the file's high bytes
+        }
+      }
       if (st) j.error = st == MI_UNSUPPORTED ? "unsupported image format (this build reads PNG and baseline/progressive 8-bit JPEG)" :
                         st == MI_NO_DEVICE ? "no HIP device (this encoder has no CPU fallback)" : "corrupt image data";
     }
@@ -307,6 +337,7 @@ int main(int argc, char **argv) {
     const Job &j = (*c->jobs)[i];
     if (!j.error.empty()) return MI_INVALID_ARGUMENT;           // reported from the job's own message below
     src->kind = source_kind(j); src->jpeg = j.jpeg; src->png = j.png;
+    if (j.resized) src->resize_filter = j.resize_filter;
     mi_image_desc *d = &src->desc;
     d->pixels = nullptr; d->width = j.w; d->height = j.h; d->stride_px = j.w; d->channels = 4;     // a JPEG or PNG into an RGBA slot: the pixels load_rgba gives it
     return MI_OK;
@@ -329,6 +360,7 @@ int main(int argc, char **argv) {
   if (timing) fprintf(stderr, "[timing] HIP runtime up %.3f s\n", now_s() - t_start);
   const int rc_all = mi_ravif_encode_sources(&enc, jobs.size(), fetch, release, &ctx, enc_out.data(), status.data(), devices.empty() ? nullptr : devices.data(), (int)devices.size());
   for (auto &t : pool) t.join();
+  if (deep_resized && !quiet) fprintf(stderr, "warning: --deep-png: 16-bit files that --fit resizes are encoded from their high bytes\n");
   if (timing) fprintf(stderr, "[timing] encoded %.3f s\n", now_s() - t_start);
   if (rc_all == MI_NO_DEVICE) for (size_t i = 0; i < jobs.size(); i++) if (jobs[i].error.empty()) status[i] = MI_NO_DEVICE;
   std::vector<size_t> who;

@@ -764,14 +764,17 @@ static int batch_reserve_scratch(mi_batch *b, size_t bytes) {
   return staging_grow(b->d_rs_scratch, b->d_rs_scratch_cap, bytes) ? MI_OK : MI_ENCODING_ERROR;
 }
 
-// The two passes: `count` pictures of s.w x s.h described by s -> slots [first, first + count).  The tables go into the batch's pinned staging and over in
-// one H2D (a call with the sizes and the filter of the one before it finds them on the device); the intermediate lies `inter_at` bytes into the scratch,
-// which the caller has reserved up to inter_at + resample_inter_bytes().  Stream order serialises the users of the scratch.  No sync.
+// The two passes: `count` pictures of s.w x s.h described by s, turned by `o` (1..8, DESIGN.md 5l: the oriented picture is resampled from where the source lies,
+// no turned copy) -> slots [first, first + count), tagged `kind`.  The tables go into the batch's pinned staging and over in one H2D (a call with the oriented
+// size, the slots' size and the filter of the one before it finds them on the device); the intermediate lies `inter_at` bytes into the scratch, which the caller
+// has reserved up to inter_at + resample_inter_bytes() of the ORIENTED height.  Stream order serialises the users of the scratch.  No sync.
 static size_t resample_inter_bytes(int count, uint32_t src_h, uint32_t dst_w) { return (size_t)count * src_h * align_up(dst_w, 4) * 4; }
-static int batch_resample(mi_batch *b, int first, int count, const IngestSrc &s, int filter, size_t inter_at) {
+static int batch_resample(mi_batch *b, int first, int count, const IngestSrc &s, int filter, size_t inter_at, int o = 1, int kind = MI_INPUT_RGB) {
   const uint32_t dw = slot_w(b, first), dh = slot_h(b, first);    // the slots' size (one for the range: the callers have checked)
-  const uint32_t key[5] = { s.w, s.h, dw, dh, (uint32_t)filter + 1 };
-  const size_t h_bytes = resample_axis_bytes(s.w, dw, filter), need = align_up(h_bytes + resample_axis_bytes(s.h, dh, filter), 256);
+  uint32_t ow, oh;
+  oriented_size(s.w, s.h, o, &ow, &oh);                           // 5..8: the source's height feeds the horizontal axis, its width the vertical one
+  const uint32_t key[5] = { ow, oh, dw, dh, (uint32_t)filter + 1 };
+  const size_t h_bytes = resample_axis_bytes(ow, dw, filter), need = align_up(h_bytes + resample_axis_bytes(oh, dh, filter), 256);
   size_t at = b->rs_key_at;
   if (memcmp(key, b->rs_key, sizeof(key)) != 0) {
     if (b->rs_used + need > b->h_rs_cap || b->rs_used + need > b->d_rs_cap) {
@@ -781,8 +784,8 @@ static int batch_resample(mi_batch *b, int first, int count, const IngestSrc &s,
     }
     at = b->rs_used; b->rs_used += need;
     uint8_t *const hb = b->h_rs.get() + at;
-    resample_axis(s.w, dw, filter, (uint32_t *)hb, (int32_t *)(hb + align_up((size_t)dw * 8, 16)));
-    resample_axis(s.h, dh, filter, (uint32_t *)(hb + h_bytes), (int32_t *)(hb + h_bytes + align_up((size_t)dh * 8, 16)));
+    resample_axis(ow, dw, filter, (uint32_t *)hb, (int32_t *)(hb + align_up((size_t)dw * 8, 16)));
+    resample_axis(oh, dh, filter, (uint32_t *)(hb + h_bytes), (int32_t *)(hb + h_bytes + align_up((size_t)dh * 8, 16)));
     HIP_OK(hipMemcpyAsync(b->d_rs.get() + at, hb, need, hipMemcpyHostToDevice, b->stream));
     memcpy(b->rs_key, key, sizeof(key)); b->rs_key_at = at;
   }
@@ -791,13 +794,17 @@ static int batch_resample(mi_batch *b, int first, int count, const IngestSrc &s,
   const int32_t *const htaps = (const int32_t *)(db + align_up((size_t)dw * 8, 16)), *const vtaps = (const int32_t *)(db + h_bytes + align_up((size_t)dh * 8, 16));
   const uint32_t pitch = (uint32_t)align_up(dw, 4);
   uint32_t *const inter = (uint32_t *)(b->d_rs_scratch.get() + inter_at);
-  hipLaunchKernelGGL(resample_h_kernel, dim3((dw + MI_RS_TW - 1) / MI_RS_TW, (s.h + MI_RS_TH - 1) / MI_RS_TH, (unsigned)count), dim3(64 * MI_RS_TH), 0, b->stream,
-                     s, hbounds, htaps, dw, pitch, inter);
+  if (orientation_turns(o))
+    hipLaunchKernelGGL(resample_t_kernel, dim3((dw + MI_RS_TT - 1) / MI_RS_TT, (s.w + MI_RS_TT - 1) / MI_RS_TT, (unsigned)count), dim3(256), 0, b->stream,
+                       s, o, hbounds, htaps, dw, pitch, inter);
+  else
+    hipLaunchKernelGGL(resample_h_kernel, dim3((dw + MI_RS_TW - 1) / MI_RS_TW, (s.h + MI_RS_TH - 1) / MI_RS_TH, (unsigned)count), dim3(64 * MI_RS_TH), 0, b->stream,
+                       s, o, hbounds, htaps, dw, pitch, inter);
   uint8_t *const slots = mi_batch_device_input(b, first);
   const int alpha = s.channels == 4 ? 1 : 0;
-  LAUNCH_BY_CHANNELS(b, b->channels, dw, dh, count, resample_v_kernel, (const uint32_t *)inter, s.h, pitch, vbounds, vtaps, dw, dh, alpha, slots);
+  LAUNCH_BY_CHANNELS(b, b->channels, dw, dh, count, resample_v_kernel, (const uint32_t *)inter, oh, pitch, vbounds, vtaps, dw, dh, alpha, slots);
   HIP_OK(hipGetLastError());
-  batch_tag(b, first, count, MI_INPUT_RGB);
+  batch_tag(b, first, count, kind);
   return MI_OK;
 }
 static bool resample_filter_known(int filter) { return filter >= MI_RESAMPLE_BOX && filter <= MI_RESAMPLE_LANCZOS3; }
@@ -1093,6 +1100,78 @@ int mi_batch_upload_png_oriented(mi_batch *b, int index, const mi_png_scanlines 
   if (int st = batch_orient(b, index, 1, orient_scratch_source(b, sl.w, sl.h, channels, sample_bytes), o, goes_deep)) return st;
   batch_tag(b, index, 1, goes_deep ? MI_INPUT_RGB16 : MI_INPUT_RGB);
   return MI_OK;
+}
+
+// ---- resize on input of a turned source: orientation and resampling in one go, from where the source lies -- no turned copy, the scratch of the plain
+// resize call.  Orientation 1 (given or the file's) is the plain mi_batch_resize_* call (ycbcr: the same two passes over the file's own triples); an oriented source
+// that already has the slot's size is the _oriented upload of its kind: neither takes the premultiply round trip.  Every check comes first: a refused call
+// allocates nothing.  8-bit only: a 16-bit PNG is taken through its high bytes, as mi_batch_resize_png takes it (resizing deep sources is out of scope). ----
+int mi_batch_resize_device_oriented(mi_batch *b, int first, int count, const mi_device_pixels *src, uint32_t src_w, uint32_t src_h, int filter, int orientation) {
+  IngestSrc s; uint32_t w, h, ow, oh;
+  if (!batch_range_sized(b, first, count, w, h) || !resample_filter_known(filter) || orientation < 1 || orientation > 8 || !resample_extent_ok(src_w, src_h) ||
+      !batch_device_source(b, src, src_w, src_h, s)) return MI_INVALID_ARGUMENT;
+  if (orientation == 1) return mi_batch_resize_device(b, first, count, src, src_w, src_h, filter);
+  oriented_size(src_w, src_h, orientation, &ow, &oh);
+  if (ow == w && oh == h) return mi_batch_orient_device(b, first, count, src, orientation);
+  (void)hipSetDevice(b->device);
+  if (int st = batch_reserve_scratch(b, resample_inter_bytes(count, oh, w))) return st;
+  if (int st = batch_join(b, src->after_stream)) return st;
+  return batch_resample(b, first, count, s, filter, 0, orientation);
+}
+
+// one parsed JPEG of any size into slot `index`, turned by `orientation` (0: as the file's Exif segment says) and resampled: decoded into the scratch as three
+// channels (ycbcr: jpeg_ycc_kernel -- the file's own (Y, Cb', Cr') triples are resampled channel by channel and the slot is tagged MI_INPUT_YCBCR), then the two passes
+int mi_batch_resize_jpeg_oriented(mi_batch *b, int index, const mi_jpeg_coeffs *c, int filter, int orientation, int ycbcr) {
+  if (!batch_index_ok(b, index) || !c || !resample_filter_known(filter) || orientation < 0 || orientation > 8) return MI_INVALID_ARGUMENT;
+  const JpegCoeffs &jc = c->jc;
+  const int o = orientation ? orientation : jc.orientation;
+  const bool ycc = ycbcr != 0;
+  if (ycc && !batch_takes_ycbcr(b)) return MI_INVALID_ARGUMENT;
+  if (batch_oriented_fits(b, index, jc.w, jc.h, o)) return mi_batch_upload_jpeg_oriented(b, index, c, o, ycbcr);
+  if (!resample_extent_ok(jc.w, jc.h)) return MI_INVALID_ARGUMENT;
+  if (ycc && jc.color == JPEG_RGB) return MI_UNSUPPORTED;
+  if (o == 1 && !ycc) return mi_batch_resize_jpeg(b, index, c, filter);
+  uint32_t ow, oh;
+  oriented_size(jc.w, jc.h, o, &ow, &oh);
+  (void)hipSetDevice(b->device);
+  const size_t inter_at = align_up((size_t)jc.w * jc.h * 3, 256);
+  if (int st = batch_reserve_scratch(b, inter_at + resample_inter_bytes(1, oh, slot_w(b, index)))) return st;
+  if (int st = batch_jpeg_decode(b, jc, b->d_rs_scratch.get(), 3, jc.w, ycc)) return st;
+  return batch_resample(b, index, 1, resample_scratch_source(b, jc.w, jc.h, 3), filter, inter_at, o, ycc ? MI_INPUT_YCBCR : MI_INPUT_RGB);
+}
+
+// one parsed PNG of any size into slot `index`, turned by `orientation` (0: as the file's eXIf chunk says) and resampled: unfiltered and expanded into the scratch
+// (RGBA when the file has alpha or tRNS, else RGB; a file of bit depth 16 through its high bytes), then the two passes
+int mi_batch_resize_png_oriented(mi_batch *b, int index, const mi_png_scanlines *p, int filter, int orientation) {
+  if (!batch_index_ok(b, index) || !p || !resample_filter_known(filter) || orientation < 0 || orientation > 8) return MI_INVALID_ARGUMENT;
+  const PngScanlines &sl = p->sl;
+  const int o = orientation ? orientation : sl.orientation, channels = sl.has_alpha() ? 4 : 3;
+  if (channels > b->channels) return MI_INVALID_ARGUMENT;     // alpha is never dropped
+  if (batch_oriented_fits(b, index, sl.w, sl.h, o)) return mi_batch_upload_png_oriented(b, index, p, o, 0);
+  if (!resample_extent_ok(sl.w, sl.h)) return MI_INVALID_ARGUMENT;
+  if (o == 1) return mi_batch_resize_png(b, index, p, filter);
+  uint32_t ow, oh;
+  oriented_size(sl.w, sl.h, o, &ow, &oh);
+  (void)hipSetDevice(b->device);
+  const size_t inter_at = align_up((size_t)sl.w * sl.h * channels, 256);
+  if (int st = batch_reserve_scratch(b, inter_at + resample_inter_bytes(1, oh, slot_w(b, index)))) return st;
+  if (int st = batch_png_expand(b, 1, &p, channels, b->d_rs_scratch.get())) return st;
+  return batch_resample(b, index, 1, resample_scratch_source(b, sl.w, sl.h, channels), filter, inter_at, o);
+}
+
+// the size of a picture of sw x sh scaled down, never up, to fit a box (an extent of 0: no bound on that axis), aspect ratio kept: the bound axis takes the
+// box's extent, the free one is rounded half up (at least 1, never past the box).  Exact 64-bit integers.
+void mi_fit_size(uint32_t sw, uint32_t sh, uint32_t box_w, uint32_t box_h, uint32_t *w, uint32_t *h) {
+  const uint64_t W = sw, H = sh, bw = box_w, bh = box_h;
+  uint64_t fw = W, fh = H;
+  // (2 a b + c) / (2 c) for 32-bit a, b, c without leaving 64 bits: the quotient of a b / c, one more when twice the remainder reaches c; at least 1
+  auto half_up = [](uint64_t a, uint64_t b, uint64_t c) { const uint64_t p = a * b, q = p / c + (2 * (p % c) >= c ? 1 : 0); return q ? q : (uint64_t)1; };
+  if (W && H && !((bw == 0 || W <= bw) && (bh == 0 || H <= bh))) {
+    if (bh == 0 || (bw != 0 && bw * H <= bh * W)) { fw = bw; fh = half_up(H, bw, W); }
+    else { fh = bh; fw = half_up(W, bh, H); }
+  }
+  if (w) *w = (uint32_t)fw;
+  if (h) *h = (uint32_t)fh;
 }
 
 }  // extern "C"

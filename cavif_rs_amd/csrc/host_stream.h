@@ -29,10 +29,16 @@ static_assert(sizeof(SOURCE_KINDS) / sizeof(SOURCE_KINDS[0]) == 8 && MI_SOURCE_H
               MI_SOURCE_JPEG_MANAGED == 5 && MI_SOURCE_PNG_MANAGED == 6 && MI_SOURCE_PNG_DEEP_MANAGED == 7, "one row per MI_SOURCE_*, in the enum's order");
 // One modifier on the kinds that carry a handle, not eight more rows: MI_SOURCE_ORIENTED (0x100) ORed into kinds 1..7 -- the picture is turned as its file says on its
 // way into the slot (the _oriented upload of its route), and desc names the oriented picture.  The row is found by kind & 0xFF.
+// A second one, MI_SOURCE_RESIZED (0x200) on kinds 1, 2, 3, 5 and 6: desc names the OUTPUT picture -- the slot --, the file has any size and is resampled
+// on its way in with mi_image_source.resize_filter (the _oriented resize call of its route; with MI_SOURCE_ORIENTED it is turned as its file asks first).
 static bool source_oriented(int kind) { return (kind & MI_SOURCE_ORIENTED) != 0; }
-static const SourceKind *source_kind(int kind) {                 // nullptr: no such kind (8..255, any other bit, the flag on host pixels)
+static bool source_resized(int kind) { return (kind & MI_SOURCE_RESIZED) != 0; }
+static const SourceKind *source_kind(int kind) {                 // nullptr: no such kind (8..255, any other bit, a flag on host pixels, MI_SOURCE_RESIZED on the deep kinds)
   const int row = kind & 0xFF;
-  return kind >= 0 && (kind & ~(0xFF | MI_SOURCE_ORIENTED)) == 0 && row < 8 && !(source_oriented(kind) && row == MI_SOURCE_HOST) ? &SOURCE_KINDS[row] : nullptr;
+  if (kind < 0 || (kind & ~(0xFF | MI_SOURCE_ORIENTED | MI_SOURCE_RESIZED)) != 0 || row >= 8) return nullptr;
+  if ((source_oriented(kind) || source_resized(kind)) && row == MI_SOURCE_HOST) return nullptr;
+  if (source_resized(kind) && SOURCE_KINDS[row].route == ROUTE_PNG_DEEP) return nullptr;      // resizing deep sources is not built
+  return &SOURCE_KINDS[row];
 }
 // the colour description of a managed source (icc_reader.h: the kind travels beside the bytes; a view into the source's handle)
 static ColourDescription source_colour_description(const mi_image_source &src) {
@@ -46,10 +52,17 @@ static int source_refusal(const mi_ravif_encoder &e, const mi_image_source &src)
   const SourceKind *const kind = source_kind(src.kind);
   if (!kind) return MI_INVALID_ARGUMENT;
   // the size desc names is the file's, or with MI_SOURCE_ORIENTED that of the file turned as it asks
-  auto fits = [&](uint32_t w, uint32_t h, int orientation) { uint32_t ow, oh; oriented_size(w, h, source_oriented(src.kind) ? orientation : 1, &ow, &oh); return ow == x.width && oh == x.height; };
+  // (a resized source's file has any size the resize calls take: desc names the output, and the filter must be one of MI_RESAMPLE_*)
+  const bool resized = source_resized(src.kind);
+  if (resized && !resample_filter_known(src.resize_filter)) return MI_INVALID_ARGUMENT;
+  auto fits = [&](uint32_t w, uint32_t h, int orientation) {
+    if (resized) return resample_extent_ok(w, h);
+    uint32_t ow, oh; oriented_size(w, h, source_oriented(src.kind) ? orientation : 1, &ow, &oh); return ow == x.width && oh == x.height;
+  };
   const bool have = kind->handle == HANDLE_NONE ? x.pixels != nullptr : kind->handle == HANDLE_JPEG ? src.jpeg && fits(src.jpeg->jc.w, src.jpeg->jc.h, src.jpeg->jc.orientation) :
                     src.png && fits(src.png->sl.w, src.png->sl.h, src.png->sl.orientation) && !(x.channels == 3 && src.png->sl.has_alpha());
   if (!have || !x.width || !x.height || (x.channels != 3 && x.channels != 4)) return MI_INVALID_ARGUMENT;
+  if (resized && !resample_extent_ok(x.width, x.height)) return MI_INVALID_ARGUMENT;
   if (kind->route == ROUTE_JPEG_YCBCR && !batch_takes_ycbcr(e, x.channels)) return MI_INVALID_ARGUMENT;      // the batch's rule first, then the file's colour, as in mi_batch_upload_jpeg_ycbcr
   if (kind->route == ROUTE_JPEG_YCBCR && src.jpeg->jc.color == JPEG_RGB) return MI_UNSUPPORTED;
   if (kind->route == ROUTE_PNG_DEEP && png_goes_deep(src.png) && !batch_takes_deep(e, x.channels, src.png->sl.has_alpha() ? 4 : 3)) return MI_INVALID_ARGUMENT;
@@ -77,7 +90,7 @@ static constexpr int NSLOT_MAX = 4, NSLOT = MI_STREAM_SLOTS_DEFAULT;
 static size_t est_bytes(uint32_t w, uint32_t h, int ch, size_t images) { return images * (size_t)w * h * (ch == 4 ? 110 : 82) + ((size_t)32 << 20); }   // arena + records + staging per pixel (measured on the planner)
 // what a batch object adds at its first JPEG image: MI_BATCH_JPEG_STAGED images' coefficients (at most three full planes of int16) pinned and on the device, one image's planes
 static size_t est_jpeg_bytes(uint32_t w, uint32_t h) { return ((size_t)w + 15) * ((size_t)h + 15) * (2 * MI_BATCH_JPEG_STAGED * 6 + 3) + ((size_t)3 << 20); }
-struct Slot { mi_batch *b = nullptr; std::future<mi_batch *> making; std::vector<size_t> idx; bool busy = false, jpeg = false, deep = false; size_t bytes = 0, png_bytes = 0, scratch_bytes = 0; };
+struct Slot { mi_batch *b = nullptr; std::future<mi_batch *> making; std::vector<size_t> idx; bool busy = false, deep = false; size_t bytes = 0, jpeg_bytes = 0, png_bytes = 0, scratch_bytes = 0; };
 struct Shape { uint32_t w, h; int ch; size_t cap; Slot slot[NSLOT_MAX]; int next = 0; size_t runs = 0, last_use = 0; bool mixed = false; };
 // mixed runs (mi_ravif_encoder.mixed_runs == 1): one rotation per channel count whose objects are made for `cap` pictures of this reference size and
 // hold runs of pictures of any sizes that fit what such an object reserves (mi_batch_fits); the bench's own batch, under MI_SLOT_BYTES for both channel counts
@@ -107,7 +120,7 @@ struct StreamWorker {
     return baked.back().t;
   }
   void charge(Slot &sl, size_t extra) { sl.bytes += extra; live_bytes += extra; }      // what a slot's object holds on the device and pinned counts against the worker's budget
-  void reset_accounting(Slot &sl) { live_bytes -= std::min(live_bytes, sl.bytes); sl.bytes = 0; sl.jpeg = false; sl.deep = false; sl.png_bytes = 0; sl.scratch_bytes = 0; }
+  void reset_accounting(Slot &sl) { live_bytes -= std::min(live_bytes, sl.bytes); sl.bytes = 0; sl.jpeg_bytes = 0; sl.deep = false; sl.png_bytes = 0; sl.scratch_bytes = 0; }
   // finish the slot's run, if any (its files and statuses go to the caller), and take an object that is being made: sl.b is the slot's object afterwards, or null
   void settle(Slot &sl) {
     if (sl.busy) {
@@ -180,10 +193,15 @@ struct StreamWorker {
   int stage(const Shape &sh, Slot &sl, const Sources &d, const Run &run) {
     auto source = [&](size_t k) -> const mi_image_source & { return d[run[k]]; };
     // (an oriented source's picture is decoded into the batch's scratch first: one picture of the slot's size, two bytes a sample on the deep route, joins the worker's budget)
-    auto charge_scratch = [&](bool deep_route, const mi_image_desc &x) { const size_t need = (size_t)x.width * x.height * 4 * (deep_route ? 2 : 1) + ((size_t)1 << 20); if (need > sl.scratch_bytes) { charge(sl, need - sl.scratch_bytes); sl.scratch_bytes = need; } };
-    const int rc = for_each_group(run.size(), [&](size_t k) { return (int)source_kind(source(k).kind)->route | (source(k).kind & MI_SOURCE_ORIENTED); }, [&](size_t from, size_t to) -> int {
+    auto charge_bytes = [&](size_t need) { if (need > sl.scratch_bytes) { charge(sl, need - sl.scratch_bytes); sl.scratch_bytes = need; } };
+    auto charge_scratch = [&](bool deep_route, const mi_image_desc &x) { charge_bytes((size_t)x.width * x.height * 4 * (deep_route ? 2 : 1) + ((size_t)1 << 20)); };
+    // (a resized source: the decoded file of fw x fh and the intermediate of the two passes, at most max(fw, fh) rows of the slot's width -- the slot is charged what its largest source needs)
+    auto charge_resize = [&](uint32_t fw, uint32_t fh, const mi_image_desc &x) { charge_bytes((size_t)fw * fh * 4 + resample_inter_bytes(1, std::max(fw, fh), x.width) + ((size_t)2 << 20)); };
+    // (the JPEG staging follows the largest file: the shape's size, or a resized source's own)
+    auto charge_jpeg = [&](uint32_t fw, uint32_t fh) { const size_t need = est_jpeg_bytes(fw, fh); if (need > sl.jpeg_bytes) { charge(sl, need - sl.jpeg_bytes); sl.jpeg_bytes = need; } };
+    const int rc = for_each_group(run.size(), [&](size_t k) { return (int)source_kind(source(k).kind)->route | (source(k).kind & (MI_SOURCE_ORIENTED | MI_SOURCE_RESIZED)); }, [&](size_t from, size_t to) -> int {
       const UploadRoute route = source_kind(source(from).kind)->route;
-      const bool oriented = source_oriented(source(from).kind);
+      const bool oriented = source_oriented(source(from).kind), resized = source_resized(source(from).kind);
       switch (route) {
       case ROUTE_HOST: {                                         // every image into the pinned staging, then one H2D
         for (size_t k = from; k < to; k++) {                      // (a slot has its source's size: the shape's, or in a mixed run the one mi_batch_set_sizes gave it)
@@ -198,8 +216,14 @@ struct StreamWorker {
         return mi_batch_upload_async(sl.b, (int)from, (int)(to - from));
       }
       case ROUTE_JPEG: case ROUTE_JPEG_YCBCR:                    // coefficients to the batch's own staging, decoded into the slot on the batch's stream
-        if (!sl.jpeg) { sl.jpeg = true; charge(sl, est_jpeg_bytes(sh.w, sh.h)); }
+        charge_jpeg(sh.w, sh.h);
         for (size_t k = from; k < to; k++) {
+          if (resized) {                                         // any size: turned as the file asks (orientation 0) or not at all (1), resampled into the slot
+            const JpegCoeffs &jc = source(k).jpeg->jc;
+            charge_jpeg(jc.w, jc.h); charge_resize(jc.w, jc.h, source(k).desc);
+            if (const int st = mi_batch_resize_jpeg_oriented(sl.b, (int)k, source(k).jpeg, source(k).resize_filter, oriented ? 0 : 1, route == ROUTE_JPEG_YCBCR)) return st;
+            continue;
+          }
           if (oriented) charge_scratch(false, source(k).desc);
           if (const int st = oriented ? mi_batch_upload_jpeg_oriented(sl.b, (int)k, source(k).jpeg, 0, route == ROUTE_JPEG_YCBCR) :
                              route == ROUTE_JPEG_YCBCR ? mi_batch_upload_jpeg_ycbcr(sl.b, (int)k, source(k).jpeg) : mi_batch_upload_jpeg(sl.b, (int)k, source(k).jpeg)) return st;
@@ -211,6 +235,13 @@ struct StreamWorker {
         const size_t extra = 2 * (png_call_bytes((int)pngs.size(), pngs.data()) + ((size_t)1 << 20));
         if (extra > sl.png_bytes) { charge(sl, extra - sl.png_bytes); sl.png_bytes = extra; }
         if (route == ROUTE_PNG_DEEP && !sl.deep) { sl.deep = true; charge(sl, sh.cap * (size_t)sh.w * sh.h * sh.ch * 2); }   // the deep slots join the worker's budget
+        if (resized) {                                           // one file a call, as above (never the deep route: source_kind)
+          for (size_t k = from; k < to; k++) {
+            charge_resize(source(k).png->sl.w, source(k).png->sl.h, source(k).desc);
+            if (const int st = mi_batch_resize_png_oriented(sl.b, (int)k, source(k).png, source(k).resize_filter, oriented ? 0 : 1)) return st;
+          }
+          return MI_OK;
+        }
         if (oriented) {                                          // one file a call: each goes through the scratch
           for (size_t k = from; k < to; k++) charge_scratch(route == ROUTE_PNG_DEEP, source(k).desc);
           for (size_t k = from; k < to; k++) if (const int st = mi_batch_upload_png_oriented(sl.b, (int)k, source(k).png, 0, route == ROUTE_PNG_DEEP)) return st;
@@ -278,6 +309,7 @@ struct StreamWorker {
       auto flush = [&](bool more) { if (!run.empty()) { submit(*run_shape, d, run, i0, more); run.clear(); run_w.clear(); run_h.clear(); } };
       for (size_t i = i0; i < i1; i++) {
         mi_image_source &src = d[i - i0];
+        src.resize_filter = -1;                                  // no filter: a caller that sets MI_SOURCE_RESIZED says which (one that does not know the field cannot ask for a resize)
         if (const int rc = call.fetch(call.user, i, &src)) { call.st[i] = rc; continue; }
         if (const int why = source_refusal(*call.e, src)) { call.st[i] = why; if (call.release) call.release(call.user, i); continue; }
         const SourceKind &kind = *source_kind(src.kind);
@@ -345,7 +377,7 @@ int mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source
 }
 // the host-pixel form: every source is MI_SOURCE_HOST
 struct StreamAdapter { mi_fetch_fn fetch; mi_release_fn release; void *user; };
-static int fetch_host_source(void *user, size_t i, mi_image_source *src) { const StreamAdapter *a = (const StreamAdapter *)user; src->kind = MI_SOURCE_HOST; src->jpeg = nullptr; src->png = nullptr; return a->fetch(a->user, i, &src->desc); }
+static int fetch_host_source(void *user, size_t i, mi_image_source *src) { const StreamAdapter *a = (const StreamAdapter *)user; src->kind = MI_SOURCE_HOST; src->jpeg = nullptr; src->png = nullptr; src->resize_filter = 0; return a->fetch(a->user, i, &src->desc); }
 static void release_host_source(void *user, size_t i) { const StreamAdapter *a = (const StreamAdapter *)user; a->release(a->user, i); }
 int mi_ravif_encode_stream(const mi_ravif_encoder *e, size_t n, mi_fetch_fn fetch, mi_release_fn release, void *user, mi_encoded_image *out, int *status, const int *devices, int ndev) {
   if (!e || !fetch || (n && !out)) return MI_INVALID_ARGUMENT;

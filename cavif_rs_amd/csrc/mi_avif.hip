@@ -71,7 +71,7 @@ struct mi_batch {
   // resize on input: the per-axis tables (bounds + taps) of the mi_batch_resize_* calls since the stream last drained, pinned and on the device, the last call's
   // kept for the next one of the same sizes and filter; one device scratch for a decoded JPEG / PNG source and the intermediate of the two passes
   PinBuf<uint8_t> h_rs; DevBuf<uint8_t> d_rs, d_rs_scratch; size_t h_rs_cap = 0, d_rs_cap = 0, rs_used = 0, d_rs_scratch_cap = 0;
-  uint32_t rs_key[5] = { 0, 0, 0, 0, 0 }; size_t rs_key_at = 0;     // src_w, src_h, dst_w, dst_h, filter + 1 of the tables at rs_key_at (0 in [4]: none)
+  uint32_t rs_key[5] = { 0, 0, 0, 0, 0 }; size_t rs_key_at = 0;     // oriented src_w, src_h, dst_w, dst_h, filter + 1 of the tables at rs_key_at (0 in [4]: none)
   // quality metrics (mi_batch_measure): `encoded` = the planes of a completed encode of the current image count are on the device, `measured` = h_quality holds
   // that encode's records.  The records live at the end of the arena (FrameSet::d_records); their pinned D2H target is made by the first measure.
   bool encoded = false, measured = false;

@@ -51,7 +51,7 @@ class _ImageDesc(C.Structure):
 
 
 class _ImageSource(C.Structure):
-    _fields_ = [('kind', C.c_int), ('desc', _ImageDesc), ('jpeg', C.c_void_p), ('png', C.c_void_p)]
+    _fields_ = [('kind', C.c_int), ('desc', _ImageDesc), ('jpeg', C.c_void_p), ('png', C.c_void_p), ('resize_filter', C.c_int)]
 
 
 class _DevicePixels(C.Structure):
@@ -139,6 +139,10 @@ _PROTOTYPES = {
     'mi_batch_resize_device': (_STATUS, [_P, _I, _I, C.POINTER(_DevicePixels), _U32, _U32, _I]),
     'mi_batch_resize_jpeg': (_STATUS, [_P, _I, _P, _I]),
     'mi_batch_resize_png': (_STATUS, [_P, _I, _P, _I]),
+    'mi_batch_resize_device_oriented': (_STATUS, [_P, _I, _I, C.POINTER(_DevicePixels), _U32, _U32, _I, _I]),
+    'mi_batch_resize_jpeg_oriented': (_STATUS, [_P, _I, _P, _I, _I, _I]),
+    'mi_batch_resize_png_oriented': (_STATUS, [_P, _I, _P, _I, _I]),
+    'mi_fit_size': (None, [_U32, _U32, _U32, _U32, _PU32, _PU32]),
     'mi_ravif_encode_device_resized': (_STATUS, [_ENC, C.POINTER(_DevicePixels), _U32, _U32, _U32, _U32, _I, _OUT]),
     'mi_batch_measure': (_STATUS, [_P]),
     'mi_batch_get_quality': (_STATUS, [_P, _I, _QUAL]),
@@ -258,6 +262,18 @@ def exif_orientation(exif):
     o = C.c_int(1)
     _ok(load_library().mi_exif_orientation(exif, len(exif), C.byref(o)))
     return o.value
+
+
+def fit_size(sw, sh, box):
+    """mi_fit_size: (width, height) of a picture of sw x sh scaled down, never up, to fit box = (width, height) or one number for both, aspect ratio kept; a box
+    extent of 0 is no bound on that axis.  The free axis is rounded half up and never exceeds the box."""
+    bw, bh = (box, box) if isinstance(box, int) else box
+    vals = [int(v) for v in (sw, sh, bw, bh)]
+    if any(v < 0 or v >= 1 << 32 for v in vals):
+        raise AvifError(4)
+    w, h = C.c_uint32(), C.c_uint32()
+    load_library().mi_fit_size(*vals, C.byref(w), C.byref(h))
+    return w.value, h.value
 
 
 def oriented_size(width, height, orientation):
@@ -449,6 +465,7 @@ DECODED_WHICH = {'recon': 0, 'source': 1}                   # MI_DECODED_*
 INPUT_RGB, INPUT_YCBCR, INPUT_RGB16, INPUT_YCBCR16 = range(4)   # MI_INPUT_*: what the samples of a batch slot mean (BatchEncoder.input_kind)
 SOURCE_HOST, SOURCE_JPEG, SOURCE_PNG, SOURCE_JPEG_YCBCR, SOURCE_PNG_DEEP, SOURCE_JPEG_MANAGED, SOURCE_PNG_MANAGED, SOURCE_PNG_DEEP_MANAGED = range(8)   # MI_SOURCE_*: what mi_ravif_encode_sources takes
 SOURCE_ORIENTED = 0x100                                  # MI_SOURCE_ORIENTED: ORed into kinds 1..7, the picture is turned as its file asks and desc names the oriented size
+SOURCE_RESIZED = 0x200                                   # MI_SOURCE_RESIZED: ORed into kinds 1, 2, 3, 5 and 6, desc names the output size and resize_filter the filter
 _SOURCE_HANDLE_FIELD = {SOURCE_HOST: None, SOURCE_JPEG: 'jpeg', SOURCE_PNG: 'png', SOURCE_JPEG_YCBCR: 'jpeg', SOURCE_PNG_DEEP: 'png',      # the field of mi_image_source that carries
                         SOURCE_JPEG_MANAGED: 'jpeg', SOURCE_PNG_MANAGED: 'png', SOURCE_PNG_DEEP_MANAGED: 'png'}                      # the kind's handle (None: host pixels in desc)
 
@@ -848,16 +865,22 @@ class Encoder:
         h, w, _ = a.shape
         return self._call_once(L.mi_ravif_encode_rgba if channels == 4 else L.mi_ravif_encode_rgb, None, a.ctypes.data, w, h, w)
 
-    def encode_resized(self, source, size, filter='lanczos'):
+    def encode_resized(self, source, size, filter='lanczos', oriented=False, ycbcr=False):
         """`source` resampled to size = (width, height) on the device, then encoded: the file of encode_rgb / encode_rgba over the pixels Pillow's
         Image.resize(size, resample=filter, reducing_gap=None) gives.  source: an object with __cuda_array_interface__ (uint8, (H, W, C) or (C, H, W), any
         size; encoded as RGB or RGBA by its channels), a JpegCoeffs (RGB) or a PngScanlines (RGBA when the file has alpha or tRNS, else RGB).
-        filter: 'box', 'bilinear', 'bicubic' or 'lanczos'."""
+        filter: 'box', 'bilinear', 'bicubic' or 'lanczos'.
+        oriented=True (handles): the file is turned as its EXIF orientation asks and then resampled, in one go on the device (resize_jpeg / resize_png with the
+        file's own orientation); ycbcr=True (a JpegCoeffs): the file's own Y, Cb, Cr are resampled channel by channel and coded without the detour over RGB."""
         L = load_library()
         f = _named(RESAMPLE_FILTERS, filter)
         w, h = int(size[0]), int(size[1])
         if w < 1 or h < 1:
             raise AvifError(4)
+        if (oriented or ycbcr) and not isinstance(source, (JpegCoeffs, PngScanlines)):
+            raise TypeError('oriented and ycbcr are for JpegCoeffs and PngScanlines (a device array: BatchEncoder.resize_device with an orientation)')
+        if ycbcr and not isinstance(source, JpegCoeffs):
+            raise TypeError('ycbcr is for a JpegCoeffs')
         if _is_device_array(source):
             d, _, sh, sw, index = _device_pixels(source)
             return self._call_once(L.mi_ravif_encode_device_resized, index, C.byref(d), sw, sh, w, h, f)
@@ -868,7 +891,10 @@ class Encoder:
         else:
             raise TypeError('encode_resized takes a device array, a JpegCoeffs or a PngScanlines (host pixels: resize them where they are)')
         with BatchEncoder(self, 1, w, h, channels) as b:   # the handle forms go through a one-image batch
-            (b.resize_jpeg if isinstance(source, JpegCoeffs) else b.resize_png)(0, source, filter)
+            if isinstance(source, JpegCoeffs):
+                b.resize_jpeg(0, source, filter, orientation=0 if oriented else 1, ycbcr=ycbcr)
+            else:
+                b.resize_png(0, source, filter, orientation=0 if oriented else 1)
             b.encode()
             return b.get(0)
 
@@ -1034,7 +1060,7 @@ def _source_kind(handle, jpeg_ycbcr, png_deep, managed):
     return SOURCE_JPEG_YCBCR if jpeg_ycbcr and handle.color != 'rgb' else SOURCE_JPEG
 
 
-def encode_many(encoder, images, devices=None, jpeg_ycbcr=False, png_deep=False, managed=False, oriented=False):
+def encode_many(encoder, images, devices=None, jpeg_ycbcr=False, png_deep=False, managed=False, oriented=False, fit=None, resize_filter='lanczos'):
     """mi_ravif_encode_sources: the reference's files.into_par_iter() (src/main.rs:223) over the node's GPUs.
     images: list of HxWx3 / HxWx4 uint8 arrays (shapes may differ), JpegCoeffs objects (parse_jpeg; encoded as the RGBA pictures decode_jpeg
     gives, decoded on the device) and PngScanlines objects (parse_png; encoded as the RGBA pictures load_rgba gives, unfiltered and expanded on the
@@ -1046,11 +1072,22 @@ def encode_many(encoder, images, devices=None, jpeg_ycbcr=False, png_deep=False,
     the identity goes the RGB way (the conversion needs RGB), every other one keeps its YCbCr: cavif_mi's rule.  Host arrays are never converted.
     oriented=True: a parsed file is turned on the device as its EXIF orientation asks (SOURCE_ORIENTED) and grouped into runs by its oriented shape; host arrays are
     taken as they are.
+    fit=(w, h) (or one number for both; 0: no bound on that axis): a parsed file larger than the box -- with oriented=True, its oriented picture -- is resampled on the
+    device on its way in (SOURCE_RESIZED) to fit_size of its size, with resize_filter ('box', 'bilinear', 'bicubic' or 'lanczos'); files that fit are untouched, host
+    arrays are taken as they are, and with png_deep=True a file that must be resized goes as the non-deep kind (its high bytes).  managed=True converts after the
+    resize (the resampling is not done in linear light).
     Returns a list of EncodedImage."""
     items = []
+    rf = _named(RESAMPLE_FILTERS, resize_filter)
     for im in images:
         if isinstance(im, (JpegCoeffs, PngScanlines)):
             _live(im, (JpegCoeffs, PngScanlines))
+            size = oriented_size(im.width, im.height, im.orientation if oriented else 1)
+            fitted = fit_size(size[0], size[1], fit) if fit is not None else size
+            if fitted != size:
+                kind = _source_kind(im, jpeg_ycbcr, False, managed) | SOURCE_RESIZED
+                items.append((kind | (SOURCE_ORIENTED if oriented else 0), im, 4, fitted, rf))
+                continue
             items.append((_source_kind(im, jpeg_ycbcr, png_deep, managed) | (SOURCE_ORIENTED if oriented else 0), im, 4))
             continue
         if _is_device_array(im):
@@ -1064,16 +1101,20 @@ def encode_many(encoder, images, devices=None, jpeg_ycbcr=False, png_deep=False,
 
 def _encode_sources(encoder, items, devices):
     """mi_ravif_encode_sources over (kind, object, channels of the slot) triples: SOURCE_HOST a contiguous uint8 array, SOURCE_JPEG / _JPEG_YCBCR a JpegCoeffs,
-    SOURCE_PNG / _PNG_DEEP a PngScanlines; with SOURCE_ORIENTED desc names the oriented size"""
+    SOURCE_PNG / _PNG_DEEP a PngScanlines; with SOURCE_ORIENTED desc names the oriented size; with SOURCE_RESIZED the item is (kind, object, channels, (width, height)
+    of the output, MI_RESAMPLE_* filter)"""
     L = load_library()
 
     def fetch(_user, i, src):
-        (kind, it, channels), s = items[i], src.contents
+        (kind, it, channels), s = items[i][:3], src.contents
         s.kind, s.jpeg, s.png = kind, None, None
         field = _SOURCE_HANDLE_FIELD[kind & 0xFF]
         if field:
             setattr(s, field, it._h)
-            w, h = oriented_size(it.width, it.height, it.orientation if kind & SOURCE_ORIENTED else 1)
+            if kind & SOURCE_RESIZED:
+                (w, h), s.resize_filter = items[i][3], items[i][4]
+            else:
+                w, h = oriented_size(it.width, it.height, it.orientation if kind & SOURCE_ORIENTED else 1)
             s.desc.pixels, s.desc.width, s.desc.height, s.desc.stride_px, s.desc.channels = None, w, h, w, channels
         else:
             s.desc.pixels, s.desc.width, s.desc.height, s.desc.stride_px, s.desc.channels = it.ctypes.data, it.shape[1], it.shape[0], it.shape[1], channels
@@ -1233,21 +1274,24 @@ class BatchEncoder(_Handle):
         _ok(self._L.mi_batch_convert_colour(self._h, first, count, _live(transform, ColourTransform)))
         self._sources.append(transform)
 
-    def resize_device(self, first, pixels, filter='lanczos'):
+    def resize_device(self, first, pixels, filter='lanczos', orientation=1):
         """upload_device for pictures of any size (taken from the array): resampled into the slots on the batch's stream, the pixels of Pillow's
-        Image.resize((w, h), resample=filter, reducing_gap=None); filter: 'box', 'bilinear', 'bicubic' or 'lanczos'"""
+        Image.resize((w, h), resample=filter, reducing_gap=None); filter: 'box', 'bilinear', 'bicubic' or 'lanczos'.
+        orientation 2..8 (mi_batch_resize_device_oriented): the pictures are turned by the map of orient_device and resampled in one go, no turned copy."""
         d, n, h, w, _ = _device_pixels(pixels, batched=True)
-        _ok(self._L.mi_batch_resize_device(self._h, first, n, C.byref(d), w, h, _named(RESAMPLE_FILTERS, filter)))
+        _ok(self._L.mi_batch_resize_device_oriented(self._h, first, n, C.byref(d), w, h, _named(RESAMPLE_FILTERS, filter), int(orientation)))      # orientation 1: the plain call
         self._sources.append(pixels)
 
-    def resize_jpeg(self, index, coeffs, filter='lanczos'):
-        """upload_jpeg for a file of any size: decoded and resampled into slot `index` on the batch's stream"""
-        _ok(self._L.mi_batch_resize_jpeg(self._h, index, _live(coeffs, JpegCoeffs), _named(RESAMPLE_FILTERS, filter)))
+    def resize_jpeg(self, index, coeffs, filter='lanczos', orientation=1, ycbcr=False):
+        """upload_jpeg for a file of any size: decoded and resampled into slot `index` on the batch's stream.  orientation 2..8, or 0 for the file's own
+        (mi_batch_resize_jpeg_oriented): turned and resampled in one go; ycbcr=True: the file's own (Y, Cb, Cr) are resampled, the slot's kind is INPUT_YCBCR
+        (an RGB file raises Unsupported)."""
+        _ok(self._L.mi_batch_resize_jpeg_oriented(self._h, index, _live(coeffs, JpegCoeffs), _named(RESAMPLE_FILTERS, filter), int(orientation), int(bool(ycbcr))))
 
-    def resize_png(self, index, scanlines, filter='lanczos'):
+    def resize_png(self, index, scanlines, filter='lanczos', orientation=1):
         """upload_png for one file of any size: unfiltered, expanded and resampled into slot `index` on the batch's stream.  A file with alpha or tRNS into
-        a 3-channel batch raises InvalidArgument."""
-        _ok(self._L.mi_batch_resize_png(self._h, index, _live(scanlines, PngScanlines), _named(RESAMPLE_FILTERS, filter)))
+        a 3-channel batch raises InvalidArgument.  orientation 2..8, or 0 for the file's own (mi_batch_resize_png_oriented): turned and resampled in one go."""
+        _ok(self._L.mi_batch_resize_png_oriented(self._h, index, _live(scanlines, PngScanlines), _named(RESAMPLE_FILTERS, filter), int(orientation)))
 
     def device_input(self, index):
         """device address (int) of the HBM input slot of image `index`: h * w * channels bytes, rows packed"""

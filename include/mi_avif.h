@@ -129,11 +129,19 @@ int  mi_ravif_encode_stream(const mi_ravif_encoder *e, size_t n, mi_fetch_fn fet
  * its kind below; for the managed kinds the conversion follows as before: a permutation of pixels and a map of each pixel commute).  desc.width / height then name the
  * ORIENTED picture -- mi_oriented_size of the file's size and mi_jpeg_coeffs_orientation / mi_png_scanlines_orientation -- and runs are grouped by that shape; a source
  * whose oriented size differs from them is MI_INVALID_ARGUMENT, for that image alone.  So is a kind of 8..255, any other bit, and the flag on kind 0.
+ * MI_SOURCE_RESIZED (0x200), ORed into kinds 1, 2, 3, 5 and 6: desc.width / height name the OUTPUT picture, which is the slot; the file may have any size
+ * (extents 1..65536) and is resampled on its way in with the filter in mi_image_source.resize_filter (the mi_batch_resize_*_oriented call of its route below; the pixels
+ * are specified exactly).  With MI_SOURCE_ORIENTED the file is turned as it asks and then resampled.  The managed kinds convert after the resize, in the slot, as they
+ * convert after an upload: the resampling is done on the file's own sample values, not in linear light.  Runs are grouped by desc as before, so by the output shape.
+ * MI_INVALID_ARGUMENT, for that image alone: the flag on kind 0 or on kinds 4 and 7 (resizing deep sources is not built), a filter that is none of MI_RESAMPLE_*
+ * (the library sets the field to -1 before it calls fetch, so a caller that sets the flag has to set the filter), a file extent outside 1..65536, a PNG with alpha
+ * or tRNS into channels 3.
  * mi_ravif_encode_stream is this call with MI_SOURCE_HOST throughout.  Pictures in device memory are not a kind here (a pointer belongs to one
  * device, the shared cursor hands images to any): they enter through mi_ravif_encode_device and mi_batch_upload_device. */
 enum { MI_SOURCE_HOST = 0, MI_SOURCE_JPEG = 1, MI_SOURCE_PNG = 2, MI_SOURCE_JPEG_YCBCR = 3, MI_SOURCE_PNG_DEEP = 4,
        MI_SOURCE_JPEG_MANAGED = 5, MI_SOURCE_PNG_MANAGED = 6, MI_SOURCE_PNG_DEEP_MANAGED = 7,
-       MI_SOURCE_ORIENTED = 0x100 /* a modifier, ORed into kinds 1 to 7 */ };
+       MI_SOURCE_ORIENTED = 0x100 /* a modifier, ORed into kinds 1 to 7 */,
+       MI_SOURCE_RESIZED = 0x200 /* a second modifier, ORed into kinds 1, 2, 3, 5 and 6: desc names the output size, resize_filter the filter */ };
 typedef struct mi_jpeg_coeffs mi_jpeg_coeffs;   /* opaque: one parsed file, host memory only */
 typedef struct mi_png_scanlines mi_png_scanlines;      /* opaque: one inflated file, host memory only */
 typedef struct mi_image_source {
@@ -144,6 +152,8 @@ typedef struct mi_image_source {
   mi_image_desc desc;
   const mi_jpeg_coeffs *jpeg;
   const mi_png_scanlines *png; /* kinds 2, 4, 6 and 7 only (the struct grew by this field at its tail: never read for kinds 0 and 1) */
+  int resize_filter;           /* one of MI_RESAMPLE_* (below); read only when kind carries MI_SOURCE_RESIZED (the struct grew by this field at its tail: a fetch callback
+                                  that never sets the flag need not know it) */
 } mi_image_source;
 typedef int (*mi_fetch_source_fn)(void *user, size_t index, mi_image_source *src);
 int  mi_ravif_encode_sources(const mi_ravif_encoder *e, size_t n, mi_fetch_source_fn fetch, mi_release_fn release, void *user, mi_encoded_image *out,
@@ -432,8 +442,8 @@ int  mi_batch_convert_colour(mi_batch *b, int first, int count, mi_colour_transf
  * gives that call's bytes and touches no scratch.  The slot bytes of every other orientation are the plain call's bytes permuted by the map above.
  * MI_INVALID_ARGUMENT: an orientation outside the call's range, a source whose oriented size is not the batch's, a range past the capacity, null pointers, 4 channels
  * into a 3-channel batch, a refusal of the kind, a call between mi_batch_encode_async and mi_batch_wait; a refused call allocates nothing (mi_batch_footprint).
- * MI_ENCODING_ERROR when staging or scratch cannot be allocated.  Orientation together with resize, the YCbCr planes of mi_batch_upload_device_ycbcr and
- * mi_batch_upload_device16 are not built; an Exif blob passed through mi_ravif_encoder's exif field is written as it is and should not still carry an orientation other than 1. */
+ * MI_ENCODING_ERROR when staging or scratch cannot be allocated.  Orientation together with resize: the mi_batch_resize_*_oriented calls below.  The YCbCr planes of
+ * mi_batch_upload_device_ycbcr and mi_batch_upload_device16 are not built; an Exif blob passed through mi_ravif_encoder's exif field is written as it is and should not still carry an orientation other than 1. */
 int  mi_exif_orientation(const uint8_t *exif, size_t len, int *orientation);
 int  mi_jpeg_coeffs_orientation(const mi_jpeg_coeffs *c, int *orientation);
 int  mi_png_scanlines_orientation(const mi_png_scanlines *p, int *orientation);
@@ -456,6 +466,29 @@ enum { MI_RESAMPLE_BOX = 0, MI_RESAMPLE_BILINEAR = 1, MI_RESAMPLE_BICUBIC = 2, M
 int  mi_batch_resize_device(mi_batch *b, int first, int count, const mi_device_pixels *src, uint32_t src_w, uint32_t src_h, int filter);
 int  mi_batch_resize_jpeg(mi_batch *b, int index, const mi_jpeg_coeffs *c, int filter);
 int  mi_batch_resize_png(mi_batch *b, int index, const mi_png_scanlines *p, int filter);
+/* resize on input of a turned source (opt-in): the source is turned by the map of the orientation calls above and resampled into the slot in one go.
+ * With O the source turned by `orientation`, the slot receives exactly the bytes the two existing calls give one after the other -- mi_batch_orient_device (or the
+ * _oriented upload) into a slot of O's size, then mi_batch_resize_* from there: the horizontal pass along O's x axis first, into the clipped 8-bit intermediate, then
+ * the vertical one.  No turned copy is made: orientations 2..4 are addressing in the horizontal pass, 5..8 filter down the source's columns and transpose a tile in
+ * LDS, and the scratch a call needs is that of the plain resize call (device sources: the intermediate; handles: the decoded source and the intermediate).
+ * mi_batch_resize_device_oriented: mi_batch_resize_device with an orientation of 1..8; src_w x src_h is the size of the source as it lies in memory.
+ * mi_batch_resize_jpeg_oriented / _png_oriented: one parsed file into slot `index`, orientation 1..8, or 0: the file's own.  ycbcr != 0: the file's own (Y, Cb, Cr)
+ * triples, as mi_batch_upload_jpeg_ycbcr stores them, are resampled channel by channel (what Pillow gives for a YCbCr mode image) and the slot is tagged
+ * MI_INPUT_YCBCR; that call's refusals apply (MI_UNSUPPORTED for a file whose colour is RGB).  A PNG of bit depth 16 is taken through its high bytes, as
+ * mi_batch_resize_png takes it: resizing deep sources is not built.
+ * Orientation 1, given or read from the file, is the plain mi_batch_resize_* call (with ycbcr: the same two passes over the triples); an oriented source that already
+ * has the slot's size is the _oriented upload of its kind (orientation 1 as well: the plain upload).  Neither takes the premultiply round trip.
+ * MI_INVALID_ARGUMENT: the refusals of the resize calls and of the orient calls -- an unknown filter, an orientation outside the call's range, a zero extent or one
+ * above 65536, strides below the packed row, a range past the capacity or of slots of different sizes, 4 channels into a 3-channel batch, a PNG with alpha or tRNS
+ * into a 3-channel batch, null pointers, a call between mi_batch_encode_async and mi_batch_wait, with ycbcr an encoder that does not take YCbCr input.
+ * MI_ENCODING_ERROR when staging or scratch cannot be allocated.  Every check comes first: a refused call allocates nothing (mi_batch_footprint).
+ * mi_fit_size: the size of a picture of sw x sh scaled down, never up, to fit a box, aspect ratio kept, in exact 64-bit integers.  A box extent of 0 is no bound on
+ * that axis.  A picture that fits keeps (sw, sh).  Otherwise, if box_h == 0 or (box_w != 0 and box_w * sh <= box_h * sw): w = box_w, h = max(1, (2 sh box_w + sw) /
+ * (2 sw)); else h = box_h, w = max(1, (2 sw box_h + sh) / (2 sh)): the free axis is rounded half up and never exceeds the box.  Either pointer may be NULL. */
+int  mi_batch_resize_device_oriented(mi_batch *b, int first, int count, const mi_device_pixels *src, uint32_t src_w, uint32_t src_h, int filter, int orientation);   /* orientation 1..8 */
+int  mi_batch_resize_jpeg_oriented(mi_batch *b, int index, const mi_jpeg_coeffs *c, int filter, int orientation, int ycbcr);   /* 0 = the file's own */
+int  mi_batch_resize_png_oriented(mi_batch *b, int index, const mi_png_scanlines *p, int filter, int orientation);             /* 0 = the file's own */
+void mi_fit_size(uint32_t sw, uint32_t sh, uint32_t box_w, uint32_t box_h, uint32_t *w, uint32_t *h);
 int  mi_batch_set_count(mi_batch *b, int n_images);                                       /* images of the next run (<= the count the batch was created for), each of the batch's w x h */
 /* ---- mixed-size layouts: the pictures of a run differ in size.  A batch is made as before, mi_batch_create(e, cap, W, H, channels); everything it
  * reserves for cap pictures of W x H -- the slot arrays, the arena, tile jobs, payload and pre-carry capacity, symbol records, the search queue's items and snapshots,
