@@ -1,6 +1,6 @@
 // cavif_mi -- the cavif command line (src/main.rs) on top of libmi_avif.so: same flags, path rules and report line;
 // the rayon fan-out over files (src/main.rs:223) becomes mi_ravif_encode_batch (one host thread per MI355X).
-//   cavif_mi [-Q n] [-s n] [-j n] [-f] [-o path] [-q] [--dirty-alpha] [--color ycbcr|rgb] [--depth 8|10|auto] [--jpeg-ycbcr] [--deep-png] [--color-managed] [--exif-orientation] [--mixed-sizes] [--fit WxH] [--resize-filter f] IMAGES...
+//   cavif_mi [-Q n] [-s n] [-j n] [-f] [-o path] [-q] [--dirty-alpha] [--color ycbcr|rgb] [--depth 8|10|auto] [--jpeg-ycbcr] [--deep-png] [--color-managed] [--exif-orientation] [--mixed-sizes] [--fit WxH] [--resize-filter f] [--deep-resize] IMAGES...
 // Input: PNG and baseline / progressive 8-bit JPEG, told apart by their first bytes as load_image does.  A loader thread does the serial half of the
 // decode -- inflate of a PNG (mi_png_parse), Huffman decoding of a JPEG (mi_jpeg_parse) -- and hands scanlines or coefficients to the encoder, which
 // finishes the picture on the GPU inside the batch that encodes it (mi_ravif_encode_sources): the loaders never touch a device.  Differences, deliberate:
@@ -16,6 +16,8 @@
 // size -- with --exif-orientation, of its oriented size -- on the GPU on its way in (MI_SOURCE_RESIZED), with `--resize-filter box|bilinear|bicubic|lanczos` (default
 // lanczos): the pixels of Pillow's Image.resize.  A file that fits goes exactly as without the flag.  It combines with --exif-orientation, --jpeg-ycbcr, --color-managed
 // (the conversion follows the resize) and --mixed-sizes; with --deep-png a 16-bit file that must be resized is coded from its high bytes (one warning line per run).
+// `--deep-resize` (off by default) means something only together with --deep-png and --fit: a 16-bit file that --fit resizes stays on the deep route and is resampled
+// at 16 bits on the GPU (MI_SOURCE_RESIZED_DEEP), and no warning line is printed; without --deep-png or --fit it is accepted and changes nothing.
 #include <sched.h>
 #include <sys/stat.h>
 #include <cerrno>
@@ -97,7 +99,8 @@ int host_threads() {
 int usage(const char *msg) {
   fprintf(stderr, "error: %s\nusage: cavif_mi [-Q quality 1-100] [-s speed 1-10] [-j threads] [-f|--overwrite] [-o path] [-q] [--dirty-alpha]\n"
                   "                [--color ycbcr|rgb] [--depth 8|10|auto] [--devices 0,1,..] [--rdo-passes 1|2] [--jpeg-ycbcr] [--deep-png] [--color-managed]\n"
-                  "                [--exif-orientation] [--mixed-sizes] [--fit WxH] [--resize-filter box|bilinear|bicubic|lanczos] IMAGES...   (\"-\" = stdin/stdout)\n"
+                  "                [--exif-orientation] [--mixed-sizes] [--fit WxH] [--resize-filter box|bilinear|bicubic|lanczos] [--deep-resize]\n"
+                  "                IMAGES...   (\"-\" = stdin/stdout)\n"
                   "  --color-managed  convert every file to sRGB by its own colour description (an ICC profile, or PNG gAMA / cHRM) on the GPU; a file whose profile\n"
                   "                   is unsupported or malformed is encoded unmanaged (one warning line unless -q).  With --jpeg-ycbcr a JPEG whose description\n"
                   "                   asks for a conversion goes the RGB way: the conversion needs RGB.  Combines with --deep-png.\n"
@@ -107,7 +110,9 @@ int usage(const char *msg) {
                   "  --fit WxH        scale every picture that is larger than the box down to fit it, aspect ratio kept, on the GPU (N = NxN; an extent of 0 = no bound on that\n"
                   "                   axis); a file that fits is encoded as without the flag.  --resize-filter picks the filter (default lanczos).  Combines with\n"
                   "                   --exif-orientation (the box holds the turned picture), --jpeg-ycbcr, --color-managed and --mixed-sizes; with --deep-png a 16-bit file\n"
-                  "                   that must be resized is coded from its high bytes.\n", msg);
+                  "                   that must be resized is coded from its high bytes, unless --deep-resize is given.\n"
+                  "  --deep-resize    with --deep-png and --fit: a 16-bit file that must be resized is resampled at 16 bits on the GPU and coded from all 16 bits;\n"
+                  "                   without them it changes nothing.\n", msg);
   return 1;
 }
 
@@ -121,14 +126,14 @@ int usage(const char *msg) {
 #include <sys/wait.h>
 static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 // one input file: where it goes, what its loader made of it (a JPEG leaves it as coefficients, a PNG as filtered scanlines) and how it is to be sent
-struct Job { std::string in_name, out_path; bool out_stdio = false; mi_jpeg_coeffs *jpeg = nullptr; mi_png_scanlines *png = nullptr; uint32_t w = 0, h = 0; bool ycbcr = false, deep = false, managed = false, oriented = false, resized = false; int resize_filter = 0; std::string error; };
+struct Job { std::string in_name, out_path; bool out_stdio = false; mi_jpeg_coeffs *jpeg = nullptr; mi_png_scanlines *png = nullptr; uint32_t w = 0, h = 0; bool ycbcr = false, deep = false, managed = false, oriented = false, resized = false, resized_deep = false; int resize_filter = 0; std::string error; };
 // the source kind (MI_SOURCE_*) of a loaded job: its file type, then managed (which has switched ycbcr off), ycbcr / deep; --exif-orientation and --fit add their modifiers
 static int source_kind_plain(const Job &j) {
   if (j.jpeg) return j.managed ? MI_SOURCE_JPEG_MANAGED : j.ycbcr ? MI_SOURCE_JPEG_YCBCR : MI_SOURCE_JPEG;
   if (j.png) return j.managed ? (j.deep ? MI_SOURCE_PNG_DEEP_MANAGED : MI_SOURCE_PNG_MANAGED) : j.deep ? MI_SOURCE_PNG_DEEP : MI_SOURCE_PNG;
   return MI_SOURCE_HOST;
 }
-static int source_kind(const Job &j) { return source_kind_plain(j) | (j.oriented ? MI_SOURCE_ORIENTED : 0) | (j.resized ? MI_SOURCE_RESIZED : 0); }
+static int source_kind(const Job &j) { return source_kind_plain(j) | (j.oriented ? MI_SOURCE_ORIENTED : 0) | (j.resized ? (j.resized_deep ? MI_SOURCE_RESIZED_DEEP : MI_SOURCE_RESIZED) : 0); }
 // --color-managed: what the parsed file says about its colour, probed (parsed, no tables) to learn whether it can be converted; the encoder bakes one transform per
 // distinct description.  True: a usable transform that is not the identity.  An unsupported or malformed profile: one warning line (unless quiet), false.
 static bool probe_managed(const Job &j, bool quiet) {
@@ -174,7 +179,7 @@ int main(int argc, char **argv) {
     }
   }
   float quality = 80.f; int speed = 4, threads = 0, depth = 0, color_model = 0, rdo_passes = 1;
-  bool overwrite = false, quiet = false, dirty_alpha = false, have_output = false, output_stdio = false, jpeg_ycbcr = false, deep_png = false, color_managed = false, exif_orientation = false, mixed_sizes = false, have_fit = false;
+  bool overwrite = false, quiet = false, dirty_alpha = false, have_output = false, output_stdio = false, jpeg_ycbcr = false, deep_png = false, color_managed = false, exif_orientation = false, mixed_sizes = false, have_fit = false, deep_resize = false;
   uint32_t fit_w = 0, fit_h = 0; int resize_filter = MI_RESAMPLE_LANCZOS3;
   std::atomic<bool> deep_resized{ false };
   std::string output; std::vector<std::string> images; std::vector<int> devices;
@@ -212,6 +217,7 @@ int main(int argc, char **argv) {
     else if (a == "-q" || a == "--quiet") quiet = true;
     else if (a == "--dirty-alpha") dirty_alpha = true;
     else if (a == "--jpeg-ycbcr") jpeg_ycbcr = true;                                                                                                   // extension: not a cavif flag
+    else if (a == "--deep-resize") deep_resize = true;                                                                                                 // extension: not a cavif flag
     else if (a == "--deep-png") deep_png = true;                                                                                                       // extension: not a cavif flag
     else if (a == "--color-managed") color_managed = true;                                                                                             // extension: not a cavif flag
     else if (a == "--mixed-sizes") mixed_sizes = true;                                                                                                 // extension: not a cavif flag
@@ -294,7 +300,8 @@ int main(int argc, char **argv) {
         mi_fit_size(j.w, j.h, fit_w, fit_h, &fw, &fh);
         if (fw != j.w || fh != j.h) {
           j.resized = true; j.resize_filter = resize_filter; j.w = fw; j.h = fh;
-          if (j.deep) { j.deep = false; deep_resized = true; }        // resizing deep sources is not built: the file's high bytes
+          if (j.deep && deep_resize) j.resized_deep = true;           // stays on the deep route: resampled at 16 bits (MI_SOURCE_RESIZED_DEEP)
+          else if (j.deep) { j.deep = false; deep_resized = true; }   // without --deep-resize: the file's high bytes
         }
       }
       if (st) j.error = st == MI_UNSUPPORTED ? "unsupported image format (this build reads PNG and baseline/progressive 8-bit JPEG)" :

@@ -387,17 +387,21 @@ int mi_batch_upload_device_ycbcr(mi_batch *b, int first, int count, const mi_dev
 uint16_t *mi_batch_device_input16(mi_batch *b, int index) { return batch_slot<uint16_t>(b, index); }
 int mi_batch_read_input16(mi_batch *b, int index, uint16_t *dst) { return batch_read_slot(b, index, dst); }
 
+// (what mi_batch_upload_device16 and mi_batch_resize_device16 ask of a uint16 source of w x h and make of it; false = refused)
+static bool batch_device_source16(const mi_batch *b, const mi_device_pixels16 *src, uint32_t w, uint32_t h, Ingest16Src &s) {
+  if (!src || !src->dev) return false;
+  if ((src->layout != 0 && src->layout != 1) || !batch_takes_deep(b, src->channels)) return false;   // alpha is never dropped; the alpha rules of the kind
+  if (src->bits < 8 || src->bits > 16 || (src->msb_aligned != 0 && src->msb_aligned != 1)) return false;
+  if (((uintptr_t)src->dev | src->row_stride | src->pixel_or_plane_stride | src->image_stride) & 1) return false;   // uint16 samples
+  s.w = w; s.h = h; s.bits = src->bits; s.msb_aligned = src->msb_aligned;
+  return strided_resolve(*src, w, h, 2, false, s);
+}
 // images [first, first + count) from uint16 pictures in the memory of the batch's device: one ingest16_kernel launch on the batch's stream, after whatever
 // src->after_stream holds at this moment; the slots are tagged MI_INPUT_RGB16.  Every check comes before the deep slots are made: a refused call allocates nothing.
 int mi_batch_upload_device16(mi_batch *b, int first, int count, const mi_device_pixels16 *src) {
   uint32_t w, h;
-  if (!batch_range_sized(b, first, count, w, h) || !src || !src->dev) return MI_INVALID_ARGUMENT;
-  if ((src->layout != 0 && src->layout != 1) || !batch_takes_deep(b, src->channels)) return MI_INVALID_ARGUMENT;   // alpha is never dropped; the alpha rules of the kind
-  if (src->bits < 8 || src->bits > 16 || (src->msb_aligned != 0 && src->msb_aligned != 1)) return MI_INVALID_ARGUMENT;
-  if (((uintptr_t)src->dev | src->row_stride | src->pixel_or_plane_stride | src->image_stride) & 1) return MI_INVALID_ARGUMENT;   // uint16 samples
   Ingest16Src s;
-  s.w = w; s.h = h; s.bits = src->bits; s.msb_aligned = src->msb_aligned;
-  if (!strided_resolve(*src, w, h, 2, false, s)) return MI_INVALID_ARGUMENT;
+  if (!batch_range_sized(b, first, count, w, h) || !batch_device_source16(b, src, w, h, s)) return MI_INVALID_ARGUMENT;
   uint16_t *const slots = mi_batch_device_input16(b, first);
   if (!slots) return MI_ENCODING_ERROR;
   (void)hipSetDevice(b->device);
@@ -732,11 +736,13 @@ static size_t resample_ksize(uint32_t in, uint32_t out, int filter) {
   return (size_t)ceil(supports[filter] * (scale < 1.0 ? 1.0 : scale)) * 2 + 1;
 }
 static size_t resample_axis_bytes(uint32_t in, uint32_t out, int filter) { return align_up((size_t)out * 8, 16) + align_up(resample_ksize(in, out, filter) * out * 4, 16); }
-// bounds[2 i] = first sample, bounds[2 i + 1] = taps of output sample i; tap j of output i at taps[j * out + i], 22 fractional bits (unused ones 0).
+// bounds[2 i] = first sample, bounds[2 i + 1] = taps of output sample i; tap j of output i at taps[j * out + i], `bits` fractional bits (MI_RS_BITS for the
+// 8-bit kernels, MI_RS16_BITS for the deep ones; unused taps 0).  Bounds and the normalised double coefficients do not depend on `bits`.
 // An axis that keeps its length: the identity (its pass is skipped: the kernel moves the samples unchanged).
-static void resample_axis(uint32_t in, uint32_t out, int filter, uint32_t *bounds, int32_t *taps) {
+static void resample_axis(uint32_t in, uint32_t out, int filter, int bits, uint32_t *bounds, int32_t *taps) {
   const size_t ksize = resample_ksize(in, out, filter);
-  if (in == out) { for (uint32_t i = 0; i < out; i++) { bounds[2 * i] = i; bounds[2 * i + 1] = 1; taps[i] = 1 << MI_RS_BITS; } return; }
+  const int one = 1 << bits;
+  if (in == out) { for (uint32_t i = 0; i < out; i++) { bounds[2 * i] = i; bounds[2 * i + 1] = 1; taps[i] = one; } return; }
   static const double supports[4] = { 0.5, 1.0, 2.0, 3.0 };
   const double scale = (double)in / out, fs = scale < 1.0 ? 1.0 : scale, support = supports[filter] * fs;
   std::vector<double> k(ksize);
@@ -751,7 +757,7 @@ static void resample_axis(uint32_t in, uint32_t out, int filter, uint32_t *bound
     for (int j = 0; j < n; j++) { k[j] = resample_filter(filter, (j + xmin - centre + 0.5) / fs); sum += k[j]; }
     for (int j = 0; j < n; j++) {
       const double v = sum != 0.0 ? k[j] / sum : k[j];
-      taps[(size_t)j * out + i] = v < 0 ? (int)(-0.5 + v * (1 << MI_RS_BITS)) : (int)(0.5 + v * (1 << MI_RS_BITS));
+      taps[(size_t)j * out + i] = v < 0 ? (int)(-0.5 + v * one) : (int)(0.5 + v * one);
     }
     bounds[2 * i] = (uint32_t)xmin; bounds[2 * i + 1] = (uint32_t)n;
   }
@@ -769,11 +775,11 @@ static int batch_reserve_scratch(mi_batch *b, size_t bytes) {
 // size, the slots' size and the filter of the one before it finds them on the device); the intermediate lies `inter_at` bytes into the scratch, which the caller
 // has reserved up to inter_at + resample_inter_bytes() of the ORIENTED height.  Stream order serialises the users of the scratch.  No sync.
 static size_t resample_inter_bytes(int count, uint32_t src_h, uint32_t dst_w) { return (size_t)count * src_h * align_up(dst_w, 4) * 4; }
-static int batch_resample(mi_batch *b, int first, int count, const IngestSrc &s, int filter, size_t inter_at, int o = 1, int kind = MI_INPUT_RGB) {
-  const uint32_t dw = slot_w(b, first), dh = slot_h(b, first);    // the slots' size (one for the range: the callers have checked)
-  uint32_t ow, oh;
-  oriented_size(s.w, s.h, o, &ow, &oh);                           // 5..8: the source's height feeds the horizontal axis, its width the vertical one
-  const uint32_t key[5] = { ow, oh, dw, dh, (uint32_t)filter + 1 };
+// (the tables of both axes with `bits` fractional bits, on the device when the stream gets there: horizontal bounds, taps, vertical bounds, taps.  The key holds
+// the bit count, so an 8-bit call and a deep call of one shape never share a table)
+struct ResampleTables { const uint32_t *hbounds, *vbounds; const int32_t *htaps, *vtaps; };
+static int batch_resample_tables(mi_batch *b, uint32_t ow, uint32_t oh, uint32_t dw, uint32_t dh, int filter, int bits, ResampleTables &t) {
+  const uint32_t key[6] = { ow, oh, dw, dh, (uint32_t)filter + 1, (uint32_t)bits };
   const size_t h_bytes = resample_axis_bytes(ow, dw, filter), need = align_up(h_bytes + resample_axis_bytes(oh, dh, filter), 256);
   size_t at = b->rs_key_at;
   if (memcmp(key, b->rs_key, sizeof(key)) != 0) {
@@ -784,27 +790,61 @@ static int batch_resample(mi_batch *b, int first, int count, const IngestSrc &s,
     }
     at = b->rs_used; b->rs_used += need;
     uint8_t *const hb = b->h_rs.get() + at;
-    resample_axis(ow, dw, filter, (uint32_t *)hb, (int32_t *)(hb + align_up((size_t)dw * 8, 16)));
-    resample_axis(oh, dh, filter, (uint32_t *)(hb + h_bytes), (int32_t *)(hb + h_bytes + align_up((size_t)dh * 8, 16)));
+    resample_axis(ow, dw, filter, bits, (uint32_t *)hb, (int32_t *)(hb + align_up((size_t)dw * 8, 16)));
+    resample_axis(oh, dh, filter, bits, (uint32_t *)(hb + h_bytes), (int32_t *)(hb + h_bytes + align_up((size_t)dh * 8, 16)));
     HIP_OK(hipMemcpyAsync(b->d_rs.get() + at, hb, need, hipMemcpyHostToDevice, b->stream));
     memcpy(b->rs_key, key, sizeof(key)); b->rs_key_at = at;
   }
   const uint8_t *const db = b->d_rs.get() + at;
-  const uint32_t *const hbounds = (const uint32_t *)db, *const vbounds = (const uint32_t *)(db + h_bytes);
-  const int32_t *const htaps = (const int32_t *)(db + align_up((size_t)dw * 8, 16)), *const vtaps = (const int32_t *)(db + h_bytes + align_up((size_t)dh * 8, 16));
+  t.hbounds = (const uint32_t *)db; t.vbounds = (const uint32_t *)(db + h_bytes);
+  t.htaps = (const int32_t *)(db + align_up((size_t)dw * 8, 16)); t.vtaps = (const int32_t *)(db + h_bytes + align_up((size_t)dh * 8, 16));
+  return MI_OK;
+}
+static int batch_resample(mi_batch *b, int first, int count, const IngestSrc &s, int filter, size_t inter_at, int o = 1, int kind = MI_INPUT_RGB) {
+  const uint32_t dw = slot_w(b, first), dh = slot_h(b, first);    // the slots' size (one for the range: the callers have checked)
+  uint32_t ow, oh;
+  oriented_size(s.w, s.h, o, &ow, &oh);                           // 5..8: the source's height feeds the horizontal axis, its width the vertical one
+  ResampleTables t;
+  if (int st = batch_resample_tables(b, ow, oh, dw, dh, filter, MI_RS_BITS, t)) return st;
   const uint32_t pitch = (uint32_t)align_up(dw, 4);
   uint32_t *const inter = (uint32_t *)(b->d_rs_scratch.get() + inter_at);
   if (orientation_turns(o))
     hipLaunchKernelGGL(resample_t_kernel, dim3((dw + MI_RS_TT - 1) / MI_RS_TT, (s.w + MI_RS_TT - 1) / MI_RS_TT, (unsigned)count), dim3(256), 0, b->stream,
-                       s, o, hbounds, htaps, dw, pitch, inter);
+                       s, o, t.hbounds, t.htaps, dw, pitch, inter);
   else
     hipLaunchKernelGGL(resample_h_kernel, dim3((dw + MI_RS_TW - 1) / MI_RS_TW, (s.h + MI_RS_TH - 1) / MI_RS_TH, (unsigned)count), dim3(64 * MI_RS_TH), 0, b->stream,
-                       s, o, hbounds, htaps, dw, pitch, inter);
+                       s, o, t.hbounds, t.htaps, dw, pitch, inter);
   uint8_t *const slots = mi_batch_device_input(b, first);
   const int alpha = s.channels == 4 ? 1 : 0;
-  LAUNCH_BY_CHANNELS(b, b->channels, dw, dh, count, resample_v_kernel, (const uint32_t *)inter, oh, pitch, vbounds, vtaps, dw, dh, alpha, slots);
+  LAUNCH_BY_CHANNELS(b, b->channels, dw, dh, count, resample_v_kernel, (const uint32_t *)inter, oh, pitch, t.vbounds, t.vtaps, dw, dh, alpha, slots);
   HIP_OK(hipGetLastError());
   batch_tag(b, first, count, kind);
+  return MI_OK;
+}
+// The deep form (kernels: dev_resample16.h): uint16 pictures described by s -> deep slots [first, first + count), tagged MI_INPUT_RGB16.  The same
+// tables with MI_RS16_BITS fractional bits, the same grids; the intermediate holds 8 bytes a pixel (resample_inter16_bytes() of the ORIENTED height, reserved
+// by the caller `inter_at` bytes into the scratch, a multiple of 32).  The deep slots exist (the callers have made them).  No sync.
+static size_t resample_inter16_bytes(int count, uint32_t src_h, uint32_t dst_w) { return (size_t)count * src_h * align_up(dst_w, 4) * 8; }
+static int batch_resample16(mi_batch *b, int first, int count, const Ingest16Src &s, int filter, size_t inter_at, int o = 1) {
+  const uint32_t dw = slot_w(b, first), dh = slot_h(b, first);
+  uint32_t ow, oh;
+  oriented_size(s.w, s.h, o, &ow, &oh);
+  uint16_t *const slots = mi_batch_device_input16(b, first);
+  if (!slots) return MI_ENCODING_ERROR;
+  ResampleTables t;
+  if (int st = batch_resample_tables(b, ow, oh, dw, dh, filter, MI_RS16_BITS, t)) return st;
+  const uint32_t pitch = (uint32_t)align_up(dw, 4);
+  uint2 *const inter = (uint2 *)(b->d_rs_scratch.get() + inter_at);
+  if (orientation_turns(o))
+    hipLaunchKernelGGL(resample_t16_kernel, dim3((dw + MI_RS_TT - 1) / MI_RS_TT, (s.w + MI_RS_TT - 1) / MI_RS_TT, (unsigned)count), dim3(256), 0, b->stream,
+                       s, o, t.hbounds, t.htaps, dw, pitch, inter);
+  else
+    hipLaunchKernelGGL(resample_h16_kernel, dim3((dw + MI_RS_TW - 1) / MI_RS_TW, (s.h + MI_RS_TH - 1) / MI_RS_TH, (unsigned)count), dim3(64 * MI_RS_TH), 0, b->stream,
+                       s, o, t.hbounds, t.htaps, dw, pitch, inter);
+  const int alpha = s.channels == 4 ? 1 : 0;
+  LAUNCH_BY_CHANNELS(b, b->channels, dw, dh, count, resample_v16_kernel, (const uint2 *)inter, oh, pitch, t.vbounds, t.vtaps, dw, dh, alpha, slots);
+  HIP_OK(hipGetLastError());
+  batch_tag(b, first, count, MI_INPUT_RGB16);
   return MI_OK;
 }
 static bool resample_filter_known(int filter) { return filter >= MI_RESAMPLE_BOX && filter <= MI_RESAMPLE_LANCZOS3; }
@@ -819,6 +859,18 @@ int mi_batch_resize_device(mi_batch *b, int first, int count, const mi_device_pi
   if (int st = batch_reserve_scratch(b, resample_inter_bytes(count, src_h, w))) return st;
   if (int st = batch_join(b, src->after_stream)) return st;
   return batch_resample(b, first, count, s, filter, 0);
+}
+// the same for uint16 pictures, resampled at 16 bits into the deep slots: the refusals of mi_batch_upload_device16 and of mi_batch_resize_device,
+// all before the deep slots are made (a refused call allocates nothing); of the batch's own size: mi_batch_upload_device16.  No orientation.
+int mi_batch_resize_device16(mi_batch *b, int first, int count, const mi_device_pixels16 *src, uint32_t src_w, uint32_t src_h, int filter) {
+  Ingest16Src s; uint32_t w, h;
+  if (!batch_range_sized(b, first, count, w, h) || !resample_filter_known(filter) || !resample_extent_ok(src_w, src_h) || !batch_device_source16(b, src, src_w, src_h, s)) return MI_INVALID_ARGUMENT;
+  if (src_w == w && src_h == h) return mi_batch_upload_device16(b, first, count, src);
+  if (!batch_deep(b)) return MI_ENCODING_ERROR;
+  (void)hipSetDevice(b->device);
+  if (int st = batch_reserve_scratch(b, resample_inter16_bytes(count, src_h, w))) return st;
+  if (int st = batch_join(b, src->after_stream)) return st;
+  return batch_resample16(b, first, count, s, filter, 0);
 }
 
 // a decoded source at the start of the scratch, packed, `channels` channels: what the two forms below resample
@@ -1105,7 +1157,8 @@ int mi_batch_upload_png_oriented(mi_batch *b, int index, const mi_png_scanlines 
 // ---- resize on input of a turned source: orientation and resampling in one go, from where the source lies -- no turned copy, the scratch of the plain
 // resize call.  Orientation 1 (given or the file's) is the plain mi_batch_resize_* call (ycbcr: the same two passes over the file's own triples); an oriented source
 // that already has the slot's size is the _oriented upload of its kind: neither takes the premultiply round trip.  Every check comes first: a refused call
-// allocates nothing.  8-bit only: a 16-bit PNG is taken through its high bytes, as mi_batch_resize_png takes it (resizing deep sources is out of scope). ----
+// allocates nothing.  These four fill 8-bit slots: a 16-bit PNG is taken through its high bytes, as mi_batch_resize_png takes it; mi_batch_resize_png_deep and
+// mi_batch_resize_device16 resample 16-bit sources into the deep slots. ----
 int mi_batch_resize_device_oriented(mi_batch *b, int first, int count, const mi_device_pixels *src, uint32_t src_w, uint32_t src_h, int filter, int orientation) {
   IngestSrc s; uint32_t w, h, ow, oh;
   if (!batch_range_sized(b, first, count, w, h) || !resample_filter_known(filter) || orientation < 1 || orientation > 8 || !resample_extent_ok(src_w, src_h) ||
@@ -1157,6 +1210,30 @@ int mi_batch_resize_png_oriented(mi_batch *b, int index, const mi_png_scanlines 
   if (int st = batch_reserve_scratch(b, inter_at + resample_inter_bytes(1, oh, slot_w(b, index)))) return st;
   if (int st = batch_png_expand(b, 1, &p, channels, b->d_rs_scratch.get())) return st;
   return batch_resample(b, index, 1, resample_scratch_source(b, sl.w, sl.h, channels), filter, inter_at, o);
+}
+
+// the deep form: a file that png_goes_deep accepts is expanded as uint16 samples into the scratch and resampled at 16 bits into its deep slot (kind
+// MI_INPUT_RGB16), the flips and turns as above; every other file goes exactly as mi_batch_resize_png_oriented sends it (its bytes, kind MI_INPUT_RGB).  An oriented
+// source of the slot's size is mi_batch_upload_png_oriented(.., 1).  The alpha rules of deep input (batch_takes_deep); every check comes first.
+int mi_batch_resize_png_deep(mi_batch *b, int index, const mi_png_scanlines *p, int filter, int orientation) {
+  if (!batch_index_ok(b, index) || !p || !resample_filter_known(filter) || orientation < 0 || orientation > 8) return MI_INVALID_ARGUMENT;
+  if (!png_goes_deep(p)) return mi_batch_resize_png_oriented(b, index, p, filter, orientation);
+  const PngScanlines &sl = p->sl;
+  const int o = orientation ? orientation : sl.orientation, channels = sl.has_alpha() ? 4 : 3;
+  if (channels > b->channels || !batch_takes_deep(b, channels)) return MI_INVALID_ARGUMENT;     // alpha is never dropped; the alpha rules of the kind
+  if (batch_oriented_fits(b, index, sl.w, sl.h, o)) return mi_batch_upload_png_oriented(b, index, p, o, 1);
+  if (!resample_extent_ok(sl.w, sl.h)) return MI_INVALID_ARGUMENT;
+  if (!batch_deep(b)) return MI_ENCODING_ERROR;
+  uint32_t ow, oh;
+  oriented_size(sl.w, sl.h, o, &ow, &oh);
+  (void)hipSetDevice(b->device);
+  const size_t inter_at = align_up((size_t)sl.w * sl.h * channels * 2, 256);
+  if (int st = batch_reserve_scratch(b, inter_at + resample_inter16_bytes(1, oh, slot_w(b, index)))) return st;
+  if (int st = batch_png_expand(b, 1, &p, channels, b->d_rs_scratch.get(), true)) return st;
+  Ingest16Src s;
+  static_cast<IngestSrc &>(s) = orient_scratch_source(b, sl.w, sl.h, channels, 2);
+  s.bits = 16; s.msb_aligned = 0;
+  return batch_resample16(b, index, 1, s, filter, inter_at, o);
 }
 
 // the size of a picture of sw x sh scaled down, never up, to fit a box (an extent of 0: no bound on that axis), aspect ratio kept: the bound axis takes the

@@ -32,12 +32,17 @@ static_assert(sizeof(SOURCE_KINDS) / sizeof(SOURCE_KINDS[0]) == 8 && MI_SOURCE_H
 // A second one, MI_SOURCE_RESIZED (0x200) on kinds 1, 2, 3, 5 and 6: desc names the OUTPUT picture -- the slot --, the file has any size and is resampled
 // on its way in with mi_image_source.resize_filter (the _oriented resize call of its route; with MI_SOURCE_ORIENTED it is turned as its file asks first).
 static bool source_oriented(int kind) { return (kind & MI_SOURCE_ORIENTED) != 0; }
+// A third one, MI_SOURCE_RESIZED_DEEP (0x400) on kinds 4 and 7 alone: desc and resize_filter as under MI_SOURCE_RESIZED; a 16-bit file is resampled at 16
+// bits into its deep slot (mi_batch_resize_png_deep), every other file as under MI_SOURCE_RESIZED on kind 2.  Never together with MI_SOURCE_RESIZED.
 static bool source_resized(int kind) { return (kind & MI_SOURCE_RESIZED) != 0; }
-static const SourceKind *source_kind(int kind) {                 // nullptr: no such kind (8..255, any other bit, a flag on host pixels, MI_SOURCE_RESIZED on the deep kinds)
+static bool source_resized_deep(int kind) { return (kind & MI_SOURCE_RESIZED_DEEP) != 0; }
+static bool source_any_resize(int kind) { return (kind & (MI_SOURCE_RESIZED | MI_SOURCE_RESIZED_DEEP)) != 0; }
+static const SourceKind *source_kind(int kind) {                 // nullptr: no such kind (8..255, any other bit, a flag on host pixels, MI_SOURCE_RESIZED on the deep kinds, MI_SOURCE_RESIZED_DEEP on any other, both flags)
   const int row = kind & 0xFF;
-  if (kind < 0 || (kind & ~(0xFF | MI_SOURCE_ORIENTED | MI_SOURCE_RESIZED)) != 0 || row >= 8) return nullptr;
-  if ((source_oriented(kind) || source_resized(kind)) && row == MI_SOURCE_HOST) return nullptr;
-  if (source_resized(kind) && SOURCE_KINDS[row].route == ROUTE_PNG_DEEP) return nullptr;      // resizing deep sources is not built
+  if (kind < 0 || (kind & ~(0xFF | MI_SOURCE_ORIENTED | MI_SOURCE_RESIZED | MI_SOURCE_RESIZED_DEEP)) != 0 || row >= 8) return nullptr;
+  if ((source_oriented(kind) || source_any_resize(kind)) && row == MI_SOURCE_HOST) return nullptr;
+  if (source_resized(kind) && SOURCE_KINDS[row].route == ROUTE_PNG_DEEP) return nullptr;      // the deep kinds resize under their own flag
+  if (source_resized_deep(kind) && (SOURCE_KINDS[row].route != ROUTE_PNG_DEEP || source_resized(kind))) return nullptr;
   return &SOURCE_KINDS[row];
 }
 // the colour description of a managed source (icc_reader.h: the kind travels beside the bytes; a view into the source's handle)
@@ -53,7 +58,7 @@ static int source_refusal(const mi_ravif_encoder &e, const mi_image_source &src)
   if (!kind) return MI_INVALID_ARGUMENT;
   // the size desc names is the file's, or with MI_SOURCE_ORIENTED that of the file turned as it asks
   // (a resized source's file has any size the resize calls take: desc names the output, and the filter must be one of MI_RESAMPLE_*)
-  const bool resized = source_resized(src.kind);
+  const bool resized = source_any_resize(src.kind);
   if (resized && !resample_filter_known(src.resize_filter)) return MI_INVALID_ARGUMENT;
   auto fits = [&](uint32_t w, uint32_t h, int orientation) {
     if (resized) return resample_extent_ok(w, h);
@@ -197,9 +202,11 @@ struct StreamWorker {
     auto charge_scratch = [&](bool deep_route, const mi_image_desc &x) { charge_bytes((size_t)x.width * x.height * 4 * (deep_route ? 2 : 1) + ((size_t)1 << 20)); };
     // (a resized source: the decoded file of fw x fh and the intermediate of the two passes, at most max(fw, fh) rows of the slot's width -- the slot is charged what its largest source needs)
     auto charge_resize = [&](uint32_t fw, uint32_t fh, const mi_image_desc &x) { charge_bytes((size_t)fw * fh * 4 + resample_inter_bytes(1, std::max(fw, fh), x.width) + ((size_t)2 << 20)); };
+    // (the deep form: two bytes a sample of the decoded file, eight a pixel of the intermediate)
+    auto charge_resize16 = [&](uint32_t fw, uint32_t fh, const mi_image_desc &x) { charge_bytes((size_t)fw * fh * 8 + resample_inter16_bytes(1, std::max(fw, fh), x.width) + ((size_t)2 << 20)); };
     // (the JPEG staging follows the largest file: the shape's size, or a resized source's own)
     auto charge_jpeg = [&](uint32_t fw, uint32_t fh) { const size_t need = est_jpeg_bytes(fw, fh); if (need > sl.jpeg_bytes) { charge(sl, need - sl.jpeg_bytes); sl.jpeg_bytes = need; } };
-    const int rc = for_each_group(run.size(), [&](size_t k) { return (int)source_kind(source(k).kind)->route | (source(k).kind & (MI_SOURCE_ORIENTED | MI_SOURCE_RESIZED)); }, [&](size_t from, size_t to) -> int {
+    const int rc = for_each_group(run.size(), [&](size_t k) { return (int)source_kind(source(k).kind)->route | (source(k).kind & (MI_SOURCE_ORIENTED | MI_SOURCE_RESIZED | MI_SOURCE_RESIZED_DEEP)); }, [&](size_t from, size_t to) -> int {
       const UploadRoute route = source_kind(source(from).kind)->route;
       const bool oriented = source_oriented(source(from).kind), resized = source_resized(source(from).kind);
       switch (route) {
@@ -235,6 +242,13 @@ struct StreamWorker {
         const size_t extra = 2 * (png_call_bytes((int)pngs.size(), pngs.data()) + ((size_t)1 << 20));
         if (extra > sl.png_bytes) { charge(sl, extra - sl.png_bytes); sl.png_bytes = extra; }
         if (route == ROUTE_PNG_DEEP && !sl.deep) { sl.deep = true; charge(sl, sh.cap * (size_t)sh.w * sh.h * sh.ch * 2); }   // the deep slots join the worker's budget
+        if (source_resized_deep(source(from).kind)) {            // one file a call: a 16-bit file at 16 bits into its deep slot, any other as under MI_SOURCE_RESIZED
+          for (size_t k = from; k < to; k++) {
+            charge_resize16(source(k).png->sl.w, source(k).png->sl.h, source(k).desc);
+            if (const int st = mi_batch_resize_png_deep(sl.b, (int)k, source(k).png, source(k).resize_filter, oriented ? 0 : 1)) return st;
+          }
+          return MI_OK;
+        }
         if (resized) {                                           // one file a call, as above (never the deep route: source_kind)
           for (size_t k = from; k < to; k++) {
             charge_resize(source(k).png->sl.w, source(k).png->sl.h, source(k).desc);

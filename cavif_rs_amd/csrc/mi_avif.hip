@@ -26,6 +26,7 @@
 #include "dev_quality.h"
 #include "dev_decoded.h"
 #include "dev_deep.h"
+#include "dev_resample16.h"
 #include "icc_reader.h"
 #include "dev_colour.h"
 #include "dev_orient.h"
@@ -71,7 +72,7 @@ struct mi_batch {
   // resize on input: the per-axis tables (bounds + taps) of the mi_batch_resize_* calls since the stream last drained, pinned and on the device, the last call's
   // kept for the next one of the same sizes and filter; one device scratch for a decoded JPEG / PNG source and the intermediate of the two passes
   PinBuf<uint8_t> h_rs; DevBuf<uint8_t> d_rs, d_rs_scratch; size_t h_rs_cap = 0, d_rs_cap = 0, rs_used = 0, d_rs_scratch_cap = 0;
-  uint32_t rs_key[5] = { 0, 0, 0, 0, 0 }; size_t rs_key_at = 0;     // oriented src_w, src_h, dst_w, dst_h, filter + 1 of the tables at rs_key_at (0 in [4]: none)
+  uint32_t rs_key[6] = { 0, 0, 0, 0, 0, 0 }; size_t rs_key_at = 0;  // oriented src_w, src_h, dst_w, dst_h, filter + 1, fractional bits of the tables at rs_key_at (0 in [4]: none)
   // quality metrics (mi_batch_measure): `encoded` = the planes of a completed encode of the current image count are on the device, `measured` = h_quality holds
   // that encode's records.  The records live at the end of the arena (FrameSet::d_records); their pinned D2H target is made by the first measure.
   bool encoded = false, measured = false;
@@ -595,6 +596,11 @@ int mi_ravif_encode_device_ycbcr16(const mi_ravif_encoder *e, const mi_device_pl
 int mi_ravif_encode_device_resized(const mi_ravif_encoder *e, const mi_device_pixels *src, uint32_t src_w, uint32_t src_h, uint32_t w, uint32_t h, int filter, mi_encoded_image *out) {
   if (!src || !src->dev || (src->channels != 3 && src->channels != 4)) return MI_INVALID_ARGUMENT;
   return encode_pooled(e, w, h, src->channels, out, [&](mi_batch *b) { return mi_batch_resize_device(b, 0, 1, src, src_w, src_h, filter); });
+}
+// the same for a uint16 picture: resampled at 16 bits into the deep slot (mi_batch_resize_device16)
+int mi_ravif_encode_device16_resized(const mi_ravif_encoder *e, const mi_device_pixels16 *src, uint32_t src_w, uint32_t src_h, uint32_t w, uint32_t h, int filter, mi_encoded_image *out) {
+  if (!src || !src->dev || (src->channels != 3 && src->channels != 4)) return MI_INVALID_ARGUMENT;
+  return encode_pooled(e, w, h, src->channels, out, [&](mi_batch *b) { return mi_batch_resize_device16(b, 0, 1, src, src_w, src_h, filter); });
 }
 
 }  // extern "C"

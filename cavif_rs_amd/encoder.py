@@ -142,6 +142,9 @@ _PROTOTYPES = {
     'mi_batch_resize_device_oriented': (_STATUS, [_P, _I, _I, C.POINTER(_DevicePixels), _U32, _U32, _I, _I]),
     'mi_batch_resize_jpeg_oriented': (_STATUS, [_P, _I, _P, _I, _I, _I]),
     'mi_batch_resize_png_oriented': (_STATUS, [_P, _I, _P, _I, _I]),
+    'mi_batch_resize_device16': (_STATUS, [_P, _I, _I, C.POINTER(_DevicePixels16), _U32, _U32, _I]),
+    'mi_batch_resize_png_deep': (_STATUS, [_P, _I, _P, _I, _I]),
+    'mi_ravif_encode_device16_resized': (_STATUS, [_ENC, C.POINTER(_DevicePixels16), _U32, _U32, _U32, _U32, _I, _OUT]),
     'mi_fit_size': (None, [_U32, _U32, _U32, _U32, _PU32, _PU32]),
     'mi_ravif_encode_device_resized': (_STATUS, [_ENC, C.POINTER(_DevicePixels), _U32, _U32, _U32, _U32, _I, _OUT]),
     'mi_batch_measure': (_STATUS, [_P]),
@@ -466,6 +469,7 @@ INPUT_RGB, INPUT_YCBCR, INPUT_RGB16, INPUT_YCBCR16 = range(4)   # MI_INPUT_*: wh
 SOURCE_HOST, SOURCE_JPEG, SOURCE_PNG, SOURCE_JPEG_YCBCR, SOURCE_PNG_DEEP, SOURCE_JPEG_MANAGED, SOURCE_PNG_MANAGED, SOURCE_PNG_DEEP_MANAGED = range(8)   # MI_SOURCE_*: what mi_ravif_encode_sources takes
 SOURCE_ORIENTED = 0x100                                  # MI_SOURCE_ORIENTED: ORed into kinds 1..7, the picture is turned as its file asks and desc names the oriented size
 SOURCE_RESIZED = 0x200                                   # MI_SOURCE_RESIZED: ORed into kinds 1, 2, 3, 5 and 6, desc names the output size and resize_filter the filter
+SOURCE_RESIZED_DEEP = 0x400                              # MI_SOURCE_RESIZED_DEEP: ORed into kinds 4 and 7, as SOURCE_RESIZED; a 16-bit file is resampled at 16 bits into its deep slot
 _SOURCE_HANDLE_FIELD = {SOURCE_HOST: None, SOURCE_JPEG: 'jpeg', SOURCE_PNG: 'png', SOURCE_JPEG_YCBCR: 'jpeg', SOURCE_PNG_DEEP: 'png',      # the field of mi_image_source that carries
                         SOURCE_JPEG_MANAGED: 'jpeg', SOURCE_PNG_MANAGED: 'png', SOURCE_PNG_DEEP_MANAGED: 'png'}                      # the kind's handle (None: host pixels in desc)
 
@@ -865,13 +869,16 @@ class Encoder:
         h, w, _ = a.shape
         return self._call_once(L.mi_ravif_encode_rgba if channels == 4 else L.mi_ravif_encode_rgb, None, a.ctypes.data, w, h, w)
 
-    def encode_resized(self, source, size, filter='lanczos', oriented=False, ycbcr=False):
+    def encode_resized(self, source, size, filter='lanczos', oriented=False, ycbcr=False, deep=False, bits=16, msb_aligned=False):
         """`source` resampled to size = (width, height) on the device, then encoded: the file of encode_rgb / encode_rgba over the pixels Pillow's
         Image.resize(size, resample=filter, reducing_gap=None) gives.  source: an object with __cuda_array_interface__ (uint8, (H, W, C) or (C, H, W), any
         size; encoded as RGB or RGBA by its channels), a JpegCoeffs (RGB) or a PngScanlines (RGBA when the file has alpha or tRNS, else RGB).
         filter: 'box', 'bilinear', 'bicubic' or 'lanczos'.
         oriented=True (handles): the file is turned as its EXIF orientation asks and then resampled, in one go on the device (resize_jpeg / resize_png with the
-        file's own orientation); ycbcr=True (a JpegCoeffs): the file's own Y, Cb, Cr are resampled channel by channel and coded without the detour over RGB."""
+        file's own orientation); ycbcr=True (a JpegCoeffs): the file's own Y, Cb, Cr are resampled channel by channel and coded without the detour over RGB.
+        Deep resize: a uint16 device array is resampled at 16 bits into the deep slot (`bits` of a sample count, its low ones or, msb_aligned, its
+        high ones), and deep=True does the same for a PngScanlines of bit depth 16 (any other file goes as without it): the file of encode_rgb / encode_rgba
+        over the uint16 pixels the specification in include/mi_avif.h gives."""
         L = load_library()
         f = _named(RESAMPLE_FILTERS, filter)
         w, h = int(size[0]), int(size[1])
@@ -881,8 +888,13 @@ class Encoder:
             raise TypeError('oriented and ycbcr are for JpegCoeffs and PngScanlines (a device array: BatchEncoder.resize_device with an orientation)')
         if ycbcr and not isinstance(source, JpegCoeffs):
             raise TypeError('ycbcr is for a JpegCoeffs')
+        if deep and not isinstance(source, PngScanlines):
+            raise TypeError('deep is for a PngScanlines (a uint16 device array is resampled at 16 bits as it is)')
         if _is_device_array(source):
-            d, _, sh, sw, index = _device_pixels(source)
+            d, _, sh, sw, index = _device_pixels(source, deep_ok=True)
+            if isinstance(d, _DevicePixels16):          # uint16 samples: resampled at 16 bits into the deep slot
+                d.bits, d.msb_aligned = int(bits), int(bool(msb_aligned))
+                return self._call_once(L.mi_ravif_encode_device16_resized, index, C.byref(d), sw, sh, w, h, f)
             return self._call_once(L.mi_ravif_encode_device_resized, index, C.byref(d), sw, sh, w, h, f)
         if isinstance(source, JpegCoeffs):
             channels = 3
@@ -894,7 +906,7 @@ class Encoder:
             if isinstance(source, JpegCoeffs):
                 b.resize_jpeg(0, source, filter, orientation=0 if oriented else 1, ycbcr=ycbcr)
             else:
-                b.resize_png(0, source, filter, orientation=0 if oriented else 1)
+                b.resize_png(0, source, filter, orientation=0 if oriented else 1, deep=deep)
             b.encode()
             return b.get(0)
 
@@ -1060,7 +1072,7 @@ def _source_kind(handle, jpeg_ycbcr, png_deep, managed):
     return SOURCE_JPEG_YCBCR if jpeg_ycbcr and handle.color != 'rgb' else SOURCE_JPEG
 
 
-def encode_many(encoder, images, devices=None, jpeg_ycbcr=False, png_deep=False, managed=False, oriented=False, fit=None, resize_filter='lanczos'):
+def encode_many(encoder, images, devices=None, jpeg_ycbcr=False, png_deep=False, managed=False, oriented=False, fit=None, resize_filter='lanczos', deep_resize=False):
     """mi_ravif_encode_sources: the reference's files.into_par_iter() (src/main.rs:223) over the node's GPUs.
     images: list of HxWx3 / HxWx4 uint8 arrays (shapes may differ), JpegCoeffs objects (parse_jpeg; encoded as the RGBA pictures decode_jpeg
     gives, decoded on the device) and PngScanlines objects (parse_png; encoded as the RGBA pictures load_rgba gives, unfiltered and expanded on the
@@ -1074,8 +1086,9 @@ def encode_many(encoder, images, devices=None, jpeg_ycbcr=False, png_deep=False,
     taken as they are.
     fit=(w, h) (or one number for both; 0: no bound on that axis): a parsed file larger than the box -- with oriented=True, its oriented picture -- is resampled on the
     device on its way in (SOURCE_RESIZED) to fit_size of its size, with resize_filter ('box', 'bilinear', 'bicubic' or 'lanczos'); files that fit are untouched, host
-    arrays are taken as they are, and with png_deep=True a file that must be resized goes as the non-deep kind (its high bytes).  managed=True converts after the
-    resize (the resampling is not done in linear light).
+    arrays are taken as they are, and with png_deep=True a file that must be resized goes as the non-deep kind (its high bytes) unless deep_resize=True: then a
+    PngScanlines of bit depth 16 that must be resized goes as SOURCE_PNG_DEEP[_MANAGED] | SOURCE_RESIZED_DEEP and is resampled at 16 bits into its deep slot
+    (DESIGN.md 5m).  deep_resize means something only together with png_deep and fit.  managed=True converts after the resize (the resampling is not done in linear light).
     Returns a list of EncodedImage."""
     items = []
     rf = _named(RESAMPLE_FILTERS, resize_filter)
@@ -1085,7 +1098,10 @@ def encode_many(encoder, images, devices=None, jpeg_ycbcr=False, png_deep=False,
             size = oriented_size(im.width, im.height, im.orientation if oriented else 1)
             fitted = fit_size(size[0], size[1], fit) if fit is not None else size
             if fitted != size:
-                kind = _source_kind(im, jpeg_ycbcr, False, managed) | SOURCE_RESIZED
+                if deep_resize and png_deep and isinstance(im, PngScanlines) and im.bit_depth == 16 and im.color_type != 3:
+                    kind = _source_kind(im, jpeg_ycbcr, True, managed) | SOURCE_RESIZED_DEEP
+                else:
+                    kind = _source_kind(im, jpeg_ycbcr, False, managed) | SOURCE_RESIZED
                 items.append((kind | (SOURCE_ORIENTED if oriented else 0), im, 4, fitted, rf))
                 continue
             items.append((_source_kind(im, jpeg_ycbcr, png_deep, managed) | (SOURCE_ORIENTED if oriented else 0), im, 4))
@@ -1102,7 +1118,7 @@ def encode_many(encoder, images, devices=None, jpeg_ycbcr=False, png_deep=False,
 def _encode_sources(encoder, items, devices):
     """mi_ravif_encode_sources over (kind, object, channels of the slot) triples: SOURCE_HOST a contiguous uint8 array, SOURCE_JPEG / _JPEG_YCBCR a JpegCoeffs,
     SOURCE_PNG / _PNG_DEEP a PngScanlines; with SOURCE_ORIENTED desc names the oriented size; with SOURCE_RESIZED the item is (kind, object, channels, (width, height)
-    of the output, MI_RESAMPLE_* filter)"""
+    of the output, MI_RESAMPLE_* filter), and likewise with SOURCE_RESIZED_DEEP"""
     L = load_library()
 
     def fetch(_user, i, src):
@@ -1111,7 +1127,7 @@ def _encode_sources(encoder, items, devices):
         field = _SOURCE_HANDLE_FIELD[kind & 0xFF]
         if field:
             setattr(s, field, it._h)
-            if kind & SOURCE_RESIZED:
+            if kind & (SOURCE_RESIZED | SOURCE_RESIZED_DEEP):
                 (w, h), s.resize_filter = items[i][3], items[i][4]
             else:
                 w, h = oriented_size(it.width, it.height, it.orientation if kind & SOURCE_ORIENTED else 1)
@@ -1274,11 +1290,20 @@ class BatchEncoder(_Handle):
         _ok(self._L.mi_batch_convert_colour(self._h, first, count, _live(transform, ColourTransform)))
         self._sources.append(transform)
 
-    def resize_device(self, first, pixels, filter='lanczos', orientation=1):
+    def resize_device(self, first, pixels, filter='lanczos', orientation=1, bits=16, msb_aligned=False):
         """upload_device for pictures of any size (taken from the array): resampled into the slots on the batch's stream, the pixels of Pillow's
         Image.resize((w, h), resample=filter, reducing_gap=None); filter: 'box', 'bilinear', 'bicubic' or 'lanczos'.
-        orientation 2..8 (mi_batch_resize_device_oriented): the pictures are turned by the map of orient_device and resampled in one go, no turned copy."""
-        d, n, h, w, _ = _device_pixels(pixels, batched=True)
+        orientation 2..8 (mi_batch_resize_device_oriented): the pictures are turned by the map of orient_device and resampled in one go, no turned copy.
+        uint16 arrays of the same shapes are resampled at 16 bits into the deep slots (mi_batch_resize_device16, input kind 2): `bits` (8..16) of a
+        sample count, its low ones or (msb_aligned) its high ones; an orientation other than 1 with a uint16 array is a TypeError."""
+        d, n, h, w, _ = _device_pixels(pixels, batched=True, deep_ok=True)
+        if isinstance(d, _DevicePixels16):
+            if int(orientation) != 1:
+                raise TypeError('uint16 device arrays are resized without an orientation (turning them is not built)')
+            d.bits, d.msb_aligned = int(bits), int(bool(msb_aligned))
+            _ok(self._L.mi_batch_resize_device16(self._h, first, n, C.byref(d), w, h, _named(RESAMPLE_FILTERS, filter)))
+            self._sources.append(pixels)
+            return
         _ok(self._L.mi_batch_resize_device_oriented(self._h, first, n, C.byref(d), w, h, _named(RESAMPLE_FILTERS, filter), int(orientation)))      # orientation 1: the plain call
         self._sources.append(pixels)
 
@@ -1288,9 +1313,13 @@ class BatchEncoder(_Handle):
         (an RGB file raises Unsupported)."""
         _ok(self._L.mi_batch_resize_jpeg_oriented(self._h, index, _live(coeffs, JpegCoeffs), _named(RESAMPLE_FILTERS, filter), int(orientation), int(bool(ycbcr))))
 
-    def resize_png(self, index, scanlines, filter='lanczos', orientation=1):
+    def resize_png(self, index, scanlines, filter='lanczos', orientation=1, deep=False):
         """upload_png for one file of any size: unfiltered, expanded and resampled into slot `index` on the batch's stream.  A file with alpha or tRNS into
-        a 3-channel batch raises InvalidArgument.  orientation 2..8, or 0 for the file's own (mi_batch_resize_png_oriented): turned and resampled in one go."""
+        a 3-channel batch raises InvalidArgument.  orientation 2..8, or 0 for the file's own (mi_batch_resize_png_oriented): turned and resampled in one go.
+        deep=True (mi_batch_resize_png_deep): a file of bit depth 16 is resampled at 16 bits into its deep slot (input kind 2); every other file goes as before."""
+        if deep:
+            _ok(self._L.mi_batch_resize_png_deep(self._h, index, _live(scanlines, PngScanlines), _named(RESAMPLE_FILTERS, filter), int(orientation)))
+            return
         _ok(self._L.mi_batch_resize_png_oriented(self._h, index, _live(scanlines, PngScanlines), _named(RESAMPLE_FILTERS, filter), int(orientation)))
 
     def device_input(self, index):

@@ -133,15 +133,20 @@ int  mi_ravif_encode_stream(const mi_ravif_encoder *e, size_t n, mi_fetch_fn fet
  * (extents 1..65536) and is resampled on its way in with the filter in mi_image_source.resize_filter (the mi_batch_resize_*_oriented call of its route below; the pixels
  * are specified exactly).  With MI_SOURCE_ORIENTED the file is turned as it asks and then resampled.  The managed kinds convert after the resize, in the slot, as they
  * convert after an upload: the resampling is done on the file's own sample values, not in linear light.  Runs are grouped by desc as before, so by the output shape.
- * MI_INVALID_ARGUMENT, for that image alone: the flag on kind 0 or on kinds 4 and 7 (resizing deep sources is not built), a filter that is none of MI_RESAMPLE_*
+ * MI_INVALID_ARGUMENT, for that image alone: the flag on kind 0 or on kinds 4 and 7 (they resize under MI_SOURCE_RESIZED_DEEP), a filter that is none of MI_RESAMPLE_*
  * (the library sets the field to -1 before it calls fetch, so a caller that sets the flag has to set the filter), a file extent outside 1..65536, a PNG with alpha
  * or tRNS into channels 3.
+ * MI_SOURCE_RESIZED_DEEP (0x400), ORed into kinds 4 and 7 alone, optionally with MI_SOURCE_ORIENTED: desc and resize_filter are read as under
+ * MI_SOURCE_RESIZED; a file of bit depth 16 is resampled at 16 bits into its deep slot (mi_batch_resize_png_deep below: the pixels are specified exactly), every other
+ * file goes as under MI_SOURCE_RESIZED on kind 2.  Kind 7 converts after the resize, in the deep slot.  MI_INVALID_ARGUMENT, for that image alone: the flag on any
+ * other kind, the flag together with MI_SOURCE_RESIZED, a filter that is none of MI_RESAMPLE_*, a file extent outside 1..65536, the alpha refusals of kind 4.
  * mi_ravif_encode_stream is this call with MI_SOURCE_HOST throughout.  Pictures in device memory are not a kind here (a pointer belongs to one
  * device, the shared cursor hands images to any): they enter through mi_ravif_encode_device and mi_batch_upload_device. */
 enum { MI_SOURCE_HOST = 0, MI_SOURCE_JPEG = 1, MI_SOURCE_PNG = 2, MI_SOURCE_JPEG_YCBCR = 3, MI_SOURCE_PNG_DEEP = 4,
        MI_SOURCE_JPEG_MANAGED = 5, MI_SOURCE_PNG_MANAGED = 6, MI_SOURCE_PNG_DEEP_MANAGED = 7,
        MI_SOURCE_ORIENTED = 0x100 /* a modifier, ORed into kinds 1 to 7 */,
-       MI_SOURCE_RESIZED = 0x200 /* a second modifier, ORed into kinds 1, 2, 3, 5 and 6: desc names the output size, resize_filter the filter */ };
+       MI_SOURCE_RESIZED = 0x200 /* a second modifier, ORed into kinds 1, 2, 3, 5 and 6: desc names the output size, resize_filter the filter */,
+       MI_SOURCE_RESIZED_DEEP = 0x400 /* the same for kinds 4 and 7: a 16-bit file is resampled at 16 bits into its deep slot */ };
 typedef struct mi_jpeg_coeffs mi_jpeg_coeffs;   /* opaque: one parsed file, host memory only */
 typedef struct mi_png_scanlines mi_png_scanlines;      /* opaque: one inflated file, host memory only */
 typedef struct mi_image_source {
@@ -152,7 +157,7 @@ typedef struct mi_image_source {
   mi_image_desc desc;
   const mi_jpeg_coeffs *jpeg;
   const mi_png_scanlines *png; /* kinds 2, 4, 6 and 7 only (the struct grew by this field at its tail: never read for kinds 0 and 1) */
-  int resize_filter;           /* one of MI_RESAMPLE_* (below); read only when kind carries MI_SOURCE_RESIZED (the struct grew by this field at its tail: a fetch callback
+  int resize_filter;           /* one of MI_RESAMPLE_* (below); read only when kind carries MI_SOURCE_RESIZED or MI_SOURCE_RESIZED_DEEP (the struct grew by this field at its tail: a fetch callback
                                   that never sets the flag need not know it) */
 } mi_image_source;
 typedef int (*mi_fetch_source_fn)(void *user, size_t index, mi_image_source *src);
@@ -475,7 +480,7 @@ int  mi_batch_resize_png(mi_batch *b, int index, const mi_png_scanlines *p, int 
  * mi_batch_resize_jpeg_oriented / _png_oriented: one parsed file into slot `index`, orientation 1..8, or 0: the file's own.  ycbcr != 0: the file's own (Y, Cb, Cr)
  * triples, as mi_batch_upload_jpeg_ycbcr stores them, are resampled channel by channel (what Pillow gives for a YCbCr mode image) and the slot is tagged
  * MI_INPUT_YCBCR; that call's refusals apply (MI_UNSUPPORTED for a file whose colour is RGB).  A PNG of bit depth 16 is taken through its high bytes, as
- * mi_batch_resize_png takes it: resizing deep sources is not built.
+ * mi_batch_resize_png takes it; mi_batch_resize_png_deep (below) resamples all 16 bits.
  * Orientation 1, given or read from the file, is the plain mi_batch_resize_* call (with ycbcr: the same two passes over the triples); an oriented source that already
  * has the slot's size is the _oriented upload of its kind (orientation 1 as well: the plain upload).  Neither takes the premultiply round trip.
  * MI_INVALID_ARGUMENT: the refusals of the resize calls and of the orient calls -- an unknown filter, an orientation outside the call's range, a zero extent or one
@@ -489,6 +494,36 @@ int  mi_batch_resize_device_oriented(mi_batch *b, int first, int count, const mi
 int  mi_batch_resize_jpeg_oriented(mi_batch *b, int index, const mi_jpeg_coeffs *c, int filter, int orientation, int ycbcr);   /* 0 = the file's own */
 int  mi_batch_resize_png_oriented(mi_batch *b, int index, const mi_png_scanlines *p, int filter, int orientation);             /* 0 = the file's own */
 void mi_fit_size(uint32_t sw, uint32_t sh, uint32_t box_w, uint32_t box_h, uint32_t *w, uint32_t *h);
+/* deep resize (opt-in): a 16-bit source of any size is resampled at 16 bits into the DEEP slot, kind MI_INPUT_RGB16.  The structure is that of the
+ * 8-bit calls above, in exact integers:
+ *   tables   bounds and normalised double coefficients exactly as above (same filters, same support, same first sample and count per output sample); each tap is
+ *            rounded to 28 fractional bits, (int)(v * 2^28 +- 0.5), an int32 (the largest |tap| is about 1.25); an axis that keeps its length has the one tap 2^28.
+ *   a pass   out = clamp((2^27 + sum k_j * s_j) >> 28, 0, 65535): a signed 64-bit sum that does not wrap (|sum| < 2^46, any order), an arithmetic shift.
+ *   order    the horizontal pass first, along the oriented picture's x axis, into a clipped 16-bit intermediate, then the vertical one; a pass whose axis keeps
+ *            its length moves the samples unchanged.
+ *   alpha    a 4-channel source is premultiplied on load: t = c * a + 32768 (uint32), p = (t + (t >> 16)) >> 16 = floor((2 c a + 65535) / 131070); after the
+ *            vertical pass, for a not 0 and not 65535, c = min(65535, 65535 * c / a) in integer division.  3 channels into a 4-channel batch: A = 65535, no
+ *            premultiplication.
+ *   samples  a device sample is first reduced to `bits` and widened by bit replication, exactly as mi_batch_upload_device16 does; then premultiplied, then filtered.
+ * A source that already has the slot's size takes the plain call of its kind (mi_batch_upload_device16, mi_batch_upload_png_deep, mi_batch_upload_png_oriented(.., 1))
+ * and gives that call's bytes: no premultiply round trip.  The alpha rules are those of deep input: a 4-channel source needs alpha_mode 0, alpha_mode 2 takes none
+ * into a 4-channel batch, 4 channels into a 3-channel batch are refused.
+ * mi_batch_resize_device16: images [first, first+count) from uint16 pictures of src_w x src_h, described and ordered as for mi_batch_upload_device16.  The refusals
+ * of that call (an odd pointer or stride, bits outside 8..16, msb_aligned not 0 or 1, strides below the packed extent, the alpha rules) and of mi_batch_resize_device.
+ * No orientation: turning mi_batch_upload_device16 sources is not built.
+ * mi_batch_resize_png_deep: one parsed PNG into slot `index`, turned by `orientation` (1..8, or 0: the file's own) and resampled.  A file of bit depth 16 that is
+ * not palette-coded is expanded as uint16 samples into the batch's scratch and resampled from where it lies (orientations 2..4 are addressing, 5..8 filter down the
+ * columns and transpose a tile, as in the 8-bit calls): the slot receives the bytes of mi_batch_upload_png_oriented(.., deep = 1) into a slot of the oriented size
+ * followed by the plain deep resize from there.  Every other file goes exactly as mi_batch_resize_png_oriented sends it: its bytes, kind MI_INPUT_RGB.
+ * The scratch is the batch's one shared scratch: the decoded source (w * h * channels * 2 bytes) and the intermediate (count * oriented height * dst_w rounded up to
+ * 4 * 8 bytes).  MI_INVALID_ARGUMENT: every refusal above, an unknown filter, an orientation outside 0..8, a zero extent or one above 65536, a range past the capacity
+ * or of slots of different sizes, null pointers, a call between mi_batch_encode_async and mi_batch_wait.  Every check comes first: a refused call allocates nothing
+ * (mi_batch_footprint).  MI_ENCODING_ERROR when the deep slots, staging or scratch cannot be allocated.
+ * mi_ravif_encode_device16_resized: mi_ravif_encode_device16 for a picture of src_w x src_h resampled to w x h through mi_batch_resize_device16. */
+int  mi_batch_resize_device16(mi_batch *b, int first, int count, const mi_device_pixels16 *src, uint32_t src_w, uint32_t src_h, int filter);
+int  mi_batch_resize_png_deep(mi_batch *b, int index, const mi_png_scanlines *p, int filter, int orientation);                 /* 1..8, 0 = the file's own */
+int  mi_ravif_encode_device16_resized(const mi_ravif_encoder *e, const mi_device_pixels16 *src, uint32_t src_w, uint32_t src_h, uint32_t w, uint32_t h,
+                                      int filter, mi_encoded_image *out);
 int  mi_batch_set_count(mi_batch *b, int n_images);                                       /* images of the next run (<= the count the batch was created for), each of the batch's w x h */
 /* ---- mixed-size layouts: the pictures of a run differ in size.  A batch is made as before, mi_batch_create(e, cap, W, H, channels); everything it
  * reserves for cap pictures of W x H -- the slot arrays, the arena, tile jobs, payload and pre-carry capacity, symbol records, the search queue's items and snapshots,
