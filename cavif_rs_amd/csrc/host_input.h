@@ -438,6 +438,32 @@ int mi_batch_upload16(mi_batch *b, int index, const uint16_t *pixels, size_t str
   return MI_OK;
 }
 
+// ---- float sources (dev_float.h) ----
+static size_t sample_bytes_of(int sample) { return sample == MI_SAMPLE_F32 ? 4 : 2; }
+static bool full_scale_ok(float full_scale) { return std::isfinite(full_scale) && full_scale > 0.0f; }
+// images [first, first + count) from binary16 or binary32 pictures in the memory of the batch's device: one ingest_float_kernel launch on the batch's stream,
+// after whatever src->after_stream holds at this moment; the slots are tagged MI_INPUT_RGB16.  mi_batch_upload_device16's rules (the alpha rules of deep input
+// among them), the strides counted in the sample's size.  Every check comes before the deep slots are made: a refused call allocates nothing.
+int mi_batch_upload_device_float(mi_batch *b, int first, int count, const mi_device_pixels_float *src) {
+  uint32_t w, h;
+  IngestFloatSrc s;
+  if (!batch_range_sized(b, first, count, w, h) || !src || !src->dev) return MI_INVALID_ARGUMENT;
+  if ((src->layout != 0 && src->layout != 1) || !batch_takes_deep(b, src->channels)) return MI_INVALID_ARGUMENT;   // alpha is never dropped; the alpha rules of the kind
+  if ((src->sample != MI_SAMPLE_F16 && src->sample != MI_SAMPLE_F32) || !full_scale_ok(src->full_scale)) return MI_INVALID_ARGUMENT;
+  const size_t sb = sample_bytes_of(src->sample);
+  if (((uintptr_t)src->dev | src->row_stride | src->pixel_or_plane_stride | src->image_stride) & (sb - 1)) return MI_INVALID_ARGUMENT;   // whole samples
+  s.w = w; s.h = h; s.sample = src->sample; s.full_scale = src->full_scale;
+  if (!strided_resolve(*src, w, h, sb, false, s)) return MI_INVALID_ARGUMENT;
+  uint16_t *const slots = mi_batch_device_input16(b, first);
+  if (!slots) return MI_ENCODING_ERROR;
+  (void)hipSetDevice(b->device);
+  if (int st = batch_join(b, src->after_stream)) return st;
+  LAUNCH_BY_CHANNELS(b, b->channels, w, h, count, ingest_float_kernel, s, slots);
+  HIP_OK(hipGetLastError());
+  batch_tag(b, first, count, MI_INPUT_RGB16);
+  return MI_OK;
+}
+
 // ---- deep YCbCr planes (dev_planes.h) ----
 // the multiply-high form of one sample map of include/mi_avif.h for planes_ingest16_kernel: W = clamp(floor((65535 v + bias) / d), 0, 65535), where
 // full range has d = P = 2^bits - 1 and the rounding term (P - 1) / 2, narrow range d = 219 s (luma) | 224 s (chroma), s = 2^(bits - 8), and the rounding term
@@ -526,6 +552,57 @@ int mi_batch_decode(mi_batch *b, int index, int which, int channels, uint8_t *ds
   t.dev = b->d_decoded.get(); t.layout = 0; t.channels = channels;
   if (const int st = mi_batch_decode_device(b, index, 1, which, &t)) return st;
   HIP_OK(hipMemcpy(dst, b->d_decoded.get(), slot_px(b, index) * channels, hipMemcpyDeviceToHost));
+  return MI_OK;
+}
+
+// ---- full-depth decoded pixels (dev_decoded16.h) ----
+// mi_batch_decode_device with uint16, binary16 or binary32 samples: its state rule, one-size rule, alpha rule and stride rules, the packed extents counted in
+// the sample's size; one decoded_deep_kernel launch, then the batch's stream is waited for.
+int mi_batch_decode_device_deep(mi_batch *b, int first, int count, int which, const mi_device_target_deep *dst) {
+  if (!batch_encoded_ok(b, first, count) || !slots_one_size(b, first, count) || !dst || !dst->dev) return MI_INVALID_ARGUMENT;
+  const uint32_t w = slot_w(b, first), h = slot_h(b, first);
+  if ((which != MI_DECODED_RECON && which != MI_DECODED_SOURCE) || (dst->layout != 0 && dst->layout != 1) || (dst->channels != 3 && dst->channels != 4)) return MI_INVALID_ARGUMENT;
+  if (dst->sample != MI_SAMPLE_U16 && dst->sample != MI_SAMPLE_F16 && dst->sample != MI_SAMPLE_F32) return MI_INVALID_ARGUMENT;
+  if (dst->sample != MI_SAMPLE_U16 && !full_scale_ok(dst->full_scale)) return MI_INVALID_ARGUMENT;
+  const size_t sb = sample_bytes_of(dst->sample);
+  if (((uintptr_t)dst->dev | dst->row_stride | dst->pixel_or_plane_stride | dst->image_stride) & (sb - 1)) return MI_INVALID_ARGUMENT;   // whole samples
+  if ((size_t)b->n * (b->channels == 4 ? 2 : 1) != b->fs.frames.size()) return MI_INVALID_ARGUMENT;
+  if (dst->channels == 3 && b->channels == 4)
+    for (int i = first; i < first + count; i++) if (b->alpha_flags[i]) return MI_INVALID_ARGUMENT;      // alpha is never dropped
+  DecodedDeepDst d;
+  d.first = first; d.n = b->n; d.alpha_frames = b->channels == 4; d.source = which == MI_DECODED_SOURCE;
+  d.sample = dst->sample; d.full_scale = dst->sample == MI_SAMPLE_U16 ? 1.0f : dst->full_scale;
+  if (!strided_resolve(*dst, w, h, sb, true, d)) return MI_INVALID_ARGUMENT;
+  (void)hipSetDevice(b->device);
+  if (int st = batch_join(b, dst->after_stream)) return st;
+  const dim3 grid = grid_by_four(w, h, count);
+  const FrameDev *const frames = b->fs.d_frames.get();
+  const bool rgb_model = b->fs.frames[first].cfg.matrix == 0;
+  if (b->depth == 8) {
+    if (rgb_model) hipLaunchKernelGGL((decoded_deep_kernel<8, 1>), grid, dim3(64), 0, b->stream, frames, d);
+    else hipLaunchKernelGGL((decoded_deep_kernel<8, 0>), grid, dim3(64), 0, b->stream, frames, d);
+  } else {
+    if (rgb_model) hipLaunchKernelGGL((decoded_deep_kernel<10, 1>), grid, dim3(64), 0, b->stream, frames, d);
+    else hipLaunchKernelGGL((decoded_deep_kernel<10, 0>), grid, dim3(64), 0, b->stream, frames, d);
+  }
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipStreamSynchronize(b->stream));
+  return MI_OK;
+}
+// One image into host memory (rows packed): the same launch into the batch's one-image decode scratch, grown to the sample size asked for, one D2H.
+int mi_batch_decode_deep(mi_batch *b, int index, int which, int channels, int sample, float full_scale, void *dst) {
+  if (!batch_encoded_ok(b, index, 1) || !dst || (channels != 3 && channels != 4)) return MI_INVALID_ARGUMENT;
+  if ((which != MI_DECODED_RECON && which != MI_DECODED_SOURCE) || (channels == 3 && b->channels == 4 && b->alpha_flags[index])) return MI_INVALID_ARGUMENT;
+  if (sample != MI_SAMPLE_U16 && sample != MI_SAMPLE_F16 && sample != MI_SAMPLE_F32) return MI_INVALID_ARGUMENT;
+  if (sample != MI_SAMPLE_U16 && !full_scale_ok(full_scale)) return MI_INVALID_ARGUMENT;                // before the scratch grows: a refused call allocates nothing
+  (void)hipSetDevice(b->device);
+  const size_t sb = sample_bytes_of(sample);
+  if (!staging_grow(b->d_decoded, b->d_decoded_cap, slot_px(b, index) * 4 * sb)) return MI_ENCODING_ERROR;
+  mi_device_target_deep t;
+  memset(&t, 0, sizeof(t));
+  t.dev = b->d_decoded.get(); t.layout = 0; t.channels = channels; t.sample = sample; t.full_scale = full_scale;
+  if (const int st = mi_batch_decode_device_deep(b, index, 1, which, &t)) return st;
+  HIP_OK(hipMemcpy(dst, b->d_decoded.get(), slot_px(b, index) * channels * sb, hipMemcpyDeviceToHost));
   return MI_OK;
 }
 

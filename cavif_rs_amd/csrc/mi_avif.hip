@@ -30,6 +30,8 @@
 #include "icc_reader.h"
 #include "dev_colour.h"
 #include "dev_orient.h"
+#include "dev_float.h"
+#include "dev_decoded16.h"
 #include "host_frames.h"
 
 // The product library reads no environment variables; probe builds (tools/) get MI_AVIF_TIMING=1 (-DMI_TUNING_KNOBS: host-side timeline on stderr)
@@ -581,6 +583,11 @@ int mi_ravif_encode_device(const mi_ravif_encoder *e, const mi_device_pixels *sr
 int mi_ravif_encode_device16(const mi_ravif_encoder *e, const mi_device_pixels16 *src, uint32_t w, uint32_t h, mi_encoded_image *out) {
   if (!src || !src->dev || (src->channels != 3 && src->channels != 4)) return MI_INVALID_ARGUMENT;
   return encode_pooled(e, w, h, src->channels, out, [&](mi_batch *b) { return mi_batch_upload_device16(b, 0, 1, src); });
+}
+// the same for a binary16 or binary32 picture in the memory of device e->device (mi_batch_upload_device_float)
+int mi_ravif_encode_device_float(const mi_ravif_encoder *e, const mi_device_pixels_float *src, uint32_t w, uint32_t h, mi_encoded_image *out) {
+  if (!src || !src->dev || (src->channels != 3 && src->channels != 4)) return MI_INVALID_ARGUMENT;
+  return encode_pooled(e, w, h, src->channels, out, [&](mi_batch *b) { return mi_batch_upload_device_float(b, 0, 1, src); });
 }
 // the same for YCbCr planes in the memory of device e->device: the file of a 3-channel batch fed through mi_batch_upload_device_ycbcr
 int mi_ravif_encode_device_ycbcr(const mi_ravif_encoder *e, const mi_device_planes *src, uint32_t w, uint32_t h, mi_encoded_image *out) {

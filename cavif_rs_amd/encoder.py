@@ -63,6 +63,14 @@ class _DevicePixels16(C.Structure):                    # mi_device_pixels16: _De
     _fields_ = _DevicePixels._fields_ + [('bits', C.c_int), ('msb_aligned', C.c_int)]
 
 
+class _DevicePixelsFloat(C.Structure):                 # mi_device_pixels_float: _DevicePixels for binary16 / binary32 samples + the value that means white
+    _fields_ = _DevicePixels._fields_ + [('sample', C.c_int), ('full_scale', C.c_float)]
+
+
+class _DeviceTargetDeep(C.Structure):                  # mi_device_target_deep: a writable _DevicePixels of uint16 / binary16 / binary32 samples
+    _fields_ = _DevicePixels._fields_ + [('sample', C.c_int), ('full_scale', C.c_float)]
+
+
 class _DevicePlanes(C.Structure):                      # mi_device_planes
     _fields_ = [('y', C.c_void_p), ('cb', C.c_void_p), ('cr', C.c_void_p), ('hsub', C.c_int), ('vsub', C.c_int), ('y_row_stride', C.c_size_t),
                 ('c_row_stride', C.c_size_t), ('y_image_stride', C.c_size_t), ('c_image_stride', C.c_size_t), ('after_stream', C.c_void_p)]
@@ -192,6 +200,10 @@ _PROTOTYPES = {
     'mi_batch_set_sizes': (_STATUS, [_P, _I, _PU32, _PU32]),
     'mi_batch_fits': (_STATUS, [_P, _I, _PU32, _PU32]),
     'mi_batch_image_size': (_STATUS, [_P, _I, _PU32, _PU32]),
+    'mi_batch_upload_device_float': (_STATUS, [_P, _I, _I, C.POINTER(_DevicePixelsFloat)]),
+    'mi_ravif_encode_device_float': (_STATUS, [_ENC, C.POINTER(_DevicePixelsFloat), _U32, _U32, _OUT]),
+    'mi_batch_decode_device_deep': (_STATUS, [_P, _I, _I, _I, C.POINTER(_DeviceTargetDeep)]),
+    'mi_batch_decode_deep': (_STATUS, [_P, _I, _I, _I, _I, C.c_float, _P]),
 }
 # declared in the header and left without a prototype: their callers (tests, tools) pass ctypes values of their own
 _UNBOUND = ('mi_device_count', 'mi_png_decode_rgba', 'mi_ravif_encode_batch', 'mi_ravif_encode_stream', 'mi_release_cached')
@@ -544,6 +556,82 @@ def _device_pixels(x, batched=False, writable=False, deep_ok=False):
     return d, n, h, w, index
 
 
+SAMPLE_U16, SAMPLE_F16, SAMPLE_F32 = 1, 2, 3             # MI_SAMPLE_*
+_SAMPLE_OF_TYPESTR = {'<u2': SAMPLE_U16, '<f2': SAMPLE_F16, '<f4': SAMPLE_F32}
+_SAMPLE_BYTES = {SAMPLE_U16: 2, SAMPLE_F16: 2, SAMPLE_F32: 4}
+
+
+def _device_samples(x, full_scale, batched=False, writable=False):
+    """_device_pixels for the full-depth calls: (_DevicePixelsFloat, images, height, width, device index or None) of a source with typestr
+    '<f2' or '<f4', or with writable=True (_DeviceTargetDeep, ...) of a target with '<u2', '<f2' or '<f4'.  The shapes and views are _device_pixels' with the
+    sample's size in the place of one byte."""
+    ai = x.__cuda_array_interface__
+    if writable and ai['data'][1]:
+        raise ValueError('the target array is read-only')
+    typestr = ai.get('typestr')
+    sample = _SAMPLE_OF_TYPESTR.get(typestr)
+    if sample is None or (sample == SAMPLE_U16 and not writable):
+        raise TypeError('%s must be %sfloat16 or float32 (got typestr %r)' % (('the target array', 'uint16, ') if writable else ('float device pixels', '')) + (typestr,))
+    item = _SAMPLE_BYTES[sample]
+    shape = tuple(int(v) for v in ai['shape'])
+    strides = ai.get('strides')
+    if strides is None:
+        strides, acc = [], item
+        for n_ in reversed(shape):
+            strides.insert(0, acc); acc *= n_
+    strides = tuple(int(v) for v in strides)
+    ptr, index = ai['data'][0], getattr(getattr(x, 'device', None), 'index', None)
+    if not ptr or not shape or min(shape) < 1 or min(strides) < 0:
+        raise AvifError(4)
+    if len(shape) == 4 and batched:
+        n, img_stride, shape, strides = shape[0], strides[0], shape[1:], strides[1:]
+    elif len(shape) == 3:
+        n, img_stride = 1, 0
+    else:
+        raise AvifError(4)
+    if shape[0] in (3, 4) and shape[2] not in (3, 4):
+        (c, h, w), (sc, sh, sw) = shape, strides
+    else:
+        (h, w, c), (sh, sw, sc) = shape, strides
+    if c not in (3, 4):
+        raise AvifError(4)
+    if writable and (any(n_ > 1 and s_ == 0 for n_, s_ in zip(shape, strides)) or (n > 1 and img_stride == 0)):
+        raise ValueError('the target array is an expanded (stride 0) view: its elements share memory')
+    d = _DeviceTargetDeep() if writable else _DevicePixelsFloat()
+    d.dev, d.channels, d.row_stride, d.image_stride = ptr, c, sh, img_stride
+    d.sample, d.full_scale = sample, float(full_scale)
+    if sc == item:
+        d.layout, d.pixel_or_plane_stride = 0, sw                  # interleaved: from pixel to pixel
+    elif sw == item:
+        d.layout, d.pixel_or_plane_stride = 1, sc                  # planar: from plane to plane
+    else:
+        raise AvifError(4)
+    if n > 1 and img_stride == 0:
+        raise AvifError(4)
+    d.after_stream = _after_stream(index)
+    return d, n, h, w, index
+
+
+def _float_to_deep(a, full_scale=1.0):
+    """float16 / float32 samples -> uint16 at full scale by the rule of include/mi_avif.h, in float64: NaN and v <= 0 give 0, v >= full_scale gives 65535, else
+    rint(v * 65535 / full_scale), ties to even -- what mi_batch_upload_device_float does on the device"""
+    if a.dtype not in (np.float16, np.float32):
+        raise TypeError('float pixels must be float16 or float32 (got %s)' % (a.dtype,))
+    fs = np.float32(full_scale)
+    if not np.isfinite(fs) or not fs > 0:
+        raise AvifError(4)
+    v = a.astype(np.float32)                                       # exact for float16
+    with np.errstate(invalid='ignore', over='ignore'):
+        u = np.rint(v.astype(np.float64) * 65535.0 / np.float64(fs))
+        return np.where(v >= fs, 65535, np.where(v > 0, u, 0)).astype(np.uint16)      # (NaN fails both comparisons)
+
+
+def _chw_to_hwc(a):
+    """(C, H, W) -> (H, W, C) where the first dimension is 3 or 4 and the last is not (the convention of _device_pixels); (layout was CHW, the array)"""
+    chw = a.ndim == 3 and a.shape[0] in (3, 4) and a.shape[2] not in (3, 4)
+    return chw, (a.transpose(1, 2, 0) if chw else a)
+
+
 def _widen16(a, bits=16, msb_aligned=False):
     """uint16 samples of `bits` significant bits (8..16; low bits, or high bits when msb_aligned) at full scale: reduced to `bits`, then widened by bit
     replication -- what mi_batch_upload_device16 does on the device"""
@@ -612,16 +700,16 @@ def _planes16_fill(d, bits, msb_aligned, narrow_range):
     return True
 
 
-def _empty_like_device(x, shape):
-    """an uninitialised uint8 device array of `shape` from the library `x` comes from, on x's device"""
+def _empty_like_device(x, shape, same_dtype=False):
+    """an uninitialised uint8 device array of `shape` (same_dtype: of x's own dtype) from the library `x` comes from, on x's device"""
     mod = type(x).__module__.split('.')[0]
     if mod == 'torch':
         import torch
-        return torch.empty(shape, dtype=torch.uint8, device=x.device)
+        return torch.empty(shape, dtype=x.dtype if same_dtype else torch.uint8, device=x.device)
     if mod == 'cupy':
         import cupy
         with x.device:
-            return cupy.empty(shape, dtype=cupy.uint8)
+            return cupy.empty(shape, dtype=x.dtype if same_dtype else cupy.uint8)
     raise TypeError('encode_decoded cannot allocate a device array of %s: decode into an array of your own with BatchEncoder.decode_into' % type(x).__module__)
 
 
@@ -934,6 +1022,62 @@ class Encoder:
                 out = b.decoded(0)
             return b.get(0), out, bool(alpha and self.alpha_mode == 2)
 
+    def _one_image_float(self, x, full_scale):
+        """_one_image for float pixels: (a one-image BatchEncoder whose deep slot holds `x`, whether x came from device memory, whether x is (C, H, W))"""
+        dev = _is_device_array(x)
+        if dev:
+            d, _, h, w, index = _device_samples(x, full_scale)
+            channels, chw, enc = d.channels, d.layout == 1, (self if index is None else self.with_device(index))
+        else:
+            x = np.asarray(x)
+            if x.ndim != 3:
+                raise AvifError(4)
+            chw, hwc = _chw_to_hwc(x)
+            deep = np.ascontiguousarray(_float_to_deep(hwc, full_scale))
+            (h, w, channels), enc = deep.shape, self
+            if channels not in (3, 4):
+                raise AvifError(4)
+        b = BatchEncoder(enc, 1, w, h, channels)
+        try:
+            if dev:
+                b.upload_device_float(0, x, full_scale)
+            else:
+                b.upload(0, deep)
+        except BaseException:
+            b.close()
+            raise
+        return b, dev, chw
+
+    def encode_float(self, x, full_scale=1.0):
+        """float16 / float32 pixels, (H, W, C) or (C, H, W) with C = 3 or 4 and values in 0 .. full_scale, coded from 16 bits per sample: a
+        sample becomes rint(v * 65535 / full_scale) of the deep slot (NaN and negatives 0, values past full_scale 65535).  A device array (torch, cupy) is
+        converted on the device and never crosses to the host; a host numpy array is converted here by the same rule in float64 and goes through the deep
+        host upload: the same file either way."""
+        if _is_device_array(x):
+            L = load_library()
+            d, _, h, w, index = _device_samples(x, full_scale)
+            return self._call_once(L.mi_ravif_encode_device_float, index, C.byref(d), w, h)
+        with self._one_image_float(x, full_scale)[0] as b:
+            b.encode()
+            return b.get(0)
+
+    def encode_decoded_float(self, x, full_scale=1.0):
+        """(EncodedImage, decoded, premultiplied) of float pixels: the file of encode_float and the pixels a viewer's decoder reconstructs from it at full depth,
+        in x's own dtype, layout convention ((H, W, C) or (C, H, W)) and library (numpy, torch, cupy), on the same device, with white at full_scale; c = 4 when
+        the image uses alpha, else 3.  Only the file crosses to the host for a device array.  `premultiplied` as in encode_decoded."""
+        b, dev, chw = self._one_image_float(x, full_scale)
+        with b:
+            b.encode()
+            c = 4 if b.uses_alpha(0) else 3
+            if dev:
+                out = _empty_like_device(x, (c, b.h, b.w) if chw else (b.h, b.w, c), same_dtype=True)
+                b.decode_into_deep(0, out, full_scale=full_scale)
+            else:
+                out = b.decoded_deep(0, dtype=np.asarray(x).dtype, full_scale=full_scale)
+                if chw:
+                    out = np.ascontiguousarray(out.transpose(2, 0, 1))
+            return b.get(0), out, bool(c == 4 and self.alpha_mode == 2)
+
     def encode_to_target(self, pixels, target_db, metric='ssim', lo=1, hi=100):
         """The smallest integer quality in [lo, hi] whose encode reaches `target_db` in `metric`: 'ssim' (ImageQuality.ssim_db) or 'psnr' (ImageQuality.psnr_db).
         The encode at `hi` comes first; below the target it is returned with reached=False.  Otherwise a bisection over l, h = lo, hi: mid = (l + h) // 2,
@@ -1222,6 +1366,16 @@ class BatchEncoder(_Handle):
         _ok((self._L.mi_batch_upload_device16 if deep else self._L.mi_batch_upload_device)(self._h, first, n, C.byref(d)))
         self._sources.append(pixels)
 
+    def upload_device_float(self, first, x, full_scale=1.0):
+        """upload_device for float pixels: images first.. from an object with __cuda_array_interface__ of typestr '<f2' or '<f4', the shapes and
+        views of upload_device, into the deep slots (input kind 2).  A sample v becomes rint(v * 65535 / full_scale); NaN and v <= 0 give 0, v >= full_scale
+        gives 65535.  The object is kept referenced until wait()."""
+        d, n, h, w, _ = _device_samples(x, full_scale, batched=True)
+        if (h, w) != self._hw(first):
+            raise AvifError(4)
+        _ok(self._L.mi_batch_upload_device_float(self._h, first, n, C.byref(d)))
+        self._sources.append(x)
+
     def upload_jpeg(self, index, coeffs, ycbcr=False, orientation=None):
         """one parsed JPEG (parse_jpeg) of the batch's size into slot `index`: dequantisation, IDCT, upsampling and colour run on the batch's stream.
         ycbcr=True: no colour step, the slot holds the file's own (Y, Cb, Cr) and is of input kind 1 (a file whose colour is RGB raises Unsupported).
@@ -1421,6 +1575,28 @@ class BatchEncoder(_Handle):
         if (h, w) != self._hw(first):
             raise AvifError(4)
         _ok(self._L.mi_batch_decode_device(self._h, first, n, _named(DECODED_WHICH, which), C.byref(d)))
+
+    def decoded_deep(self, index, channels=None, which='recon', dtype=np.uint16, full_scale=1.0):
+        """decoded() at full depth: (h, w, c) of dtype uint16 (0 .. 65535), float16 or float32 (0 .. full_scale), made on the device, one D2H"""
+        w = _named(DECODED_WHICH, which)
+        dtype = np.dtype(dtype)
+        sample = _SAMPLE_OF_TYPESTR.get(dtype.str)
+        if sample is None:
+            raise TypeError('decoded_deep gives uint16, float16 or float32 (asked for %s)' % (dtype,))
+        if channels is None:
+            channels = 4 if self.uses_alpha(index) else 3
+        if channels not in (3, 4):
+            raise AvifError(4)
+        a = np.empty(self._hw(index) + (channels,), dtype)
+        _ok(self._L.mi_batch_decode_deep(self._h, index, w, channels, sample, float(full_scale), a.ctypes.data))
+        return a
+
+    def decode_into_deep(self, first, target, which='recon', full_scale=1.0):
+        """decode_into() at full depth: the target has typestr '<u2' (0 .. 65535), '<f2' or '<f4' (0 .. full_scale); the shapes and views of decode_into"""
+        d, n, h, w, _ = _device_samples(target, full_scale, batched=True, writable=True)
+        if (h, w) != self._hw(first):
+            raise AvifError(4)
+        _ok(self._L.mi_batch_decode_device_deep(self._h, first, n, _named(DECODED_WHICH, which), C.byref(d)))
 
     def measure(self):
         """mi_batch_measure + mi_batch_get_quality: the ImageQuality of every image of the last encode, computed on the device"""

@@ -611,6 +611,53 @@ typedef struct mi_device_target {          /* mi_device_pixels with a writable p
 int  mi_batch_uses_alpha(mi_batch *b, int index, int *uses_alpha);
 int  mi_batch_decode_device(mi_batch *b, int first, int count, int which, const mi_device_target *dst);
 int  mi_batch_decode(mi_batch *b, int index, int which, int channels, uint8_t *dst);
+/* ---- full-depth tensors: binary16 / binary32 sources into the deep slots, and decoded pixels as uint16, binary16 or binary32 samples.  Opt-in:
+ * a batch that never asks allocates and launches nothing for it.  Everything is exact; a restatement in float64 and integers gives the same bits.
+ * FLOAT SOURCE TO DEEP SLOT SAMPLE W.  v = the source sample; a binary16 sample is converted to binary32 exactly (subnormal halves are values, not zero).
+ * full_scale = the binary32 value that means white, finite and > 0 (1.0 for normalised tensors, 255.0 for byte-valued floats).  In this order:
+ *   v is NaN                                  W = 0
+ *   v <= 0          (-0.0, -inf)              W = 0
+ *   v >= full_scale (+inf)                    W = 65535
+ *   otherwise       u = ((double)v * 65535.0) / (double)full_scale,  W = (uint16)rint(u), round half to even.
+ * The product is exact in binary64 (24 by 16 bits) and the division its one rounding (none when full_scale is 1).  3 channels into a 4-channel batch get
+ * A = 65535; a float alpha sample goes through the same map.  The slot is of kind MI_INPUT_RGB16 and is coded by the formulas of deep input above.
+ * DEEP DECODED SAMPLE D.  mi_batch_decode's formulas with 65535 in the place of 255: for exact integers n, d > 0
+ *   q16(n, d) = clamp(floor((2 * 65535 * n + d * peak) / (2 * d * peak)), 0, 65535)          (0 whenever the numerator is negative)
+ * with the same n and d per channel and colour model (R = q16(1000 p0 + 1402 cr, 1000), G = q16(587000 p0 - 202008 cb - 419198 cr, 587000),
+ * B = q16(1000 p0 + 1772 cb, 1000); or G, B, R = q16(p, 1)); A = q16(a, 1) when the image uses alpha, else 65535.  No alpha association step, as at 8 bits.
+ * TARGET SAMPLE.  MI_SAMPLE_U16: D.  MI_SAMPLE_F32: (float)(((double)D * (double)full_scale) / 65535.0) -- an exact product, one binary64 division, one
+ * conversion to binary32 that rounds to nearest even.  MI_SAMPLE_F16: that binary32 value converted to binary16, round to nearest even.
+ * mi_batch_upload_device_float: mi_batch_upload_device16 (after_stream, ordering, lifetimes, the one-size rule, stride rules in BYTES, the alpha rules of deep
+ * input) for float samples; the slots are tagged MI_INPUT_RGB16; one launch for all images of the call.  MI_INVALID_ARGUMENT: what mi_batch_upload_device16
+ * refuses, an unknown `sample`, a full_scale that is not finite or not > 0, a pointer or stride that is no multiple of the sample size, a call between
+ * mi_batch_encode_async and mi_batch_wait -- all checked before the deep slots are made: a refused call allocates nothing (mi_batch_footprint).
+ * mi_ravif_encode_device_float: mi_ravif_encode_device16 for such a source.  Blocking, pooled.
+ * mi_batch_decode_device_deep: mi_batch_decode_device (state rule, one-size rule, alpha never dropped, stride rules, synchronisation) with the packed extents
+ * counted in the sample's size; the pointer and every stride are multiples of it; full_scale is read for float samples only.  mi_batch_decode_deep: one image
+ * into host memory (w * h * channels samples, rows packed) through the scratch of mi_batch_decode, grown to the sample size asked for. */
+enum { MI_SAMPLE_U16 = 1, MI_SAMPLE_F16 = 2, MI_SAMPLE_F32 = 3 };
+typedef struct mi_device_pixels_float {    /* mi_device_pixels for binary16 / binary32 samples */
+  const void *dev;
+  int layout;        /* 0 = HWC, 1 = CHW */
+  int channels;      /* 3 | 4 */
+  size_t row_stride, pixel_or_plane_stride, image_stride;   /* bytes, multiples of the sample size; 0 = packed */
+  void *after_stream; /* hipStream_t the pixels were produced on, or NULL = already complete */
+  int sample;        /* MI_SAMPLE_F16 | MI_SAMPLE_F32 */
+  float full_scale;  /* the value that means white: finite, > 0 */
+} mi_device_pixels_float;
+typedef struct mi_device_target_deep {     /* mi_device_target for uint16 / binary16 / binary32 samples */
+  void *dev;
+  int layout;        /* 0 = HWC, 1 = CHW */
+  int channels;      /* 3 | 4 */
+  size_t row_stride, pixel_or_plane_stride, image_stride;   /* bytes, multiples of the sample size; 0 = packed */
+  void *after_stream; /* hipStream_t whose queued work must finish before dst is written, or NULL */
+  int sample;        /* MI_SAMPLE_U16 | MI_SAMPLE_F16 | MI_SAMPLE_F32 */
+  float full_scale;  /* floats only: the value white is written as */
+} mi_device_target_deep;
+int  mi_batch_upload_device_float(mi_batch *b, int first, int count, const mi_device_pixels_float *src);
+int  mi_ravif_encode_device_float(const mi_ravif_encoder *e, const mi_device_pixels_float *src, uint32_t w, uint32_t h, mi_encoded_image *out);
+int  mi_batch_decode_device_deep(mi_batch *b, int first, int count, int which, const mi_device_target_deep *dst);
+int  mi_batch_decode_deep(mi_batch *b, int index, int which, int channels, int sample, float full_scale, void *dst);
 /* per-kernel HIP-event time (ms) of the last mi_batch_encode: 0 front-end, 1 tile search, 2 deblock, 3 cdef, 4 entropy, 5 pack+D2H, 6 host assembly */
 double mi_batch_stage_ms(const mi_batch *b, int stage);
 int  mi_batch_num_tiles(const mi_batch *b);
